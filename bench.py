@@ -11,6 +11,7 @@ resident in HBM before the timed region.  The direct-light-only frame (path_seg_
 measured beside it and reported under "also".
 
   python bench.py --gpus 1 --steps 5 --warmup 1
+  python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR    # + what the last timed step computed, as DIR/*.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -35,6 +36,9 @@ WORKLOADS = {
     "cfg3": (3840, 2160, 64, 23040, 46080, (13680, 27360)),
     "cfg4": (7680, 4320, 256, 46080, 92160, (13680, 27360)),
 }
+DUMP_BYTES_MAX = 64 << 20     # --dump-outputs: the most the .npy files may hold together
+DUMP_SAMPLE_PX = 1 << 20      # ... and the pixels sampled from a frame too large for that
+DUMP_SEED = 0x44554D50
 COUNT_KEYS = ("primary_rays", "primary_hits", "shadow_rays", "bounce_rays", "height_samples", "colour_fetches",
               "background_fetches", "dem_fetches", "mip_fetches", "camera_height_samples", "camera_dem_fetches",
               "camera_mip_fetches", "camera_colour_fetches", "camera_background_fetches")
@@ -62,6 +66,26 @@ def source_hash():
         with open(os.path.join(ROOT, rel), "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(rt, with_hits, out_dir):
+    """--dump-outputs: what the timed path leaves its caller after the last timed step, as float32 .npy files in `out_dir` --
+    linear_radiance.npy (the accumulated radiance, float4 per pixel) and, where rank 0 holds it, hits.npy (hx, hy, hz, hd per
+    pixel).  A frame whose arrays exceed DUMP_BYTES_MAX is sampled at DUMP_SAMPLE_PX pixels drawn once from a fixed seed: the
+    arrays are then (N, 4) and pixel_index.npy (float64, sorted) holds each row's index y * width + x."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"linear_radiance": rt.read_linear()}
+    if with_hits:
+        arrays["hits"] = rt.read_hits()
+    n_px = rt.width * rt.height
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BYTES_MAX:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_px, DUMP_SAMPLE_PX, replace=False))
+        arrays = {k: np.ascontiguousarray(a.reshape(n_px, 4)[idx]) for k, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def algorithmic_bytes(st, width, height, nominal=False, pixels=True):
@@ -284,7 +308,11 @@ def main():
     ap.add_argument("--zoom", type=float, default=0.0, metavar="VFOV_DEG",
                     help="profiling aid: make the zoomed terminator view (this vertical field of view) the timed scene")
     ap.add_argument("--inwave-paths", action="store_true", help="A/B: keep D6 paths inside the render wave (MRTX_F_INWAVE_PATHS)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     from moonrtx_amd import build, _lib
     build.build_native()
@@ -364,6 +392,9 @@ def main():
     for _ in range(args.warmup):
         step()
     elapsed, km = timed(args.steps)
+    dumped = None
+    if args.dump_outputs and rank == 0:     # before the side measurements below re-render with other scenes
+        dumped = dump_outputs(rt, gather.with_hits, args.dump_outputs)
 
     # whole-job numbers: max time over ranks, counts summed over ranks
     red_dev = "cpu" if backend == "gloo" else "cuda"
@@ -603,6 +634,8 @@ def main():
             out["also_starmap"] = starmap
         if facade is not None:
             out["facade"] = facade
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, dem_buf, (dem_h, dem_w), col_buf, col_shape, frame,
                                                args.cpu_budget_s)
