@@ -23,13 +23,16 @@ def dem_small():
     return synth_np.dem(360, 720, seed=5, craters=60)
 
 
-def check(scene, dem, color=None, bg=None, blocks=(1,)):
-    lin_h, hits_h, st_h, _ = render_hip(scene, dem, color, bg, blocks)
+def check(scene, dem, color=None, bg=None, blocks=(1,), flags=1):
+    """flags: the instantiation under test (1 = F_COUNT_STATS, the counting kernels; 0 = production, which counts nothing:
+    its counters are not compared)."""
+    lin_h, hits_h, st_h, _ = render_hip(scene, dem, color, bg, blocks, flags=flags)
     lin_o, hits_o, st_o = render_oracle(scene, dem, color, bg, blocks)
     assert np.abs(lin_h - lin_o).max() < L_INF_BAR
     assert_bit_equal(lin_h, lin_o, "linear radiance")
     assert_bit_equal(hits_h, hits_o, "hit buffer")
-    assert {k: st_h[k] for k in STAT_KEYS} == {k: st_o[k] for k in STAT_KEYS}
+    if flags & 1:
+        assert {k: st_h[k] for k in STAT_KEYS} == {k: st_o[k] for k in STAT_KEYS}
     assert lin_o[..., :3].max() > 0.01, "scene rendered black: test is vacuous"
     return lin_h, st_h
 
@@ -73,13 +76,16 @@ def test_domain_restricted_reciprocal_and_sqrt_are_ieee_exact(native_lib):
 
 @pytest.mark.parametrize("name", ["S1", "S2", "S3"])
 def test_first_light_1spp(native_lib, dem_small, name):
-    """BASELINE config 1 shape: 1 spp, grey albedo (reduced image so the oracle takes seconds)."""
-    check(named_scene(name, 192, 160, spp_per_launch=1), dem_small)
+    """BASELINE config 1 shape: 1 spp, grey albedo (reduced image so the oracle takes seconds).  Counting (1) and
+    production (0) instantiations: their launch bounds and register allocation differ."""
+    for flags in (1, 0):
+        check(named_scene(name, 192, 160, spp_per_launch=1), dem_small, flags=flags)
 
 
 @pytest.mark.parametrize("spp", [2, 4, 8, 16, 32, 64])
 def test_wave_packing_all_spp(native_lib, dem_small, spp):
-    check(named_scene("S1", 72, 56, spp_per_launch=spp), dem_small)
+    for flags in (1, 0):        # counting and production instantiations
+        check(named_scene("S1", 72, 56, spp_per_launch=spp), dem_small, flags=flags)
 
 
 def test_accumulation_blocks_match_oracle_and_single_launch(native_lib, dem_small):
@@ -201,7 +207,8 @@ def test_sky_tile_cull_is_result_preserving(native_lib, dem_small):
 
 @pytest.mark.parametrize("seg", [(2, 2), (2, 4), (1, 3)])
 def test_multi_bounce_paths_match_oracle(native_lib, dem_small, seg):
-    """D6: path continuation with Russian roulette, next-event estimation at every vertex, environment on escape."""
+    """D6: path continuation with Russian roulette, next-event estimation at every vertex, environment on escape.
+    Counting (1) and production (0) instantiations; the production kernels count nothing."""
     col = synth_np.colour_map(90, 180)
     rng = np.random.default_rng(11)
     bg = rng.integers(0, 255, (32, 64, 4), dtype=np.uint8)
@@ -214,9 +221,11 @@ def test_multi_bounce_paths_match_oracle(native_lib, dem_small, seg):
         assert st["bounce_rays"] >= st["primary_hits"]             # the first continuation is guaranteed
         if seg[1] > 2:
             assert st["bounce_rays"] > st["primary_hits"]          # some paths went on to a third segment
+    check(s, rough, col, bg, flags=0)
     s2 = named_scene("S3", 64, 48, spp_per_launch=4)
     s2.path_seg_min, s2.path_seg_max = seg
-    check(s2, dem_small, blocks=(2, 1))
+    for flags in (1, 0):
+        check(s2, dem_small, blocks=(2, 1), flags=flags)
 
 
 def test_edge_case_parameters_match_oracle(native_lib, dem_small):
