@@ -260,6 +260,35 @@ int mrtx_probe_stream(int32_t device, uint64_t bytes, int32_t repeats);
 int mrtx_probe_latlon(int32_t device, const float* a, const float* b, const float* c, float* lat, float* lon,
                       int32_t n);
 
+/* ---- Sun illumination of the terrain (additive to ABI 7) ----------------------------------
+ * The question the status bar answers with astro.sun_altitude_at over the smooth sphere (renderer_status.py:121-157):
+ * is this spot lit, and how much of the Sun does it see -- here on the real terrain, under the light and Moon frame
+ * last given to mrtx_set_light / mrtx_set_moon_frame, with the march parameters of mrtx_set_params.  Per node, float4:
+ *   lit  fraction of the n_sun Sun samples with cos > 0 whose shadow ray escapes (the visible fraction of the disk);
+ *   irr  (1/n_sun) * sum of what those samples carry: the D5 direct term per unit albedo;
+ *   mu   n . l toward the light centre (signed; the incidence);
+ *   D    the displacement factor at the node (local radius / R).
+ * The result depends on neither the camera, the seed, spp, path_seg_range nor the capsules; the render state
+ * (accumulation, hit buffer, samples done) is left exactly as it was.  n_sun is 1, 2, 4, ..., 64. */
+typedef struct MrtxIllumGrid {
+    double lat_north, lat_south;   /* degrees, lat_north > lat_south, both in [-90, 90]                           */
+    double lon_west, lon_east;     /* degrees, lon_west < lon_east (may run past +-180: the DEM wraps in longitude) */
+    int32_t h, w;                  /* cells of the whole map; node (i, j) is the centre of cell (i, j), row 0 north */
+    int32_t row_begin, row_end;    /* the band computed by this call: rows [row_begin, row_end) of the map         */
+    int32_t n_sun;
+    int32_t reserved;              /* 0 */
+} MrtxIllumGrid;
+/* A lat/lon map, one band of rows per call: (row_end - row_begin) x w float4, row-major, into dev_out (a device buffer of
+ * the context's device) and / or host_out (at least one of them).  Bands are independent: a map is the concatenation of
+ * its bands.  out may be NULL. */
+int mrtx_illum_grid(mrtx_ctx* ctx, const MrtxIllumGrid* grid, void* dev_out, float* host_out, MrtxStats* out);
+/* The same at n arbitrary points: latlon_deg = n (lat, lon) pairs in degrees, host_out4 = n float4.  A point placed on a
+ * grid node gives that node's output bit for bit -- the status bar's cursor query (renderer_status.py:121-157). */
+int mrtx_illum_points(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t n_sun, float* host_out4, MrtxStats* out);
+/* The deterministic Sun-sample table the two calls above use: n (u2, u3) float pairs (n = 1: the Sun's centre (0, 0);
+ * otherwise the Fibonacci set u2 = (i + 1/2) / n, u3 = frac(i * 0.6180339887498949), float64 rounded once).  No GPU. */
+int mrtx_illum_sun_samples(int32_t n, float* out2);
+
 /* Math conformance probe (ABI 7): the kernels' domain-restricted reciprocal (v_rcp_f32 + Newton steps) and square root (v_sqrt_f32 + a
  * +-1 ulp residual fix) against the compiler's IEEE expansions of 1.0f / x and sqrtf(x), ON THE DEVICE, for the n float bit patterns
  * from lo_bits on: which = 0 one Newton step, 1 two steps (what the kernels use), 2 the square root.  mismatches = how many differ;

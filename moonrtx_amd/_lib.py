@@ -37,6 +37,13 @@ class MrtxStats(C.Structure):
                 ("camera_colour_fetches", C.c_uint64), ("camera_background_fetches", C.c_uint64)]
 
 
+class MrtxIllumGrid(C.Structure):
+    """One band of a lat/lon Sun-illumination map (mrtx_illum_grid)."""
+    _fields_ = [("lat_north", C.c_double), ("lat_south", C.c_double), ("lon_west", C.c_double), ("lon_east", C.c_double),
+                ("h", C.c_int32), ("w", C.c_int32), ("row_begin", C.c_int32), ("row_end", C.c_int32),
+                ("n_sun", C.c_int32), ("reserved", C.c_int32)]
+
+
 F_COUNT_STATS = 1
 F_FORCE_WIDE = 2
 F_NO_SKIP = 4
@@ -97,6 +104,9 @@ SIGNATURES = {
     "mrtx_probe_stream": (C.c_int, [C.c_int32, C.c_uint64, C.c_int32]),
     "mrtx_probe_cr": (C.c_int, [C.c_int32, C.c_int32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "mrtx_probe_latlon": (C.c_int, [C.c_int32, _VP, _VP, _VP, _VP, _VP, C.c_int32]),
+    "mrtx_illum_grid": (C.c_int, [_VP, C.POINTER(MrtxIllumGrid), _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_illum_points": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_illum_sun_samples": (C.c_int, [C.c_int32, _VP]),
 }
 
 _lib = None

@@ -52,6 +52,7 @@ hipError_t mrtx_launch_hmip(const float* mip, int mh, int mw, int shift, float* 
                             hipStream_t st);
 hipError_t mrtx_launch_probe_stream(const void* src, int64_t n_pairs, float* out, hipStream_t st);
 hipError_t mrtx_launch_probe_cr(uint32_t lo, uint64_t n, int which, unsigned long long* out2, hipStream_t st);
+hipError_t mrtx_launch_illum(const FrameC& f, IllumC g, bool stats, hipStream_t st);
 
 struct mrtx_ctx {
     MrtxConfig cfg{};
@@ -132,6 +133,12 @@ struct mrtx_ctx {
     double center[3] = {0, 0, 0}, radius = 10.0, u[3] = {0, 0, 1}, v[3] = {0, -1, 0};
     double light_pos[3] = {0, -21460, 0}, light_radius = 100.0, light_radiance = 0.0;
     double sun_pos[3] = {0, 3100, 0}, sun_radius = 0.0, sun_radiance = 2.0;
+    bool moon_set = false, light_set = false;   // mrtx_set_moon_frame / mrtx_set_light were called (the illumination stage needs both)
+    // Sun illumination stage (mrtx_illum_*): its OWN cold block, counters and buffers, so that it leaves the render state alone
+    FrameCold* illum_cold = nullptr;
+    unsigned long long* illum_stats = nullptr;   // ST_N counters
+    float* illum_tab = nullptr; size_t illum_tab_bytes = 0;    // sample table + (sin, cos) tables
+    float* illum_out = nullptr; size_t illum_out_bytes = 0;    // float4 per node when the caller gives no device buffer
     std::string err;
 };
 
@@ -614,6 +621,10 @@ void mrtx_destroy(mrtx_ctx* c) {
     if (c->color) (void)hipFree(c->color);
     if (c->bg) (void)hipFree(c->bg);
     if (c->overlay) (void)hipFree(c->overlay);
+    if (c->illum_cold) (void)hipFree(c->illum_cold);
+    if (c->illum_stats) (void)hipFree(c->illum_stats);
+    if (c->illum_tab) (void)hipFree(c->illum_tab);
+    if (c->illum_out) (void)hipFree(c->illum_out);
     if (c->stream2) { (void)hipStreamSynchronize(c->stream2); put_stream(c->cfg.device, c->stream2); }
     put_event(c->cfg.device, c->ov_done[0]); put_event(c->cfg.device, c->ov_done[1]); put_event(c->cfg.device, c->ov_join);
     put_event(c->cfg.device, c->ev0);
@@ -799,6 +810,7 @@ int mrtx_set_moon_frame(mrtx_ctx* c, const double center[3], double radius, cons
     if (!((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2] > 0.0)) return fail(c, MRTX_E_INVALID, "moon u and v are parallel");
     for (int i = 0; i < 3; i++) { c->center[i] = center[i]; c->u[i] = u[i]; c->v[i] = v[i]; }
     c->radius = radius;
+    c->moon_set = true;
     c->scene_version++;
     return MRTX_OK;
 }
@@ -807,6 +819,7 @@ int mrtx_set_light(mrtx_ctx* c, const double pos[3], double radius, double radia
     if (!check_vec(pos) || !(radius >= 0.0) || !(radiance >= 0.0)) return fail(c, MRTX_E_INVALID, "bad light");
     for (int i = 0; i < 3; i++) c->light_pos[i] = pos[i];
     c->light_radius = radius; c->light_radiance = radiance;
+    c->light_set = true;
     return MRTX_OK;
 }
 int mrtx_set_sun_disk(mrtx_ctx* c, const double pos[3], double radius, double radiance) {
@@ -1187,6 +1200,134 @@ int mrtx_render_part(mrtx_ctx* c, int32_t n_blocks, int32_t part, int32_t n_part
         }
     }
     return MRTX_OK;
+}
+
+// ---- Sun illumination of the terrain ------------------------------------------------------------
+static bool illum_n_ok(int32_t n) { return n >= 1 && n <= 64 && (n & (n - 1)) == 0; }
+
+int mrtx_illum_sun_samples(int32_t n, float* out2) {
+    if (!illum_n_ok(n) || !out2) return MRTX_E_INVALID;
+    for (int32_t i = 0; i < n; i++) {
+        if (n == 1) { out2[0] = 0.0f; out2[1] = 0.0f; break; }     // the Sun's centre: a point-light terminator
+        const double t = (double)i * 0.6180339887498949;
+        out2[2 * i] = (float)(((double)i + 0.5) / (double)n);
+        out2[2 * i + 1] = (float)(t - std::floor(t));
+    }
+    return MRTX_OK;
+}
+
+// (sin, cos) of an angle in degrees: float64, rounded once each
+static void illum_sc(double deg, float* sc) {
+    const double r = deg * (kPiD / 180.0);
+    sc[0] = (float)std::sin(r);
+    sc[1] = (float)std::cos(r);
+}
+
+// Everything after the argument checks: state, tables, one launch into `dev_out`, counters.  rtab / ctab are host tables of
+// (sin, cos) pairs: n_r and n_c entries.
+static int illum_run(mrtx_ctx* c, const std::vector<float>& rtab, const std::vector<float>& ctab, int rows, int cols, bool points,
+                     int n_sun, void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
+    if (!c->moon_set) return fail(c, MRTX_E_STATE, "no moon frame: call mrtx_set_moon_frame first");
+    if (!c->light_set) return fail(c, MRTX_E_STATE, "no light: call mrtx_set_light first");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (!(c->prm.flags & MRTX_F_NO_SKIP)) { const int rc_ = ensure_mip(c); if (rc_ != MRTX_OK) return rc_; }
+    FrameC f;
+    FrameCold cold;
+    std::memset(&cold, 0, sizeof cold);
+    build_frame(c, f, cold);
+    if (!c->illum_cold) HIPCHK(c, hipMalloc((void**)&c->illum_cold, sizeof(FrameCold)));
+    if (!c->illum_stats) HIPCHK(c, hipMalloc((void**)&c->illum_stats, 16 * sizeof(unsigned long long)));
+    cold.accum = nullptr; cold.hits = nullptr; cold.stats = c->illum_stats; cold.stats_paths = nullptr;
+    f.cold = c->illum_cold;
+    const bool stats = (c->prm.flags & MRTX_F_COUNT_STATS) != 0;
+    if (c->prm.flags & MRTX_F_FORCE_WIDE) f.dem_wide = 1;
+    if (c->prm.flags & MRTX_F_NO_SKIP) f.mip = nullptr;   // (build_frame leaves the horizon mip out as well)
+    // one device block: sample table (64 pairs), row table, column table
+    const size_t tab_bytes = (128 + rtab.size() + ctab.size()) * sizeof(float);
+    if (tab_bytes > c->illum_tab_bytes) {
+        if (c->illum_tab) { HIPCHK(c, hipFree(c->illum_tab)); c->illum_tab = nullptr; c->illum_tab_bytes = 0; }
+        HIPCHK(c, hipMalloc((void**)&c->illum_tab, tab_bytes));
+        c->illum_tab_bytes = tab_bytes;
+    }
+    std::vector<float> host((size_t)128 + rtab.size() + ctab.size(), 0.0f);
+    mrtx_illum_sun_samples(n_sun, host.data());
+    std::copy(rtab.begin(), rtab.end(), host.begin() + 128);
+    std::copy(ctab.begin(), ctab.end(), host.begin() + 128 + (ptrdiff_t)rtab.size());
+    const size_t out_bytes = (size_t)rows * (size_t)cols * 16;
+    if (!dev_out) {
+        if (out_bytes > c->illum_out_bytes) {
+            if (c->illum_out) { HIPCHK(c, hipFree(c->illum_out)); c->illum_out = nullptr; c->illum_out_bytes = 0; }
+            HIPCHK(c, hipMalloc((void**)&c->illum_out, out_bytes));
+            c->illum_out_bytes = out_bytes;
+        }
+        dev_out = c->illum_out;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->illum_cold, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->illum_tab, host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+    if (stats) HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
+    IllumC g;
+    std::memset(&g, 0, sizeof g);
+    g.sun = c->illum_tab; g.rtab = c->illum_tab + 128; g.ctab = g.rtab + rtab.size();
+    g.out = (float*)dev_out; g.rows = rows; g.cols = cols; g.points = points ? 1 : 0; g.n_sun = n_sun;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    HIPCHK(c, mrtx_launch_illum(f, g, stats, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // also: the pageable tables above are no longer read
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (host_out) HIPCHK(c, hipMemcpy(host_out, dev_out, out_bytes, hipMemcpyDeviceToHost));
+    if (out) {
+        std::memset(out, 0, sizeof *out);
+        out->kernel_ms = ms;
+        out->launches = 1;
+        if (stats) {
+            unsigned long long h[16];
+            HIPCHK(c, hipMemcpy(h, c->illum_stats, sizeof h, hipMemcpyDeviceToHost));
+            out->shadow_rays = h[2]; out->height_samples = h[3]; out->dem_fetches = h[6]; out->mip_fetches = h[7];
+        }
+    }
+    return MRTX_OK;
+}
+
+int mrtx_illum_grid(mrtx_ctx* c, const MrtxIllumGrid* g, void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!g) return fail(c, MRTX_E_INVALID, "null grid");
+    if (!std::isfinite(g->lat_north) || !std::isfinite(g->lat_south) || !(g->lat_north > g->lat_south) || g->lat_north > 90.0 ||
+        g->lat_south < -90.0)
+        return fail(c, MRTX_E_INVALID, "latitudes must satisfy 90 >= lat_north > lat_south >= -90");
+    if (!std::isfinite(g->lon_west) || !std::isfinite(g->lon_east) || !(g->lon_east > g->lon_west) || std::fabs(g->lon_west) > 1e6 ||
+        std::fabs(g->lon_east) > 1e6)
+        return fail(c, MRTX_E_INVALID, "longitudes must be finite with lon_west < lon_east");
+    if (g->h < 1 || g->w < 1) return fail(c, MRTX_E_INVALID, "empty grid (%d x %d)", g->h, g->w);
+    if (g->row_begin < 0 || g->row_end > g->h || g->row_begin >= g->row_end)
+        return fail(c, MRTX_E_INVALID, "bad band [%d, %d) of %d rows", g->row_begin, g->row_end, g->h);
+    if (!illum_n_ok(g->n_sun)) return fail(c, MRTX_E_INVALID, "n_sun must be 1, 2, 4, ..., 64 (got %d)", g->n_sun);
+    if ((int64_t)(g->row_end - g->row_begin) * (int64_t)g->w > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "a band holds at most 2^31 nodes: split the map into more bands");
+    if (!dev_out && !host_out) return fail(c, MRTX_E_INVALID, "no output buffer");
+    const int rows = g->row_end - g->row_begin;
+    std::vector<float> rtab((size_t)rows * 2), ctab((size_t)g->w * 2);
+    const double dlat = (g->lat_north - g->lat_south) / (double)g->h, dlon = (g->lon_east - g->lon_west) / (double)g->w;
+    for (int i = 0; i < rows; i++) illum_sc(g->lat_north - ((double)(g->row_begin + i) + 0.5) * dlat, &rtab[(size_t)i * 2]);
+    for (int j = 0; j < g->w; j++) illum_sc(g->lon_west + ((double)j + 0.5) * dlon, &ctab[(size_t)j * 2]);
+    return illum_run(c, rtab, ctab, rows, g->w, false, g->n_sun, dev_out, host_out, out);
+}
+
+int mrtx_illum_points(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_sun, float* host_out4, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (n < 1) return fail(c, MRTX_E_INVALID, "n must be >= 1 (got %d)", n);
+    if (!latlon || !host_out4) return fail(c, MRTX_E_INVALID, "null point list or output");
+    if (!illum_n_ok(n_sun)) return fail(c, MRTX_E_INVALID, "n_sun must be 1, 2, 4, ..., 64 (got %d)", n_sun);
+    std::vector<float> rtab((size_t)n * 2), ctab((size_t)n * 2);
+    for (int32_t i = 0; i < n; i++) {
+        const double la = latlon[2 * (size_t)i], lo = latlon[2 * (size_t)i + 1];
+        if (!std::isfinite(la) || !std::isfinite(lo) || la > 90.0 || la < -90.0 || std::fabs(lo) > 1e6)
+            return fail(c, MRTX_E_INVALID, "point %d: latitude must lie in [-90, 90] and longitude be finite", i);
+        illum_sc(la, &rtab[(size_t)i * 2]);
+        illum_sc(lo, &ctab[(size_t)i * 2]);
+    }
+    return illum_run(c, rtab, ctab, 1, n, true, n_sun, nullptr, host_out4, out);
 }
 
 int mrtx_samples_done(mrtx_ctx* c, uint32_t* out) {

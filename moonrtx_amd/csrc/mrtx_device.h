@@ -171,3 +171,17 @@ struct PathQ {
 #define MRTX_PATH_REC_BYTES (MRTX_C_AOS == 1 ? 68 : 64)  // per record: 3 x float4 + 3 x float (or one float4) + 1 word
 #define MRTX_REC_RESUME 64u
 #define MRTX_REC_HIT 128u
+
+// Sun illumination stage (mrtx_illum_grid / mrtx_illum_points): by value -> SGPRs.  A node is (row, col) of
+// a rows x cols block; its unit vector comes from the float32 (sin, cos) tables the host built in float64.
+struct IllumC {
+    const float* rtab;      // (sin lat, cos lat) per row of the band; a point list: per point
+    const float* ctab;      // (sin lon, cos lon) per column; a point list: per point
+    const float* sun;       // n_sun (u2, u3) pairs
+    float* out;             // rows x cols float4 (lit, irr, mu, D)
+    int32_t rows, cols;     // a point list is one row of n points
+    int32_t points;         // 1: row table indexed by the column (the point) as well
+    int32_t n_sun, n_log2;  // samples per node (power of two <= 64)
+    int32_t pw_log2;        // a wave's node block is (1 << pw_log2) columns wide (set by the launcher)
+    int32_t waves_x;        // node blocks per row of blocks (set by the launcher)
+};

@@ -1961,6 +1961,125 @@ render_kernel(const FrameC f, const PathQ pq) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Sun illumination of the terrain (DESIGN.md sections 3.6 and 4.8): per node of a lat/lon band or a point list, the vertex
+// of the camera path's first hit (hit_vertex at p = R D(node) u) and n_sun light samples of the fixed table marched like its
+// shadow ray (light_sample + march, the body of direct_light with the visibility kept apart from what a sample carries).
+// MRTX_ILLUM_MAP 0: one wave = 64/n adjacent nodes x n samples in adjacent lanes (render_kernel's idea: the lanes march from
+// nearly one point in nearly one direction); 1: lane = node, the samples in a loop (the alternative, measured in 4.8).
+#ifndef MRTX_ILLUM_MAP
+#define MRTX_ILLUM_MAP 0
+#endif
+// (sum over the n lanes of a node, the pairwise order of tree_sum<n>) for a run-time n
+__device__ __forceinline__ float group_sum(float v, int n) {
+    for (int m = 1; m < n; m <<= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+// the node's surface vertex and D (what every sample of the node shares)
+template <bool STATS, bool WIDE>
+__device__ __forceinline__ float illum_vertex(const FrameC& f, const IllumC& g, int row, int col, Vertex& v, uint32_t* cnt) {
+    const float2 rt = reinterpret_cast<const float2*>(g.rtab)[g.points ? col : row];
+    const float2 ct = reinterpret_cast<const float2*>(g.ctab)[col];
+    const float ua = rt.y * ct.x, ub = rt.y * ct.y, uc = rt.x;     // (cos lat sin lon, cos lat cos lon, sin lat)
+    float lat, lon;
+    latlon(ua, ub, uc, fmaf(ub, ub, ua * ua), lat, lon);
+    const float D = dem_march<WIDE>(f, fmaf(lat, f.gd.row_scale, f.gd.row_off), fmaf(lon, f.gd.col_scale, f.gd.col_off));
+    if (STATS) { cnt[ST_HEIGHT]++; cnt[ST_FETCH]++; }
+    const float rD = f.Rf * D;
+    hit_vertex<STATS, WIDE>(f, rD * ua, rD * ub, rD * uc, v, cnt);
+    return D;
+}
+// mu = n . l toward the light centre, l formed as light_sample forms it from the lifted origin
+__device__ __forceinline__ float illum_mu(const FrameC& f, const Vertex& v) {
+    const float eps = CF(f)->scene_eps;
+    const float oa = fmaf(eps, v.na, v.pa), ob = fmaf(eps, v.nb, v.pb), oc = fmaf(eps, v.nc, v.pc);
+    const float ta = CF(f)->Lb[0] - oa, tb = CF(f)->Lb[1] - ob, tc = CF(f)->Lb[2] - oc;
+    const float inv_dist = rcp_cr(sqrt_sh(fmaf(tc, tc, fmaf(tb, tb, ta * ta))));
+    return fmaf(v.nc, tc * inv_dist, fmaf(v.nb, tb * inv_dist, v.na * (ta * inv_dist)));
+}
+// one light sample: true if it arrives (cos > 0 and the shadow ray escapes); `carried` = what it carries then
+template <bool STATS, bool WIDE>
+__device__ __forceinline__ bool illum_sample(const FrameC& f, const Vertex& v, float u2, float u3, float& carried, uint32_t* cnt) {
+    float oa, ob, oc, wa, wb, wc;
+    if (!light_sample(f, v, u2, u3, oa, ob, oc, wa, wb, wc, carried)) return false;
+    if (STATS) cnt[ST_SHADOW]++;
+    Seg ssg;
+    float sk_occ;
+    return !march<WIDE, false, STATS, MRTX_STEP_BATCH, 2>(f, oa, ob, oc, wa, wb, wc, 0.0f, ssg, sk_occ, cnt);
+}
+
+template <bool STATS, bool WIDE>
+__global__ void __launch_bounds__(64) illum_kernel(const FrameC f, const IllumC g) {
+    const int lane = threadIdx.x;
+    const int n = g.n_sun;
+#if MRTX_ILLUM_MAP == 0
+    const int s = lane & (n - 1), p = lane >> g.n_log2;
+#else
+    const int s = 0, p = lane;
+#endif
+    // the wave's node block: PW x PH nodes in raster order
+    const int pw = 1 << g.pw_log2;
+    const int wx = (int)(blockIdx.x % (unsigned)g.waves_x), wy = (int)(blockIdx.x / (unsigned)g.waves_x);
+    const int col = wx * pw + (p & (pw - 1));
+    const int row = wy * ((64 >> (MRTX_ILLUM_MAP == 0 ? g.n_log2 : 0)) >> g.pw_log2) + (p >> g.pw_log2);
+    const bool in = row < g.rows && col < g.cols;
+    uint32_t cnt_store[STATS ? ST_N : 1];
+    uint32_t* const cnt = STATS ? cnt_store : nullptr;
+    if (STATS) {
+#pragma unroll
+        for (int i = 0; i < ST_N; i++) cnt[i] = 0;
+    }
+    float lit = 0.0f, irr = 0.0f, mu = 0.0f, D = 0.0f;
+    if (in) {
+        Vertex v;
+        D = illum_vertex<STATS, WIDE>(f, g, row, col, v, cnt);
+        mu = illum_mu(f, v);
+        const float2* sun = reinterpret_cast<const float2*>(g.sun);
+#if MRTX_ILLUM_MAP == 0
+        const float2 us = sun[s];
+        float carried;
+        if (illum_sample<STATS, WIDE>(f, v, us.x, us.y, carried, cnt)) { lit = 1.0f; irr = carried; }
+#else
+        // the n samples in turn; their sum in tree_sum's pairwise order: part[t] holds the pending sum of 2^t samples
+        float part[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < n; i++) {
+            const float2 us = sun[i];
+            float carried, x = 0.0f;
+            if (illum_sample<STATS, WIDE>(f, v, us.x, us.y, carried, cnt)) { lit += 1.0f; x = carried; }
+            if (STATS && i > 0) { cnt[ST_HEIGHT] += 5; cnt[ST_FETCH] += 5; }   // the spec counts the vertex per sample
+            bool pending = true;
+#pragma unroll
+            for (int t = 0; t < 7; t++) {
+                if (pending) {
+                    if ((i >> t) & 1) x = part[t] + x;
+                    else { part[t] = x; pending = false; }
+                }
+            }
+        }
+        irr = part[0];
+#pragma unroll
+        for (int t = 1; t < 7; t++) irr = g.n_log2 == t ? part[t] : irr;   // (no run-time index into a register array)
+#endif
+    }
+#if MRTX_ILLUM_MAP == 0
+    lit = group_sum(lit, n);    // a count: exact
+    irr = group_sum(irr, n);
+#endif
+    const float inv_n = 1.0f / (float)n;   // a power of two: the scalings below are exact
+    if (in && s == 0)
+        reinterpret_cast<float4*>(g.out)[(int64_t)row * g.cols + col] = make_float4(lit * inv_n, irr * inv_n, mu, D);
+    if (STATS) {
+        const int which[4] = {ST_SHADOW, ST_HEIGHT, ST_FETCH, ST_MIP};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            uint32_t c = cnt[which[i]];
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) c += __shfl_xor(c, m, 64);
+            if (lane == 0) atomicAdd(&CF(f)->stats[which[i]], (unsigned long long)c);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // D6 behind a queue: what is left of a path after render_kernel<MODE 2> (set_uint("path_seg_range", 2, 4),
 // moon_renderer.py:583).
 //
@@ -3227,6 +3346,29 @@ hipError_t mrtx_launch_render(const FrameC& f, int S, bool stats, int mode, bool
 #undef MRTX_CASE2
 #undef MRTX_CASE3
 #undef MRTX_LAUNCH
+    return hipGetLastError();
+}
+
+// The Sun illumination stage (illum_kernel): one wave per block of nodes -- 64 / n_sun nodes (MRTX_ILLUM_MAP 0) or 64 (1) in a
+// PW x PH block, PW as render_geometry picks it for as many pixels.  g.rows x g.cols nodes; g.pw_log2 and g.waves_x are set here.
+hipError_t mrtx_launch_illum(const FrameC& f, IllumC g, bool stats, hipStream_t st) {
+    if (g.n_sun < 1 || g.n_sun > 64 || (g.n_sun & (g.n_sun - 1)) || g.rows < 1 || g.cols < 1) return hipErrorInvalidValue;
+    g.n_log2 = 0;
+    while ((1 << g.n_log2) < g.n_sun) g.n_log2++;
+    const int P = MRTX_ILLUM_MAP == 0 ? 64 >> g.n_log2 : 64;
+    int PW = P >= 32 ? 8 : P >= 8 ? 4 : P >= 2 ? 2 : 1;
+    if (g.rows == 1) PW = P;                    // a point list (or a one-row band): the nodes side by side
+    g.pw_log2 = PW == 64 ? 6 : PW == 32 ? 5 : PW == 16 ? 4 : PW == 8 ? 3 : PW == 4 ? 2 : PW == 2 ? 1 : 0;
+    const int PH = P / PW;
+    g.waves_x = (g.cols + PW - 1) / PW;
+    const uint64_t waves = (uint64_t)g.waves_x * (uint64_t)((g.rows + PH - 1) / PH);
+    if (waves > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)waves), block(64);
+    const bool wide = f.dem_wide != 0;
+    if (stats) { if (wide) hipLaunchKernelGGL((mrtx::illum_kernel<true, true>), grid, block, 0, st, f, g);
+                 else hipLaunchKernelGGL((mrtx::illum_kernel<true, false>), grid, block, 0, st, f, g); }
+    else { if (wide) hipLaunchKernelGGL((mrtx::illum_kernel<false, true>), grid, block, 0, st, f, g);
+           else hipLaunchKernelGGL((mrtx::illum_kernel<false, false>), grid, block, 0, st, f, g); }
     return hipGetLastError();
 }
 

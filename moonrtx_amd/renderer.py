@@ -240,6 +240,71 @@ class MoonRT:
         self._check(self._lib.mrtx_read_hits(self._ctx, out.ctypes.data), "mrtx_read_hits")
         return out
 
+    # ---- Sun illumination of the terrain
+    @staticmethod
+    def sun_samples(n):
+        """The (u2, u3) float32 table of n Sun samples the illumination stage uses, (n, 2)."""
+        out = np.empty((int(n), 2), np.float32)
+        if _lib.load().mrtx_illum_sun_samples(int(n), out.ctypes.data) != 0:
+            raise ValueError("n_sun must be 1, 2, 4, ..., 64")
+        return out
+
+    @staticmethod
+    def grid_nodes(lat=(90.0, -90.0), lon=(-180.0, 180.0), shape=(180, 360)):
+        """float64 (lat, lon) in degrees of the nodes of a map, the centres of its cells, computed as the library computes
+        them -- a point list at these coordinates gives the map's values bit for bit."""
+        (la_n, la_s), (lo_w, lo_e), (h, w) = (float(lat[0]), float(lat[1])), (float(lon[0]), float(lon[1])), shape
+        dlat, dlon = (la_n - la_s) / h, (lo_e - lo_w) / w
+        return la_n - (np.arange(h) + 0.5) * dlat, lo_w + (np.arange(w) + 0.5) * dlon
+
+    def illumination_map(self, lat=(90.0, -90.0), lon=(-180.0, 180.0), shape=(180, 360), n_sun=16, rows=None, stats=None,
+                         band_bytes=256 << 20):
+        """(rows, w, 4) float32 map of (lit, irr, mu, D) over lat = (north, south), lon = (west, east) in degrees with
+        shape = (h, w) cells; rows = (first, end) computes that band only (default: all).  Bands of at most band_bytes go
+        through one device buffer.  `stats`, if a dict, receives the summed counters of the launches."""
+        h, w = int(shape[0]), int(shape[1])
+        r0, r1 = (0, h) if rows is None else (int(rows[0]), int(rows[1]))
+        g = _lib.MrtxIllumGrid(float(lat[0]), float(lat[1]), float(lon[0]), float(lon[1]), h, w, r0, r1, int(n_sun), 0)
+        out = np.empty((max(r1 - r0, 0), w, 4), np.float32)
+        step = max(1, int(band_bytes) // (16 * max(w, 1)))
+        if r1 - r0 <= step:      # one band: straight into the host array
+            st = MrtxStats()
+            self._check(self._lib.mrtx_illum_grid(self._ctx, C.byref(g), None, out.ctypes.data, C.byref(st)), "mrtx_illum_grid")
+            self._add_stats(stats, st)
+            return out
+        buf = DeviceBuffer(16 * step * w, self.config()["device"])
+        try:
+            for a in range(r0, r1, step):
+                g.row_begin, g.row_end = a, min(a + step, r1)
+                st = MrtxStats()
+                self._check(self._lib.mrtx_illum_grid(self._ctx, C.byref(g), buf.ptr, None, C.byref(st)), "mrtx_illum_grid")
+                self._add_stats(stats, st)
+                out[a - r0:g.row_end - r0] = buf.download(np.float32, (g.row_end - a, w, 4))
+        finally:
+            buf.free()
+        return out
+
+    def illumination_at(self, lat_deg, lon_deg, n_sun=16, stats=None):
+        """(N, 4) float32 (lit, irr, mu, D) at N selenographic points (degrees): the status bar's Sun altitude
+        (renderer_status.py:121-157) on the real terrain."""
+        la = np.atleast_1d(np.asarray(lat_deg, np.float64)).ravel()
+        lo = np.atleast_1d(np.asarray(lon_deg, np.float64)).ravel()
+        if la.shape != lo.shape:
+            raise ValueError("lat_deg and lon_deg must have the same number of points")
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        out = np.empty((la.size, 4), np.float32)
+        st = MrtxStats()
+        self._check(self._lib.mrtx_illum_points(self._ctx, pts.ctypes.data, la.size, int(n_sun), out.ctypes.data, C.byref(st)),
+                    "mrtx_illum_points")
+        self._add_stats(stats, st)
+        return out
+
+    @staticmethod
+    def _add_stats(acc, st):
+        if isinstance(acc, dict):
+            for k in ("shadow_rays", "height_samples", "dem_fetches", "mip_fetches", "kernel_ms", "launches"):
+                acc[k] = acc.get(k, 0) + getattr(st, k)
+
     def config(self):
         """The configuration the context runs with, defaults filled in (mrtx_get_config): device, width, height, rank, world,
         tile_w, tile_h."""

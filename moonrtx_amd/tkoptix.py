@@ -562,6 +562,17 @@ class TkOptiX:
             return float(h[0]), float(h[1]), float(h[2]), float(h[3])
         return 0.0, 0.0, 0.0, -1.0
 
+    def illumination_at(self, lat, lon, n_sun=16):
+        """(N, 4) float32 (lit, irr, mu, D) at selenographic (lat, lon) in degrees under the scene as it stands: the
+        terrain-aware companion of the status bar's Sun altitude (renderer_status.py:121-157, astro.sun_altitude_at).  The
+        march knobs set through set_float are pushed first; the render cycle is not touched."""
+        with self._padlock:
+            f = self._floats
+            kw = {k: f[k] for k in ("scene_epsilon", "marching_step", "marching_step_eps") if k in f}
+            if kw:
+                self._rt.set_params(**kw)
+            return self._rt.illumination_at(lat, lon, n_sun=n_sun)
+
     def get_image(self):
         return self._image
 
