@@ -289,6 +289,23 @@ int mrtx_illum_points(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_
  * otherwise the Fibonacci set u2 = (i + 1/2) / n, u3 = frac(i * 0.6180339887498949), float64 rounded once).  No GPU. */
 int mrtx_illum_sun_samples(int32_t n, float* out2);
 
+/* ---- Sun illumination over many dates (additive to ABI 7) ---------------------------------------
+ * An epoch is what mrtx_set_light + mrtx_set_moon_frame would set for one date; the Moon radius and the march parameters
+ * are the context's.  112 bytes. */
+typedef struct MrtxIllumEpoch {
+    double light_pos[3], light_radius, light_radiance;   /* as mrtx_set_light */
+    double center[3], u[3], v[3];                         /* as mrtx_set_moon_frame (without the radius) */
+} MrtxIllumEpoch;
+/* Point p reads the `count` consecutive epochs first[p], ..., first[p] + count - 1 of epochs[0 .. n_epochs) (first = NULL:
+ * every point reads [0, count)); points may repeat.  Output: n_points x count float4 (lit, irr, mu, D), point-major, into
+ * dev_out (a device buffer of the context's device) and / or host_out (at least one of them).  Entry (p, j) equals, bit for
+ * bit, mrtx_illum_points at point p after mrtx_set_light / mrtx_set_moon_frame were given epoch first[p] + j, and the
+ * counters equal the sum of those calls'.  Needs a DEM, but neither mrtx_set_light nor mrtx_set_moon_frame; leaves the
+ * context's light, Moon frame and render state as they were.  At most 2^31 outputs per call.  out may be NULL. */
+int mrtx_illum_series(mrtx_ctx* ctx, const double* latlon_deg, int32_t n_points, const MrtxIllumEpoch* epochs,
+                      int32_t n_epochs, const int32_t* first, int32_t count, int32_t n_sun, void* dev_out, float* host_out,
+                      MrtxStats* out);
+
 /* Math conformance probe (ABI 7): the kernels' domain-restricted reciprocal (v_rcp_f32 + Newton steps) and square root (v_sqrt_f32 + a
  * +-1 ulp residual fix) against the compiler's IEEE expansions of 1.0f / x and sqrtf(x), ON THE DEVICE, for the n float bit patterns
  * from lo_bits on: which = 0 one Newton step, 1 two steps (what the kernels use), 2 the square root.  mismatches = how many differ;

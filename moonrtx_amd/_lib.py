@@ -44,6 +44,13 @@ class MrtxIllumGrid(C.Structure):
                 ("n_sun", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MrtxIllumEpoch(C.Structure):
+    """One date of a Sun-illumination series (mrtx_illum_series): what mrtx_set_light and
+    mrtx_set_moon_frame would set for it."""
+    _fields_ = [("light_pos", C.c_double * 3), ("light_radius", C.c_double), ("light_radiance", C.c_double),
+                ("center", C.c_double * 3), ("u", C.c_double * 3), ("v", C.c_double * 3)]
+
+
 F_COUNT_STATS = 1
 F_FORCE_WIDE = 2
 F_NO_SKIP = 4
@@ -107,6 +114,8 @@ SIGNATURES = {
     "mrtx_illum_grid": (C.c_int, [_VP, C.POINTER(MrtxIllumGrid), _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_illum_points": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.POINTER(MrtxStats)]),
     "mrtx_illum_sun_samples": (C.c_int, [C.c_int32, _VP]),
+    "mrtx_illum_series": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP,
+                                    C.POINTER(MrtxStats)]),
 }
 
 _lib = None

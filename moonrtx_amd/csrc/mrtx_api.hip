@@ -53,6 +53,7 @@ hipError_t mrtx_launch_hmip(const float* mip, int mh, int mw, int shift, float* 
 hipError_t mrtx_launch_probe_stream(const void* src, int64_t n_pairs, float* out, hipStream_t st);
 hipError_t mrtx_launch_probe_cr(uint32_t lo, uint64_t n, int which, unsigned long long* out2, hipStream_t st);
 hipError_t mrtx_launch_illum(const FrameC& f, IllumC g, bool stats, hipStream_t st);
+hipError_t mrtx_launch_illum_series(const FrameC& f, IllumSeriesC q, bool stats, hipStream_t st);
 
 struct mrtx_ctx {
     MrtxConfig cfg{};
@@ -243,6 +244,29 @@ void set_grid(GridC& g, int h, int w) {
     g.wf = (float)w;
 }
 
+// moon frame rows: east-90, lon-0, north.  u = north pole, v = longitude-0 direction
+// (moon_renderer.py:621, :844-845; renderer_navigation.py:47-53)
+static void moon_rows(const double u[3], const double v[3], double M[3][3]) {
+    double ez[3] = {u[0], u[1], u[2]}, v0[3], ex[3];
+    unit3(ez);
+    const double dp = (v[0] * ez[0] + v[1] * ez[1]) + v[2] * ez[2];
+    for (int i = 0; i < 3; i++) v0[i] = v[i] - dp * ez[i];
+    unit3(v0);
+    cross(ez, v0, ex);
+    for (int j = 0; j < 3; j++) { M[0][j] = ex[j]; M[1][j] = v0[j]; M[2][j] = ez[j]; }
+}
+// D5's light constants: the light centre in the moon frame relative to the Moon centre, radius^2 and 2 x radiance.  build_frame
+// and the per-epoch table of mrtx_illum_series both form them here, so that a series epoch and a set_light / set_moon_frame
+// date give the same bits.
+static void light_consts(const double M[3][3], const double center[3], const double pos[3], double radius, double radiance,
+                         float Lb[3], float& rL2, float& rad2) {
+    double lr[3];
+    for (int i = 0; i < 3; i++) lr[i] = pos[i] - center[i];
+    for (int i = 0; i < 3; i++) Lb[i] = (float)((M[i][0] * lr[0] + M[i][1] * lr[1]) + M[i][2] * lr[2]);
+    rL2 = (float)(radius * radius);
+    rad2 = (float)(2.0 * radiance);
+}
+
 // Scene (float64) -> per-launch constants.  DESIGN.md section 3.1 lists every formula; the oracle
 // derives the same block on its own and tests compare the two float for float.
 void build_frame(const mrtx_ctx* c, FrameC& f, FrameCold& k) {
@@ -267,24 +291,12 @@ void build_frame(const mrtx_ctx* c, FrameC& f, FrameCold& k) {
     k.two_over_w = (float)(2.0 / (double)f.W);
     k.two_over_h = (float)(2.0 / (double)f.H);
     k.cq = ((k.oc[0] * k.oc[0] + k.oc[1] * k.oc[1]) + k.oc[2] * k.oc[2]) - c->radius * c->radius;
-    // moon frame rows: east-90, lon-0, north.  u = north pole, v = longitude-0 direction
-    // (moon_renderer.py:621, :844-845; renderer_navigation.py:47-53)
-    double ez[3] = {c->u[0], c->u[1], c->u[2]}, v0[3], ex[3];
-    unit3(ez);
-    const double dp = (c->v[0] * ez[0] + c->v[1] * ez[1]) + c->v[2] * ez[2];
-    for (int i = 0; i < 3; i++) v0[i] = c->v[i] - dp * ez[i];
-    unit3(v0);
-    cross(ez, v0, ex);
-    for (int j = 0; j < 3; j++) { k.M[0][j] = ex[j]; k.M[1][j] = v0[j]; k.M[2][j] = ez[j]; }
+    moon_rows(c->u, c->v, k.M);
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) k.Mf[i][j] = (float)k.M[i][j];
     f.Rf = (float)c->radius;
     f.R2f = f.Rf * f.Rf;
-    double lr[3];
-    for (int i = 0; i < 3; i++) lr[i] = c->light_pos[i] - c->center[i];
-    for (int i = 0; i < 3; i++) k.Lb[i] = (float)((k.M[i][0] * lr[0] + k.M[i][1] * lr[1]) + k.M[i][2] * lr[2]);
-    k.rL2 = (float)(c->light_radius * c->light_radius);
-    k.rad2 = (float)(2.0 * c->light_radiance);
+    light_consts(k.M, c->center, c->light_pos, c->light_radius, c->light_radiance, k.Lb, k.rL2, k.rad2);
     k.sun_on = c->sun_radius > 0.0 ? 1 : 0;
     double sr[3];
     for (int i = 0; i < 3; i++) { sr[i] = c->sun_pos[i] - c->eye[i]; k.sc[i] = (float)sr[i]; }
@@ -1224,12 +1236,14 @@ static void illum_sc(double deg, float* sc) {
 }
 
 // Everything after the argument checks: state, tables, one launch into `dev_out`, counters.  rtab / ctab are host tables of
-// (sin, cos) pairs: n_r and n_c entries.
+// (sin, cos) pairs: n_r and n_c entries.  A series (mrtx_illum_series) passes `lights`, 8 floats per epoch, and `first` (per
+// point, or null): then rows = points, cols = the window's length, and the context's own light and Moon frame are not used.
 static int illum_run(mrtx_ctx* c, const std::vector<float>& rtab, const std::vector<float>& ctab, int rows, int cols, bool points,
-                     int n_sun, void* dev_out, float* host_out, MrtxStats* out) {
+                     int n_sun, void* dev_out, float* host_out, MrtxStats* out, const std::vector<float>* lights = nullptr,
+                     const int32_t* first = nullptr) {
     if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
-    if (!c->moon_set) return fail(c, MRTX_E_STATE, "no moon frame: call mrtx_set_moon_frame first");
-    if (!c->light_set) return fail(c, MRTX_E_STATE, "no light: call mrtx_set_light first");
+    if (!lights && !c->moon_set) return fail(c, MRTX_E_STATE, "no moon frame: call mrtx_set_moon_frame first");
+    if (!lights && !c->light_set) return fail(c, MRTX_E_STATE, "no light: call mrtx_set_light first");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (!(c->prm.flags & MRTX_F_NO_SKIP)) { const int rc_ = ensure_mip(c); if (rc_ != MRTX_OK) return rc_; }
     FrameC f;
@@ -1243,17 +1257,22 @@ static int illum_run(mrtx_ctx* c, const std::vector<float>& rtab, const std::vec
     const bool stats = (c->prm.flags & MRTX_F_COUNT_STATS) != 0;
     if (c->prm.flags & MRTX_F_FORCE_WIDE) f.dem_wide = 1;
     if (c->prm.flags & MRTX_F_NO_SKIP) f.mip = nullptr;   // (build_frame leaves the horizon mip out as well)
-    // one device block: sample table (64 pairs), row table, column table
-    const size_t tab_bytes = (128 + rtab.size() + ctab.size()) * sizeof(float);
+    // one device block: sample table (64 pairs), row table, column table[, epoch lights (16-byte aligned: the tables above hold
+    // 4 floats per point), first epochs]
+    const size_t n_lights = lights ? lights->size() : 0, n_first = first ? (size_t)rows : 0;
+    const size_t tab_bytes = (128 + rtab.size() + ctab.size() + n_lights + n_first) * sizeof(float);
     if (tab_bytes > c->illum_tab_bytes) {
         if (c->illum_tab) { HIPCHK(c, hipFree(c->illum_tab)); c->illum_tab = nullptr; c->illum_tab_bytes = 0; }
         HIPCHK(c, hipMalloc((void**)&c->illum_tab, tab_bytes));
         c->illum_tab_bytes = tab_bytes;
     }
-    std::vector<float> host((size_t)128 + rtab.size() + ctab.size(), 0.0f);
+    std::vector<float> host((size_t)128 + rtab.size() + ctab.size() + n_lights + n_first, 0.0f);
     mrtx_illum_sun_samples(n_sun, host.data());
     std::copy(rtab.begin(), rtab.end(), host.begin() + 128);
     std::copy(ctab.begin(), ctab.end(), host.begin() + 128 + (ptrdiff_t)rtab.size());
+    const size_t lights_at = 128 + rtab.size() + ctab.size(), first_at = lights_at + n_lights;
+    if (lights) std::copy(lights->begin(), lights->end(), host.begin() + (ptrdiff_t)lights_at);
+    if (first) std::memcpy(host.data() + first_at, first, n_first * sizeof(int32_t));
     const size_t out_bytes = (size_t)rows * (size_t)cols * 16;
     if (!dev_out) {
         if (out_bytes > c->illum_out_bytes) {
@@ -1271,7 +1290,15 @@ static int illum_run(mrtx_ctx* c, const std::vector<float>& rtab, const std::vec
     g.sun = c->illum_tab; g.rtab = c->illum_tab + 128; g.ctab = g.rtab + rtab.size();
     g.out = (float*)dev_out; g.rows = rows; g.cols = cols; g.points = points ? 1 : 0; g.n_sun = n_sun;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    HIPCHK(c, mrtx_launch_illum(f, g, stats, c->stream));
+    if (lights) {
+        IllumSeriesC q;
+        q.g = g;
+        q.lights = c->illum_tab + lights_at;
+        q.first = first ? reinterpret_cast<const int32_t*>(c->illum_tab + first_at) : nullptr;
+        HIPCHK(c, mrtx_launch_illum_series(f, q, stats, c->stream));
+    } else {
+        HIPCHK(c, mrtx_launch_illum(f, g, stats, c->stream));
+    }
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));     // also: the pageable tables above are no longer read
     float ms = 0.0f;
@@ -1328,6 +1355,49 @@ int mrtx_illum_points(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_su
         illum_sc(lo, &ctab[(size_t)i * 2]);
     }
     return illum_run(c, rtab, ctab, 1, n, true, n_sun, nullptr, host_out4, out);
+}
+
+int mrtx_illum_series(mrtx_ctx* c, const double* latlon, int32_t n_points, const MrtxIllumEpoch* ep, int32_t n_epochs,
+                      const int32_t* first, int32_t count, int32_t n_sun, void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!latlon || !ep) return fail(c, MRTX_E_INVALID, "null point list or epoch table");
+    if (!dev_out && !host_out) return fail(c, MRTX_E_INVALID, "no output buffer");
+    if (n_points < 1 || n_epochs < 1 || count < 1)
+        return fail(c, MRTX_E_INVALID, "n_points, n_epochs and count must be >= 1 (got %d, %d, %d)", n_points, n_epochs, count);
+    if (!illum_n_ok(n_sun)) return fail(c, MRTX_E_INVALID, "n_sun must be 1, 2, 4, ..., 64 (got %d)", n_sun);
+    if ((int64_t)n_points * (int64_t)count > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "a series holds at most 2^31 outputs: split the points into more calls");
+    for (int32_t p = 0; p < n_points; p++) {
+        const int64_t f0 = first ? (int64_t)first[p] : 0;
+        if (f0 < 0 || f0 + count > n_epochs)
+            return fail(c, MRTX_E_INVALID, "point %d: window [%lld, %lld) runs outside the %d epochs", p, (long long)f0,
+                        (long long)(f0 + count), n_epochs);
+    }
+    std::vector<float> rtab((size_t)n_points * 2), ctab((size_t)n_points * 2);
+    for (int32_t i = 0; i < n_points; i++) {
+        const double la = latlon[2 * (size_t)i], lo = latlon[2 * (size_t)i + 1];
+        if (!std::isfinite(la) || !std::isfinite(lo) || la > 90.0 || la < -90.0 || std::fabs(lo) > 1e6)
+            return fail(c, MRTX_E_INVALID, "point %d: latitude must lie in [-90, 90] and longitude be finite", i);
+        illum_sc(la, &rtab[(size_t)i * 2]);
+        illum_sc(lo, &ctab[(size_t)i * 2]);
+    }
+    // per epoch what build_frame forms from mrtx_set_light + mrtx_set_moon_frame, after the checks those two make
+    std::vector<float> lights((size_t)n_epochs * 8, 0.0f);
+    for (int32_t k = 0; k < n_epochs; k++) {
+        const MrtxIllumEpoch& e = ep[k];
+        if (!check_vec(e.light_pos) || !std::isfinite(e.light_radius) || !std::isfinite(e.light_radiance) ||
+            !(e.light_radius >= 0.0) || !(e.light_radiance >= 0.0))
+            return fail(c, MRTX_E_INVALID, "epoch %d: bad light", k);
+        if (!check_vec(e.center) || !check_vec(e.u) || !check_vec(e.v)) return fail(c, MRTX_E_INVALID, "epoch %d: bad moon frame", k);
+        double x[3];
+        cross(e.u, e.v, x);
+        if (!((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2] > 0.0)) return fail(c, MRTX_E_INVALID, "epoch %d: moon u and v are parallel", k);
+        double M[3][3];
+        moon_rows(e.u, e.v, M);
+        float* l = &lights[(size_t)k * 8];
+        light_consts(M, e.center, e.light_pos, e.light_radius, e.light_radiance, l, l[3], l[4]);
+    }
+    return illum_run(c, rtab, ctab, n_points, count, true, n_sun, dev_out, host_out, out, &lights, first);
 }
 
 int mrtx_samples_done(mrtx_ctx* c, uint32_t* out) {

@@ -185,3 +185,11 @@ struct IllumC {
     int32_t pw_log2;        // a wave's node block is (1 << pw_log2) columns wide (set by the launcher)
     int32_t waves_x;        // node blocks per row of blocks (set by the launcher)
 };
+
+// Sun illumination over many dates (mrtx_illum_series): a point list (g.points = 1, g.rows = points,
+// g.cols = the window's length) and a table of per-epoch light constants, two float4 per epoch: (Lb.xyz, rL2), (rad2, 0, 0, 0).
+struct IllumSeriesC {
+    IllumC g;
+    const float* lights;    // 8 floats per epoch, 16-byte aligned
+    const int32_t* first;   // per point: its window's first epoch; null: every window starts at epoch 0
+};

@@ -967,18 +967,34 @@ __device__ __forceinline__ void hit_vertex(const FrameC& f, float ha, float hb, 
     }
 }
 
+// D5's light constants (Lb, rL2, rad2) as light_sample and illum_mu read them: the frame's cold block (every render kernel,
+// illum_kernel: scalar loads where the code uses them), or one epoch's, held in registers (illum_series_kernel)
+struct FrameLight {
+    const FrameC& f;
+    __device__ __forceinline__ float Lb(int i) const { return CF(f)->Lb[i]; }
+    __device__ __forceinline__ float rL2() const { return CF(f)->rL2; }
+    __device__ __forceinline__ float rad2() const { return CF(f)->rad2; }
+};
+struct EpochLight {
+    float lb[3], rl2, r2;
+    __device__ __forceinline__ float Lb(int i) const { return lb[i]; }
+    __device__ __forceinline__ float rL2() const { return rl2; }
+    __device__ __forceinline__ float rad2() const { return r2; }
+};
+
 // D5: one sample of the spherical light from a vertex: the shadow ray (origin lifted by scene_epsilon, direction
 // uniform in the cone the light subtends) and what it carries if it arrives, radiance * solid angle / pi * cos(theta_i);
 // false when the sampled direction lies below the surface (no shadow ray, no contribution).
-__device__ __forceinline__ bool light_sample(const FrameC& f, const Vertex& v, float u2, float u3, float& oa, float& ob,
-                                             float& oc, float& wa, float& wb, float& wc, float& carried) {
+template <class L>
+__device__ __forceinline__ bool light_sample(const FrameC& f, const L& lt, const Vertex& v, float u2, float u3, float& oa,
+                                             float& ob, float& oc, float& wa, float& wb, float& wc, float& carried) {
     const float eps = CF(f)->scene_eps;
     oa = fmaf(eps, v.na, v.pa); ob = fmaf(eps, v.nb, v.pb); oc = fmaf(eps, v.nc, v.pc);
-    const float ta = CF(f)->Lb[0] - oa, tb = CF(f)->Lb[1] - ob, tc = CF(f)->Lb[2] - oc;
+    const float ta = lt.Lb(0) - oa, tb = lt.Lb(1) - ob, tc = lt.Lb(2) - oc;
     const float d2 = fmaf(tc, tc, fmaf(tb, tb, ta * ta));
     const float inv_dist = rcp_cr(sqrt_sh(d2));   // distance to the light: ~2e4 R
     const float la = ta * inv_dist, lb = tb * inv_dist, lc = tc * inv_dist;
-    float sin2 = CF(f)->rL2 * (inv_dist * inv_dist);
+    float sin2 = lt.rL2() * (inv_dist * inv_dist);
     if (sin2 > 1.0f) sin2 = 1.0f;
     const float cosmax = sqrt_sh(1.0f - sin2);     // 0 or >= 2^-24
     const float omc = sin2 / (1.0f + cosmax);
@@ -994,8 +1010,13 @@ __device__ __forceinline__ bool light_sample(const FrameC& f, const Vertex& v, f
     wb = fmaf(cost, lb, fmaf(sa, b2b, ca * b1b));
     wc = fmaf(cost, lc, fmaf(sa, b2c, ca * b1c));
     const float cosi = fmaf(v.nc, wc, fmaf(v.nb, wb, v.na * wa));
-    carried = (CF(f)->rad2 * omc) * cosi;
+    carried = (lt.rad2() * omc) * cosi;
     return cosi > 0.0f;
+}
+// the frame's light (every caller but illum_series_kernel)
+__device__ __forceinline__ bool light_sample(const FrameC& f, const Vertex& v, float u2, float u3, float& oa, float& ob,
+                                             float& oc, float& wa, float& wb, float& wc, float& carried) {
+    return light_sample(f, FrameLight{f}, v, u2, u3, oa, ob, oc, wa, wb, wc, carried);
 }
 
 // the light sample with its shadow ray marched through the same height field: carried radiance * visibility
@@ -1989,18 +2010,20 @@ __device__ __forceinline__ float illum_vertex(const FrameC& f, const IllumC& g, 
     return D;
 }
 // mu = n . l toward the light centre, l formed as light_sample forms it from the lifted origin
-__device__ __forceinline__ float illum_mu(const FrameC& f, const Vertex& v) {
+template <class L>
+__device__ __forceinline__ float illum_mu(const FrameC& f, const L& lt, const Vertex& v) {
     const float eps = CF(f)->scene_eps;
     const float oa = fmaf(eps, v.na, v.pa), ob = fmaf(eps, v.nb, v.pb), oc = fmaf(eps, v.nc, v.pc);
-    const float ta = CF(f)->Lb[0] - oa, tb = CF(f)->Lb[1] - ob, tc = CF(f)->Lb[2] - oc;
+    const float ta = lt.Lb(0) - oa, tb = lt.Lb(1) - ob, tc = lt.Lb(2) - oc;
     const float inv_dist = rcp_cr(sqrt_sh(fmaf(tc, tc, fmaf(tb, tb, ta * ta))));
     return fmaf(v.nc, tc * inv_dist, fmaf(v.nb, tb * inv_dist, v.na * (ta * inv_dist)));
 }
 // one light sample: true if it arrives (cos > 0 and the shadow ray escapes); `carried` = what it carries then
-template <bool STATS, bool WIDE>
-__device__ __forceinline__ bool illum_sample(const FrameC& f, const Vertex& v, float u2, float u3, float& carried, uint32_t* cnt) {
+template <bool STATS, bool WIDE, class L>
+__device__ __forceinline__ bool illum_sample(const FrameC& f, const L& lt, const Vertex& v, float u2, float u3, float& carried,
+                                             uint32_t* cnt) {
     float oa, ob, oc, wa, wb, wc;
-    if (!light_sample(f, v, u2, u3, oa, ob, oc, wa, wb, wc, carried)) return false;
+    if (!light_sample(f, lt, v, u2, u3, oa, ob, oc, wa, wb, wc, carried)) return false;
     if (STATS) cnt[ST_SHADOW]++;
     Seg ssg;
     float sk_occ;
@@ -2032,19 +2055,19 @@ __global__ void __launch_bounds__(64) illum_kernel(const FrameC f, const IllumC 
     if (in) {
         Vertex v;
         D = illum_vertex<STATS, WIDE>(f, g, row, col, v, cnt);
-        mu = illum_mu(f, v);
+        mu = illum_mu(f, FrameLight{f}, v);
         const float2* sun = reinterpret_cast<const float2*>(g.sun);
 #if MRTX_ILLUM_MAP == 0
         const float2 us = sun[s];
         float carried;
-        if (illum_sample<STATS, WIDE>(f, v, us.x, us.y, carried, cnt)) { lit = 1.0f; irr = carried; }
+        if (illum_sample<STATS, WIDE>(f, FrameLight{f}, v, us.x, us.y, carried, cnt)) { lit = 1.0f; irr = carried; }
 #else
         // the n samples in turn; their sum in tree_sum's pairwise order: part[t] holds the pending sum of 2^t samples
         float part[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         for (int i = 0; i < n; i++) {
             const float2 us = sun[i];
             float carried, x = 0.0f;
-            if (illum_sample<STATS, WIDE>(f, v, us.x, us.y, carried, cnt)) { lit += 1.0f; x = carried; }
+            if (illum_sample<STATS, WIDE>(f, FrameLight{f}, v, us.x, us.y, carried, cnt)) { lit += 1.0f; x = carried; }
             if (STATS && i > 0) { cnt[ST_HEIGHT] += 5; cnt[ST_FETCH] += 5; }   // the spec counts the vertex per sample
             bool pending = true;
 #pragma unroll
@@ -2067,6 +2090,58 @@ __global__ void __launch_bounds__(64) illum_kernel(const FrameC f, const IllumC 
     const float inv_n = 1.0f / (float)n;   // a power of two: the scalings below are exact
     if (in && s == 0)
         reinterpret_cast<float4*>(g.out)[(int64_t)row * g.cols + col] = make_float4(lit * inv_n, irr * inv_n, mu, D);
+    if (STATS) {
+        const int which[4] = {ST_SHADOW, ST_HEIGHT, ST_FETCH, ST_MIP};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            uint32_t c = cnt[which[i]];
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) c += __shfl_xor(c, m, 64);
+            if (lane == 0) atomicAdd(&CF(f)->stats[which[i]], (unsigned long long)c);
+        }
+    }
+}
+
+// Sun illumination over many dates (DESIGN.md sections 3.7 and 4.9): entry (point, j) of a series is illum_kernel's output at
+// the point under epoch first[point] + j, whose light constants come from a table instead of the cold block.  One wave = 64/n
+// (point, epoch) pairs x n samples in adjacent lanes, laid out as illum_kernel's node block with points as rows and the
+// epochs of a window as columns: 64/n consecutive epochs of one point (the Sun moves ~0.085 deg in 10 minutes, a third of
+// its radius: the lanes march from one origin in nearly one direction), or several points when the window is shorter.
+template <bool STATS, bool WIDE>
+__global__ void __launch_bounds__(64) illum_series_kernel(const FrameC f, const IllumSeriesC q) {
+    const IllumC& g = q.g;
+    const int lane = threadIdx.x;
+    const int n = g.n_sun;
+    const int s = lane & (n - 1), p = lane >> g.n_log2;
+    const int pw = 1 << g.pw_log2;
+    const int wx = (int)(blockIdx.x % (unsigned)g.waves_x), wy = (int)(blockIdx.x / (unsigned)g.waves_x);
+    const int j = wx * pw + (p & (pw - 1));                                         // epoch within the window
+    const int pt = wy * ((64 >> g.n_log2) >> g.pw_log2) + (p >> g.pw_log2);         // point
+    const bool in = pt < g.rows && j < g.cols;
+    uint32_t cnt_store[STATS ? ST_N : 1];
+    uint32_t* const cnt = STATS ? cnt_store : nullptr;
+    if (STATS) {
+#pragma unroll
+        for (int i = 0; i < ST_N; i++) cnt[i] = 0;
+    }
+    float lit = 0.0f, irr = 0.0f, mu = 0.0f, D = 0.0f;
+    if (in) {
+        const int64_t k = (int64_t)(q.first ? q.first[pt] : 0) + j;
+        const float4 l0 = reinterpret_cast<const float4*>(q.lights)[2 * k];
+        const float4 l1 = reinterpret_cast<const float4*>(q.lights)[2 * k + 1];
+        const EpochLight lt{{l0.x, l0.y, l0.z}, l0.w, l1.x};
+        Vertex v;
+        D = illum_vertex<STATS, WIDE>(f, g, pt, pt, v, cnt);      // g.points = 1: both tables indexed by the point
+        mu = illum_mu(f, lt, v);
+        const float2 us = reinterpret_cast<const float2*>(g.sun)[s];
+        float carried;
+        if (illum_sample<STATS, WIDE>(f, lt, v, us.x, us.y, carried, cnt)) { lit = 1.0f; irr = carried; }
+    }
+    lit = group_sum(lit, n);    // a count: exact
+    irr = group_sum(irr, n);
+    const float inv_n = 1.0f / (float)n;   // a power of two: the scalings below are exact
+    if (in && s == 0)
+        reinterpret_cast<float4*>(g.out)[(int64_t)pt * g.cols + j] = make_float4(lit * inv_n, irr * inv_n, mu, D);
     if (STATS) {
         const int which[4] = {ST_SHADOW, ST_HEIGHT, ST_FETCH, ST_MIP};
 #pragma unroll
@@ -3369,6 +3444,33 @@ hipError_t mrtx_launch_illum(const FrameC& f, IllumC g, bool stats, hipStream_t 
                  else hipLaunchKernelGGL((mrtx::illum_kernel<true, false>), grid, block, 0, st, f, g); }
     else { if (wide) hipLaunchKernelGGL((mrtx::illum_kernel<false, true>), grid, block, 0, st, f, g);
            else hipLaunchKernelGGL((mrtx::illum_kernel<false, false>), grid, block, 0, st, f, g); }
+    return hipGetLastError();
+}
+
+// The series (illum_series_kernel): the node block of mrtx_launch_illum with points as rows and a window's epochs as columns,
+// PW = 64 / n_sun epochs wide, narrowed to the window (the least power of two >= count) so that a wave holds several points
+// when the window is short.  g.rows points x g.cols epochs; g.n_log2, g.pw_log2 and g.waves_x are set here.
+hipError_t mrtx_launch_illum_series(const FrameC& f, IllumSeriesC q, bool stats, hipStream_t st) {
+    IllumC& g = q.g;
+    if (g.n_sun < 1 || g.n_sun > 64 || (g.n_sun & (g.n_sun - 1)) || g.rows < 1 || g.cols < 1 || !g.points || !q.lights)
+        return hipErrorInvalidValue;
+    g.n_log2 = 0;
+    while ((1 << g.n_log2) < g.n_sun) g.n_log2++;
+    const int P = 64 >> g.n_log2;
+    int PW = P;
+    while (PW > 1 && PW / 2 >= g.cols) PW /= 2;
+    g.pw_log2 = 0;
+    while ((1 << g.pw_log2) < PW) g.pw_log2++;
+    const int PH = P / PW;
+    g.waves_x = (g.cols + PW - 1) / PW;
+    const uint64_t waves = (uint64_t)g.waves_x * (uint64_t)((g.rows + PH - 1) / PH);
+    if (waves > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)waves), block(64);
+    const bool wide = f.dem_wide != 0;
+    if (stats) { if (wide) hipLaunchKernelGGL((mrtx::illum_series_kernel<true, true>), grid, block, 0, st, f, q);
+                 else hipLaunchKernelGGL((mrtx::illum_series_kernel<true, false>), grid, block, 0, st, f, q); }
+    else { if (wide) hipLaunchKernelGGL((mrtx::illum_series_kernel<false, true>), grid, block, 0, st, f, q);
+           else hipLaunchKernelGGL((mrtx::illum_series_kernel<false, false>), grid, block, 0, st, f, q); }
     return hipGetLastError();
 }
 

@@ -487,3 +487,17 @@ def scene_from_ephemeris(eph, width, height, **kw):
     s.rotation = np.asarray(eph.rotation_matrix, float)
     s.u, s.v = moon_axes(s.rotation)
     return s
+
+
+def epoch_of_scene(s):
+    """SceneDesc -> one row of a Sun-illumination series (MrtxIllumEpoch): light_pos[3], light_radius,
+    light_radiance, center[3], u[3], v[3] -- what MoonRT.set_light and MoonRT.set_moon_frame push for it."""
+    return np.concatenate([np.asarray(s.light_pos, float).ravel(), [float(s.light_radius), float(s.light_radiance)],
+                           np.asarray(s.center, float).ravel(), np.asarray(s.u, float).ravel(), np.asarray(s.v, float).ravel()])
+
+
+def sun_epochs(times, observer=None):
+    """(m, 14) float64 epochs for MoonRT.illumination_series, one row per timezone-aware datetime: the light and Moon frame
+    of calculate_moon_ephemeris -> scene_from_ephemeris, the values tools/illumination_map.py sets per date."""
+    rows = [epoch_of_scene(scene_from_ephemeris(calculate_moon_ephemeris(t, False, observer), 16, 16)) for t in times]
+    return np.array(rows, np.float64).reshape(-1, 14)

@@ -299,6 +299,43 @@ class MoonRT:
         self._add_stats(stats, st)
         return out
 
+    def illumination_series(self, lat_deg, lon_deg, epochs, n_sun=16, first=None, count=None, stats=None, chunk_bytes=256 << 20):
+        """(N, count, 4) float32 (lit, irr, mu, D) at N points over many dates: entry (p, j) is what
+        illumination_at gives at point p after the light and Moon frame of epoch first[p] + j were set, bit for bit.
+        `epochs`: the (m, 14) float64 array of ephemeris.sun_epochs, or a sequence of SceneDesc.  first = None: every point
+        reads epochs [0, count) (count defaults to m); otherwise N window starts and count is required.  Calls hold at most
+        chunk_bytes of output each (points split between calls); `stats`, if a dict, receives the summed counters."""
+        from .ephemeris import epoch_of_scene
+        la = np.atleast_1d(np.asarray(lat_deg, np.float64)).ravel()
+        lo = np.atleast_1d(np.asarray(lon_deg, np.float64)).ravel()
+        if la.shape != lo.shape:
+            raise ValueError("lat_deg and lon_deg must have the same number of points")
+        if not isinstance(epochs, np.ndarray):
+            epochs = np.array([epoch_of_scene(e) for e in epochs], np.float64).reshape(-1, 14)
+        ep = np.ascontiguousarray(epochs, np.float64)
+        if ep.ndim != 2 or ep.shape[1] != 14:
+            raise ValueError("epochs must be an (m, 14) array (ephemeris.sun_epochs) or a sequence of SceneDesc")
+        if first is None:
+            count = ep.shape[0] if count is None else int(count)
+        else:
+            if count is None:
+                raise ValueError("count is required with first")
+            first = np.ascontiguousarray(np.atleast_1d(np.asarray(first)).ravel(), np.int32)
+            if first.shape != la.shape:
+                raise ValueError("first must hold one window start per point")
+            count = int(count)
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        out = np.empty((la.size, max(count, 0), 4), np.float32)
+        step = max(1, min(int(chunk_bytes) // (16 * max(count, 1)), (1 << 31) // max(count, 1)))
+        for a in range(0, la.size, step):
+            b = min(a + step, la.size)
+            st = MrtxStats()
+            fp = None if first is None else first[a:].ctypes.data
+            self._check(self._lib.mrtx_illum_series(self._ctx, pts[a:].ctypes.data, b - a, ep.ctypes.data, ep.shape[0], fp, count,
+                                                    int(n_sun), None, out[a:].ctypes.data, C.byref(st)), "mrtx_illum_series")
+            self._add_stats(stats, st)
+        return out
+
     @staticmethod
     def _add_stats(acc, st):
         if isinstance(acc, dict):
