@@ -306,6 +306,25 @@ int mrtx_illum_series(mrtx_ctx* ctx, const double* latlon_deg, int32_t n_points,
                       int32_t n_epochs, const int32_t* first, int32_t count, int32_t n_sun, void* dev_out, float* host_out,
                       MrtxStats* out);
 
+/* ---- Terrain horizons (additive to ABI 7) --------------------------------------------------------
+ * Per point and azimuth a = 0 .. n_az-1 (a / n_az of a turn from north through east) the elevation, degrees, found by n_bis
+ * bisection probes over [-90, +90]; each probe is an illumination sample's visibility decision from the point's lifted origin
+ * (the vertex of mrtx_illum_points).  n_az a power of two in [4, 4096], n_bis in [1, 24].  Output: n x n_az float32,
+ * point-major, into exactly one of dev_out (a device buffer of the context's device) and host_out.  Needs a DEM, but neither
+ * mrtx_set_light nor mrtx_set_moon_frame; leaves the light, Moon frame and render state as they were.  At most 2^31 outputs
+ * per call.  out may be NULL. */
+int mrtx_horizon_points(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t n_az, int32_t n_bis, void* dev_out,
+                        float* host_out, MrtxStats* out);
+/* The Sun against those horizons: per (point, epoch) the fraction f of the light's disc above the
+ * horizon, interpolated at the light's azimuth.  The horizons (n x n_az float32, as mrtx_horizon_points writes them) come
+ * from exactly one of dev_horizon and host_horizon; the epochs are mrtx_illum_series's.  mode 0 (FULL): n x m float32 f,
+ * point-major; mode 1 (SUMMARY): n float4 (mean f, share of epochs with f > 0, share with f == 1, longest run of consecutive
+ * epochs with f == 0, in epochs).  Output into exactly one of dev_out and host_out.  m <= 2^24 (the run is a float count,
+ * exact to there); FULL: at most 2^31 outputs per call. */
+int mrtx_horizon_sun(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t n_az, const void* dev_horizon,
+                     const float* host_horizon, const MrtxIllumEpoch* epochs, int32_t m, int32_t mode, void* dev_out,
+                     float* host_out, MrtxStats* out);
+
 /* Math conformance probe (ABI 7): the kernels' domain-restricted reciprocal (v_rcp_f32 + Newton steps) and square root (v_sqrt_f32 + a
  * +-1 ulp residual fix) against the compiler's IEEE expansions of 1.0f / x and sqrtf(x), ON THE DEVICE, for the n float bit patterns
  * from lo_bits on: which = 0 one Newton step, 1 two steps (what the kernels use), 2 the square root.  mismatches = how many differ;

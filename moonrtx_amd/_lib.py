@@ -116,6 +116,9 @@ SIGNATURES = {
     "mrtx_illum_sun_samples": (C.c_int, [C.c_int32, _VP]),
     "mrtx_illum_series": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP,
                                     C.POINTER(MrtxStats)]),
+    "mrtx_horizon_points": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_horizon_sun": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP,
+                                   C.POINTER(MrtxStats)]),
 }
 
 _lib = None

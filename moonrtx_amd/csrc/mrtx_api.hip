@@ -54,6 +54,8 @@ hipError_t mrtx_launch_probe_stream(const void* src, int64_t n_pairs, float* out
 hipError_t mrtx_launch_probe_cr(uint32_t lo, uint64_t n, int which, unsigned long long* out2, hipStream_t st);
 hipError_t mrtx_launch_illum(const FrameC& f, IllumC g, bool stats, hipStream_t st);
 hipError_t mrtx_launch_illum_series(const FrameC& f, IllumSeriesC q, bool stats, hipStream_t st);
+hipError_t mrtx_launch_horizon(const FrameC& f, HorizonC h, bool stats, hipStream_t st);
+hipError_t mrtx_launch_horizon_sun(const FrameC& f, HorizonSunC q, hipStream_t st);
 
 struct mrtx_ctx {
     MrtxConfig cfg{};
@@ -1357,6 +1359,27 @@ int mrtx_illum_points(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_su
     return illum_run(c, rtab, ctab, 1, n, true, n_sun, nullptr, host_out4, out);
 }
 
+// per epoch what build_frame forms from mrtx_set_light + mrtx_set_moon_frame, after the checks those two make: 8 floats per
+// epoch, (Lb.xyz, rL2), (rad2, 0, 0, 0)
+static int epoch_lights(mrtx_ctx* c, const MrtxIllumEpoch* ep, int32_t n_epochs, std::vector<float>& lights) {
+    lights.assign((size_t)n_epochs * 8, 0.0f);
+    for (int32_t k = 0; k < n_epochs; k++) {
+        const MrtxIllumEpoch& e = ep[k];
+        if (!check_vec(e.light_pos) || !std::isfinite(e.light_radius) || !std::isfinite(e.light_radiance) ||
+            !(e.light_radius >= 0.0) || !(e.light_radiance >= 0.0))
+            return fail(c, MRTX_E_INVALID, "epoch %d: bad light", k);
+        if (!check_vec(e.center) || !check_vec(e.u) || !check_vec(e.v)) return fail(c, MRTX_E_INVALID, "epoch %d: bad moon frame", k);
+        double x[3];
+        cross(e.u, e.v, x);
+        if (!((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2] > 0.0)) return fail(c, MRTX_E_INVALID, "epoch %d: moon u and v are parallel", k);
+        double M[3][3];
+        moon_rows(e.u, e.v, M);
+        float* l = &lights[(size_t)k * 8];
+        light_consts(M, e.center, e.light_pos, e.light_radius, e.light_radiance, l, l[3], l[4]);
+    }
+    return MRTX_OK;
+}
+
 int mrtx_illum_series(mrtx_ctx* c, const double* latlon, int32_t n_points, const MrtxIllumEpoch* ep, int32_t n_epochs,
                       const int32_t* first, int32_t count, int32_t n_sun, void* dev_out, float* host_out, MrtxStats* out) {
     if (!c) return MRTX_E_INVALID;
@@ -1381,23 +1404,166 @@ int mrtx_illum_series(mrtx_ctx* c, const double* latlon, int32_t n_points, const
         illum_sc(la, &rtab[(size_t)i * 2]);
         illum_sc(lo, &ctab[(size_t)i * 2]);
     }
-    // per epoch what build_frame forms from mrtx_set_light + mrtx_set_moon_frame, after the checks those two make
-    std::vector<float> lights((size_t)n_epochs * 8, 0.0f);
-    for (int32_t k = 0; k < n_epochs; k++) {
-        const MrtxIllumEpoch& e = ep[k];
-        if (!check_vec(e.light_pos) || !std::isfinite(e.light_radius) || !std::isfinite(e.light_radiance) ||
-            !(e.light_radius >= 0.0) || !(e.light_radiance >= 0.0))
-            return fail(c, MRTX_E_INVALID, "epoch %d: bad light", k);
-        if (!check_vec(e.center) || !check_vec(e.u) || !check_vec(e.v)) return fail(c, MRTX_E_INVALID, "epoch %d: bad moon frame", k);
-        double x[3];
-        cross(e.u, e.v, x);
-        if (!((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2] > 0.0)) return fail(c, MRTX_E_INVALID, "epoch %d: moon u and v are parallel", k);
-        double M[3][3];
-        moon_rows(e.u, e.v, M);
-        float* l = &lights[(size_t)k * 8];
-        light_consts(M, e.center, e.light_pos, e.light_radius, e.light_radiance, l, l[3], l[4]);
-    }
+    std::vector<float> lights;
+    const int rc = epoch_lights(c, ep, n_epochs, lights);
+    if (rc != MRTX_OK) return rc;
     return illum_run(c, rtab, ctab, n_points, count, true, n_sun, dev_out, host_out, out, &lights, first);
+}
+
+// ---- Terrain horizons and the Sun against them (DESIGN.md sections 3.8 and 3.9) --------------------------------------------
+static bool horizon_az_ok(int32_t n_az) { return n_az >= 4 && n_az <= 4096 && (n_az & (n_az - 1)) == 0; }
+static int log2_of(int32_t n) { int l = 0; while ((1 << l) < n) l++; return l; }
+
+// the point list as the illumination stage's tables: n (sin lat, cos lat) pairs, then n (sin lon, cos lon) pairs
+static int point_tables(mrtx_ctx* c, const double* latlon, int32_t n, std::vector<float>& tab) {
+    tab.assign((size_t)n * 4, 0.0f);
+    for (int32_t i = 0; i < n; i++) {
+        const double la = latlon[2 * (size_t)i], lo = latlon[2 * (size_t)i + 1];
+        if (!std::isfinite(la) || !std::isfinite(lo) || la > 90.0 || la < -90.0 || std::fabs(lo) > 1e6)
+            return fail(c, MRTX_E_INVALID, "point %d: latitude must lie in [-90, 90] and longitude be finite", i);
+        illum_sc(la, &tab[(size_t)i * 2]);
+        illum_sc(lo, &tab[((size_t)n + i) * 2]);
+    }
+    return MRTX_OK;
+}
+
+// grow one of the stage's device buffers to at least `bytes`
+static int stage_buffer(mrtx_ctx* c, float*& p, size_t& cap, size_t bytes) {
+    if (bytes > cap) {
+        if (p) { HIPCHK(c, hipFree(p)); p = nullptr; cap = 0; }
+        HIPCHK(c, hipMalloc((void**)&p, bytes));
+        cap = bytes;
+    }
+    return MRTX_OK;
+}
+
+// the frame of a horizon launch: the context's DEM and march parameters, the illumination stage's own cold block and counters
+// (the context's light and Moon frame are not read).  Called after every argument check.
+static int horizon_frame(mrtx_ctx* c, FrameC& f, FrameCold& cold, bool march) {
+    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (march && !(c->prm.flags & MRTX_F_NO_SKIP)) { const int rc_ = ensure_mip(c); if (rc_ != MRTX_OK) return rc_; }
+    std::memset(&cold, 0, sizeof cold);
+    build_frame(c, f, cold);
+    if (!c->illum_cold) HIPCHK(c, hipMalloc((void**)&c->illum_cold, sizeof(FrameCold)));
+    if (!c->illum_stats) HIPCHK(c, hipMalloc((void**)&c->illum_stats, 16 * sizeof(unsigned long long)));
+    cold.accum = nullptr; cold.hits = nullptr; cold.stats = c->illum_stats; cold.stats_paths = nullptr;
+    f.cold = c->illum_cold;
+    if (c->prm.flags & MRTX_F_FORCE_WIDE) f.dem_wide = 1;
+    if (c->prm.flags & MRTX_F_NO_SKIP) f.mip = nullptr;
+    return MRTX_OK;
+}
+
+// after the launch (between c->ev0 and c->ev1): wait, time, read back, counters
+static int horizon_finish(mrtx_ctx* c, bool stats, const void* dev_out, float* host_out, size_t out_bytes, MrtxStats* out) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // also: the pageable tables are no longer read
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (host_out) HIPCHK(c, hipMemcpy(host_out, dev_out, out_bytes, hipMemcpyDeviceToHost));
+    if (out) {
+        std::memset(out, 0, sizeof *out);
+        out->kernel_ms = ms;
+        out->launches = 1;
+        if (stats) {
+            unsigned long long h[16];
+            HIPCHK(c, hipMemcpy(h, c->illum_stats, sizeof h, hipMemcpyDeviceToHost));
+            out->shadow_rays = h[2]; out->height_samples = h[3]; out->dem_fetches = h[6]; out->mip_fetches = h[7];
+        }
+    }
+    return MRTX_OK;
+}
+
+int mrtx_horizon_points(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, int32_t n_bis, void* dev_out, float* host_out,
+                        MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!latlon) return fail(c, MRTX_E_INVALID, "null point list");
+    if (n < 1) return fail(c, MRTX_E_INVALID, "n must be >= 1 (got %d)", n);
+    if (!horizon_az_ok(n_az)) return fail(c, MRTX_E_INVALID, "n_az must be 4, 8, ..., 4096 (got %d)", n_az);
+    if (n_bis < 1 || n_bis > 24) return fail(c, MRTX_E_INVALID, "n_bis must lie in [1, 24] (got %d)", n_bis);
+    if ((int64_t)n * (int64_t)n_az > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "a call holds at most 2^31 outputs: split the points into more calls");
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    std::vector<float> tab;
+    int rc = point_tables(c, latlon, n, tab);
+    if (rc != MRTX_OK) return rc;
+    FrameC f;
+    FrameCold cold;
+    if ((rc = horizon_frame(c, f, cold, true)) != MRTX_OK) return rc;
+    const bool stats = (c->prm.flags & MRTX_F_COUNT_STATS) != 0;
+    const size_t tab_bytes = tab.size() * sizeof(float), out_bytes = (size_t)n * (size_t)n_az * sizeof(float);
+    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, tab_bytes)) != MRTX_OK) return rc;
+    if (!dev_out) {
+        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, out_bytes)) != MRTX_OK) return rc;
+        dev_out = c->illum_out;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->illum_cold, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->illum_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+    if (stats) HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
+    HorizonC h;
+    std::memset(&h, 0, sizeof h);
+    h.g.rtab = c->illum_tab; h.g.ctab = c->illum_tab + 2 * (size_t)n;
+    h.g.rows = n; h.g.cols = n; h.g.points = 1;
+    h.out = (float*)dev_out; h.az_log2 = log2_of(n_az); h.n_bis = n_bis;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    HIPCHK(c, mrtx_launch_horizon(f, h, stats, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    return horizon_finish(c, stats, dev_out, host_out, out_bytes, out);
+}
+
+int mrtx_horizon_sun(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon, const float* host_horizon,
+                     const MrtxIllumEpoch* epochs, int32_t m, int32_t mode, void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!latlon || !epochs) return fail(c, MRTX_E_INVALID, "null point list or epoch table");
+    if (n < 1 || m < 1) return fail(c, MRTX_E_INVALID, "n and m must be >= 1 (got %d, %d)", n, m);
+    // the kernel's epoch loop and the dark run (a float count, exact up to 2^24) stay exact below this
+    if (m > (1 << 24)) return fail(c, MRTX_E_INVALID, "at most 2^24 epochs per call (got %d)", m);
+    if (!horizon_az_ok(n_az)) return fail(c, MRTX_E_INVALID, "n_az must be 4, 8, ..., 4096 (got %d)", n_az);
+    if (mode != 0 && mode != 1) return fail(c, MRTX_E_INVALID, "mode must be 0 (FULL) or 1 (SUMMARY) (got %d)", mode);
+    if ((dev_horizon == nullptr) == (host_horizon == nullptr))
+        return fail(c, MRTX_E_INVALID, "give exactly one of dev_horizon and host_horizon");
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    if ((int64_t)n * (int64_t)n_az > (int64_t)1 << 31) return fail(c, MRTX_E_INVALID, "at most 2^31 horizon samples per call");
+    if (mode == 0 && (int64_t)n * (int64_t)m > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "FULL holds at most 2^31 outputs per call: split the points into more calls");
+    if (host_horizon) {
+        const size_t nh = (size_t)n * (size_t)n_az;
+        for (size_t i = 0; i < nh; i++)
+            if (!(host_horizon[i] >= -90.0f && host_horizon[i] <= 90.0f))
+                return fail(c, MRTX_E_INVALID, "horizon entry %zu is not an elevation in [-90, 90] degrees", i);
+    }
+    std::vector<float> tab, lights;
+    int rc = point_tables(c, latlon, n, tab);
+    if (rc != MRTX_OK) return rc;
+    if ((rc = epoch_lights(c, epochs, m, lights)) != MRTX_OK) return rc;
+    FrameC f;
+    FrameCold cold;
+    if ((rc = horizon_frame(c, f, cold, false)) != MRTX_OK) return rc;
+    // one device block: point tables (4 floats per point: the lights that follow are 16-byte aligned), epoch lights[, horizons]
+    const size_t nh = host_horizon ? (size_t)n * (size_t)n_az : 0;
+    const size_t tab_bytes = (tab.size() + lights.size() + nh) * sizeof(float);
+    const size_t out_bytes = mode == 0 ? (size_t)n * (size_t)m * sizeof(float) : (size_t)n * 16;
+    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, tab_bytes)) != MRTX_OK) return rc;
+    if (!dev_out) {
+        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, out_bytes)) != MRTX_OK) return rc;
+        dev_out = c->illum_out;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->illum_cold, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->illum_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->illum_tab + tab.size(), lights.data(), lights.size() * sizeof(float), hipMemcpyHostToDevice,
+                             c->stream));
+    if (nh) HIPCHK(c, hipMemcpyAsync(c->illum_tab + tab.size() + lights.size(), host_horizon, nh * sizeof(float),
+                                     hipMemcpyHostToDevice, c->stream));
+    HorizonSunC q;
+    std::memset(&q, 0, sizeof q);
+    q.g.rtab = c->illum_tab; q.g.ctab = c->illum_tab + 2 * (size_t)n;
+    q.g.rows = n; q.g.cols = n; q.g.points = 1;
+    q.lights = c->illum_tab + tab.size();
+    q.horizon = nh ? c->illum_tab + tab.size() + lights.size() : (const float*)dev_horizon;
+    q.out = (float*)dev_out; q.az_log2 = log2_of(n_az); q.m = m; q.mode = mode;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    HIPCHK(c, mrtx_launch_horizon_sun(f, q, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    return horizon_finish(c, false, dev_out, host_out, out_bytes, out);
 }
 
 int mrtx_samples_done(mrtx_ctx* c, uint32_t* out) {

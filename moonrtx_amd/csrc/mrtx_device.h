@@ -193,3 +193,24 @@ struct IllumSeriesC {
     const float* lights;    // 8 floats per epoch, 16-byte aligned
     const int32_t* first;   // per point: its window's first epoch; null: every window starts at epoch 0
 };
+
+// Terrain horizons (mrtx_horizon_points): a point list as the illumination stage holds it (g.points = 1,
+// g.rows = points; only the row / column tables are read) and n_az = 1 << az_log2 azimuths per point, n_bis probes each.
+struct HorizonC {
+    IllumC g;
+    float* out;             // n_points x n_az float32 elevations (degrees), point-major
+    int32_t az_log2;        // log2(n_az), 2 .. 12
+    int32_t n_bis;          // probes per (point, azimuth), 1 .. 24
+};
+
+// The Sun against a horizon (mrtx_horizon_sun): per (point, epoch) the visible fraction of the light's
+// disc above the point's horizon.  One wave per point walks the epochs 64 at a time.
+struct HorizonSunC {
+    IllumC g;               // the point list (g.rows points), as in HorizonC
+    const float* horizon;   // n_points x n_az float32 elevations (degrees)
+    const float* lights;    // 8 floats per epoch, as IllumSeriesC's
+    float* out;             // mode 0: n_points x m float32 fractions; mode 1: n_points float4 (mean, lit, full, longest dark run)
+    int32_t az_log2;        // log2(n_az)
+    int32_t m;              // epochs
+    int32_t mode;           // 0 FULL, 1 SUMMARY
+};

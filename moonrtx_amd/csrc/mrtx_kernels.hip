@@ -2154,6 +2154,156 @@ __global__ void __launch_bounds__(64) illum_series_kernel(const FrameC f, const 
     }
 }
 
+// Terrain horizons (DESIGN.md sections 3.8 and 4.10): per (point, azimuth) a bisection over the elevation whose n_bis probes
+// are each exactly an illumination sample's visibility decision -- n . d > 0 and the shadow march from the lifted origin
+// escapes (light_sample's origin, illum_sample's march).  Lane = (point, azimuth), point-major: one wave = 64 consecutive
+// azimuths of one point (64 / n_az points when n_az < 64), so the 64 lanes leave one origin.  Steep probes end after a few
+// steps; the last probes graze the horizon and run the length of the bounding shell.
+template <bool STATS, bool WIDE>
+__global__ void __launch_bounds__(64) horizon_kernel(const FrameC f, const HorizonC h) {
+    const int lane = threadIdx.x;
+    const int64_t gid = (int64_t)blockIdx.x * 64 + lane;
+    const int n_az = 1 << h.az_log2;
+    const int pt = (int)(gid >> h.az_log2), az = (int)(gid & (int64_t)(n_az - 1));
+    const bool in = pt < h.g.rows;
+    uint32_t cnt_store[STATS ? ST_N : 1];
+    uint32_t* const cnt = STATS ? cnt_store : nullptr;
+    if (STATS) {
+#pragma unroll
+        for (int i = 0; i < ST_N; i++) cnt[i] = 0;
+    }
+    if (in) {
+        Vertex v;
+        (void)illum_vertex<STATS, WIDE>(f, h.g, pt, pt, v, cnt);    // g.points = 1: both tables indexed by the point
+        const float2 rt = reinterpret_cast<const float2*>(h.g.rtab)[pt];   // (s_lat, c_lat)
+        const float2 ct = reinterpret_cast<const float2*>(h.g.ctab)[pt];   // (s_lon, c_lon)
+        // local frame: U = u, E = (c_lon, -s_lon, 0), N = (-s_lat s_lon, -s_lat c_lon, c_lat)
+        const float ua = rt.y * ct.x, ub = rt.y * ct.y, uc = rt.x;
+        const float Na = -(rt.x * ct.x), Nb = -(rt.x * ct.y), Nc = rt.y;
+        float cp, sp;
+        sincos_turn((float)az * (1.0f / (float)n_az), cp, sp);     // a / n_az: exact
+        const float ha = fmaf(cp, Na, sp * ct.y), hb = fmaf(cp, Nb, -(sp * ct.x)), hc = cp * Nc;
+        const float eps = CF(f)->scene_eps;
+        const float oa = fmaf(eps, v.na, v.pa), ob = fmaf(eps, v.nb, v.pb), oc = fmaf(eps, v.nc, v.pc);
+        float lo = 0.0f, hi = 1.0f;
+        for (int i = 0; i < h.n_bis; i++) {
+            const float mid = 0.5f * (lo + hi);                     // dyadic, at most 24 fraction bits: exact
+            float ce, se;
+            sincos_turn((mid - 0.5f) * 0.5f, ce, se);               // e in (-1/4, 1/4) turn: quadrants -1 and 0
+            const float da = fmaf(se, ua, ce * ha), db = fmaf(se, ub, ce * hb), dc = fmaf(se, uc, ce * hc);
+            bool clear = false;
+            if (fmaf(v.nc, dc, fmaf(v.nb, db, v.na * da)) > 0.0f) {
+                if (STATS) cnt[ST_SHADOW]++;
+                Seg ssg;
+                float sk_occ;
+                clear = !march<WIDE, false, STATS, MRTX_STEP_BATCH, 2>(f, oa, ob, oc, da, db, dc, 0.0f, ssg, sk_occ, cnt);
+            }
+            hi = clear ? mid : hi;
+            lo = clear ? lo : mid;
+        }
+        h.out[gid] = (hi - 0.5f) * 180.0f;
+    }
+    if (STATS) {
+        const int which[4] = {ST_SHADOW, ST_HEIGHT, ST_FETCH, ST_MIP};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            uint32_t c = cnt[which[i]];
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) c += __shfl_xor(c, m, 64);
+            if (lane == 0) atomicAdd(&CF(f)->stats[which[i]], (unsigned long long)c);
+        }
+    }
+}
+
+// The Sun against a horizon (DESIGN.md sections 3.9 and 4.10): per (point, epoch) the share of the light's disc above the
+// point's horizon, interpolated at the light's azimuth.  One wave = one point; it walks the epochs 64 at a time (lane = epoch),
+// so the point's vertex is formed once and its horizon row stays in L1.  FULL writes every fraction; SUMMARY reduces them in
+// the wave: the sum in float64 (per lane over its epochs k = lane mod 64 in order, then the xor butterfly), the two counts, and
+// the longest run of dark epochs carried from chunk to chunk (the run that reaches a chunk's last epoch continues into the next).
+template <bool WIDE>
+__global__ void __launch_bounds__(64) horizon_sun_kernel(const FrameC f, const HorizonSunC q) {
+    const int lane = threadIdx.x;
+    const int pt = (int)blockIdx.x;
+    const int n_az = 1 << q.az_log2;
+    Vertex v;
+    (void)illum_vertex<false, WIDE>(f, q.g, pt, pt, v, nullptr);
+    const float2 rt = reinterpret_cast<const float2*>(q.g.rtab)[pt];
+    const float2 ct = reinterpret_cast<const float2*>(q.g.ctab)[pt];
+    const float ua = rt.y * ct.x, ub = rt.y * ct.y, uc = rt.x;
+    const float Na = -(rt.x * ct.x), Nb = -(rt.x * ct.y), Nc = rt.y;
+    const float eps = CF(f)->scene_eps;
+    const float oa = fmaf(eps, v.na, v.pa), ob = fmaf(eps, v.nb, v.pb), oc = fmaf(eps, v.nc, v.pc);
+    const float* const hz = q.horizon + ((int64_t)pt << q.az_log2);
+    const float4* const lights = reinterpret_cast<const float4*>(q.lights);
+    constexpr float kDeg = 57.2957795130823209f, kInvTurn = 0.159154943091895336f, kInvPi = 0.318309886183790672f;
+    double sum = 0.0;
+    uint32_t n_lit = 0, n_full = 0;
+    int cur = 0, best = 0;      // wave-uniform: the dark run reaching the previous chunk's end, the longest so far
+    for (int k0 = 0; k0 < q.m; k0 += 64) {
+        const int k = k0 + lane;
+        const bool in = k < q.m;
+        float fr = 0.0f;
+        if (in) {
+            const float4 l0 = lights[2 * (int64_t)k];
+            // the direction to the light centre as light_sample forms it
+            const float ta = l0.x - oa, tb = l0.y - ob, tc = l0.z - oc;
+            const float inv_dist = rcp_cr(sqrt_sh(fmaf(tc, tc, fmaf(tb, tb, ta * ta))));
+            const float la = ta * inv_dist, lb = tb * inv_dist, lc = tc * inv_dist;
+            const float xu = fmaf(uc, lc, fmaf(ub, lb, ua * la));
+            const float xn = fmaf(Nc, lc, fmaf(Nb, lb, Na * la));
+            const float xe = fmaf(-ct.x, lb, ct.y * la);
+            const float es = atan2f(xu, sqrtf(fmaf(xe, xe, xn * xn))) * kDeg;
+            float ph = atan2f(xe, xn) * kInvTurn;                   // turns from north through east, [-1/2, 1/2]
+            ph = ph < 0.0f ? ph + 1.0f : ph;
+            const float x = ph * (float)n_az;
+            const float x0 = floorf(x);
+            const float w = x - x0;
+            const int i0 = (int)x0 & (n_az - 1), i1 = (i0 + 1) & (n_az - 1);
+            const float h0 = hz[i0], h1 = hz[i1];
+            const float hh = fmaf(w, h1 - h0, h0);
+            const float alpha = asinf(fminf(1.0f, sqrtf(l0.w) * inv_dist)) * kDeg;
+            if (alpha > 0.0f) {
+                const float r = (hh - es) / alpha;
+                if (r <= -1.0f) fr = 1.0f;
+                else if (r < 1.0f) fr = fminf(1.0f, fmaxf(0.0f, (acosf(r) - r * sqrtf(1.0f - r * r)) * kInvPi));
+            } else {
+                fr = es > hh ? 1.0f : 0.0f;
+            }
+            if (q.mode == 0) q.out[(int64_t)pt * q.m + k] = fr;
+        }
+        if (q.mode != 0) {
+            sum += (double)fr;
+            n_lit += (in && fr > 0.0f) ? 1u : 0u;
+            n_full += (in && fr == 1.0f) ? 1u : 0u;
+            const unsigned long long dark = __ballot(in && fr == 0.0f);
+            // the dark run ending at this lane's epoch (0 if it is lit): back to the nearest lit epoch of the chunk, or
+            // through the chunk's start into the run carried in
+            const unsigned long long below = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
+            const unsigned long long lit = ~dark & below;
+            int run = lit ? lane - (63 - __clzll((long long)lit)) : lane + 1 + cur;
+            run = in ? run : 0;
+            const int nv = min(64, q.m - k0);
+            cur = __shfl(run, nv - 1, 64);
+#pragma unroll
+            for (int s = 1; s < 64; s <<= 1) run = max(run, __shfl_xor(run, s, 64));
+            best = max(best, run);
+        }
+    }
+    if (q.mode != 0) {
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            sum += __shfl_xor(sum, s, 64);
+            n_lit += __shfl_xor(n_lit, s, 64);
+            n_full += __shfl_xor(n_full, s, 64);
+        }
+        if (lane == 0) {
+            const double inv_m = 1.0 / (double)q.m;
+            reinterpret_cast<float4*>(q.out)[pt] =
+                make_float4((float)(sum * inv_m), (float)((double)n_lit * inv_m), (float)((double)n_full * inv_m), (float)best);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // D6 behind a queue: what is left of a path after render_kernel<MODE 2> (set_uint("path_seg_range", 2, 4),
 // moon_renderer.py:583).
@@ -3471,6 +3621,32 @@ hipError_t mrtx_launch_illum_series(const FrameC& f, IllumSeriesC q, bool stats,
                  else hipLaunchKernelGGL((mrtx::illum_series_kernel<true, false>), grid, block, 0, st, f, q); }
     else { if (wide) hipLaunchKernelGGL((mrtx::illum_series_kernel<false, true>), grid, block, 0, st, f, q);
            else hipLaunchKernelGGL((mrtx::illum_series_kernel<false, false>), grid, block, 0, st, f, q); }
+    return hipGetLastError();
+}
+
+// Terrain horizons (horizon_kernel): lane = (point, azimuth), point-major, 64 lanes per wave.  h.g.rows points.
+hipError_t mrtx_launch_horizon(const FrameC& f, HorizonC h, bool stats, hipStream_t st) {
+    if (h.g.rows < 1 || h.az_log2 < 2 || h.az_log2 > 12 || h.n_bis < 1 || h.n_bis > 24 || !h.g.points || !h.out)
+        return hipErrorInvalidValue;
+    const uint64_t lanes = (uint64_t)h.g.rows << h.az_log2;
+    if (lanes > (1ull << 31)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((lanes + 63) / 64)), block(64);
+    const bool wide = f.dem_wide != 0;
+    if (stats) { if (wide) hipLaunchKernelGGL((mrtx::horizon_kernel<true, true>), grid, block, 0, st, f, h);
+                 else hipLaunchKernelGGL((mrtx::horizon_kernel<true, false>), grid, block, 0, st, f, h); }
+    else { if (wide) hipLaunchKernelGGL((mrtx::horizon_kernel<false, true>), grid, block, 0, st, f, h);
+           else hipLaunchKernelGGL((mrtx::horizon_kernel<false, false>), grid, block, 0, st, f, h); }
+    return hipGetLastError();
+}
+
+// The Sun against a horizon (horizon_sun_kernel): one wave per point.
+hipError_t mrtx_launch_horizon_sun(const FrameC& f, HorizonSunC q, hipStream_t st) {
+    if (q.g.rows < 1 || q.az_log2 < 2 || q.az_log2 > 12 || q.m < 1 || (q.mode != 0 && q.mode != 1) || !q.g.points || !q.horizon ||
+        !q.lights || !q.out)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)q.g.rows), block(64);
+    if (f.dem_wide) hipLaunchKernelGGL((mrtx::horizon_sun_kernel<true>), grid, block, 0, st, f, q);
+    else hipLaunchKernelGGL((mrtx::horizon_sun_kernel<false>), grid, block, 0, st, f, q);
     return hipGetLastError();
 }
 

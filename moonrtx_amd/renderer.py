@@ -305,16 +305,8 @@ class MoonRT:
         `epochs`: the (m, 14) float64 array of ephemeris.sun_epochs, or a sequence of SceneDesc.  first = None: every point
         reads epochs [0, count) (count defaults to m); otherwise N window starts and count is required.  Calls hold at most
         chunk_bytes of output each (points split between calls); `stats`, if a dict, receives the summed counters."""
-        from .ephemeris import epoch_of_scene
-        la = np.atleast_1d(np.asarray(lat_deg, np.float64)).ravel()
-        lo = np.atleast_1d(np.asarray(lon_deg, np.float64)).ravel()
-        if la.shape != lo.shape:
-            raise ValueError("lat_deg and lon_deg must have the same number of points")
-        if not isinstance(epochs, np.ndarray):
-            epochs = np.array([epoch_of_scene(e) for e in epochs], np.float64).reshape(-1, 14)
-        ep = np.ascontiguousarray(epochs, np.float64)
-        if ep.ndim != 2 or ep.shape[1] != 14:
-            raise ValueError("epochs must be an (m, 14) array (ephemeris.sun_epochs) or a sequence of SceneDesc")
+        la, lo = self._points(lat_deg, lon_deg)
+        ep = self._epochs(epochs)
         if first is None:
             count = ep.shape[0] if count is None else int(count)
         else:
@@ -335,6 +327,91 @@ class MoonRT:
                                                     int(n_sun), None, out[a:].ctypes.data, C.byref(st)), "mrtx_illum_series")
             self._add_stats(stats, st)
         return out
+
+    @staticmethod
+    def _points(lat_deg, lon_deg):
+        la = np.atleast_1d(np.asarray(lat_deg, np.float64)).ravel()
+        lo = np.atleast_1d(np.asarray(lon_deg, np.float64)).ravel()
+        if la.shape != lo.shape:
+            raise ValueError("lat_deg and lon_deg must have the same number of points")
+        return la, lo
+
+    @staticmethod
+    def _epochs(epochs):
+        from .ephemeris import epoch_of_scene
+        if not isinstance(epochs, np.ndarray):
+            epochs = np.array([epoch_of_scene(e) for e in epochs], np.float64).reshape(-1, 14)
+        ep = np.ascontiguousarray(epochs, np.float64)
+        if ep.ndim != 2 or ep.shape[1] != 14:
+            raise ValueError("epochs must be an (m, 14) array (ephemeris.sun_epochs) or a sequence of SceneDesc")
+        return ep
+
+    @staticmethod
+    def horizon_azimuths(n_az):
+        """Azimuths of the n_az horizon samples, degrees from north through east: a * 360 / n_az."""
+        n = int(n_az)
+        if n < 4 or n > 4096 or n & (n - 1):
+            raise ValueError(f"n_az must be 4, 8, ..., 4096 (got {n_az})")
+        return np.arange(n, dtype=np.float64) * (360.0 / n)
+
+    def horizon(self, lat_deg, lon_deg, n_az=256, n_bis=14, stats=None, out=None, chunk_bytes=256 << 20):
+        """(N, n_az) float32: the terrain's horizon elevation, degrees, seen from N points (degrees) at horizon_azimuths(n_az),
+        found by n_bis bisection probes that are each an illumination sample's visibility decision.
+        out = a DeviceBuffer of at least N * n_az * 4 bytes: the horizons are written there (point-major) and `out` is
+        returned.  Calls hold at most chunk_bytes of output each (points split between calls); `stats`, if a dict, receives
+        the summed counters."""
+        la, lo = self._points(lat_deg, lon_deg)
+        n_az = int(n_az)
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        if out is not None and out.nbytes < la.size * max(n_az, 0) * 4:
+            raise ValueError("the device buffer is smaller than N x n_az float32")
+        host = np.empty((la.size, max(n_az, 0)), np.float32) if out is None else None
+        step = max(1, min(int(chunk_bytes) // (4 * max(n_az, 1)), (1 << 31) // max(n_az, 1)))
+        for a in range(0, max(la.size, 1), step):
+            b = min(a + step, la.size)
+            st = MrtxStats()
+            dev = None if out is None else out.ptr + a * n_az * 4
+            hp = None if out is not None else host[a:].ctypes.data
+            self._check(self._lib.mrtx_horizon_points(self._ctx, pts[a:].ctypes.data, b - a, n_az, int(n_bis), dev, hp,
+                                                      C.byref(st)), "mrtx_horizon_points")
+            self._add_stats(stats, st)
+        return out if out is not None else host
+
+    def horizon_sun(self, lat_deg, lon_deg, horizon, epochs, summary=False, stats=None, n_az=None, chunk_bytes=256 << 20):
+        """The Sun against the horizons of `horizon`: per (point, epoch) the fraction of the light's
+        disc above the point's horizon.  `horizon`: the (N, n_az) array of MoonRT.horizon, or a DeviceBuffer holding it
+        (then n_az is required); `epochs` as for illumination_series.  summary=False: (N, m) float32 fractions;
+        summary=True: (N, 4) float32 (mean fraction, share of epochs with any of the disc up, share with all of it up,
+        longest run of consecutive epochs with none of it up, in epochs).  FULL calls hold at most chunk_bytes of output."""
+        la, lo = self._points(lat_deg, lon_deg)
+        ep = self._epochs(epochs)
+        m = ep.shape[0]
+        if isinstance(horizon, DeviceBuffer):
+            if n_az is None:
+                raise ValueError("n_az is required with a device buffer")
+            n_az = int(n_az)
+            if horizon.nbytes < la.size * n_az * 4:
+                raise ValueError("the device buffer is smaller than N x n_az float32")
+            hz = None
+        else:
+            hz = np.ascontiguousarray(horizon, np.float32)
+            if hz.ndim != 2 or hz.shape[0] != la.size:
+                raise ValueError("horizon must be an (N, n_az) array")
+            n_az = hz.shape[1]
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        width = 4 if summary else m
+        res = np.empty((la.size, width), np.float32)
+        step = la.size if summary else max(1, min(int(chunk_bytes) // (4 * max(m, 1)), (1 << 31) // max(m, 1)))
+        for a in range(0, max(la.size, 1), max(step, 1)):
+            b = min(a + step, la.size)
+            st = MrtxStats()
+            dh = None if hz is not None else horizon.ptr + a * n_az * 4
+            hh = None if hz is None else hz[a:].ctypes.data
+            self._check(self._lib.mrtx_horizon_sun(self._ctx, pts[a:].ctypes.data, b - a, n_az, dh, hh, ep.ctypes.data, m,
+                                                   1 if summary else 0, None, res[a:].ctypes.data, C.byref(st)),
+                        "mrtx_horizon_sun")
+            self._add_stats(stats, st)
+        return res
 
     @staticmethod
     def _add_stats(acc, st):

@@ -81,3 +81,42 @@ def terrain_sun_events(rt, lat, lon, start, days, step_min=10, n_sun=16, refine=
                                float(ephemeris.sun_altitude_at(e.subsolar_lat, e.subsolar_lon, la[p], lo[p])), float(e.alt)))
     events.sort(key=lambda ev: (ev.point, ev.t_hi, ev.kind))
     return SunEvents(events, times, coarse_st, refine_st)
+
+
+class IlluminationStatistics(NamedTuple):
+    mean_fraction: np.ndarray     # (N,) mean over the dates of the visible share of the Sun's disc
+    lit_fraction: np.ndarray      # (N,) share of the dates with any of the disc above the horizon
+    full_fraction: np.ndarray     # (N,) share of the dates with all of the disc above the horizon
+    longest_dark_h: np.ndarray    # (N,) longest run of consecutive dates with none of the disc up, in hours (run x step)
+    times: list                   # the dates used
+    stats: dict                   # summed counters and kernel times of the horizon and the Sun calls
+
+
+def illumination_statistics(rt, lat, lon, start, days, step_min=60, n_az=256, n_bis=14, observer=None, chunk=65536):
+    """Long-term Sun statistics of the points (lat, lon in degrees) from `start` (timezone-aware) over `days` at `step_min`
+    minutes (DESIGN.md sections 3.8 and 3.9): each point's horizon is computed once (MoonRT.horizon, n_az azimuths, n_bis
+    probes), then compared with the Sun on every date (MoonRT.horizon_sun, SUMMARY).  Points are streamed `chunk` at a time;
+    their horizons stay in a device buffer.  Returns IlluminationStatistics."""
+    from .renderer import DeviceBuffer
+    la = np.atleast_1d(np.asarray(lat, np.float64)).ravel()
+    lo = np.atleast_1d(np.asarray(lon, np.float64)).ravel()
+    if la.shape != lo.shape:
+        raise ValueError("lat and lon must have the same number of points")
+    m = int(round(days * 1440.0 / step_min))
+    if m < 1:
+        raise ValueError("days / step_min gives no date")
+    times = [start + timedelta(minutes=k * step_min) for k in range(m)]
+    ep = ephemeris.sun_epochs(times, observer)
+    rt.horizon_azimuths(n_az)       # checks n_az
+    chunk = max(1, min(int(chunk), la.size, (1 << 31) // int(n_az)))
+    out = np.empty((la.size, 4), np.float32)
+    stats = {}
+    buf = DeviceBuffer(chunk * int(n_az) * 4, rt.config()["device"])
+    try:
+        for a in range(0, la.size, chunk):
+            b = min(a + chunk, la.size)
+            rt.horizon(la[a:b], lo[a:b], n_az=n_az, n_bis=n_bis, stats=stats, out=buf)
+            out[a:b] = rt.horizon_sun(la[a:b], lo[a:b], buf, ep, summary=True, stats=stats, n_az=n_az)
+    finally:
+        buf.free()
+    return IlluminationStatistics(out[:, 0], out[:, 1], out[:, 2], out[:, 3].astype(np.float64) * (step_min / 60.0), times, stats)
