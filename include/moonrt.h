@@ -325,6 +325,40 @@ int mrtx_horizon_sun(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t
                      const float* host_horizon, const MrtxIllumEpoch* epochs, int32_t m, int32_t mode, void* dev_out,
                      float* host_out, MrtxStats* out);
 
+/* ---- Regolith surface temperatures (additive to ABI 7) ------------------------------------------
+ * One heat-conduction column per point, driven by the Sun against the point's horizon.  The layer tables are built on the host
+ * in float64 (MoonRT.thermal_grid); node i sits at depth z_i, dz[i] = z_{i+1} - z_i (i < n_nodes - 1). */
+#define MRTX_THERMAL_MAX_NODES 32
+typedef struct MrtxThermalModel {
+    int32_t n_nodes;              /* 3 .. MRTX_THERMAL_MAX_NODES                                                          */
+    int32_t n_sub;                /* explicit steps per epoch: Delta = spacing_s / n_sub                                  */
+    int32_t n_spin;               /* leading spin-up epochs: stepped, not recorded (< m outside FLUX)                     */
+    int32_t block;                /* epochs per spin-up block (one lunation), >= 1                                        */
+    int32_t n_reset;              /* after each of the first n_reset spin-up blocks the nodes below ref_node are set to
+                                     the block's mean of T[ref_node]; n_reset * block <= n_spin                           */
+    int32_t ref_node;             /* 1 .. n_nodes - 2                                                                     */
+    double spacing_s;             /* epoch spacing, seconds                                                               */
+    double dz[MRTX_THERMAL_MAX_NODES];    /* node spacings, m                                                             */
+    double rho[MRTX_THERMAL_MAX_NODES];   /* density per node, kg m^-3                                                    */
+    double kc[MRTX_THERMAL_MAX_NODES];    /* contact conductivity per node, W m^-1 K^-1                                   */
+    double chi;                   /* radiative conductivity: k(T) = kc (1 + chi (T / 350)^3)                              */
+    double c[5];                  /* heat capacity c0 + c1 T + c2 T^2 + c3 T^3 + c4 T^4, J kg^-1 K^-1                     */
+    double emissivity, sigma;     /* eps, Stefan-Boltzmann constant                                                       */
+    double q_geo;                 /* geothermal flux, W m^-2                                                              */
+    double albedo[3];             /* A0, a, b: A(theta) = A0 + a (theta / 45 deg)^3 + b (theta / 90 deg)^8                */
+} MrtxThermalModel;
+/* Per point the absorbed flux Q_abs = (1 - A(theta)) S_k f max(mu, 0) of every epoch (f: mrtx_horizon_sun's disc fraction,
+ * mu = n . l as mrtx_illum_points forms it, theta = acos(mu), S_k = flux_Wm2[k]) and the column stepped through the epochs
+ * (DESIGN.md section 3.10).  Horizons and epochs as for mrtx_horizon_sun (exactly one horizon source); the epochs are evenly
+ * spaced by model->spacing_s.  mode 0 (FULL): n x (m - n_spin) float32 surface temperatures after each recorded epoch,
+ * point-major; 1 (SUMMARY): n float4 (max, min, mean surface temperature, mean bottom-node temperature over the recorded
+ * epochs); 2 (FLUX): n x m float32 Q_abs, no stepping.  Output into exactly one of dev_out and host_out; at most 2^31 outputs
+ * per call, m <= 2^24.  Needs a DEM; leaves the light, Moon frame and render state as they were.  out->reserved receives the
+ * number of surface solves that reached the Newton cap (saturating), kernel_ms and launches as usual. */
+int mrtx_thermal(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t n_az, const void* dev_horizon,
+                 const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux_Wm2, int32_t m,
+                 const MrtxThermalModel* model, int32_t mode, void* dev_out, float* host_out, MrtxStats* out);
+
 /* Math conformance probe (ABI 7): the kernels' domain-restricted reciprocal (v_rcp_f32 + Newton steps) and square root (v_sqrt_f32 + a
  * +-1 ulp residual fix) against the compiler's IEEE expansions of 1.0f / x and sqrtf(x), ON THE DEVICE, for the n float bit patterns
  * from lo_bits on: which = 0 one Newton step, 1 two steps (what the kernels use), 2 the square root.  mismatches = how many differ;

@@ -51,6 +51,18 @@ class MrtxIllumEpoch(C.Structure):
                 ("center", C.c_double * 3), ("u", C.c_double * 3), ("v", C.c_double * 3)]
 
 
+THERMAL_MAX_NODES = 32
+
+
+class MrtxThermalModel(C.Structure):
+    """The layer tables and constants of the regolith column (mrtx_thermal)."""
+    _fields_ = [("n_nodes", C.c_int32), ("n_sub", C.c_int32), ("n_spin", C.c_int32), ("block", C.c_int32),
+                ("n_reset", C.c_int32), ("ref_node", C.c_int32), ("spacing_s", C.c_double),
+                ("dz", C.c_double * THERMAL_MAX_NODES), ("rho", C.c_double * THERMAL_MAX_NODES),
+                ("kc", C.c_double * THERMAL_MAX_NODES), ("chi", C.c_double), ("c", C.c_double * 5),
+                ("emissivity", C.c_double), ("sigma", C.c_double), ("q_geo", C.c_double), ("albedo", C.c_double * 3)]
+
+
 F_COUNT_STATS = 1
 F_FORCE_WIDE = 2
 F_NO_SKIP = 4
@@ -119,6 +131,8 @@ SIGNATURES = {
     "mrtx_horizon_points": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_horizon_sun": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP,
                                    C.POINTER(MrtxStats)]),
+    "mrtx_thermal": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
+                               C.POINTER(MrtxStats)]),
 }
 
 _lib = None

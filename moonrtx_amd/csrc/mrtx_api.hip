@@ -56,6 +56,7 @@ hipError_t mrtx_launch_illum(const FrameC& f, IllumC g, bool stats, hipStream_t 
 hipError_t mrtx_launch_illum_series(const FrameC& f, IllumSeriesC q, bool stats, hipStream_t st);
 hipError_t mrtx_launch_horizon(const FrameC& f, HorizonC h, bool stats, hipStream_t st);
 hipError_t mrtx_launch_horizon_sun(const FrameC& f, HorizonSunC q, hipStream_t st);
+hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, hipStream_t st);
 
 struct mrtx_ctx {
     MrtxConfig cfg{};
@@ -1564,6 +1565,158 @@ int mrtx_horizon_sun(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az,
     HIPCHK(c, mrtx_launch_horizon_sun(f, q, c->stream));
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     return horizon_finish(c, false, dev_out, host_out, out_bytes, out);
+}
+
+// ---- Regolith surface temperatures ---------------------------------------------------------------
+static double thermal_c(const MrtxThermalModel& md, double T) {
+    return md.c[0] + T * (md.c[1] + T * (md.c[2] + T * (md.c[3] + T * md.c[4])));
+}
+
+// the model's checks; on success the step bound Delta_max at F = 1/2 (section 3.10) is in *dmax
+static int thermal_model_ok(mrtx_ctx* c, const MrtxThermalModel& md, int32_t m, int32_t mode, double* dmax) {
+    const int n = md.n_nodes;
+    if (n < 3 || n > MRTX_THERMAL_MAX_NODES)
+        return fail(c, MRTX_E_INVALID, "n_nodes must lie in [3, %d] (got %d)", MRTX_THERMAL_MAX_NODES, n);
+    for (int i = 0; i < n; i++) {
+        if (!(std::isfinite(md.rho[i]) && md.rho[i] > 0.0) || !(std::isfinite(md.kc[i]) && md.kc[i] > 0.0) ||
+            (i < n - 1 && !(std::isfinite(md.dz[i]) && md.dz[i] > 0.0)))
+            return fail(c, MRTX_E_INVALID, "node %d: dz, rho and kc must be finite and positive", i);
+    }
+    bool fin = std::isfinite(md.chi) && std::isfinite(md.emissivity) && std::isfinite(md.sigma) && std::isfinite(md.q_geo);
+    for (int i = 0; i < 5; i++) fin = fin && std::isfinite(md.c[i]);
+    for (int i = 0; i < 3; i++) fin = fin && std::isfinite(md.albedo[i]);
+    if (!fin) return fail(c, MRTX_E_INVALID, "the model's constants must be finite");
+    if (!(md.chi >= 0.0) || !(md.emissivity > 0.0) || !(md.sigma > 0.0) || !(md.q_geo >= 0.0) || !(md.albedo[0] >= 0.0) ||
+        !(md.albedo[0] < 1.0))
+        return fail(c, MRTX_E_INVALID, "need chi >= 0, emissivity > 0, sigma > 0, q_geo >= 0 and 0 <= A0 < 1");
+    if (!(std::isfinite(md.spacing_s) && md.spacing_s > 0.0)) return fail(c, MRTX_E_INVALID, "spacing_s must be positive");
+    if (md.n_sub < 1) return fail(c, MRTX_E_INVALID, "n_sub must be >= 1 (got %d)", md.n_sub);
+    if (md.block < 1) return fail(c, MRTX_E_INVALID, "block must be >= 1 (got %d)", md.block);
+    if (md.n_spin < 0 || (mode != 2 && md.n_spin >= m))
+        return fail(c, MRTX_E_INVALID, "n_spin must lie in [0, m) (got %d for m = %d)", md.n_spin, m);
+    if (md.n_reset < 0 || (int64_t)md.n_reset * md.block > md.n_spin)
+        return fail(c, MRTX_E_INVALID, "need 0 <= n_reset and n_reset * block <= n_spin");
+    if (md.ref_node < 1 || md.ref_node > n - 2) return fail(c, MRTX_E_INVALID, "ref_node must lie in [1, n_nodes - 2]");
+    // Delta_max = 1/2 min_i rho_i min(dz_{i-1}, dz_i)^2 min_{T in [20, 450] K, 1 K grid} c(T) / k_i(T) over the interior nodes
+    double best = INFINITY;
+    for (int T = 20; T <= 450; T++) {
+        const double cT = thermal_c(md, (double)T), r = (double)T / 350.0;
+        if (!(cT > 0.0)) return fail(c, MRTX_E_INVALID, "the heat capacity must be positive on [20, 450] K");
+        for (int i = 1; i < n - 1; i++) {
+            const double dz = std::min(md.dz[i - 1], md.dz[i]);
+            best = std::min(best, md.rho[i] * dz * dz * cT / (md.kc[i] * (1.0 + md.chi * r * r * r)));
+        }
+    }
+    *dmax = 0.5 * best;
+    if (!(md.spacing_s / md.n_sub <= *dmax))
+        return fail(c, MRTX_E_INVALID, "spacing_s / n_sub = %g s exceeds the stable step %g s", md.spacing_s / md.n_sub, *dmax);
+    return MRTX_OK;
+}
+
+int mrtx_thermal(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon, const float* host_horizon,
+                 const MrtxIllumEpoch* epochs, const double* flux, int32_t m, const MrtxThermalModel* model, int32_t mode,
+                 void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!latlon || !epochs || !flux || !model) return fail(c, MRTX_E_INVALID, "null point list, epoch table, flux or model");
+    if (n < 1 || m < 1) return fail(c, MRTX_E_INVALID, "n and m must be >= 1 (got %d, %d)", n, m);
+    if (m > (1 << 24)) return fail(c, MRTX_E_INVALID, "at most 2^24 epochs per call (got %d)", m);
+    if (!horizon_az_ok(n_az)) return fail(c, MRTX_E_INVALID, "n_az must be 4, 8, ..., 4096 (got %d)", n_az);
+    if (mode < 0 || mode > 2) return fail(c, MRTX_E_INVALID, "mode must be 0 (FULL), 1 (SUMMARY) or 2 (FLUX) (got %d)", mode);
+    if ((dev_horizon == nullptr) == (host_horizon == nullptr))
+        return fail(c, MRTX_E_INVALID, "give exactly one of dev_horizon and host_horizon");
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    if ((int64_t)n * (int64_t)n_az > (int64_t)1 << 31) return fail(c, MRTX_E_INVALID, "at most 2^31 horizon samples per call");
+    const MrtxThermalModel& md = *model;
+    double dmax = 0.0;
+    int rc = thermal_model_ok(c, md, m, mode, &dmax);
+    if (rc != MRTX_OK) return rc;
+    const int64_t width = mode == 0 ? (int64_t)m - md.n_spin : mode == 2 ? (int64_t)m : 4;
+    if ((int64_t)n * width > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "a call holds at most 2^31 outputs: split the points into more calls");
+    double s_max = 0.0;
+    for (int32_t k = 0; k < m; k++) {
+        if (!std::isfinite(flux[k]) || !(flux[k] >= 0.0))
+            return fail(c, MRTX_E_INVALID, "epoch %d: the solar flux must be finite and >= 0 (got %g)", k, flux[k]);
+        s_max = std::max(s_max, flux[k]);
+    }
+    // the hottest the surface can get, radiative equilibrium under the largest absorbed flux, must stay inside the range the
+    // step bound covers
+    double a_max = 0.0;
+    for (int t = 0; t <= 900; t++) {
+        const double th = 0.1 * t, x = th / 45.0, y = th / 90.0, y2 = y * y, y4 = y2 * y2;
+        const double A = md.albedo[0] + md.albedo[1] * x * x * x + md.albedo[2] * y4 * y4;
+        a_max = std::max(a_max, (1.0 - A) * std::cos(th * (M_PI / 180.0)));
+    }
+    if (mode != 2) {
+        const double t_eq = std::pow((a_max * s_max + md.q_geo) / (md.emissivity * md.sigma), 0.25);
+        if (!(t_eq <= 450.0))
+            return fail(c, MRTX_E_INVALID, "the radiative-equilibrium temperature %.1f K exceeds 450 K, the model's range", t_eq);
+    }
+    if (host_horizon) {
+        const size_t nh = (size_t)n * (size_t)n_az;
+        for (size_t i = 0; i < nh; i++)
+            if (!(host_horizon[i] >= -90.0f && host_horizon[i] <= 90.0f))
+                return fail(c, MRTX_E_INVALID, "horizon entry %zu is not an elevation in [-90, 90] degrees", i);
+    }
+    std::vector<float> tab, lights;
+    if ((rc = point_tables(c, latlon, n, tab)) != MRTX_OK) return rc;
+    if ((rc = epoch_lights(c, epochs, m, lights)) != MRTX_OK) return rc;
+    FrameC f;
+    FrameCold cold;
+    if ((rc = horizon_frame(c, f, cold, false)) != MRTX_OK) return rc;
+    // one device block: point tables, epoch lights, fluxes[, horizons]
+    std::vector<float> fl((size_t)m);
+    for (int32_t k = 0; k < m; k++) fl[k] = (float)flux[k];
+    const size_t nh = host_horizon ? (size_t)n * (size_t)n_az : 0;
+    const size_t tab_bytes = (tab.size() + lights.size() + fl.size() + nh) * sizeof(float);
+    const size_t out_bytes = (size_t)n * (size_t)width * sizeof(float);
+    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, tab_bytes)) != MRTX_OK) return rc;
+    if (!dev_out) {
+        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, out_bytes)) != MRTX_OK) return rc;
+        dev_out = c->illum_out;
+    }
+    float* const d_lights = c->illum_tab + tab.size();
+    float* const d_flux = d_lights + lights.size();
+    float* const d_hz = d_flux + fl.size();
+    HIPCHK(c, hipMemcpyAsync(c->illum_cold, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->illum_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_lights, lights.data(), lights.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_flux, fl.data(), fl.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (nh) HIPCHK(c, hipMemcpyAsync(d_hz, host_horizon, nh * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
+    ThermalC q;
+    std::memset(&q, 0, sizeof q);
+    q.g.rtab = c->illum_tab; q.g.ctab = c->illum_tab + 2 * (size_t)n;
+    q.g.rows = n; q.g.cols = n; q.g.points = 1;
+    q.horizon = nh ? d_hz : (const float*)dev_horizon;
+    q.lights = d_lights; q.flux = d_flux; q.out = (float*)dev_out; q.caps = c->illum_stats;
+    q.az_log2 = log2_of(n_az); q.m = m; q.mode = mode;
+    const int nn = md.n_nodes;
+    q.n_nodes = nn; q.n_sub = md.n_sub; q.n_spin = md.n_spin; q.block = md.block; q.n_reset = md.n_reset; q.ref = md.ref_node;
+    const double delta = md.spacing_s / md.n_sub;
+    q.es = (float)(md.emissivity * md.sigma);
+    q.q_geo = (float)md.q_geo;
+    q.chi3 = (float)(md.chi / (350.0 * 350.0 * 350.0));
+    for (int i = 0; i < 5; i++) q.c[i] = (float)md.c[i];
+    for (int i = 0; i < 3; i++) q.alb[i] = (float)md.albedo[i];
+    q.inv_dz0 = (float)(1.0 / md.dz[0]);
+    for (int i = 0; i < nn; i++) {
+        q.kc[i] = (float)md.kc[i];
+        if (i < nn - 1) q.hdz[i] = (float)(0.5 / md.dz[i]);
+        if (i < nn - 1) q.qdz[i] = (float)(md.q_geo * md.dz[i]);
+        if (i > 0 && i < nn - 1) q.a[i] = (float)(delta * 2.0 / (md.rho[i] * (md.dz[i - 1] + md.dz[i])));
+    }
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    HIPCHK(c, mrtx_launch_thermal(f, q, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    rc = horizon_finish(c, false, dev_out, host_out, out_bytes, out);
+    if (rc != MRTX_OK) return rc;
+    if (out) {
+        unsigned long long caps = 0;
+        HIPCHK(c, hipMemcpy(&caps, c->illum_stats, sizeof caps, hipMemcpyDeviceToHost));
+        out->reserved = caps > 0xffffffffull ? 0xffffffffu : (uint32_t)caps;
+    }
+    return MRTX_OK;
 }
 
 int mrtx_samples_done(mrtx_ctx* c, uint32_t* out) {

@@ -214,3 +214,36 @@ struct HorizonSunC {
     int32_t m;              // epochs
     int32_t mode;           // 0 FULL, 1 SUMMARY
 };
+
+// Regolith surface temperatures (mrtx_thermal): per point the absorbed flux of every epoch from its
+// vertex, its horizon row and the epoch's light constants, and a 1D heat-conduction column stepped through the epochs.  One
+// lane per point; the column lives in registers, so the node count is capped at compile time.  The layer tables are shared by
+// every point and travel in the kernel arguments (scalar loads).
+#define MRTX_THERMAL_NODES 32
+struct ThermalC {
+    IllumC g;                   // the point list (g.rows points), as in HorizonC
+    const float* horizon;       // n_points x n_az float32 elevations (degrees)
+    const float* lights;        // 8 floats per epoch, as IllumSeriesC's
+    const float* flux;          // per epoch the solar flux at the Moon, W m^-2
+    float* out;                 // mode 0: n x (m - n_spin) float32 surface temperatures; 1: n float4; 2: n x m float32 fluxes
+    unsigned long long* caps;   // surface solves that reached the Newton cap (one counter, zeroed by the host)
+    int32_t az_log2;            // log2(n_az)
+    int32_t m;                  // epochs, spin-up included
+    int32_t mode;               // 0 FULL, 1 SUMMARY, 2 FLUX
+    int32_t n_nodes;            // 3 .. MRTX_THERMAL_NODES
+    int32_t n_sub;              // explicit steps per epoch
+    int32_t n_spin;             // spin-up epochs (stepped, not recorded), < m outside FLUX
+    int32_t block;              // epochs per spin-up block
+    int32_t n_reset;            // spin-up blocks after which the nodes below ref are reset
+    int32_t ref;                // the reference node of the reset
+    float es;                   // emissivity x Stefan-Boltzmann
+    float q_geo;                // geothermal flux, W m^-2
+    float chi3;                 // chi / 350^3: k(T) = kc (1 + chi3 T^3)
+    float c[5];                 // heat capacity c0 + c1 T + ... + c4 T^4, J kg^-1 K^-1
+    float alb[3];               // A0, a, b of A(theta) = A0 + a (theta / 45)^3 + b (theta / 90)^8, theta in degrees
+    float inv_dz0;              // 1 / dz_0
+    float kc[MRTX_THERMAL_NODES];   // contact conductivity per node
+    float hdz[MRTX_THERMAL_NODES];  // 0.5 / dz_i: link i joins nodes i and i + 1 (its k is the mean of theirs)
+    float a[MRTX_THERMAL_NODES];    // Delta x 2 / (rho_i (dz_{i-1} + dz_i)), interior nodes
+    float qdz[MRTX_THERMAL_NODES];  // Q x dz_i: the steady step of link i (the bottom node's step: i = N - 2)
+};

@@ -2215,6 +2215,40 @@ __global__ void __launch_bounds__(64) horizon_kernel(const FrameC f, const Horiz
     }
 }
 
+// The visible share of the light's disc above a point's horizon, from the epoch's (Lb.xyz, rL2) l0,
+// the lifted origin o, the local frame (U = u, N, and E from ct = (s_lon, c_lon)) and the point's horizon row hz of n_az
+// samples.  (la, lb, lc): the unit direction to the light centre as light_sample forms it (illum_mu's l).
+__device__ __forceinline__ float disc_fraction(const float4 l0, float oa, float ob, float oc, float ua, float ub, float uc,
+                                               float Na, float Nb, float Nc, const float2 ct, const float* hz, int n_az,
+                                               float& la, float& lb, float& lc) {
+    constexpr float kDeg = 57.2957795130823209f, kInvTurn = 0.159154943091895336f, kInvPi = 0.318309886183790672f;
+    const float ta = l0.x - oa, tb = l0.y - ob, tc = l0.z - oc;
+    const float inv_dist = rcp_cr(sqrt_sh(fmaf(tc, tc, fmaf(tb, tb, ta * ta))));
+    la = ta * inv_dist; lb = tb * inv_dist; lc = tc * inv_dist;
+    const float xu = fmaf(uc, lc, fmaf(ub, lb, ua * la));
+    const float xn = fmaf(Nc, lc, fmaf(Nb, lb, Na * la));
+    const float xe = fmaf(-ct.x, lb, ct.y * la);
+    const float es = atan2f(xu, sqrtf(fmaf(xe, xe, xn * xn))) * kDeg;
+    float ph = atan2f(xe, xn) * kInvTurn;                   // turns from north through east, [-1/2, 1/2]
+    ph = ph < 0.0f ? ph + 1.0f : ph;
+    const float x = ph * (float)n_az;
+    const float x0 = floorf(x);
+    const float w = x - x0;
+    const int i0 = (int)x0 & (n_az - 1), i1 = (i0 + 1) & (n_az - 1);
+    const float h0 = hz[i0], h1 = hz[i1];
+    const float hh = fmaf(w, h1 - h0, h0);
+    const float alpha = asinf(fminf(1.0f, sqrtf(l0.w) * inv_dist)) * kDeg;
+    float fr = 0.0f;
+    if (alpha > 0.0f) {
+        const float r = (hh - es) / alpha;
+        if (r <= -1.0f) fr = 1.0f;
+        else if (r < 1.0f) fr = fminf(1.0f, fmaxf(0.0f, (acosf(r) - r * sqrtf(1.0f - r * r)) * kInvPi));
+    } else {
+        fr = es > hh ? 1.0f : 0.0f;
+    }
+    return fr;
+}
+
 // The Sun against a horizon (DESIGN.md sections 3.9 and 4.10): per (point, epoch) the share of the light's disc above the
 // point's horizon, interpolated at the light's azimuth.  One wave = one point; it walks the epochs 64 at a time (lane = epoch),
 // so the point's vertex is formed once and its horizon row stays in L1.  FULL writes every fraction; SUMMARY reduces them in
@@ -2235,7 +2269,6 @@ __global__ void __launch_bounds__(64) horizon_sun_kernel(const FrameC f, const H
     const float oa = fmaf(eps, v.na, v.pa), ob = fmaf(eps, v.nb, v.pb), oc = fmaf(eps, v.nc, v.pc);
     const float* const hz = q.horizon + ((int64_t)pt << q.az_log2);
     const float4* const lights = reinterpret_cast<const float4*>(q.lights);
-    constexpr float kDeg = 57.2957795130823209f, kInvTurn = 0.159154943091895336f, kInvPi = 0.318309886183790672f;
     double sum = 0.0;
     uint32_t n_lit = 0, n_full = 0;
     int cur = 0, best = 0;      // wave-uniform: the dark run reaching the previous chunk's end, the longest so far
@@ -2244,31 +2277,8 @@ __global__ void __launch_bounds__(64) horizon_sun_kernel(const FrameC f, const H
         const bool in = k < q.m;
         float fr = 0.0f;
         if (in) {
-            const float4 l0 = lights[2 * (int64_t)k];
-            // the direction to the light centre as light_sample forms it
-            const float ta = l0.x - oa, tb = l0.y - ob, tc = l0.z - oc;
-            const float inv_dist = rcp_cr(sqrt_sh(fmaf(tc, tc, fmaf(tb, tb, ta * ta))));
-            const float la = ta * inv_dist, lb = tb * inv_dist, lc = tc * inv_dist;
-            const float xu = fmaf(uc, lc, fmaf(ub, lb, ua * la));
-            const float xn = fmaf(Nc, lc, fmaf(Nb, lb, Na * la));
-            const float xe = fmaf(-ct.x, lb, ct.y * la);
-            const float es = atan2f(xu, sqrtf(fmaf(xe, xe, xn * xn))) * kDeg;
-            float ph = atan2f(xe, xn) * kInvTurn;                   // turns from north through east, [-1/2, 1/2]
-            ph = ph < 0.0f ? ph + 1.0f : ph;
-            const float x = ph * (float)n_az;
-            const float x0 = floorf(x);
-            const float w = x - x0;
-            const int i0 = (int)x0 & (n_az - 1), i1 = (i0 + 1) & (n_az - 1);
-            const float h0 = hz[i0], h1 = hz[i1];
-            const float hh = fmaf(w, h1 - h0, h0);
-            const float alpha = asinf(fminf(1.0f, sqrtf(l0.w) * inv_dist)) * kDeg;
-            if (alpha > 0.0f) {
-                const float r = (hh - es) / alpha;
-                if (r <= -1.0f) fr = 1.0f;
-                else if (r < 1.0f) fr = fminf(1.0f, fmaxf(0.0f, (acosf(r) - r * sqrtf(1.0f - r * r)) * kInvPi));
-            } else {
-                fr = es > hh ? 1.0f : 0.0f;
-            }
+            float la, lb, lc;
+            fr = disc_fraction(lights[2 * (int64_t)k], oa, ob, oc, ua, ub, uc, Na, Nb, Nc, ct, hz, n_az, la, lb, lc);
             if (q.mode == 0) q.out[(int64_t)pt * q.m + k] = fr;
         }
         if (q.mode != 0) {
@@ -2302,6 +2312,163 @@ __global__ void __launch_bounds__(64) horizon_sun_kernel(const FrameC f, const H
                 make_float4((float)(sum * inv_m), (float)((double)n_lit * inv_m), (float)((double)n_full * inv_m), (float)best);
         }
     }
+}
+
+// Regolith surface temperatures (DESIGN.md sections 3.10 and 4.11).  One lane = one point: its vertex and local frame are
+// formed once, then per epoch the absorbed flux (the disc fraction of horizon_sun_kernel, illum_mu's mu, the albedo law) and
+// n_sub explicit steps of its heat-conduction column.  The column's temperatures are float64 registers (a deep node moves by
+// a few ulp of float32 per step, so float32 state would round its change away); the rates of a step are float32.  The layer
+// tables are the kernel arguments' (wave-uniform, scalar loads); the node loops are unrolled to MRTX_THERMAL_NODES with a
+// wave-uniform bound, so every index is a constant and the column never leaves the registers.  Lanes past the last point
+// repeat it and store nothing.
+template <bool WIDE>
+__global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const ThermalC q) {
+    constexpr int NN = MRTX_THERMAL_NODES;
+    constexpr float kDeg = 57.2957795130823209f;
+    const int lane = threadIdx.x;
+    const int pt0 = (int)blockIdx.x * 64 + lane;
+    const bool in = pt0 < q.g.rows;
+    const int pt = in ? pt0 : q.g.rows - 1;
+    const int n_az = 1 << q.az_log2;
+    const int n = q.n_nodes;
+    Vertex v;
+    (void)illum_vertex<false, WIDE>(f, q.g, pt, pt, v, nullptr);
+    const float2 rt = reinterpret_cast<const float2*>(q.g.rtab)[pt];
+    const float2 ct = reinterpret_cast<const float2*>(q.g.ctab)[pt];
+    const float ua = rt.y * ct.x, ub = rt.y * ct.y, uc = rt.x;
+    const float Na = -(rt.x * ct.x), Nb = -(rt.x * ct.y), Nc = rt.y;
+    const float eps = CF(f)->scene_eps;
+    const float oa = fmaf(eps, v.na, v.pa), ob = fmaf(eps, v.nb, v.pb), oc = fmaf(eps, v.nc, v.pc);
+    const float* const hz = q.horizon + ((int64_t)pt << q.az_log2);
+    const float4* const lights = reinterpret_cast<const float4*>(q.lights);
+    // Q_abs of epoch k: (1 - A(theta)) S_k f max(mu, 0), exactly 0 when f == 0 or mu <= 0
+    auto absorbed = [&](int k) -> float {
+        float la, lb, lc;
+        const float fr = disc_fraction(lights[2 * (int64_t)k], oa, ob, oc, ua, ub, uc, Na, Nb, Nc, ct, hz, n_az, la, lb, lc);
+        const float mu = fmaf(v.nc, lc, fmaf(v.nb, lb, v.na * la));      // illum_mu's expression
+        if (!(fr > 0.0f) || !(mu > 0.0f)) return 0.0f;
+        const float th = acosf(fminf(mu, 1.0f)) * kDeg;
+        const float x = th * (1.0f / 45.0f), y = th * (1.0f / 90.0f);
+        const float y2 = y * y, y4 = y2 * y2;
+        const float A = fmaf(q.alb[2], y4 * y4, fmaf(q.alb[1], x * x * x, q.alb[0]));
+        return (((1.0f - A) * q.flux[k]) * fr) * mu;
+    };
+    if (q.mode == 2) {
+        if (in)
+            for (int k = 0; k < q.m; k++) q.out[(int64_t)pt * q.m + k] = absorbed(k);
+        return;
+    }
+    // the uniform start: ((<Q_abs> over the spin-up epochs + Q) / (eps sigma))^(1/4)
+    double qs = 0.0;
+    for (int k = 0; k < q.n_spin; k++) qs += (double)absorbed(k);
+    const double t_init = sqrt(sqrt(((q.n_spin > 0 ? qs / (double)q.n_spin : 0.0) + (double)q.q_geo) / (double)q.es));
+    auto kof = [&](int i, double t) -> float {        // k_i(T) in float32
+        const float tf = (float)t;
+        return q.kc[i] * fmaf(q.chi3, tf * tf * tf, 1.0f);
+    };
+    // below node i0 the steady profile carrying Q upward from temperature `top` at node i0 (left as it is):
+    // k_{i+1/2} (T_{i+1} - T_i) / dz_i = Q, the step of each link in float32 by six fixed-point passes, the last link by the
+    // bottom rule
+    auto geotherm = [&](double* T, int i0, double top) {
+#pragma unroll
+        for (int i = 0; i < NN - 1; i++) {
+            const double ti = i == i0 ? top : T[i];
+            if (i >= i0 && i < n - 2) {
+                const float tf = (float)ti, ki = kof(i, ti);
+                float d = 0.0f;
+                for (int r = 0; r < 6; r++) {
+                    const float t = tf + d;
+                    d = q.qdz[i] / (0.5f * (ki + q.kc[i + 1] * fmaf(q.chi3, t * t * t, 1.0f)));
+                }
+                T[i + 1] = ti + (double)d;
+            } else if (i >= i0 && i == n - 2) {
+                T[i + 1] = ti + (double)(q.qdz[i] / kof(i, ti));
+            }
+        }
+    };
+    double T[NN];
+#pragma unroll
+    for (int i = 0; i < NN; i++) T[i] = t_init;
+    geotherm(T, 0, t_init);
+    uint32_t caps = 0;
+    double ref_sum = 0.0, sum_s = 0.0, sum_b = 0.0;
+    float t_max = -INFINITY, t_min = INFINITY;
+    int in_block = 0, blocks = 0;
+    const int m_rec = q.m - q.n_spin;
+    for (int k = 0; k < q.m; k++) {
+        const float qa = absorbed(k);
+        for (int s = 0; s < q.n_sub; s++) {
+            // 1. interior nodes from the old values; link i's flux k_{i+1/2} (T_{i+1} - T_i) / dz_i, k of node i carried
+            float k_lo = kof(0, T[0]), k_hi = kof(1, T[1]);
+            float g_lo = ((k_lo + k_hi) * q.hdz[0]) * (float)(T[1] - T[0]);
+#pragma unroll
+            for (int i = 1; i < NN - 1; i++) {
+                if (i < n - 1) {
+                    k_lo = k_hi;
+                    k_hi = kof(i + 1, T[i + 1]);
+                    const float g_hi = ((k_lo + k_hi) * q.hdz[i]) * (float)(T[i + 1] - T[i]);
+                    const float tf = (float)T[i];
+                    const float c = fmaf(fmaf(fmaf(fmaf(q.c[4], tf, q.c[3]), tf, q.c[2]), tf, q.c[1]), tf, q.c[0]);
+                    T[i] += (double)((q.a[i] * (g_hi - g_lo)) * rcp_cr(c));
+                    g_lo = g_hi;
+                }
+            }
+            // 2. the surface: eps sigma T0^4 = Q_abs + k_{1/2}(T0) (T1 - T0) / dz0, Newton from the previous T0
+            const float t1 = (float)T[1];
+            const float k1 = kof(1, T[1]);
+            float t0 = (float)T[0];
+            int it = 0;
+            for (; it < 30; it++) {
+                const float t2 = t0 * t0, t3 = t2 * t0;
+                const float kh = 0.5f * (q.kc[0] * fmaf(q.chi3, t3, 1.0f) + k1);
+                const float d = t1 - t0;
+                const float gv = (q.es * t3) * t0 - qa - (kh * d) * q.inv_dz0;
+                const float gd = (4.0f * q.es) * t3 + (kh - ((1.5f * q.kc[0]) * q.chi3) * t2 * d) * q.inv_dz0;
+                const float dt = gv / gd;
+                t0 -= dt;
+                if (fabsf(dt) < 1.0e-3f) break;
+            }
+            caps += it == 30 ? 1u : 0u;
+            T[0] = (double)t0;
+            // 3. the bottom: T_{N-1} = T_{N-2} + Q dz_{N-2} / k_{N-2}(T_{N-2})
+#pragma unroll
+            for (int i = 2; i < NN; i++)
+                if (i == n - 1) T[i] = T[i - 1] + (double)(q.qdz[i - 1] / kof(i - 1, T[i - 1]));
+        }
+        const float ts = (float)T[0];
+        if (k < q.n_spin) {
+            if (blocks < q.n_reset) {
+                double tr = 0.0;
+#pragma unroll
+                for (int i = 0; i < NN; i++) tr = i == q.ref ? T[i] : tr;
+                ref_sum += tr;
+                if (++in_block == q.block) {
+                    const double mean = ref_sum / (double)q.block;
+                    geotherm(T, q.ref, mean);
+                    ref_sum = 0.0;
+                    in_block = 0;
+                    blocks++;
+                }
+            }
+        } else {
+            double tb = 0.0;
+#pragma unroll
+            for (int i = 2; i < NN; i++) tb = i == n - 1 ? T[i] : tb;
+            t_max = fmaxf(t_max, ts);
+            t_min = fminf(t_min, ts);
+            sum_s += (double)ts;
+            sum_b += tb;
+            if (in && q.mode == 0) q.out[(int64_t)pt * m_rec + (k - q.n_spin)] = ts;
+        }
+    }
+    if (in && q.mode == 1) {
+        const double inv = 1.0 / (double)m_rec;
+        reinterpret_cast<float4*>(q.out)[pt] = make_float4(t_max, t_min, (float)(sum_s * inv), (float)(sum_b * inv));
+    }
+    caps = in ? caps : 0u;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) caps += __shfl_xor(caps, s, 64);
+    if (lane == 0 && caps) atomicAdd(q.caps, (unsigned long long)caps);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3647,6 +3814,19 @@ hipError_t mrtx_launch_horizon_sun(const FrameC& f, HorizonSunC q, hipStream_t s
     const dim3 grid((unsigned)q.g.rows), block(64);
     if (f.dem_wide) hipLaunchKernelGGL((mrtx::horizon_sun_kernel<true>), grid, block, 0, st, f, q);
     else hipLaunchKernelGGL((mrtx::horizon_sun_kernel<false>), grid, block, 0, st, f, q);
+    return hipGetLastError();
+}
+
+// Regolith surface temperatures (thermal_kernel): one lane per point, 64 per wave.
+hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, hipStream_t st) {
+    if (q.g.rows < 1 || q.az_log2 < 2 || q.az_log2 > 12 || q.m < 1 || q.mode < 0 || q.mode > 2 || q.n_nodes < 3 ||
+        q.n_nodes > MRTX_THERMAL_NODES || q.n_sub < 1 || q.block < 1 || q.n_spin < 0 || q.n_reset < 0 || q.ref < 0 ||
+        q.ref >= q.n_nodes - 1 || (q.mode != 2 && q.n_spin >= q.m) || !q.g.points || !q.horizon || !q.lights || !q.flux ||
+        !q.out || !q.caps)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((q.g.rows + 63) / 64)), block(64);
+    if (f.dem_wide) hipLaunchKernelGGL((mrtx::thermal_kernel<true>), grid, block, 0, st, f, q);
+    else hipLaunchKernelGGL((mrtx::thermal_kernel<false>), grid, block, 0, st, f, q);
     return hipGetLastError();
 }
 

@@ -479,6 +479,26 @@ def calculate_moon_ephemeris(dt_local, parallactic_mode, observer=None):
         rotation_matrix=view_rotation(l_top, b_top, P - q))
 
 
+def sun_flux(times, solar_constant=1361.0):
+    """Solar flux at the Moon, W m^-2, per timezone-aware datetime: solar_constant x (1 AU / r)^2 with r the Sun-Moon centre
+    distance, the geocentric Sun minus the geocentric Moon of the series calculate_moon_ephemeris uses."""
+    out = np.empty(len(times), np.float64)
+    for i, t in enumerate(times):
+        if t.tzinfo is None:
+            raise ValueError("times must be timezone-aware")
+        dt_utc = t.astimezone(timezone.utc)
+        jde = julian_day(dt_utc) + tt_minus_utc(dt_utc) / 86400.0
+        T = (jde - 2451545.0) / 36525.0
+        dpsi, _, eps, _ = nutation(T)
+        lam_m, beta_m, dist_m = moon_position(T)
+        lam_s, _, r_s, _ = sun_position(T)
+        ra_m, dec_m = ecl_to_equ(lam_m + dpsi, beta_m, eps)
+        ra_s, dec_s = ecl_to_equ(lam_s + dpsi, 0.0, eps)
+        r = np.linalg.norm(_vec(ra_s, dec_s, r_s * AU_KM) - _vec(ra_m, dec_m, dist_m)) / AU_KM
+        out[i] = solar_constant / (r * r)
+    return out
+
+
 def scene_from_ephemeris(eph, width, height, **kw):
     """MoonEphemeris -> SceneDesc: what update_view pushes for one date (moon_renderer.py:824-871)."""
     from .scene import make_scene, moon_axes

@@ -414,6 +414,63 @@ class MoonRT:
         return res
 
     @staticmethod
+    def thermal_grid(spacing_s=3600.0, spinup_lunations=None, resets=None, F=None):
+        """The MrtxThermalModel of the default regolith for epochs `spacing_s` apart: the layer
+        tables, n_sub steps per epoch from the stable step at F (default 0.5), spin-up blocks of one lunation.  Defaults:
+        thermal.SPINUP_LUNATIONS lunations of spin-up, reset after each of the first thermal.RESETS."""
+        from . import thermal
+        return thermal.model(spacing_s, thermal.SPINUP_LUNATIONS if spinup_lunations is None else spinup_lunations,
+                             thermal.RESETS if resets is None else resets, thermal.F_STEP if F is None else F)
+
+    def surface_temperature(self, lat_deg, lon_deg, horizon, epochs, flux, model=None, mode="summary", stats=None, n_az=None,
+                            chunk_bytes=256 << 20):
+        """Regolith surface temperatures driven by the Sun against the horizons of `horizon`.
+        `horizon`: the (N, n_az) array of MoonRT.horizon, or a DeviceBuffer holding it (then n_az is required); `epochs` as
+        for horizon_sun, evenly spaced by model.spacing_s, the first model.n_spin of them spin-up; `flux`: the solar flux
+        per epoch, W m^-2 (ephemeris.sun_flux); `model`: thermal_grid() (hourly epochs) unless given.
+        mode "summary": (N, 4) float32 (max, min, mean surface temperature, mean bottom-node temperature over the recorded
+        epochs); "full": (N, m - n_spin) float32 surface temperatures; "flux": (N, m) float32 absorbed flux, no stepping.
+        FULL and FLUX calls hold at most chunk_bytes of output each; `stats`, if a dict, also receives newton_cap_hits."""
+        modes = {"full": 0, "summary": 1, "flux": 2}
+        if mode not in modes:
+            raise ValueError(f"mode must be one of {sorted(modes)} (got {mode!r})")
+        la, lo = self._points(lat_deg, lon_deg)
+        ep = self._epochs(epochs)
+        m = ep.shape[0]
+        fl = np.ascontiguousarray(np.asarray(flux, np.float64).ravel())
+        if fl.size != m:
+            raise ValueError("flux must hold one value per epoch")
+        model = self.thermal_grid() if model is None else model
+        if isinstance(horizon, DeviceBuffer):
+            if n_az is None:
+                raise ValueError("n_az is required with a device buffer")
+            n_az = int(n_az)
+            if horizon.nbytes < la.size * n_az * 4:
+                raise ValueError("the device buffer is smaller than N x n_az float32")
+            hz = None
+        else:
+            hz = np.ascontiguousarray(horizon, np.float32)
+            if hz.ndim != 2 or hz.shape[0] != la.size:
+                raise ValueError("horizon must be an (N, n_az) array")
+            n_az = hz.shape[1]
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        width = {"full": max(m - int(model.n_spin), 1), "summary": 4, "flux": m}[mode]
+        res = np.empty((la.size, width), np.float32)
+        step = la.size if mode == "summary" else max(1, min(int(chunk_bytes) // (4 * width), (1 << 31) // width))
+        for a in range(0, max(la.size, 1), max(step, 1)):
+            b = min(a + step, la.size)
+            st = MrtxStats()
+            dh = None if hz is not None else horizon.ptr + a * n_az * 4
+            hh = None if hz is None else hz[a:].ctypes.data
+            self._check(self._lib.mrtx_thermal(self._ctx, pts[a:].ctypes.data, b - a, n_az, dh, hh, ep.ctypes.data,
+                                               fl.ctypes.data, m, C.byref(model), modes[mode], None, res[a:].ctypes.data,
+                                               C.byref(st)), "mrtx_thermal")
+            self._add_stats(stats, st)
+            if isinstance(stats, dict):
+                stats["newton_cap_hits"] = stats.get("newton_cap_hits", 0) + int(st.reserved)
+        return res
+
+    @staticmethod
     def _add_stats(acc, st):
         if isinstance(acc, dict):
             for k in ("shadow_rays", "height_samples", "dem_fetches", "mip_fetches", "kernel_ms", "launches"):

@@ -120,3 +120,57 @@ def illumination_statistics(rt, lat, lon, start, days, step_min=60, n_az=256, n_
     finally:
         buf.free()
     return IlluminationStatistics(out[:, 0], out[:, 1], out[:, 2], out[:, 3].astype(np.float64) * (step_min / 60.0), times, stats)
+
+
+class SurfaceTemperatures(NamedTuple):
+    t_max: np.ndarray             # (N,) highest surface temperature over the recorded dates, K
+    t_min: np.ndarray             # (N,) lowest, K
+    t_mean: np.ndarray            # (N,) mean, K
+    t_bottom_mean: np.ndarray     # (N,) mean of the column's bottom node over the recorded dates, K
+    times: list                   # the recorded dates (the spin-up dates precede them)
+    stats: dict                   # summed counters and kernel times of the horizon and the thermal calls
+
+
+def surface_temperatures(rt, lat, lon, start, days, step_min=60, spinup_lunations=None, n_az=256, n_bis=14, observer=None,
+                         chunk=65536, thermal=None):
+    """Regolith surface temperatures of the points (lat, lon in degrees) from `start` (timezone-aware) over `days` at
+    `step_min` minutes.  The column is spun up over `spinup_lunations` lunations of dates before
+    `start` (default thermal.SPINUP_LUNATIONS), stepped but not recorded.  Each point's horizon is computed once
+    (MoonRT.horizon); points are streamed `chunk` at a time and their horizons stay in a device buffer.  `thermal` replaces
+    rt.surface_temperature (same signature; it then receives the horizons as a host array).  Returns SurfaceTemperatures."""
+    from . import thermal as th
+    la = np.atleast_1d(np.asarray(lat, np.float64)).ravel()
+    lo = np.atleast_1d(np.asarray(lon, np.float64)).ravel()
+    if la.shape != lo.shape:
+        raise ValueError("lat and lon must have the same number of points")
+    m_rec = int(round(days * 1440.0 / step_min))
+    if m_rec < 1:
+        raise ValueError("days / step_min gives no date")
+    spin = th.SPINUP_LUNATIONS if spinup_lunations is None else int(spinup_lunations)
+    model = rt.thermal_grid(step_min * 60.0, spin, min(th.RESETS, spin))
+    n_spin = int(model.n_spin)
+    step = timedelta(minutes=float(step_min))
+    all_times = [start + (k - n_spin) * step for k in range(n_spin + m_rec)]
+    ep = ephemeris.sun_epochs(all_times, observer)
+    fl = ephemeris.sun_flux(all_times)
+    rt.horizon_azimuths(n_az)       # checks n_az
+    chunk = max(1, min(int(chunk), la.size, (1 << 31) // int(n_az)))
+    out = np.empty((la.size, 4), np.float32)
+    stats = {}
+    if thermal is not None:
+        for a in range(0, la.size, chunk):
+            b = min(a + chunk, la.size)
+            hz = rt.horizon(la[a:b], lo[a:b], n_az=n_az, n_bis=n_bis, stats=stats)
+            out[a:b] = thermal(la[a:b], lo[a:b], hz, ep, fl, model=model, mode="summary", stats=stats, n_az=n_az)
+    else:
+        from .renderer import DeviceBuffer
+        buf = DeviceBuffer(chunk * int(n_az) * 4, rt.config()["device"])
+        try:
+            for a in range(0, la.size, chunk):
+                b = min(a + chunk, la.size)
+                rt.horizon(la[a:b], lo[a:b], n_az=n_az, n_bis=n_bis, stats=stats, out=buf)
+                out[a:b] = rt.surface_temperature(la[a:b], lo[a:b], buf, ep, fl, model=model, mode="summary", stats=stats,
+                                                  n_az=n_az)
+        finally:
+            buf.free()
+    return SurfaceTemperatures(out[:, 0], out[:, 1], out[:, 2], out[:, 3], all_times[n_spin:], stats)
