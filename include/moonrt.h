@@ -359,6 +359,39 @@ int mrtx_thermal(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t n_a
                  const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux_Wm2, int32_t m,
                  const MrtxThermalModel* model, int32_t mode, void* dev_out, float* host_out, MrtxStats* out);
 
+/* ---- Terrain-scattered sunlight and infrared (additive to ABI 7) -----------------------------------
+ * One bounce: a point's hemisphere is sampled with K fixed cosine-weighted rays; each terrain hit becomes a point with its own
+ * horizon and column, whose per-epoch exitance (reflected sunlight + thermal emission) drives the first point's column as an
+ * extra absorbed flux: Q_sec = the mean over the K rays of (1 - A_h) M_vis + eps M_ir, sky rays adding 0. */
+/* The K (uh1, uh2) pairs of the view directions: uh1 = (j + 1/2) / K, uh2 = frac(j * 0.6180339887498949), float64 rounded once
+ * to float32; K in {16, 32, ..., 1024}.  out2: 2K floats. */
+int mrtx_view_dir_samples(int32_t k, float* out2);
+/* Per point (latlon_deg: n (lat, lon) pairs, degrees) the K view rays from the lifted vertex of mrtx_horizon_points, mapped
+ * about the normal as a path's continuation ray is and marched and refined as it is.  Output (exactly one of dev_out and
+ * host_out): n x K float2 (lat, lon) in degrees of each ray's first terrain hit, NaN for a ray that leaves the bounding sphere,
+ * point-major; then n float32 terrain view factors (hits / K).  Needs a DEM; leaves the light, Moon frame and render state as
+ * they were.  With MRTX_F_COUNT_STATS: bounce_rays (= n K), height_samples (5 per ray for its vertex + every march step + the
+ * bisections of a hit), dem_fetches, mip_fetches. */
+int mrtx_view_hits(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t k, void* dev_out, float* host_out,
+                   MrtxStats* out);
+/* The gather: Q_sec[p][e] = (1/K) sum over j = 0 .. K-1 with index[p][j] >= 0, in that order, of
+ * (1 - albedo_h) M_vis + emissivity M_ir of hit index[p][j] at epoch e, float32 (section 3.11).  index: n x K int32 host table
+ * into the hit list, -1 for sky; exitance (exactly one of dev_exitance and host_exitance, exitance_len floats available):
+ * n_hits x m float2 (M_vis, M_ir), point-major, as mrtx_thermal_scatter's EXITANCE writes it.  Output: n x m float32,
+ * point-major, into exactly one of dev_out and host_out. */
+int mrtx_scatter_flux(mrtx_ctx* ctx, const int32_t* index, int32_t n, int32_t k, const void* dev_exitance,
+                      const float* host_exitance, int64_t exitance_len, int32_t n_hits, int32_t m, double albedo_h,
+                      double emissivity, void* dev_out, float* host_out, MrtxStats* out);
+/* mrtx_thermal with two additions (MrtxThermalModel and mrtx_thermal are unchanged).  An optional extra absorbed flux, n x m
+ * float32 point-major (exactly one of dev_extra and host_extra, at least extra_len >= n x m entries, or neither: then every
+ * mode equals mrtx_thermal's bit for bit), is added to Q_abs in every epoch, spin-up and the start included; FLUX reports the
+ * sum.  mode 3 (EXITANCE): n x (m - n_spin) float2 (M_vis, M_ir) per recorded epoch k: M_vis = A(theta) S_k f max(mu, 0) the
+ * sunlight the facet reflects in epoch k, M_ir = eps sigma T0^4 with T0 the surface temperature after epoch k's steps. */
+int mrtx_thermal_scatter(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t n_az, const void* dev_horizon,
+                         const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux_Wm2, int32_t m,
+                         const MrtxThermalModel* model, int32_t mode, const void* dev_extra, const float* host_extra,
+                         int64_t extra_len, void* dev_out, float* host_out, MrtxStats* out);
+
 /* Math conformance probe (ABI 7): the kernels' domain-restricted reciprocal (v_rcp_f32 + Newton steps) and square root (v_sqrt_f32 + a
  * +-1 ulp residual fix) against the compiler's IEEE expansions of 1.0f / x and sqrtf(x), ON THE DEVICE, for the n float bit patterns
  * from lo_bits on: which = 0 one Newton step, 1 two steps (what the kernels use), 2 the square root.  mismatches = how many differ;

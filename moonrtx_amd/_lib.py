@@ -133,6 +133,12 @@ SIGNATURES = {
                                    C.POINTER(MrtxStats)]),
     "mrtx_thermal": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                C.POINTER(MrtxStats)]),
+    "mrtx_view_dir_samples": (C.c_int, [C.c_int32, _VP]),
+    "mrtx_view_hits": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_scatter_flux": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_double,
+                                    C.c_double, _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_thermal_scatter": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
+                                       C.c_int64, _VP, _VP, C.POINTER(MrtxStats)]),
 }
 
 _lib = None

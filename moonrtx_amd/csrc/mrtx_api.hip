@@ -57,6 +57,9 @@ hipError_t mrtx_launch_illum_series(const FrameC& f, IllumSeriesC q, bool stats,
 hipError_t mrtx_launch_horizon(const FrameC& f, HorizonC h, bool stats, hipStream_t st);
 hipError_t mrtx_launch_horizon_sun(const FrameC& f, HorizonSunC q, hipStream_t st);
 hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, hipStream_t st);
+hipError_t mrtx_launch_thermal_scatter(const FrameC& f, const ThermalC& q, hipStream_t st);
+hipError_t mrtx_launch_view_hits(const FrameC& f, const ViewC& q, bool stats, hipStream_t st);
+hipError_t mrtx_launch_scatter_flux(const ScatterC& q, hipStream_t st);
 
 struct mrtx_ctx {
     MrtxConfig cfg{};
@@ -1613,15 +1616,32 @@ static int thermal_model_ok(mrtx_ctx* c, const MrtxThermalModel& md, int32_t m, 
     return MRTX_OK;
 }
 
-int mrtx_thermal(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon, const float* host_horizon,
-                 const MrtxIllumEpoch* epochs, const double* flux, int32_t m, const MrtxThermalModel* model, int32_t mode,
-                 void* dev_out, float* host_out, MrtxStats* out) {
+// mrtx_thermal and, with ext, mrtx_thermal_scatter (section 3.11: mode 3 EXITANCE and the extra flux table, exactly one of
+// dev_extra and host_extra or neither, with at least n x m entries)
+static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon,
+                       const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux, int32_t m,
+                       const MrtxThermalModel* model, int32_t mode, void* dev_out, float* host_out, MrtxStats* out, bool ext,
+                       const void* dev_extra, const float* host_extra, int64_t extra_len) {
     if (!c) return MRTX_E_INVALID;
     if (!latlon || !epochs || !flux || !model) return fail(c, MRTX_E_INVALID, "null point list, epoch table, flux or model");
     if (n < 1 || m < 1) return fail(c, MRTX_E_INVALID, "n and m must be >= 1 (got %d, %d)", n, m);
     if (m > (1 << 24)) return fail(c, MRTX_E_INVALID, "at most 2^24 epochs per call (got %d)", m);
     if (!horizon_az_ok(n_az)) return fail(c, MRTX_E_INVALID, "n_az must be 4, 8, ..., 4096 (got %d)", n_az);
-    if (mode < 0 || mode > 2) return fail(c, MRTX_E_INVALID, "mode must be 0 (FULL), 1 (SUMMARY) or 2 (FLUX) (got %d)", mode);
+    if (!ext && (mode < 0 || mode > 2))
+        return fail(c, MRTX_E_INVALID, "mode must be 0 (FULL), 1 (SUMMARY) or 2 (FLUX) (got %d)", mode);
+    if (ext && (mode < 0 || mode > 3))
+        return fail(c, MRTX_E_INVALID, "mode must be 0 (FULL), 1 (SUMMARY), 2 (FLUX) or 3 (EXITANCE) (got %d)", mode);
+    if (dev_extra && host_extra) return fail(c, MRTX_E_INVALID, "give at most one of dev_extra and host_extra");
+    const bool have_extra = dev_extra || host_extra;
+    if (have_extra && extra_len < (int64_t)n * (int64_t)m)
+        return fail(c, MRTX_E_INVALID, "the extra-flux table holds %lld entries, fewer than n x m = %lld", (long long)extra_len,
+                    (long long)n * (long long)m);
+    if (host_extra) {
+        const size_t ne = (size_t)n * (size_t)m;
+        for (size_t i = 0; i < ne; i++)
+            if (!(std::isfinite(host_extra[i]) && host_extra[i] >= 0.0f))
+                return fail(c, MRTX_E_INVALID, "extra-flux entry %zu must be finite and >= 0 (got %g)", i, (double)host_extra[i]);
+    }
     if ((dev_horizon == nullptr) == (host_horizon == nullptr))
         return fail(c, MRTX_E_INVALID, "give exactly one of dev_horizon and host_horizon");
     if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
@@ -1630,7 +1650,7 @@ int mrtx_thermal(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, con
     double dmax = 0.0;
     int rc = thermal_model_ok(c, md, m, mode, &dmax);
     if (rc != MRTX_OK) return rc;
-    const int64_t width = mode == 0 ? (int64_t)m - md.n_spin : mode == 2 ? (int64_t)m : 4;
+    const int64_t width = mode == 0 ? (int64_t)m - md.n_spin : mode == 2 ? (int64_t)m : mode == 3 ? 2 * ((int64_t)m - md.n_spin) : 4;
     if ((int64_t)n * width > (int64_t)1 << 31)
         return fail(c, MRTX_E_INVALID, "a call holds at most 2^31 outputs: split the points into more calls");
     double s_max = 0.0;
@@ -1668,7 +1688,8 @@ int mrtx_thermal(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, con
     std::vector<float> fl((size_t)m);
     for (int32_t k = 0; k < m; k++) fl[k] = (float)flux[k];
     const size_t nh = host_horizon ? (size_t)n * (size_t)n_az : 0;
-    const size_t tab_bytes = (tab.size() + lights.size() + fl.size() + nh) * sizeof(float);
+    const size_t nx = host_extra ? (size_t)n * (size_t)m : 0;
+    const size_t tab_bytes = (tab.size() + lights.size() + fl.size() + nh + nx) * sizeof(float);
     const size_t out_bytes = (size_t)n * (size_t)width * sizeof(float);
     if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, tab_bytes)) != MRTX_OK) return rc;
     if (!dev_out) {
@@ -1683,6 +1704,8 @@ int mrtx_thermal(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, con
     HIPCHK(c, hipMemcpyAsync(d_lights, lights.data(), lights.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_flux, fl.data(), fl.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (nh) HIPCHK(c, hipMemcpyAsync(d_hz, host_horizon, nh * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    float* const d_x = d_hz + nh;
+    if (nx) HIPCHK(c, hipMemcpyAsync(d_x, host_extra, nx * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
     ThermalC q;
     std::memset(&q, 0, sizeof q);
@@ -1690,6 +1713,7 @@ int mrtx_thermal(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, con
     q.g.rows = n; q.g.cols = n; q.g.points = 1;
     q.horizon = nh ? d_hz : (const float*)dev_horizon;
     q.lights = d_lights; q.flux = d_flux; q.out = (float*)dev_out; q.caps = c->illum_stats;
+    q.xflux = nx ? d_x : (const float*)dev_extra;
     q.az_log2 = log2_of(n_az); q.m = m; q.mode = mode;
     const int nn = md.n_nodes;
     q.n_nodes = nn; q.n_sub = md.n_sub; q.n_spin = md.n_spin; q.block = md.block; q.n_reset = md.n_reset; q.ref = md.ref_node;
@@ -1707,7 +1731,8 @@ int mrtx_thermal(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, con
         if (i > 0 && i < nn - 1) q.a[i] = (float)(delta * 2.0 / (md.rho[i] * (md.dz[i - 1] + md.dz[i])));
     }
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    HIPCHK(c, mrtx_launch_thermal(f, q, c->stream));
+    if (ext) HIPCHK(c, mrtx_launch_thermal_scatter(f, q, c->stream));
+    else HIPCHK(c, mrtx_launch_thermal(f, q, c->stream));
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     rc = horizon_finish(c, false, dev_out, host_out, out_bytes, out);
     if (rc != MRTX_OK) return rc;
@@ -1717,6 +1742,134 @@ int mrtx_thermal(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, con
         out->reserved = caps > 0xffffffffull ? 0xffffffffu : (uint32_t)caps;
     }
     return MRTX_OK;
+}
+
+int mrtx_thermal(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon, const float* host_horizon,
+                 const MrtxIllumEpoch* epochs, const double* flux, int32_t m, const MrtxThermalModel* model, int32_t mode,
+                 void* dev_out, float* host_out, MrtxStats* out) {
+    return thermal_run(c, latlon, n, n_az, dev_horizon, host_horizon, epochs, flux, m, model, mode, dev_out, host_out, out, false,
+                       nullptr, nullptr, 0);
+}
+
+int mrtx_thermal_scatter(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon,
+                         const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux, int32_t m,
+                         const MrtxThermalModel* model, int32_t mode, const void* dev_extra, const float* host_extra,
+                         int64_t extra_len, void* dev_out, float* host_out, MrtxStats* out) {
+    return thermal_run(c, latlon, n, n_az, dev_horizon, host_horizon, epochs, flux, m, model, mode, dev_out, host_out, out, true,
+                       dev_extra, host_extra, extra_len);
+}
+
+// ---- Terrain-scattered sunlight and infrared -------------------------------------------------------
+static bool view_k_ok(int32_t k) { return k >= 16 && k <= 1024 && (k & (k - 1)) == 0; }
+
+int mrtx_view_dir_samples(int32_t k, float* out2) {
+    if (!view_k_ok(k) || !out2) return MRTX_E_INVALID;
+    for (int32_t j = 0; j < k; j++) {
+        const double t = (double)j * 0.6180339887498949;
+        out2[2 * j] = (float)(((double)j + 0.5) / (double)k);
+        out2[2 * j + 1] = (float)(t - std::floor(t));
+    }
+    return MRTX_OK;
+}
+
+int mrtx_view_hits(mrtx_ctx* c, const double* latlon, int32_t n, int32_t k, void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!latlon) return fail(c, MRTX_E_INVALID, "null point list");
+    if (n < 1) return fail(c, MRTX_E_INVALID, "n must be >= 1 (got %d)", n);
+    if (!view_k_ok(k)) return fail(c, MRTX_E_INVALID, "K must be 16, 32, ..., 1024 (got %d)", k);
+    if ((int64_t)n * (2 * (int64_t)k + 1) > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "a call holds at most 2^31 outputs: split the points into more calls");
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    std::vector<float> tab;
+    int rc = point_tables(c, latlon, n, tab);
+    if (rc != MRTX_OK) return rc;
+    FrameC f;
+    FrameCold cold;
+    if ((rc = horizon_frame(c, f, cold, true)) != MRTX_OK) return rc;
+    const bool stats = (c->prm.flags & MRTX_F_COUNT_STATS) != 0;
+    // one device block: point tables (4 floats per point), then the K direction pairs
+    tab.resize(tab.size() + 2 * (size_t)k);
+    mrtx_view_dir_samples(k, tab.data() + 4 * (size_t)n);
+    const size_t tab_bytes = tab.size() * sizeof(float), out_bytes = (size_t)n * (2 * (size_t)k + 1) * sizeof(float);
+    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, tab_bytes)) != MRTX_OK) return rc;
+    if (!dev_out) {
+        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, out_bytes)) != MRTX_OK) return rc;
+        dev_out = c->illum_out;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->illum_cold, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->illum_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+    if (stats) HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
+    ViewC q;
+    std::memset(&q, 0, sizeof q);
+    q.g.rtab = c->illum_tab; q.g.ctab = c->illum_tab + 2 * (size_t)n;
+    q.g.rows = n; q.g.cols = n; q.g.points = 1;
+    q.dirs = c->illum_tab + 4 * (size_t)n;
+    q.out = (float*)dev_out; q.K = k;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    HIPCHK(c, mrtx_launch_view_hits(f, q, stats, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    rc = horizon_finish(c, false, dev_out, host_out, out_bytes, out);
+    if (rc != MRTX_OK) return rc;
+    if (out && stats) {
+        unsigned long long h[16];
+        HIPCHK(c, hipMemcpy(h, c->illum_stats, sizeof h, hipMemcpyDeviceToHost));
+        out->bounce_rays = h[8]; out->height_samples = h[3]; out->dem_fetches = h[6]; out->mip_fetches = h[7];
+    }
+    return MRTX_OK;
+}
+
+int mrtx_scatter_flux(mrtx_ctx* c, const int32_t* index, int32_t n, int32_t k, const void* dev_exitance,
+                      const float* host_exitance, int64_t exitance_len, int32_t n_hits, int32_t m, double albedo_h,
+                      double emissivity, void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!index) return fail(c, MRTX_E_INVALID, "null index table");
+    if (n < 1 || m < 1 || n_hits < 0) return fail(c, MRTX_E_INVALID, "need n >= 1, m >= 1 and n_hits >= 0 (got %d, %d, %d)", n, m, n_hits);
+    if (!view_k_ok(k)) return fail(c, MRTX_E_INVALID, "K must be 16, 32, ..., 1024 (got %d)", k);
+    if (!(std::isfinite(albedo_h) && albedo_h >= 0.0 && albedo_h < 1.0))
+        return fail(c, MRTX_E_INVALID, "the hemispherical albedo must be finite and in [0, 1) (got %g)", albedo_h);
+    if (!(std::isfinite(emissivity) && emissivity > 0.0 && emissivity <= 1.0))
+        return fail(c, MRTX_E_INVALID, "the emissivity must be finite and in (0, 1] (got %g)", emissivity);
+    if ((dev_exitance == nullptr) == (host_exitance == nullptr))
+        return fail(c, MRTX_E_INVALID, "give exactly one of dev_exitance and host_exitance");
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    if ((int64_t)n * (int64_t)m > (int64_t)1 << 31 || (int64_t)n_hits * (int64_t)m > (int64_t)1 << 30)
+        return fail(c, MRTX_E_INVALID, "a call holds at most 2^31 outputs and 2^30 exitance pairs: split the targets");
+    if (exitance_len < 2 * (int64_t)n_hits * (int64_t)m)
+        return fail(c, MRTX_E_INVALID, "the exitance table holds %lld floats, fewer than n_hits x m x 2 = %lld",
+                    (long long)exitance_len, 2 * (long long)n_hits * (long long)m);
+    const size_t ni = (size_t)n * (size_t)k;
+    for (size_t i = 0; i < ni; i++)
+        if (index[i] < -1 || index[i] >= n_hits)
+            return fail(c, MRTX_E_INVALID, "index entry %zu = %d lies outside the hit list [0, %d) (-1: sky)", i, index[i], n_hits);
+    if (host_exitance) {
+        const size_t ne = (size_t)n_hits * (size_t)m * 2;
+        for (size_t i = 0; i < ne; i++)
+            if (!(std::isfinite(host_exitance[i]) && host_exitance[i] >= 0.0f))
+                return fail(c, MRTX_E_INVALID, "exitance entry %zu must be finite and >= 0", i);
+    }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    // one device block: the index table (padded to 4 entries), then the host exitance
+    const size_t ni4 = (ni + 3) & ~(size_t)3, ne = host_exitance ? (size_t)n_hits * (size_t)m * 2 : 0;
+    const size_t tab_bytes = (ni4 + ne) * 4, out_bytes = (size_t)n * (size_t)m * sizeof(float);
+    int rc;
+    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, std::max(tab_bytes, (size_t)16))) != MRTX_OK) return rc;
+    if (!dev_out) {
+        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, out_bytes)) != MRTX_OK) return rc;
+        dev_out = c->illum_out;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->illum_tab, index, ni * 4, hipMemcpyHostToDevice, c->stream));
+    if (ne) HIPCHK(c, hipMemcpyAsync(c->illum_tab + ni4, host_exitance, ne * 4, hipMemcpyHostToDevice, c->stream));
+    ScatterC q;
+    std::memset(&q, 0, sizeof q);
+    q.idx = reinterpret_cast<const int32_t*>(c->illum_tab);
+    q.ex = host_exitance ? c->illum_tab + ni4 : (const float*)dev_exitance;
+    q.out = (float*)dev_out;
+    q.n = n; q.K = k; q.m = m; q.chunks = (m + 63) / 64;
+    q.omah = (float)(1.0 - albedo_h); q.eps = (float)emissivity; q.inv_k = (float)(1.0 / k);
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    HIPCHK(c, mrtx_launch_scatter_flux(q, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    return horizon_finish(c, false, dev_out, host_out, out_bytes, out);
 }
 
 int mrtx_samples_done(mrtx_ctx* c, uint32_t* out) {

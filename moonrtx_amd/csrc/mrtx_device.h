@@ -246,4 +246,24 @@ struct ThermalC {
     float hdz[MRTX_THERMAL_NODES];  // 0.5 / dz_i: link i joins nodes i and i + 1 (its k is the mean of theirs)
     float a[MRTX_THERMAL_NODES];    // Delta x 2 / (rho_i (dz_{i-1} + dz_i)), interior nodes
     float qdz[MRTX_THERMAL_NODES];  // Q x dz_i: the steady step of link i (the bottom node's step: i = N - 2)
+    // thermal_kernel<EXT = true> only (mrtx_thermal_scatter, section 3.11); mode 3 (EXITANCE) writes n x (m - n_spin) float2
+    const float* xflux;             // null, or n x m float32 extra absorbed flux, point-major
+};
+
+// What terrain a point sees (mrtx_view_hits).
+struct ViewC {
+    IllumC g;                   // the point list (g.rows points), as in HorizonC
+    const float* dirs;          // K (uh1, uh2) pairs
+    float* out;                 // n x K float2 (lat, lon) of the hits, degrees (NaN: sky), then n float32 terrain shares
+    int32_t K;                  // 16, 32, ..., 1024
+};
+
+// The gather of the scattered flux (mrtx_scatter_flux, section 3.11).
+struct ScatterC {
+    const int32_t* idx;         // n x K indices into the hit list, -1: sky
+    const float* ex;            // n_hits x m float2 (M_vis, M_ir)
+    float* out;                 // n x m float32 Q_sec, point-major
+    int32_t n, K, m;
+    int32_t chunks;             // (m + 63) / 64
+    float omah, eps, inv_k;     // 1 - A_h, emissivity, 1 / K
 };

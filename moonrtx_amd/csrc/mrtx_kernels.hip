@@ -2321,7 +2321,11 @@ __global__ void __launch_bounds__(64) horizon_sun_kernel(const FrameC f, const H
 // tables are the kernel arguments' (wave-uniform, scalar loads); the node loops are unrolled to MRTX_THERMAL_NODES with a
 // wave-uniform bound, so every index is a constant and the column never leaves the registers.  Lanes past the last point
 // repeat it and store nothing.
-template <bool WIDE>
+// EXT (section 3.11, mrtx_thermal_scatter): the same column with two additions -- an extra absorbed flux q.xflux[pt][k] added
+// to Q_abs in every epoch (spin-up and the start included), and mode 3 (EXITANCE), which records per epoch the reflected
+// sunlight M_vis = A(theta) S f max(mu, 0) and the emission eps sigma T0^4 after the epoch's steps.  EXT = false is the
+// mrtx_thermal kernel unchanged.
+template <bool WIDE, bool EXT>
 __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const ThermalC q) {
     constexpr int NN = MRTX_THERMAL_NODES;
     constexpr float kDeg = 57.2957795130823209f;
@@ -2341,26 +2345,34 @@ __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const Therm
     const float oa = fmaf(eps, v.na, v.pa), ob = fmaf(eps, v.nb, v.pb), oc = fmaf(eps, v.nc, v.pc);
     const float* const hz = q.horizon + ((int64_t)pt << q.az_log2);
     const float4* const lights = reinterpret_cast<const float4*>(q.lights);
-    // Q_abs of epoch k: (1 - A(theta)) S_k f max(mu, 0), exactly 0 when f == 0 or mu <= 0
-    auto absorbed = [&](int k) -> float {
+    // Q_abs of epoch k: (1 - A(theta)) S_k f max(mu, 0), exactly 0 when f == 0 or mu <= 0; EXT: mv = A(theta) S_k f max(mu, 0)
+    auto sunlit = [&](int k, float& mv) -> float {
         float la, lb, lc;
         const float fr = disc_fraction(lights[2 * (int64_t)k], oa, ob, oc, ua, ub, uc, Na, Nb, Nc, ct, hz, n_az, la, lb, lc);
         const float mu = fmaf(v.nc, lc, fmaf(v.nb, lb, v.na * la));      // illum_mu's expression
-        if (!(fr > 0.0f) || !(mu > 0.0f)) return 0.0f;
+        if (!(fr > 0.0f) || !(mu > 0.0f)) { mv = 0.0f; return 0.0f; }
         const float th = acosf(fminf(mu, 1.0f)) * kDeg;
         const float x = th * (1.0f / 45.0f), y = th * (1.0f / 90.0f);
         const float y2 = y * y, y4 = y2 * y2;
         const float A = fmaf(q.alb[2], y4 * y4, fmaf(q.alb[1], x * x * x, q.alb[0]));
+        if constexpr (EXT) mv = ((A * q.flux[k]) * fr) * mu;
         return (((1.0f - A) * q.flux[k]) * fr) * mu;
     };
+    // what drives the surface in epoch k: Q_abs, plus EXT's extra flux
+    auto absorbed = [&](int k, float& mv) -> float {
+        const float qa = sunlit(k, mv);
+        if constexpr (EXT) return q.xflux ? qa + q.xflux[(int64_t)pt * q.m + k] : qa;
+        return qa;
+    };
+    float mv = 0.0f;
     if (q.mode == 2) {
         if (in)
-            for (int k = 0; k < q.m; k++) q.out[(int64_t)pt * q.m + k] = absorbed(k);
+            for (int k = 0; k < q.m; k++) q.out[(int64_t)pt * q.m + k] = absorbed(k, mv);
         return;
     }
     // the uniform start: ((<Q_abs> over the spin-up epochs + Q) / (eps sigma))^(1/4)
     double qs = 0.0;
-    for (int k = 0; k < q.n_spin; k++) qs += (double)absorbed(k);
+    for (int k = 0; k < q.n_spin; k++) qs += (double)absorbed(k, mv);
     const double t_init = sqrt(sqrt(((q.n_spin > 0 ? qs / (double)q.n_spin : 0.0) + (double)q.q_geo) / (double)q.es));
     auto kof = [&](int i, double t) -> float {        // k_i(T) in float32
         const float tf = (float)t;
@@ -2396,7 +2408,7 @@ __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const Therm
     int in_block = 0, blocks = 0;
     const int m_rec = q.m - q.n_spin;
     for (int k = 0; k < q.m; k++) {
-        const float qa = absorbed(k);
+        const float qa = absorbed(k, mv);
         for (int s = 0; s < q.n_sub; s++) {
             // 1. interior nodes from the old values; link i's flux k_{i+1/2} (T_{i+1} - T_i) / dz_i, k of node i carried
             float k_lo = kof(0, T[0]), k_hi = kof(1, T[1]);
@@ -2459,6 +2471,11 @@ __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const Therm
             sum_s += (double)ts;
             sum_b += tb;
             if (in && q.mode == 0) q.out[(int64_t)pt * m_rec + (k - q.n_spin)] = ts;
+            if constexpr (EXT) {
+                if (in && q.mode == 3)
+                    reinterpret_cast<float2*>(q.out)[(int64_t)pt * m_rec + (k - q.n_spin)] =
+                        make_float2(mv, q.es * ((ts * ts) * (ts * ts)));
+            }
         }
     }
     if (in && q.mode == 1) {
@@ -2469,6 +2486,100 @@ __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const Therm
 #pragma unroll
     for (int s = 1; s < 64; s <<= 1) caps += __shfl_xor(caps, s, 64);
     if (lane == 0 && caps) atomicAdd(q.caps, (unsigned long long)caps);
+}
+
+// What terrain a point sees (DESIGN.md sections 3.11 and 4.12): per point K fixed cosine-weighted directions fed through
+// continue_path's mapping (sqrt_sh, sincos_turn, duff_basis) from the lifted origin, each marched and refined exactly as a
+// path's continuation ray, to the (lat, lon) of its first terrain hit or NaN when it leaves the bounding sphere.  One lane =
+// one (point, j), point-major: every lane forms its point's vertex (5 DEM taps) and marches one ray.  Measured 3-4x faster
+// than one lane per point looping over j (4.12): a lane's rays differ in length, so the loop left most lanes of a wave idle.
+// view_share_kernel then counts each point's hits.
+template <bool WIDE, bool STATS>
+__global__ void __launch_bounds__(64) view_hits_kernel(const FrameC f, const ViewC q) {
+    constexpr float kDeg = 57.2957795130823209f;
+    const int lane = threadIdx.x;
+    const int64_t gid = (int64_t)blockIdx.x * 64 + lane;
+    uint32_t cnt_store[STATS ? ST_N : 1];
+    uint32_t* const cnt = STATS ? cnt_store : nullptr;
+    if (STATS) {
+#pragma unroll
+        for (int i = 0; i < ST_N; i++) cnt[i] = 0;
+    }
+    if (gid < (int64_t)q.g.rows * q.K) {
+        const int pt = (int)(gid / q.K), j = (int)(gid % q.K);
+        Vertex v;
+        (void)illum_vertex<STATS, WIDE>(f, q.g, pt, pt, v, cnt);    // g.points = 1: both tables indexed by the point
+        float b1a, b1b, b1c, b2a, b2b, b2c;
+        duff_basis(v.na, v.nb, v.nc, b1a, b1b, b1c, b2a, b2b, b2c);
+        const float eps = CF(f)->scene_eps;
+        const float oa = fmaf(eps, v.na, v.pa), ob = fmaf(eps, v.nb, v.pb), oc = fmaf(eps, v.nc, v.pc);
+        const float2 uh = reinterpret_cast<const float2*>(q.dirs)[j];
+        const float rr = sqrt_sh(uh.x), zz = sqrt_sh(1.0f - uh.x);
+        float cph, sph;
+        sincos_turn(uh.y, cph, sph);
+        const float xx = rr * cph, yy = rr * sph;
+        const float da = fmaf(zz, v.na, fmaf(yy, b2a, xx * b1a));
+        const float db = fmaf(zz, v.nb, fmaf(yy, b2b, xx * b1b));
+        const float dc = fmaf(zz, v.nc, fmaf(yy, b2c, xx * b1c));
+        if (STATS) cnt[ST_BOUNCE]++;
+        Seg sg;
+        float hi = 0.0f;
+        float2 o = make_float2(__builtin_nanf(""), __builtin_nanf(""));
+        if (march<WIDE, false, STATS, MRTX_STEP_BATCH>(f, oa, ob, oc, da, db, dc, 0.0f, sg, hi, cnt)) {
+            const int bk = (int)rintf(hi * f.inv_step);
+            float lo = (float)(bk - 1) * f.step;
+            refine<WIDE>(f, sg, oa, ob, oc, da, db, dc, lo, hi);
+            if (STATS) { cnt[ST_HEIGHT] += (uint32_t)f.nbis; cnt[ST_FETCH] += (uint32_t)f.nbis; }
+            const float ha = fmaf(lo, da, oa), hb = fmaf(lo, db, ob), hc = fmaf(lo, dc, oc);
+            float lat, lon;
+            latlon(ha, hb, hc, fmaf(hb, hb, ha * ha), lat, lon);
+            o = make_float2(lat * kDeg, lon * kDeg);
+        }
+        reinterpret_cast<float2*>(q.out)[gid] = o;
+    }
+    if (STATS) {
+        const int which[4] = {ST_BOUNCE, ST_HEIGHT, ST_FETCH, ST_MIP};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            uint32_t c = cnt[which[i]];
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) c += __shfl_xor(c, m, 64);
+            if (lane == 0) atomicAdd(&CF(f)->stats[which[i]], (unsigned long long)c);
+        }
+    }
+}
+
+// The terrain share of each point: its hits (non-NaN latitudes) over K, exact for a power of two.  One lane per point.
+__global__ void __launch_bounds__(64) view_share_kernel(const ViewC q) {
+    const int pt = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    if (pt >= q.g.rows) return;
+    const float2* const row = reinterpret_cast<const float2*>(q.out) + (int64_t)pt * q.K;
+    int n_hit = 0;
+    for (int j = 0; j < q.K; j++) n_hit += row[j].x == row[j].x ? 1 : 0;
+    q.out[2 * (int64_t)q.g.rows * q.K + pt] = (float)n_hit / (float)q.K;
+}
+
+// The gather of section 3.11: Q_sec[p][k] = (1/K) sum over j = 0, 1, ..., K - 1 with idx[p][j] >= 0, in that order, of
+// ((1 - A_h) M_vis + eps M_ir) of hit idx[p][j] at epoch k, each term and each partial sum rounded to float32 (no fused
+// multiply-add).  Lane = epoch: one block = 64 consecutive epochs of one target, so the hit's row is read contiguously and the
+// index row is wave-uniform (scalar loads).
+__global__ void __launch_bounds__(64) scatter_flux_kernel(const ScatterC q) {
+    const int64_t b = blockIdx.x;
+    const int p = (int)(b / q.chunks);
+    const int k = (int)(b % q.chunks) * 64 + (int)threadIdx.x;
+    if (k >= q.m) return;
+    const int32_t* const ix = q.idx + (int64_t)p * q.K;
+    const float2* const ex = reinterpret_cast<const float2*>(q.ex);
+    float s = 0.0f;
+    for (int j = 0; j < q.K; j++) {
+        const int h = ix[j];
+        if (h >= 0) {
+            const float2 e = ex[(int64_t)h * q.m + k];
+            const float t = q.omah * e.x, u = q.eps * e.y;
+            s = s + (t + u);
+        }
+    }
+    q.out[(int64_t)p * q.m + k] = s * q.inv_k;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3825,8 +3936,47 @@ hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, hipStream_t s
         !q.out || !q.caps)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)((q.g.rows + 63) / 64)), block(64);
-    if (f.dem_wide) hipLaunchKernelGGL((mrtx::thermal_kernel<true>), grid, block, 0, st, f, q);
-    else hipLaunchKernelGGL((mrtx::thermal_kernel<false>), grid, block, 0, st, f, q);
+    if (f.dem_wide) hipLaunchKernelGGL((mrtx::thermal_kernel<true, false>), grid, block, 0, st, f, q);
+    else hipLaunchKernelGGL((mrtx::thermal_kernel<false, false>), grid, block, 0, st, f, q);
+    return hipGetLastError();
+}
+
+// The same column with an extra absorbed flux and the EXITANCE mode (mrtx_thermal_scatter, section 3.11).
+hipError_t mrtx_launch_thermal_scatter(const FrameC& f, const ThermalC& q, hipStream_t st) {
+    if (q.g.rows < 1 || q.az_log2 < 2 || q.az_log2 > 12 || q.m < 1 || q.mode < 0 || q.mode > 3 || q.n_nodes < 3 ||
+        q.n_nodes > MRTX_THERMAL_NODES || q.n_sub < 1 || q.block < 1 || q.n_spin < 0 || q.n_reset < 0 || q.ref < 0 ||
+        q.ref >= q.n_nodes - 1 || (q.mode != 2 && q.n_spin >= q.m) || !q.g.points || !q.horizon || !q.lights || !q.flux ||
+        !q.out || !q.caps)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((q.g.rows + 63) / 64)), block(64);
+    if (f.dem_wide) hipLaunchKernelGGL((mrtx::thermal_kernel<true, true>), grid, block, 0, st, f, q);
+    else hipLaunchKernelGGL((mrtx::thermal_kernel<false, true>), grid, block, 0, st, f, q);
+    return hipGetLastError();
+}
+
+// View samples (view_hits_kernel): one lane per (point, j), 64 per wave; then the shares (view_share_kernel).
+hipError_t mrtx_launch_view_hits(const FrameC& f, const ViewC& q, bool stats, hipStream_t st) {
+    if (q.g.rows < 1 || q.K < 16 || q.K > 1024 || (q.K & (q.K - 1)) || !q.g.points || !q.dirs || !q.out ||
+        (int64_t)q.g.rows * q.K > 0x7fffffffLL)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((int64_t)q.g.rows * q.K + 63) / 64)), block(64);
+    if (stats) {
+        if (f.dem_wide) hipLaunchKernelGGL((mrtx::view_hits_kernel<true, true>), grid, block, 0, st, f, q);
+        else hipLaunchKernelGGL((mrtx::view_hits_kernel<false, true>), grid, block, 0, st, f, q);
+    } else {
+        if (f.dem_wide) hipLaunchKernelGGL((mrtx::view_hits_kernel<true, false>), grid, block, 0, st, f, q);
+        else hipLaunchKernelGGL((mrtx::view_hits_kernel<false, false>), grid, block, 0, st, f, q);
+    }
+    hipLaunchKernelGGL(mrtx::view_share_kernel, dim3((unsigned)((q.g.rows + 63) / 64)), block, 0, st, q);
+    return hipGetLastError();
+}
+
+// The gather (scatter_flux_kernel): one block of 64 lanes per (target, 64 epochs).
+hipError_t mrtx_launch_scatter_flux(const ScatterC& q, hipStream_t st) {
+    if (q.n < 1 || q.K < 1 || q.m < 1 || q.chunks != (q.m + 63) / 64 || !q.idx || !q.ex || !q.out) return hipErrorInvalidValue;
+    const int64_t blocks = (int64_t)q.n * q.chunks;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mrtx::scatter_flux_kernel, dim3((unsigned)blocks), dim3(64), 0, st, q);
     return hipGetLastError();
 }
 

@@ -471,6 +471,118 @@ class MoonRT:
         return res
 
     @staticmethod
+    def view_samples(k):
+        """The (uh1, uh2) float32 table of the k view directions of view_hits, (k, 2)."""
+        out = np.empty((int(k), 2), np.float32)
+        if _lib.load().mrtx_view_dir_samples(int(k), out.ctypes.data) != 0:
+            raise ValueError("K must be 16, 32, ..., 1024")
+        return out
+
+    def view_hits(self, lat_deg, lon_deg, k=64, stats=None, chunk_bytes=256 << 20):
+        """What terrain N points see: K fixed cosine-weighted rays per point, each marched as a path's
+        continuation ray.  Returns (hits, share): (N, K, 2) float32 (lat, lon) in degrees of each ray's first terrain hit, NaN
+        for sky, and (N,) float32 terrain view factors (hits / K).  Calls hold at most chunk_bytes of output each."""
+        la, lo = self._points(lat_deg, lon_deg)
+        k = int(k)
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        hits = np.empty((la.size, max(k, 0), 2), np.float32)
+        share = np.empty(la.size, np.float32)
+        width = 2 * max(k, 1) + 1
+        step = max(1, min(int(chunk_bytes) // (4 * width), (1 << 31) // width))
+        for a in range(0, max(la.size, 1), step):
+            b = min(a + step, la.size)
+            buf = np.empty((b - a) * width, np.float32) if b > a else np.empty(width, np.float32)
+            st = MrtxStats()
+            self._check(self._lib.mrtx_view_hits(self._ctx, pts[a:].ctypes.data, b - a, k, None, buf.ctypes.data, C.byref(st)),
+                        "mrtx_view_hits")
+            hits[a:b] = buf[:(b - a) * 2 * k].reshape(b - a, k, 2)
+            share[a:b] = buf[(b - a) * 2 * k:(b - a) * width]
+            self._add_stats(stats, st)
+            if isinstance(stats, dict):
+                stats["bounce_rays"] = stats.get("bounce_rays", 0) + int(st.bounce_rays)
+        return hits, share
+
+    def scatter_flux(self, index, exitance, albedo_h, emissivity, n_hits=None, m=None, out=None, stats=None):
+        """The gather of DESIGN.md section 3.11: (N, m) float32 Q_sec[p, e] = (1/K) sum over index[p, j] >= 0, in j order, of
+        (1 - albedo_h) M_vis + emissivity M_ir of that hit at epoch e.  `index`: (N, K) int32 into the hit list, -1 for sky;
+        `exitance`: the (n_hits, m, 2) float32 EXITANCE of surface_temperature_scatter, or a DeviceBuffer holding it (then
+        n_hits and m are required).  out = a DeviceBuffer of at least N * m * 4 bytes: Q_sec is written there, `out` returned."""
+        ix = np.ascontiguousarray(index, np.int32)
+        if ix.ndim != 2:
+            raise ValueError("index must be an (N, K) array")
+        n, k = ix.shape
+        if isinstance(exitance, DeviceBuffer):
+            if n_hits is None or m is None:
+                raise ValueError("n_hits and m are required with a device buffer")
+            n_hits, m = int(n_hits), int(m)
+            dev, host, length = exitance.ptr, None, exitance.nbytes // 4
+        else:
+            ex = np.ascontiguousarray(exitance, np.float32)
+            if ex.ndim != 3 or ex.shape[2] != 2:
+                raise ValueError("exitance must be an (n_hits, m, 2) array")
+            n_hits, m = ex.shape[0], ex.shape[1]
+            dev, host, length = None, ex.ctypes.data, ex.size
+        if out is not None and out.nbytes < n * m * 4:
+            raise ValueError("the device buffer is smaller than N x m float32")
+        res = np.empty((n, m), np.float32) if out is None else None
+        st = MrtxStats()
+        self._check(self._lib.mrtx_scatter_flux(self._ctx, ix.ctypes.data, n, k, dev, host, length, n_hits, m, float(albedo_h),
+                                                float(emissivity), None if out is None else out.ptr,
+                                                None if res is None else res.ctypes.data, C.byref(st)), "mrtx_scatter_flux")
+        self._add_stats(stats, st)
+        return out if out is not None else res
+
+    def surface_temperature_scatter(self, lat_deg, lon_deg, horizon, epochs, flux, model=None, mode="summary", extra_flux=None,
+                                    stats=None, n_az=None, out=None):
+        """surface_temperature with the additions of DESIGN.md section 3.11, in one call.  `extra_flux`: None, an (N, m)
+        float32 array or a DeviceBuffer holding one, added to Q_abs in every epoch.  Modes as surface_temperature's, plus
+        "exitance": (N, m - n_spin, 2) float32 (M_vis, M_ir) per recorded epoch.  out = a DeviceBuffer: the output is written
+        there and `out` returned."""
+        modes = {"full": 0, "summary": 1, "flux": 2, "exitance": 3}
+        if mode not in modes:
+            raise ValueError(f"mode must be one of {sorted(modes)} (got {mode!r})")
+        la, lo = self._points(lat_deg, lon_deg)
+        ep = self._epochs(epochs)
+        m = ep.shape[0]
+        fl = np.ascontiguousarray(np.asarray(flux, np.float64).ravel())
+        if fl.size != m:
+            raise ValueError("flux must hold one value per epoch")
+        model = self.thermal_grid() if model is None else model
+        if isinstance(horizon, DeviceBuffer):
+            if n_az is None:
+                raise ValueError("n_az is required with a device buffer")
+            n_az, dh, hh = int(n_az), horizon.ptr, None
+            if horizon.nbytes < la.size * n_az * 4:
+                raise ValueError("the device buffer is smaller than N x n_az float32")
+        else:
+            hz = np.ascontiguousarray(horizon, np.float32)
+            if hz.ndim != 2 or hz.shape[0] != la.size:
+                raise ValueError("horizon must be an (N, n_az) array")
+            n_az, dh, hh = hz.shape[1], None, hz.ctypes.data
+        dx = hx = None
+        x_len = 0
+        if isinstance(extra_flux, DeviceBuffer):
+            dx, x_len = extra_flux.ptr, extra_flux.nbytes // 4
+        elif extra_flux is not None:
+            xf = np.ascontiguousarray(extra_flux, np.float32)
+            hx, x_len = xf.ctypes.data, xf.size
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        rec = max(m - int(model.n_spin), 1)
+        shape = {"full": (la.size, rec), "summary": (la.size, 4), "flux": (la.size, m), "exitance": (la.size, rec, 2)}[mode]
+        if out is not None and out.nbytes < int(np.prod(shape)) * 4:
+            raise ValueError("the device buffer is smaller than the output")
+        res = np.empty(shape, np.float32) if out is None else None
+        st = MrtxStats()
+        self._check(self._lib.mrtx_thermal_scatter(self._ctx, pts.ctypes.data, la.size, n_az, dh, hh, ep.ctypes.data,
+                                                   fl.ctypes.data, m, C.byref(model), modes[mode], dx, hx, x_len,
+                                                   None if out is None else out.ptr, None if res is None else res.ctypes.data,
+                                                   C.byref(st)), "mrtx_thermal_scatter")
+        self._add_stats(stats, st)
+        if isinstance(stats, dict):
+            stats["newton_cap_hits"] = stats.get("newton_cap_hits", 0) + int(st.reserved)
+        return out if out is not None else res
+
+    @staticmethod
     def _add_stats(acc, st):
         if isinstance(acc, dict):
             for k in ("shadow_rays", "height_samples", "dem_fetches", "mip_fetches", "kernel_ms", "launches"):

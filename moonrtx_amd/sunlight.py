@@ -132,12 +132,17 @@ class SurfaceTemperatures(NamedTuple):
 
 
 def surface_temperatures(rt, lat, lon, start, days, step_min=60, spinup_lunations=None, n_az=256, n_bis=14, observer=None,
-                         chunk=65536, thermal=None):
+                         chunk=65536, thermal=None, scatter=0, budget_bytes=8 << 30, q_sec_mean=False, alloc=None):
     """Regolith surface temperatures of the points (lat, lon in degrees) from `start` (timezone-aware) over `days` at
     `step_min` minutes.  The column is spun up over `spinup_lunations` lunations of dates before
     `start` (default thermal.SPINUP_LUNATIONS), stepped but not recorded.  Each point's horizon is computed once
     (MoonRT.horizon); points are streamed `chunk` at a time and their horizons stay in a device buffer.  `thermal` replaces
-    rt.surface_temperature (same signature; it then receives the horizons as a host array).  Returns SurfaceTemperatures."""
+    rt.surface_temperature (same signature; it then receives the horizons as a host array).  Returns SurfaceTemperatures.
+
+    scatter = K > 0 adds the sunlight and infrared the surrounding terrain sends (section 3.11): K view rays per point, the
+    hits' own columns in EXITANCE mode, the gather and the points' columns with that extra flux.  Device tables stay under
+    about `budget_bytes` per group of points; `q_sec_mean` also returns each point's mean extra flux over the recorded dates
+    (stats["q_sec_mean"]; it downloads the flux).  `alloc(nbytes)` replaces the device allocation (tests)."""
     from . import thermal as th
     la = np.atleast_1d(np.asarray(lat, np.float64)).ravel()
     lo = np.atleast_1d(np.asarray(lon, np.float64)).ravel()
@@ -157,6 +162,9 @@ def surface_temperatures(rt, lat, lon, start, days, step_min=60, spinup_lunation
     chunk = max(1, min(int(chunk), la.size, (1 << 31) // int(n_az)))
     out = np.empty((la.size, 4), np.float32)
     stats = {}
+    if scatter:
+        return _scatter_temperatures(rt, la, lo, start, step, m_rec, model, n_az, n_bis, observer, chunk, int(scatter),
+                                     budget_bytes, q_sec_mean, alloc)
     if thermal is not None:
         for a in range(0, la.size, chunk):
             b = min(a + chunk, la.size)
@@ -174,3 +182,110 @@ def surface_temperatures(rt, lat, lon, start, days, step_min=60, spinup_lunation
         finally:
             buf.free()
     return SurfaceTemperatures(out[:, 0], out[:, 1], out[:, 2], out[:, 3], all_times[n_spin:], stats)
+
+
+def compact_hits(hits):
+    """The hit list of view_hits' (N, K, 2) output: (index (N, K) int32 into the list, -1 for sky; the hits' lat, lon as
+    float64), the hits numbered point-major."""
+    hit = ~np.isnan(hits[..., 0])
+    index = np.full(hit.shape, -1, np.int32)
+    index[hit] = np.arange(int(hit.sum()), dtype=np.int32)
+    return index, hits[..., 0][hit].astype(np.float64), hits[..., 1][hit].astype(np.float64)
+
+
+def scatter_groups(hit_counts, m_hits, m_targets, n_az, budget_bytes):
+    """Split the points of a chunk into consecutive groups [a, b) whose device tables stay within budget_bytes: per hit its
+    EXITANCE row (m_hits x 8 bytes) and horizon, per point its extra-flux row (m_targets x 4 bytes) and horizon -- and whose
+    hits' EXITANCE fits one call (at most 2^30 (M_vis, M_ir) pairs).  A group holds at least one point."""
+    per_hit = 8 * m_hits + 4 * n_az
+    per_pt = 4 * m_targets + 4 * n_az
+    max_hits = max(1, (1 << 30) // max(int(m_hits), 1))
+    groups, a, used, hits = [], 0, 0, 0
+    for i, h in enumerate(np.asarray(hit_counts, np.int64)):
+        need = int(h) * per_hit + per_pt
+        if i > a and (used + need > budget_bytes or hits + int(h) > max_hits):
+            groups.append((a, i))
+            a, used, hits = i, 0, 0
+        used += need
+        hits += int(h)
+    if a < len(hit_counts):
+        groups.append((a, len(hit_counts)))
+    return groups
+
+
+def _scatter_temperatures(rt, la, lo, start, step, m_rec, model, n_az, n_bis, observer, chunk, k, budget_bytes, q_sec_mean,
+                          alloc):
+    """surface_temperatures with scatter = K (section 3.11).  Per chunk of points: their view hits; per group of points that
+    fits the budget: their horizons, the hits' horizons, the hits' columns in EXITANCE mode over [own spin-up | the points'
+    spin-up | recorded], the gather, and the points' columns with the extra flux."""
+    import time
+    from . import thermal as th
+    rt.view_samples(k)              # checks K
+    n_spin = int(model.n_spin)
+    m_t = n_spin + m_rec
+    # the hits' epochs: their own spin-up, then the points' epochs (spin-up and recorded), which the hits record
+    times = [start + (i - 2 * n_spin) * step for i in range(2 * n_spin + m_rec)]
+    ep_h = ephemeris.sun_epochs(times, observer)
+    fl_h = ephemeris.sun_flux(times)
+    ep_t, fl_t = ep_h[n_spin:], fl_h[n_spin:]
+    a_h = th.albedo_hemispherical()
+    if alloc is None:
+        from .renderer import DeviceBuffer
+        device = rt.config()["device"]
+        alloc = lambda nbytes: DeviceBuffer(max(int(nbytes), 4), device)     # noqa: E731
+    out = np.empty((la.size, 4), np.float32)
+    stats = {"scatter_hits": 0, "view_factor": np.empty(la.size, np.float32), "stage_s": {}}
+    if q_sec_mean:
+        stats["q_sec_mean"] = np.zeros(la.size, np.float64)
+    stage = stats["stage_s"]
+
+    def timed(name, fn):
+        t0 = time.perf_counter()
+        r = fn()
+        stage[name] = stage.get(name, 0.0) + time.perf_counter() - t0
+        return r
+
+    chunk = max(1, min(int(chunk), la.size, (1 << 31) // (2 * k + 1)))
+    for a in range(0, la.size, chunk):
+        b = min(a + chunk, la.size)
+        hits, share = timed("view_hits", lambda: rt.view_hits(la[a:b], lo[a:b], k=k, stats=stats))
+        stats["view_factor"][a:b] = share
+        index, h_lat, h_lon = timed("compact", lambda: compact_hits(hits))
+        counts = (index >= 0).sum(axis=1)
+        first = np.concatenate([[0], np.cumsum(counts)])
+        for ga, gb in scatter_groups(counts, m_t, m_t, n_az, budget_bytes):
+            p0, p1 = a + ga, a + gb
+            h0, h1 = int(first[ga]), int(first[gb])
+            n_h = h1 - h0
+            stats["scatter_hits"] += n_h
+            bufs = []
+            try:
+                hz_t = alloc((p1 - p0) * n_az * 4)
+                bufs.append(hz_t)
+                timed("horizons", lambda: rt.horizon(la[p0:p1], lo[p0:p1], n_az=n_az, n_bis=n_bis, stats=stats, out=hz_t))
+                q = None
+                if n_h:
+                    hz_h = alloc(n_h * n_az * 4)
+                    bufs.append(hz_h)
+                    timed("hit_horizons", lambda: rt.horizon(h_lat[h0:h1], h_lon[h0:h1], n_az=n_az, n_bis=n_bis, stats=stats,
+                                                             out=hz_h))
+                    ex = alloc(n_h * m_t * 8)
+                    bufs.append(ex)
+                    timed("hit_columns", lambda: rt.surface_temperature_scatter(
+                        h_lat[h0:h1], h_lon[h0:h1], hz_h, ep_h, fl_h, model=model, mode="exitance", stats=stats, n_az=n_az,
+                        out=ex))
+                    q = alloc((p1 - p0) * m_t * 4)
+                    bufs.append(q)
+                    idx = np.where(index[ga:gb] >= 0, index[ga:gb] - h0, -1).astype(np.int32)
+                    timed("gather", lambda: rt.scatter_flux(idx, ex, a_h, th.EMISSIVITY, n_hits=n_h, m=m_t, out=q,
+                                                            stats=stats))
+                    if q_sec_mean:
+                        qs = q.download(np.float32, (p1 - p0, m_t))
+                        stats["q_sec_mean"][p0:p1] = qs[:, n_spin:].astype(np.float64).mean(axis=1)
+                out[p0:p1] = timed("columns", lambda: rt.surface_temperature_scatter(
+                    la[p0:p1], lo[p0:p1], hz_t, ep_t, fl_t, model=model, mode="summary", extra_flux=q, stats=stats,
+                    n_az=n_az))
+            finally:
+                for buf in bufs:
+                    buf.free()
+    return SurfaceTemperatures(out[:, 0], out[:, 1], out[:, 2], out[:, 3], times[2 * n_spin:], stats)

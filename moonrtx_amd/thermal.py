@@ -100,3 +100,18 @@ def model(spacing_s=3600.0, spinup_lunations=SPINUP_LUNATIONS, resets=RESETS, F=
     md.emissivity, md.sigma, md.q_geo = EMISSIVITY, SIGMA, Q_GEO
     md.albedo[:] = list(ALBEDO)
     return md
+
+
+def albedo(theta_deg):
+    """A(theta) of the default regolith, theta in degrees (float64)."""
+    a0, a, b = ALBEDO
+    t = np.asarray(theta_deg, np.float64)
+    return a0 + a * (t / 45.0) ** 3 + b * (t / 90.0) ** 8
+
+
+def albedo_hemispherical(n=64):
+    """A_h, the albedo under diffuse incidence: the cosine-weighted hemispherical mean of A(theta),
+    int_0^{pi/2} A(theta) 2 sin(theta) cos(theta) dtheta, by n-point Gauss-Legendre quadrature in float64."""
+    x, w = np.polynomial.legendre.leggauss(int(n))
+    th = (x + 1.0) * (math.pi / 4.0)
+    return float(np.sum(w * albedo(np.degrees(th)) * 2.0 * np.sin(th) * np.cos(th)) * (math.pi / 4.0))

@@ -5,6 +5,8 @@ the thermal stage (DESIGN.md sections 3.8 and 3.10), headless.
   python tools/temperature_map.py --window -85 -90 -180 180 --size 256 256 --time 2025-01-01T00:00:00+00:00 --days 365 \\
       --step-min 60 --out temps.npy
   python tools/temperature_map.py --point -89.5 45.0 --days 30 > series.csv
+--scatter K adds the sunlight and infrared the surrounding terrain sends, from K view rays per point (section 3.11); with
+--point it also prints the point's terrain view factor and its mean scattered flux.
 The window's nodes are MoonRT.grid_nodes; temps.npy holds a (4, h, w) float32 array: the maximum, minimum and mean surface
 temperature over the dates and the mean temperature of the column's bottom node, K.  The column is spun up over
 --spinup-lunations lunations before the first date.  Synthetic LOLA-like DEM unless --elevation-file is given."""
@@ -31,6 +33,7 @@ ap.add_argument("--n-bis", type=int, default=14)
 ap.add_argument("--downscale", type=int, default=2)
 ap.add_argument("--dem-size", type=int, nargs=2, default=None, help="synthetic DEM (h, w); default 46080/downscale x 92160/downscale")
 ap.add_argument("--elevation-file", default=None)
+ap.add_argument("--scatter", type=int, default=0, help="K view rays per point for the terrain-scattered flux (0: none)")
 ap.add_argument("--out", default="temps.npy")
 a = ap.parse_args()
 if (a.window is None) == (a.point is None):
@@ -63,8 +66,25 @@ if a.point is not None:
     times = [start + timedelta(minutes=(k - model.n_spin) * a.step_min) for k in range(model.n_spin + m_rec)]
     st = {}
     hz = rt.horizon([a.point[0]], [a.point[1]], n_az=n_az, n_bis=a.n_bis, stats=st)
-    ts = rt.surface_temperature([a.point[0]], [a.point[1]], hz, ephemeris.sun_epochs(times, obs), ephemeris.sun_flux(times),
-                                model, mode="full", stats=st)[0]
+    if a.scatter:
+        # the stages of sunlight.surface_temperatures(scatter=K) for one point, with the series kept
+        hits, share = rt.view_hits([a.point[0]], [a.point[1]], k=a.scatter, stats=st)
+        index, h_lat, h_lon = sunlight.compact_hits(hits)
+        n_spin = int(model.n_spin)
+        times_h = [start + timedelta(minutes=(k - 2 * n_spin) * a.step_min) for k in range(2 * n_spin + m_rec)]
+        q = np.zeros((1, len(times)), np.float32)
+        if h_lat.size:
+            hz_h = rt.horizon(h_lat, h_lon, n_az=n_az, n_bis=a.n_bis, stats=st)
+            ex = rt.surface_temperature_scatter(h_lat, h_lon, hz_h, ephemeris.sun_epochs(times_h, obs),
+                                                ephemeris.sun_flux(times_h), model, mode="exitance", stats=st)
+            q = rt.scatter_flux(index, ex, thermal.albedo_hemispherical(), thermal.EMISSIVITY, stats=st)
+        ts = rt.surface_temperature_scatter([a.point[0]], [a.point[1]], hz, ephemeris.sun_epochs(times, obs),
+                                            ephemeris.sun_flux(times), model, mode="full", extra_flux=q, stats=st)[0]
+        print(f"# terrain view factor {float(share[0]):.4f} ({h_lat.size} of {a.scatter} rays), mean scattered flux "
+              f"{float(q[0, n_spin:].astype(np.float64).mean()):.3f} W m^-2 over the recorded dates", file=sys.stderr)
+    else:
+        ts = rt.surface_temperature([a.point[0]], [a.point[1]], hz, ephemeris.sun_epochs(times, obs),
+                                    ephemeris.sun_flux(times), model, mode="full", stats=st)[0]
     print("time_utc,surface_temperature_K")
     for t, v in zip(times[model.n_spin:], ts):
         print(f"{t.isoformat()},{v:.4f}")
@@ -75,7 +95,7 @@ else:
     la, lo = MoonRT.grid_nodes(lat=(N, S), lon=(W, E), shape=tuple(a.size))
     LA, LO = np.meshgrid(la, lo, indexing="ij")
     r = sunlight.surface_temperatures(rt, LA.ravel(), LO.ravel(), start, a.days, a.step_min, a.spinup_lunations, n_az,
-                                      a.n_bis, obs)
+                                      a.n_bis, obs, scatter=a.scatter)
     out = np.stack([r.t_max, r.t_min, r.t_mean, r.t_bottom_mean]).reshape(4, *a.size)
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     np.save(a.out, out.astype(np.float32))
