@@ -354,7 +354,11 @@ typedef struct MrtxThermalModel {
  * point-major; 1 (SUMMARY): n float4 (max, min, mean surface temperature, mean bottom-node temperature over the recorded
  * epochs); 2 (FLUX): n x m float32 Q_abs, no stepping.  Output into exactly one of dev_out and host_out; at most 2^31 outputs
  * per call, m <= 2^24.  Needs a DEM; leaves the light, Moon frame and render state as they were.  out->reserved receives the
- * number of surface solves that reached the Newton cap (saturating), kernel_ms and launches as usual. */
+ * number of surface solves that reached the Newton cap (saturating), kernel_ms and launches as usual.  Refused before the
+ * launch: q_geo < emissivity sigma 20^4 (a geothermal floor below 20 K) and a radiative equilibrium under the largest
+ * absorbed flux above 450 K.  After each epoch's steps the kernel checks every point's column: if any node was non-finite
+ * or outside [20, 450] K, the call returns MRTX_E_INVALID with the number of such (point, epoch)s, and the output is not
+ * valid. */
 int mrtx_thermal(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t n_az, const void* dev_horizon,
                  const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux_Wm2, int32_t m,
                  const MrtxThermalModel* model, int32_t mode, void* dev_out, float* host_out, MrtxStats* out);
@@ -386,7 +390,9 @@ int mrtx_scatter_flux(mrtx_ctx* ctx, const int32_t* index, int32_t n, int32_t k,
  * float32 point-major (exactly one of dev_extra and host_extra, at least extra_len >= n x m entries, or neither: then every
  * mode equals mrtx_thermal's bit for bit), is added to Q_abs in every epoch, spin-up and the start included; FLUX reports the
  * sum.  mode 3 (EXITANCE): n x (m - n_spin) float2 (M_vis, M_ir) per recorded epoch k: M_vis = A(theta) S_k f max(mu, 0) the
- * sunlight the facet reflects in epoch k, M_ir = eps sigma T0^4 with T0 the surface temperature after epoch k's steps. */
+ * sunlight the facet reflects in epoch k, M_ir = eps sigma T0^4 with T0 the surface temperature after epoch k's steps.
+ * mrtx_thermal's checks apply; a host table's largest entry joins the 450 K check, while a device table is not scanned on
+ * the host (too costly), so only the range check after the launch guards it. */
 int mrtx_thermal_scatter(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t n_az, const void* dev_horizon,
                          const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux_Wm2, int32_t m,
                          const MrtxThermalModel* model, int32_t mode, const void* dev_extra, const float* host_extra,

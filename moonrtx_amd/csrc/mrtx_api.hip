@@ -1592,6 +1592,19 @@ static int thermal_model_ok(mrtx_ctx* c, const MrtxThermalModel& md, int32_t m, 
     if (!(md.chi >= 0.0) || !(md.emissivity > 0.0) || !(md.sigma > 0.0) || !(md.q_geo >= 0.0) || !(md.albedo[0] >= 0.0) ||
         !(md.albedo[0] < 1.0))
         return fail(c, MRTX_E_INVALID, "need chi >= 0, emissivity > 0, sigma > 0, q_geo >= 0 and 0 <= A0 < 1");
+    // A(theta) must be a reflectance at every incidence (a law above 1 at grazing incidence would absorb a negative flux)
+    for (int t = 0; t <= 900; t++) {
+        const double th = 0.1 * t, x = th / 45.0, y = th / 90.0, y2 = y * y, y4 = y2 * y2;
+        const double A = md.albedo[0] + md.albedo[1] * x * x * x + md.albedo[2] * y4 * y4;
+        if (!(A >= 0.0 && A <= 1.0))
+            return fail(c, MRTX_E_INVALID, "the albedo A(theta) = %g at theta = %.1f deg lies outside [0, 1]", A, th);
+    }
+    // a never-lit column settles on the geothermal floor (q_geo / (eps sigma))^(1/4), which must lie inside [20, 450] K too
+    const double q_floor = md.emissivity * md.sigma * (20.0 * 20.0 * 20.0 * 20.0);
+    if (!(md.q_geo >= q_floor))
+        return fail(c, MRTX_E_INVALID,
+                    "q_geo = %g W/m^2 puts the geothermal floor (q_geo / (eps sigma))^(1/4) at %.2f K, below 20 K: need q_geo >= "
+                    "eps sigma 20^4 = %g W/m^2", md.q_geo, std::pow(md.q_geo / (md.emissivity * md.sigma), 0.25), q_floor);
     if (!(std::isfinite(md.spacing_s) && md.spacing_s > 0.0)) return fail(c, MRTX_E_INVALID, "spacing_s must be positive");
     if (md.n_sub < 1) return fail(c, MRTX_E_INVALID, "n_sub must be >= 1 (got %d)", md.n_sub);
     if (md.block < 1) return fail(c, MRTX_E_INVALID, "block must be >= 1 (got %d)", md.block);
@@ -1636,11 +1649,14 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
     if (have_extra && extra_len < (int64_t)n * (int64_t)m)
         return fail(c, MRTX_E_INVALID, "the extra-flux table holds %lld entries, fewer than n x m = %lld", (long long)extra_len,
                     (long long)n * (long long)m);
+    double x_max = 0.0;         // the largest host extra flux: it joins the radiative-equilibrium check below
     if (host_extra) {
         const size_t ne = (size_t)n * (size_t)m;
-        for (size_t i = 0; i < ne; i++)
+        for (size_t i = 0; i < ne; i++) {
             if (!(std::isfinite(host_extra[i]) && host_extra[i] >= 0.0f))
                 return fail(c, MRTX_E_INVALID, "extra-flux entry %zu must be finite and >= 0 (got %g)", i, (double)host_extra[i]);
+            x_max = std::max(x_max, (double)host_extra[i]);
+        }
     }
     if ((dev_horizon == nullptr) == (host_horizon == nullptr))
         return fail(c, MRTX_E_INVALID, "give exactly one of dev_horizon and host_horizon");
@@ -1659,8 +1675,8 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
             return fail(c, MRTX_E_INVALID, "epoch %d: the solar flux must be finite and >= 0 (got %g)", k, flux[k]);
         s_max = std::max(s_max, flux[k]);
     }
-    // the hottest the surface can get, radiative equilibrium under the largest absorbed flux, must stay inside the range the
-    // step bound covers
+    // the hottest the surface can get, radiative equilibrium under the largest absorbed flux (a host extra table's largest
+    // entry added; a device table is not scanned), must stay inside the range the step bound covers
     double a_max = 0.0;
     for (int t = 0; t <= 900; t++) {
         const double th = 0.1 * t, x = th / 45.0, y = th / 90.0, y2 = y * y, y4 = y2 * y2;
@@ -1668,7 +1684,7 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
         a_max = std::max(a_max, (1.0 - A) * std::cos(th * (M_PI / 180.0)));
     }
     if (mode != 2) {
-        const double t_eq = std::pow((a_max * s_max + md.q_geo) / (md.emissivity * md.sigma), 0.25);
+        const double t_eq = std::pow((a_max * s_max + x_max + md.q_geo) / (md.emissivity * md.sigma), 0.25);
         if (!(t_eq <= 450.0))
             return fail(c, MRTX_E_INVALID, "the radiative-equilibrium temperature %.1f K exceeds 450 K, the model's range", t_eq);
     }
@@ -1736,11 +1752,14 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     rc = horizon_finish(c, false, dev_out, host_out, out_bytes, out);
     if (rc != MRTX_OK) return rc;
-    if (out) {
-        unsigned long long caps = 0;
-        HIPCHK(c, hipMemcpy(&caps, c->illum_stats, sizeof caps, hipMemcpyDeviceToHost));
-        out->reserved = caps > 0xffffffffull ? 0xffffffffu : (uint32_t)caps;
-    }
+    unsigned long long cnt[2] = {0, 0};      // Newton cap hits, (point, epoch)s whose column left [20, 450] K
+    HIPCHK(c, hipMemcpy(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost));
+    if (out) out->reserved = cnt[0] > 0xffffffffull ? 0xffffffffu : (uint32_t)cnt[0];
+    if (cnt[1])
+        return fail(c, MRTX_E_INVALID,
+                    "the column left the model's range [20, 450] K (or became non-finite) after the steps of %llu (point, epoch)s: "
+                    "the output is not valid (an extra flux too large for the step, or a transient past the step bound)",
+                    cnt[1]);
     return MRTX_OK;
 }
 

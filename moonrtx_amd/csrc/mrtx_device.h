@@ -226,7 +226,8 @@ struct ThermalC {
     const float* lights;        // 8 floats per epoch, as IllumSeriesC's
     const float* flux;          // per epoch the solar flux at the Moon, W m^-2
     float* out;                 // mode 0: n x (m - n_spin) float32 surface temperatures; 1: n float4; 2: n x m float32 fluxes
-    unsigned long long* caps;   // surface solves that reached the Newton cap (one counter, zeroed by the host)
+    unsigned long long* caps;   // two counters, zeroed by the host: [0] surface solves that reached the Newton cap, [1] the
+                                // (point, epoch)s after whose steps a node was non-finite or outside [20, 450] K
     int32_t az_log2;            // log2(n_az)
     int32_t m;                  // epochs, spin-up included
     int32_t mode;               // 0 FULL, 1 SUMMARY, 2 FLUX

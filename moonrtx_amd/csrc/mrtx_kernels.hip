@@ -2325,6 +2325,9 @@ __global__ void __launch_bounds__(64) horizon_sun_kernel(const FrameC f, const H
 // to Q_abs in every epoch (spin-up and the start included), and mode 3 (EXITANCE), which records per epoch the reflected
 // sunlight M_vis = A(theta) S f max(mu, 0) and the emission eps sigma T0^4 after the epoch's steps.  EXT = false is the
 // mrtx_thermal kernel unchanged.
+// After each epoch's steps the column is checked once (not per step, which would cost a share of the step itself): a node
+// that is not finite or lies outside [20, 450] K, the range the step bound and the heat capacity were checked on, counts
+// that (point, epoch) in q.caps[1]; the host then refuses the call's results (sections 3.10, 3.11).
 template <bool WIDE, bool EXT>
 __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const ThermalC q) {
     constexpr int NN = MRTX_THERMAL_NODES;
@@ -2402,7 +2405,7 @@ __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const Therm
 #pragma unroll
     for (int i = 0; i < NN; i++) T[i] = t_init;
     geotherm(T, 0, t_init);
-    uint32_t caps = 0;
+    uint32_t caps = 0, out_of_range = 0;
     double ref_sum = 0.0, sum_s = 0.0, sum_b = 0.0;
     float t_max = -INFINITY, t_min = INFINITY;
     int in_block = 0, blocks = 0;
@@ -2447,6 +2450,12 @@ __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const Therm
             for (int i = 2; i < NN; i++)
                 if (i == n - 1) T[i] = T[i - 1] + (double)(q.qdz[i - 1] / kof(i - 1, T[i - 1]));
         }
+        // |T - 235| <= 215 is false for NaN and +-inf as well
+        bool bad = false;
+#pragma unroll
+        for (int i = 0; i < NN; i++)
+            if (i < n) bad = bad || !(fabs(T[i] - 235.0) <= 215.0);
+        out_of_range += bad ? 1u : 0u;
         const float ts = (float)T[0];
         if (k < q.n_spin) {
             if (blocks < q.n_reset) {
@@ -2483,9 +2492,14 @@ __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const Therm
         reinterpret_cast<float4*>(q.out)[pt] = make_float4(t_max, t_min, (float)(sum_s * inv), (float)(sum_b * inv));
     }
     caps = in ? caps : 0u;
+    out_of_range = in ? out_of_range : 0u;
 #pragma unroll
-    for (int s = 1; s < 64; s <<= 1) caps += __shfl_xor(caps, s, 64);
+    for (int s = 1; s < 64; s <<= 1) {
+        caps += __shfl_xor(caps, s, 64);
+        out_of_range += __shfl_xor(out_of_range, s, 64);
+    }
     if (lane == 0 && caps) atomicAdd(q.caps, (unsigned long long)caps);
+    if (lane == 0 && out_of_range) atomicAdd(q.caps + 1, (unsigned long long)out_of_range);
 }
 
 // What terrain a point sees (DESIGN.md sections 3.11 and 4.12): per point K fixed cosine-weighted directions fed through

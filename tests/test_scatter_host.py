@@ -207,7 +207,8 @@ def test_scatter_arguments_are_checked_before_any_device_call(native_lib, ctx):
 def scatter_refusals(native_lib, ctx, ok):
     """view_hits: a bad K; scatter_flux: an index outside the hit list, a non-finite or out-of-range A_h, a bad emissivity, a
     short exitance table; thermal_scatter: a bad mode, a short, negative or non-finite extra table.  `ok` is the code a good
-    call that needs a DEM reaches (E_STATE without one, 0 with one); the gather needs none."""
+    call that needs a DEM reaches (E_STATE without one, 0 with one); the gather needs none.  A host extra table whose largest
+    entry takes the radiative equilibrium past 450 K is refused as well."""
     pts = np.array([[10.0, 20.0], [-89.5, 0.0]])
     vh = native_lib.mrtx_view_hits
     out = np.empty(2 * (2 * 64 + 1), np.float32)
@@ -263,6 +264,12 @@ def scatter_refusals(native_lib, ctx, ok):
         y = x.copy()
         y[1, 3] = v
         assert col(extra=y, length=y.size) == E_INVALID, v
+    # a host table's largest entry joins the 450 K check: 0.88 x 1361 + 1100 W m^-2 is past it, + 900 is not
+    hot = x.copy()
+    hot[1, 3] = 1100.0
+    assert col(extra=hot, length=hot.size) == E_INVALID and b"450 K" in native_lib.mrtx_last_error(ctx)
+    hot[1, 3] = 900.0
+    assert col(extra=hot, length=hot.size) == ok
     for mode in (0, 1, 2, 3):
         assert col(mode, extra=x, length=x.size) == ok, mode
     assert col(3) == ok

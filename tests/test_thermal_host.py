@@ -133,6 +133,56 @@ def test_spinup_drift_at_the_defaults():
     assert np.abs(means[-1] - means[-2]).max() < 0.25
 
 
+def test_the_model_read_from_the_struct_is_the_spec_model_at_the_defaults():
+    """run(model=md) reads the grid, constants and schedule from the MrtxThermalModel the kernel receives; with the default
+    model that is the spec's module constants exactly: the same bits as the schedule-argument call.  The pinned values are
+    the parent's model's (the generalisation changed no number)."""
+    q = smooth_sun([0.0, 60.0], 2 * 709)
+    a = tm.run(q, 3600.0, 12, 709, 709, 1)
+    md = MoonRT.thermal_grid(3600.0, 1, 1)
+    b = tm.run(q, model=md)
+    for k in ("full", "summary", "spin_surface", "bottom"):
+        assert np.array_equal(a[k], b[k]), k
+    assert a["caps"] == b["caps"] == 0 and a["coef_max"] == b["coef_max"] <= 1.0
+    assert b["out_of_range"] == 0 and 20.0 < b["t_lo"] < b["t_hi"] < 450.0
+    want = [[385.27134168829514, 97.10015556597574, 212.49605703456407, 276.81143893355227],
+            [308.6550415915498, 86.41612675055936, 172.95906312411265, 220.0906013148095]]
+    assert np.allclose(b["summary"], want, rtol=1e-12, atol=0.0), b["summary"].tolist()
+    assert tm.max_step(md) == pytest.approx(tm.max_step(), rel=1e-15)
+    assert np.array_equal(tm.absorbed(0.5, [0.1, 0.7], 1361.0, md), tm.absorbed(0.5, [0.1, 0.7], 1361.0))
+    with pytest.raises(ValueError):
+        tm.run(q, 3600.0, model=md)
+
+
+def test_reset_at_the_last_interior_node_hangs_the_bottom_from_the_mean():
+    """A 3-node grid has its reference node at N - 2 = 1.  The reset leaves node 1 as it is and sets the bottom to the
+    steady step from the block's mean `top`: T2 = top + Q dz_1 / k_1(top) (the kernel's rule), not from node 1's old value.
+    By hand: kc_1 = 2e-3, chi = 2.7, top = 175 K, so k_1 = 2e-3 (1 + 2.7 / 8) = 2.675e-3; Q dz_1 = 0.018 x 0.05 = 9e-4;
+    T2 = 175 + 0.336448598... K."""
+    T = np.array([[250.0, 180.0, 999.0]])
+    tm.geotherm(T, 1, np.array([175.0]), np.array([1e-3, 2e-3, 3e-3]), np.array([0.01, 0.05]))
+    assert T[0, 0] == 250.0 and T[0, 1] == 180.0
+    assert T[0, 2] == pytest.approx(175.0 + 9e-4 / 2.675e-3, rel=1e-14)
+    assert T[0, 2] == pytest.approx(175.336448598130841, abs=1e-12)
+
+
+def test_model_diagnostics_on_a_step_onto_a_cold_column():
+    """From the 24 K floor a step to 1600 W m^-2 at the default grid's 300 s step: node 1 is still cold (small c) when its
+    link carries the hot surface's k, so the coefficient sum passes 1 (1.26); the column stays finite and in range.  2200 W m^-2
+    at a step just under Delta_max diverges, and the diagnostics say so."""
+    md = MoonRT.thermal_grid(3600.0, 1, 1)
+    md.n_spin, md.block, md.n_reset = 24, 12, 2
+    q = np.zeros((1, 84))
+    q[0, 30:] = 1600.0
+    r = tm.run(q, model=md)
+    assert 1.2 < r["coef_max"] < 1.35 and r["caps"] == 0 and r["out_of_range"] == 0
+    assert r["t_lo"] == pytest.approx(T_GEO, abs=1e-3) and 400.0 < r["t_hi"] < 450.0
+    md.spacing_s, md.n_sub = 0.9999 * tm.max_step(md), 1
+    q[0, 30:] = 2200.0
+    r = tm.run(q, model=md)
+    assert r["caps"] > 0 and r["out_of_range"] > 0 and not np.isfinite(r["full"][0, -1])
+
+
 def test_sun_flux_at_perihelion_and_aphelion():
     peri = datetime(2025, 1, 4, 13, 28, tzinfo=timezone.utc)       # Earth at 0.983327 AU
     aph = datetime(2025, 7, 3, 19, 55, tzinfo=timezone.utc)        # Earth at 1.016644 AU
@@ -208,6 +258,21 @@ def thermal_refusals(native_lib, ctx, ok):
     assert call(fl=np.full(m, 3000.0)) == E_INVALID           # radiative equilibrium above 450 K
     assert b"450" in native_lib.mrtx_last_error(ctx)
     assert call(model(emissivity=0.0)) == E_INVALID
+    # the geothermal floor (q_geo / (eps sigma))^(1/4) must not lie below 20 K: q_geo >= eps sigma 20^4 = 8.62e-3 W m^-2
+    q_floor = model().emissivity * model().sigma * 20.0 ** 4
+    for q_geo in (0.0, 1e-3, q_floor * (1.0 - 1e-9)):
+        assert call(model(q_geo=q_geo)) == E_INVALID, q_geo
+        assert b"geothermal floor" in native_lib.mrtx_last_error(ctx) and b"20 K" in native_lib.mrtx_last_error(ctx)
+    assert call(model(q_geo=q_floor * (1.0 + 1e-9)), mode=2) == ok
+    assert call(model(q_geo=q_floor * 1.02)) == ok
+    # the albedo law must stay a reflectance on [0, 90] deg: 0.2 + 0.1 + 0.3 = 1.3 at grazing incidence would absorb < 0
+    for law in ((0.2, 0.1, 0.3), (0.12, -0.2, 0.0), (0.0, 0.0, 1.01)):
+        md = model()
+        md.albedo[:] = list(law)
+        assert call(md) == E_INVALID and b"albedo" in native_lib.mrtx_last_error(ctx), law
+    md = model()
+    md.albedo[:] = [0.1, 0.05, 0.3]
+    assert call(md) == ok
     assert call(m=(1 << 24) + 1) == E_INVALID
     for mode in (0, 1, 2):
         assert call(mode=mode) == ok, mode
