@@ -398,6 +398,34 @@ int mrtx_thermal_scatter(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int
                          const MrtxThermalModel* model, int32_t mode, const void* dev_extra, const float* host_extra,
                          int64_t extra_len, void* dev_out, float* host_out, MrtxStats* out);
 
+/* ---- Terrain line of sight (additive to ABI 7) --------------------------------------------------
+ * An end is a surface point (lat, lon, degrees) raised h >= 0 metres along its radial unit vector u, from the lifted vertex of
+ * mrtx_horizon_points: P = fmaf(hs, u, o) with hs = (float)(h / radius_m * R), R the context's Moon radius and radius_m the
+ * metric radius of D = 1 (1737400 * the DEM's radius_scale).  A probe marches the segment between the target and the
+ * observer from its lower end as a shadow ray is marched, ending before the far end.  Per target the output is the extra mast
+ * height m, metres (float32), at which it sees the observer: 0 if it does at target_h_m, otherwise n_bis - 1 bisection probes
+ * over [0, mast_max_m] after one at mast_max_m; +inf if the last probe at mast_max_m (or, n_bis = 0, at 0) is blocked.  So
+ * n_bis = 0 is a plain viewshed: m is 0 or +inf.  Needs a DEM, neither a light nor a Moon frame; leaves the light, Moon frame
+ * and render state as they were.  Output into exactly one of dev_out and host_out.  At most 2^31 outputs per call.  With
+ * MRTX_F_COUNT_STATS: shadow_rays (probes), height_samples (10 per target for the two vertices + every march step),
+ * dem_fetches, mip_fetches. */
+typedef struct MrtxSightGrid {
+    double obs_lat, obs_lon, obs_h_m;          /* the observer end */
+    double target_h_m, mast_max_m, radius_m;   /* every target's height, the bisection's mast range, metres per D = 1 */
+    double lat_north, lat_south, lon_west, lon_east;   /* as MrtxIllumGrid */
+    int32_t h, w, row_begin, row_end;          /* as MrtxIllumGrid: one band of rows per call */
+    int32_t n_bis;                             /* 0 .. 24 */
+    int32_t reserved;                          /* 0 */
+} MrtxSightGrid;
+/* The targets are the nodes of a band of a lat/lon map (mrtx_illum_grid's nodes): (row_end - row_begin) x w float32,
+ * row-major. */
+int mrtx_sight_grid(mrtx_ctx* ctx, const MrtxSightGrid* grid, void* dev_out, float* host_out, MrtxStats* out);
+/* The targets are n (lat, lon) pairs; observer_llh holds n_observers (lat, lon, h_m) triples: 1 (shared) or n (one per
+ * target).  Output: n float32. */
+int mrtx_sight_points(mrtx_ctx* ctx, const double* target_latlon, int32_t n, const double* observer_llh, int32_t n_observers,
+                      double target_h_m, double mast_max_m, double radius_m, int32_t n_bis, void* dev_out, float* host_out,
+                      MrtxStats* out);
+
 /* Math conformance probe (ABI 7): the kernels' domain-restricted reciprocal (v_rcp_f32 + Newton steps) and square root (v_sqrt_f32 + a
  * +-1 ulp residual fix) against the compiler's IEEE expansions of 1.0f / x and sqrtf(x), ON THE DEVICE, for the n float bit patterns
  * from lo_bits on: which = 0 one Newton step, 1 two steps (what the kernels use), 2 the square root.  mismatches = how many differ;

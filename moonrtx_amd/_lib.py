@@ -44,6 +44,14 @@ class MrtxIllumGrid(C.Structure):
                 ("n_sun", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MrtxSightGrid(C.Structure):
+    """One band of a viewshed map (mrtx_sight_grid)."""
+    _fields_ = [("obs_lat", C.c_double), ("obs_lon", C.c_double), ("obs_h_m", C.c_double), ("target_h_m", C.c_double),
+                ("mast_max_m", C.c_double), ("radius_m", C.c_double), ("lat_north", C.c_double), ("lat_south", C.c_double),
+                ("lon_west", C.c_double), ("lon_east", C.c_double), ("h", C.c_int32), ("w", C.c_int32),
+                ("row_begin", C.c_int32), ("row_end", C.c_int32), ("n_bis", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MrtxIllumEpoch(C.Structure):
     """One date of a Sun-illumination series (mrtx_illum_series): what mrtx_set_light and
     mrtx_set_moon_frame would set for it."""
@@ -131,6 +139,9 @@ SIGNATURES = {
     "mrtx_horizon_points": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_horizon_sun": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP,
                                    C.POINTER(MrtxStats)]),
+    "mrtx_sight_grid": (C.c_int, [_VP, C.POINTER(MrtxSightGrid), _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_sight_points": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _VP,
+                                    _VP, C.POINTER(MrtxStats)]),
     "mrtx_thermal": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                C.POINTER(MrtxStats)]),
     "mrtx_view_dir_samples": (C.c_int, [C.c_int32, _VP]),

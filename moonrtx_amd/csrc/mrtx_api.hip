@@ -56,6 +56,7 @@ hipError_t mrtx_launch_illum(const FrameC& f, IllumC g, bool stats, hipStream_t 
 hipError_t mrtx_launch_illum_series(const FrameC& f, IllumSeriesC q, bool stats, hipStream_t st);
 hipError_t mrtx_launch_horizon(const FrameC& f, HorizonC h, bool stats, hipStream_t st);
 hipError_t mrtx_launch_horizon_sun(const FrameC& f, HorizonSunC q, hipStream_t st);
+hipError_t mrtx_launch_sight(const FrameC& f, SightC q, bool stats, hipStream_t st);
 hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, hipStream_t st);
 hipError_t mrtx_launch_thermal_scatter(const FrameC& f, const ThermalC& q, hipStream_t st);
 hipError_t mrtx_launch_view_hits(const FrameC& f, const ViewC& q, bool stats, hipStream_t st);
@@ -1568,6 +1569,121 @@ int mrtx_horizon_sun(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az,
     HIPCHK(c, mrtx_launch_horizon_sun(f, q, c->stream));
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     return horizon_finish(c, false, dev_out, host_out, out_bytes, out);
+}
+
+// ---- Terrain line of sight -------------------------------------------------------------------------
+static bool sight_height_ok(double h) { return std::isfinite(h) && h >= 0.0 && h <= 1e9; }
+static bool sight_latlon_ok(double la, double lo) { return std::isfinite(la) && std::isfinite(lo) && std::fabs(la) <= 90.0 && std::fabs(lo) <= 1e6; }
+
+// the checks every sight call shares
+static int sight_check(mrtx_ctx* c, double target_h_m, double mast_max_m, double radius_m, int32_t n_bis, const void* dev_out,
+                       const float* host_out) {
+    if (!sight_height_ok(target_h_m)) return fail(c, MRTX_E_INVALID, "target height must lie in [0, 1e9] m");
+    if (!std::isfinite(mast_max_m) || mast_max_m < 0.0 || mast_max_m > 1e9 || (n_bis > 0 && !(mast_max_m > 0.0)))
+        return fail(c, MRTX_E_INVALID, "mast_max_m must lie in [0, 1e9] m, and be > 0 when n_bis > 0");
+    if (!std::isfinite(radius_m) || !(radius_m > 0.0)) return fail(c, MRTX_E_INVALID, "radius_m must be finite and > 0");
+    if (n_bis < 0 || n_bis > 24) return fail(c, MRTX_E_INVALID, "n_bis must lie in [0, 24] (got %d)", n_bis);
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    return MRTX_OK;
+}
+
+// Everything after the argument checks: the targets' tables (tgt: rows then columns, 2 floats each), the observers' point
+// tables and raised heights (scene units), one launch into the output, counters.
+static int sight_run(mrtx_ctx* c, const std::vector<float>& tgt, int rows, int cols, bool points, const std::vector<float>& obs,
+                     const std::vector<double>& obs_h_m, double target_h_m, double mast_max_m, double radius_m, int32_t n_bis,
+                     void* dev_out, float* host_out, MrtxStats* out) {
+    FrameC f;
+    FrameCold cold;
+    int rc;
+    if ((rc = horizon_frame(c, f, cold, true)) != MRTX_OK) return rc;
+    const bool stats = (c->prm.flags & MRTX_F_COUNT_STATS) != 0;
+    const int n_obs = (int)obs_h_m.size();
+    // one device block: target tables, observer tables, observer heights
+    std::vector<float> host(tgt.size() + obs.size() + (size_t)n_obs);
+    std::copy(tgt.begin(), tgt.end(), host.begin());
+    std::copy(obs.begin(), obs.end(), host.begin() + (ptrdiff_t)tgt.size());
+    float* hs = host.data() + tgt.size() + obs.size();
+    for (int i = 0; i < n_obs; i++) hs[i] = (float)(obs_h_m[(size_t)i] / radius_m * c->radius);
+    const size_t tab_bytes = host.size() * sizeof(float), out_bytes = (size_t)rows * (size_t)cols * sizeof(float);
+    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, tab_bytes)) != MRTX_OK) return rc;
+    if (!dev_out) {
+        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, out_bytes)) != MRTX_OK) return rc;
+        dev_out = c->illum_out;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->illum_cold, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->illum_tab, host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+    if (stats) HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
+    SightC q;
+    std::memset(&q, 0, sizeof q);
+    q.g.rtab = c->illum_tab; q.g.ctab = c->illum_tab + 2 * (size_t)(points ? cols : rows);
+    q.g.rows = rows; q.g.cols = cols; q.g.points = points ? 1 : 0;
+    q.obs.rtab = c->illum_tab + tgt.size(); q.obs.ctab = q.obs.rtab + 2 * (size_t)n_obs;
+    q.obs.rows = n_obs; q.obs.cols = n_obs; q.obs.points = 1;
+    q.obs_hs = c->illum_tab + tgt.size() + obs.size();
+    q.out = (float*)dev_out;
+    q.target_h_m = target_h_m; q.mast_max_m = mast_max_m; q.radius_m = radius_m; q.R = c->radius;
+    q.n_obs = n_obs; q.n_bis = n_bis;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    HIPCHK(c, mrtx_launch_sight(f, q, stats, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    return horizon_finish(c, stats, dev_out, host_out, out_bytes, out);
+}
+
+int mrtx_sight_grid(mrtx_ctx* c, const MrtxSightGrid* g, void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!g) return fail(c, MRTX_E_INVALID, "null grid");
+    if (!sight_latlon_ok(g->obs_lat, g->obs_lon))
+        return fail(c, MRTX_E_INVALID, "observer: latitude must lie in [-90, 90] and longitude be finite");
+    if (!sight_height_ok(g->obs_h_m)) return fail(c, MRTX_E_INVALID, "observer height must lie in [0, 1e9] m");
+    int rc = sight_check(c, g->target_h_m, g->mast_max_m, g->radius_m, g->n_bis, dev_out, host_out);
+    if (rc != MRTX_OK) return rc;
+    // the grid as mrtx_illum_grid checks it
+    if (!std::isfinite(g->lat_north) || !std::isfinite(g->lat_south) || !(g->lat_north > g->lat_south) || g->lat_north > 90.0 ||
+        g->lat_south < -90.0)
+        return fail(c, MRTX_E_INVALID, "latitudes must satisfy 90 >= lat_north > lat_south >= -90");
+    if (!std::isfinite(g->lon_west) || !std::isfinite(g->lon_east) || !(g->lon_east > g->lon_west) || std::fabs(g->lon_west) > 1e6 ||
+        std::fabs(g->lon_east) > 1e6)
+        return fail(c, MRTX_E_INVALID, "longitudes must be finite with lon_west < lon_east");
+    if (g->h < 1 || g->w < 1) return fail(c, MRTX_E_INVALID, "empty grid (%d x %d)", g->h, g->w);
+    if (g->row_begin < 0 || g->row_end > g->h || g->row_begin >= g->row_end)
+        return fail(c, MRTX_E_INVALID, "bad band [%d, %d) of %d rows", g->row_begin, g->row_end, g->h);
+    if ((int64_t)(g->row_end - g->row_begin) * (int64_t)g->w > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "a band holds at most 2^31 nodes: split the map into more bands");
+    const int rows = g->row_end - g->row_begin;
+    std::vector<float> tgt((size_t)rows * 2 + (size_t)g->w * 2);
+    const double dlat = (g->lat_north - g->lat_south) / (double)g->h, dlon = (g->lon_east - g->lon_west) / (double)g->w;
+    for (int i = 0; i < rows; i++) illum_sc(g->lat_north - ((double)(g->row_begin + i) + 0.5) * dlat, &tgt[(size_t)i * 2]);
+    for (int j = 0; j < g->w; j++) illum_sc(g->lon_west + ((double)j + 0.5) * dlon, &tgt[((size_t)rows + j) * 2]);
+    std::vector<float> obs;
+    const double ll[2] = {g->obs_lat, g->obs_lon};
+    if ((rc = point_tables(c, ll, 1, obs)) != MRTX_OK) return rc;
+    return sight_run(c, tgt, rows, g->w, false, obs, std::vector<double>(1, g->obs_h_m), g->target_h_m, g->mast_max_m,
+                     g->radius_m, g->n_bis, dev_out, host_out, out);
+}
+
+int mrtx_sight_points(mrtx_ctx* c, const double* target_latlon, int32_t n, const double* observer_llh, int32_t n_observers,
+                      double target_h_m, double mast_max_m, double radius_m, int32_t n_bis, void* dev_out, float* host_out,
+                      MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!target_latlon || !observer_llh) return fail(c, MRTX_E_INVALID, "null target or observer list");
+    if (n < 1) return fail(c, MRTX_E_INVALID, "n must be >= 1 (got %d)", n);
+    if (n_observers != 1 && n_observers != n)
+        return fail(c, MRTX_E_INVALID, "n_observers must be 1 or n (got %d for n = %d)", n_observers, n);
+    int rc = sight_check(c, target_h_m, mast_max_m, radius_m, n_bis, dev_out, host_out);
+    if (rc != MRTX_OK) return rc;
+    std::vector<float> tgt;
+    if ((rc = point_tables(c, target_latlon, n, tgt)) != MRTX_OK) return rc;
+    std::vector<double> oll((size_t)n_observers * 2), oh((size_t)n_observers);
+    for (int32_t i = 0; i < n_observers; i++) {
+        const double* o = observer_llh + 3 * (size_t)i;
+        if (!sight_latlon_ok(o[0], o[1]))
+            return fail(c, MRTX_E_INVALID, "observer %d: latitude must lie in [-90, 90] and longitude be finite", i);
+        if (!sight_height_ok(o[2])) return fail(c, MRTX_E_INVALID, "observer %d: height must lie in [0, 1e9] m", i);
+        oll[2 * (size_t)i] = o[0]; oll[2 * (size_t)i + 1] = o[1]; oh[(size_t)i] = o[2];
+    }
+    std::vector<float> obs;
+    if ((rc = point_tables(c, oll.data(), n_observers, obs)) != MRTX_OK) return rc;
+    return sight_run(c, tgt, 1, n, true, obs, oh, target_h_m, mast_max_m, radius_m, n_bis, dev_out, host_out, out);
 }
 
 // ---- Regolith surface temperatures ---------------------------------------------------------------

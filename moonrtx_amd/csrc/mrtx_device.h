@@ -268,3 +268,18 @@ struct ScatterC {
     int32_t chunks;             // (m + 63) / 64
     float omah, eps, inv_k;     // 1 - A_h, emissivity, 1 / K
 };
+
+// Terrain line of sight (mrtx_sight_grid / mrtx_sight_points): the targets are a band (g.rows x g.cols,
+// row / column tables) or a point list (g.points = 1, g.rows = 1, g.cols = n); the observers a point list of n_obs entries
+// (obs.points = 1; 1 or g.cols of them) with their raised heights in scene units.  One lane per target; a wave holds 64
+// neighbouring targets of one row.
+struct SightC {
+    IllumC g;               // the targets (only the row / column tables and rows, cols, points are read)
+    IllumC obs;             // the observers (tables only)
+    const float* obs_hs;    // per observer: (float)(h / radius_m * R)
+    float* out;             // rows x cols float32 extra mast heights (metres), +inf where even mast_max does not see
+    double target_h_m, mast_max_m, radius_m, R;   // a target at parameter t is raised by target_h_m + t * mast_max_m metres
+    int32_t n_obs;          // 1 or g.cols (a point list)
+    int32_t n_bis;          // 0 .. 24
+    int32_t waves_x;        // waves per row of targets (set by the launcher)
+};

@@ -456,7 +456,9 @@ __device__ __forceinline__ bool below_seg(const FrameC& f, const Seg& sg, float 
 #ifndef MRTX_STEP_BATCH_BOUNCE
 #define MRTX_STEP_BATCH_BOUNCE 1
 #endif
-template <bool WIDE, bool PRIMARY, bool STATS, bool EXACTABLE, int BATCH, int CP = 0>
+// BOUNDED (shadow rays only; mrtx_sight_*): the ray also ends before the first step with s_k >= smax, the
+// segment's far end.  Every other caller leaves it false and compiles to the code it always had.
+template <bool WIDE, bool PRIMARY, bool STATS, bool EXACTABLE, int BATCH, int CP = 0, bool BOUNDED = false>
 __device__ __forceinline__ void step_loop_from(const FrameC& f, float oa, float ob, float oc, float da, float db, float dc,
                                                float smax, const Seg& sg, int ka, int j, bool more, bool& go, bool& hit,
                                                float& sk_out, uint32_t* cnt) {
@@ -466,7 +468,7 @@ __device__ __forceinline__ void step_loop_from(const FrameC& f, float oa, float 
             const float sk = (float)k * f.step;
             const float pa = fmaf(sk, da, oa), pb = fmaf(sk, db, ob), pc = fmaf(sk, dc, oc);
             const float r2 = fmaf(pc, pc, fmaf(pb, pb, pa * pa));
-            const bool in = (PRIMARY ? (sk <= smax) : (r2 <= f.R2f)) & (k <= f.kmax);
+            const bool in = (PRIMARY ? (sk <= smax) : (r2 <= f.R2f)) & (!BOUNDED || sk < smax) & (k <= f.kmax);
             const bool bel = below_seg<WIDE, EXACTABLE, CP>(f, sg, sk, pa, pb, pc, r2);
             if (STATS) { cnt[ST_HEIGHT] += in ? 1u : 0u; cnt[ST_FETCH]++; }
 #ifdef MRTX_PROF
@@ -502,7 +504,7 @@ __device__ __forceinline__ void step_loop_from(const FrameC& f, float oa, float 
                 const float sk = (float)k * f.step;
                 const float pa = fmaf(sk, da, oa), pb = fmaf(sk, db, ob), pc = fmaf(sk, dc, oc);
                 const float r2 = fmaf(pc, pc, fmaf(pb, pb, pa * pa));
-                const bool in = (PRIMARY ? (sk <= smax) : (r2 <= f.R2f)) & (k <= f.kmax);
+                const bool in = (PRIMARY ? (sk <= smax) : (r2 <= f.R2f)) & (!BOUNDED || sk < smax) & (k <= f.kmax);
                 const bool bel = r2 <= surf[i] * surf[i];
                 if (STATS) { cnt[ST_HEIGHT] += (act & in) ? 1u : 0u; cnt[ST_FETCH] += act ? 1u : 0u; }   // speculative fetches are not credited
                 hit = act ? (in & bel) : hit;
@@ -516,16 +518,16 @@ __device__ __forceinline__ void step_loop_from(const FrameC& f, float oa, float 
     }
 }
 
-template <bool WIDE, bool PRIMARY, bool STATS, bool EXACTABLE, int BATCH, int CP = 0>
+template <bool WIDE, bool PRIMARY, bool STATS, bool EXACTABLE, int BATCH, int CP = 0, bool BOUNDED = false>
 __device__ __forceinline__ void step_loop(const FrameC& f, float oa, float ob, float oc, float da, float db, float dc,
                                           float smax, const Seg& sg, int ka, bool& go, bool& hit, float& sk_out,
                                           uint32_t* cnt) {
-    step_loop_from<WIDE, PRIMARY, STATS, EXACTABLE, BATCH, CP>(f, oa, ob, oc, da, db, dc, smax, sg, ka, sg.jlo, sg.jlo <= sg.jhi,
+    step_loop_from<WIDE, PRIMARY, STATS, EXACTABLE, BATCH, CP, BOUNDED>(f, oa, ob, oc, da, db, dc, smax, sg, ka, sg.jlo, sg.jlo <= sg.jhi,
                                                            go, hit, sk_out, cnt);
 }
 
 // STATS builds only: the spec counts a DEM evaluation at every step that is still inside; add the skipped ones.
-template <bool PRIMARY>
+template <bool PRIMARY, bool BOUNDED = false>
 __device__ __forceinline__ uint32_t count_in_steps(const FrameC& f, float oa, float ob, float oc, float da, float db,
                                                    float dc, float smax, int ka, int j_from, int j_to) {
     uint32_t n = 0;
@@ -534,7 +536,7 @@ __device__ __forceinline__ uint32_t count_in_steps(const FrameC& f, float oa, fl
         const float sk = (float)k * f.step;
         const float pa = fmaf(sk, da, oa), pb = fmaf(sk, db, ob), pc = fmaf(sk, dc, oc);
         const float r2 = fmaf(pc, pc, fmaf(pb, pb, pa * pa));
-        const bool in = (PRIMARY ? (sk <= smax) : (r2 <= f.R2f)) & (k <= f.kmax);
+        const bool in = (PRIMARY ? (sk <= smax) : (r2 <= f.R2f)) & (!BOUNDED || sk < smax) & (k <= f.kmax);
         if (!in) break;
         n++;
     }
@@ -610,12 +612,14 @@ __device__ __forceinline__ int horizon_retry(const FrameC& f, const MarchState& 
     return horizon_kend(f, t);
 }
 // STATS builds: the steps the spec evaluates after a march was cut at kend (every step while the ray is inside)
-__device__ __forceinline__ uint32_t steps_after(const FrameC& f, const MarchState& m, int k_from) {
+template <bool BOUNDED = false>
+__device__ __forceinline__ uint32_t steps_after(const FrameC& f, const MarchState& m, int k_from, float smax = 0.0f) {
     uint32_t n = 0;
     for (int k = k_from; k <= f.kmax; k++) {
         const float sk = (float)k * f.step;
         const float pa = fmaf(sk, m.da, m.oa), pb = fmaf(sk, m.db, m.ob), pc = fmaf(sk, m.dc, m.oc);
         if (!(fmaf(pc, pc, fmaf(pb, pb, pa * pa)) <= f.R2f)) break;
+        if (BOUNDED && !(sk < smax)) break;
         n++;
     }
     return n;
@@ -626,9 +630,9 @@ __device__ __forceinline__ uint32_t steps_after(const FrameC& f, const MarchStat
 // ... with the exact texel coordinates of the origin already known (m.rowA, m.colA)
 // LAZY_KEND (path_kernel): the horizon bound is left open (m.kend = -1) and looked up by the first segment set-up, in the
 // same memory round as that segment's max-mip fetch, instead of costing a round of its own here.
-template <bool PRIMARY, bool STATS, bool LAZY_KEND = false, bool PRE_CELL = false>
+template <bool PRIMARY, bool STATS, bool LAZY_KEND = false, bool PRE_CELL = false, bool BOUNDED = false>
 __device__ __forceinline__ bool march_begin_at(const FrameC& f, float oa, float ob, float oc, float da, float db, float dc,
-                                               MarchState& m, uint32_t* cnt, float cell_pre = 0.0f) {
+                                               MarchState& m, uint32_t* cnt, float cell_pre = 0.0f, float smax = 0.0f) {
     m.oa = oa; m.ob = ob; m.oc = oc; m.da = da; m.db = db; m.dc = dc;
     m.q2A = fmaf(ob, ob, oa * oa);
     m.rq.q0 = fmaf(oc, oc, m.q2A);
@@ -643,12 +647,13 @@ __device__ __forceinline__ bool march_begin_at(const FrameC& f, float oa, float 
         const float s1 = f.step;
         const float pa = fmaf(s1, da, oa), pb = fmaf(s1, db, ob), pc = fmaf(s1, dc, oc);
         go = fmaf(pc, pc, fmaf(pb, pb, pa * pa)) <= f.R2f;
+        if (BOUNDED) go = go && s1 < smax;
         if (LAZY_KEND) {
             m.kend = -1;
         } else {
             m.kend = horizon_kend<PRE_CELL>(f, m, cell_pre);
             if (go && m.kend < 1) {          // already above everything in reach: no step can hit
-                if (STATS) cnt[ST_HEIGHT] += steps_after(f, m, 1);
+                if (STATS) cnt[ST_HEIGHT] += steps_after<BOUNDED>(f, m, 1, smax);
                 go = false;
             }
         }
@@ -657,30 +662,30 @@ __device__ __forceinline__ bool march_begin_at(const FrameC& f, float oa, float 
     }
     return go;
 }
-template <bool PRIMARY, bool STATS, bool LAZY_KEND = false>
+template <bool PRIMARY, bool STATS, bool LAZY_KEND = false, bool BOUNDED = false>
 __device__ __forceinline__ bool march_begin(const FrameC& f, float oa, float ob, float oc, float da, float db, float dc,
-                                            MarchState& m, uint32_t* cnt) {
+                                            MarchState& m, uint32_t* cnt, float smax = 0.0f) {
     float q2;
     exact_rowcol(f, oa, ob, oc, m.rowA, m.colA, q2);
-    return march_begin_at<PRIMARY, STATS, LAZY_KEND>(f, oa, ob, oc, da, db, dc, m, cnt);
+    return march_begin_at<PRIMARY, STATS, LAZY_KEND, false, BOUNDED>(f, oa, ob, oc, da, db, dc, m, cnt, 0.0f, smax);
 }
 
 // End of a segment whose steps are through: a ray that is still marching (`go`) may have ended inside the skipped tail, or
 // is cut by its horizon bound; the march state moves on to the next segment.
-template <bool PRIMARY, bool STATS>
+template <bool PRIMARY, bool STATS, bool BOUNDED = false>
 __device__ __forceinline__ void segment_tail(const FrameC& f, MarchState& m, float smax, const Seg& sg, bool& go, float rowB,
                                              float colB, float q2B, uint32_t* cnt) {
     const float oa = m.oa, ob = m.ob, oc = m.oc, da = m.da, db = m.db, dc = m.dc;
     const int ka = m.ka;
     if (go) {
         // still marching after the last evaluated step: did the ray end inside the skipped tail?
-        if (STATS) cnt[ST_HEIGHT] += count_in_steps<PRIMARY>(f, oa, ob, oc, da, db, dc, smax, ka, max(sg.jhi + 1, 1), SEG_N);
+        if (STATS) cnt[ST_HEIGHT] += count_in_steps<PRIMARY, BOUNDED>(f, oa, ob, oc, da, db, dc, smax, ka, max(sg.jhi + 1, 1), SEG_N);
         const int k = ka + SEG_N;
         const float sk = (float)k * f.step;
         const float pa = fmaf(sk, da, oa), pb = fmaf(sk, db, ob), pc = fmaf(sk, dc, oc);
-        go = (PRIMARY ? (sk <= smax) : (fmaf(pc, pc, fmaf(pb, pb, pa * pa)) <= f.R2f)) & (k < f.kmax);
+        go = (PRIMARY ? (sk <= smax) : (fmaf(pc, pc, fmaf(pb, pb, pa * pa)) <= f.R2f)) & (!BOUNDED || sk < smax) & (k < f.kmax);
         if (!PRIMARY && go && k >= m.kend) {           // cut by the horizon bound: the rest of the ray is above the terrain
-            if (STATS) cnt[ST_HEIGHT] += steps_after(f, m, k + 1);
+            if (STATS) cnt[ST_HEIGHT] += steps_after<BOUNDED>(f, m, k + 1, smax);
             go = false;
         }
     }
@@ -777,7 +782,7 @@ __device__ __forceinline__ int first_kept_step(const FrameC& f, const MarchState
 // ONE 16-step segment of a march (the lanes that call it are still marching): anchors + skip interval, the steps
 // that can be at/below the surface, the termination test at the segment end.  `hit` / `sk_hit` are set by the step
 // that lands at/below the surface, `go` says whether the ray continues with the next segment.
-template <bool WIDE, bool PRIMARY, bool STATS, int BATCH, int CP = 0, int SCAN = PRIMARY ? 1 : 0>
+template <bool WIDE, bool PRIMARY, bool STATS, int BATCH, int CP = 0, int SCAN = PRIMARY ? 1 : 0, bool BOUNDED = false>
 __device__ __forceinline__ void march_segment(const FrameC& f, MarchState& m, float smax, Seg& sg, bool& go, bool& hit,
                                               float& sk_hit, uint32_t* cnt) {
     const float oa = m.oa, ob = m.ob, oc = m.oc, da = m.da, db = m.db, dc = m.dc;
@@ -789,7 +794,7 @@ __device__ __forceinline__ void march_segment(const FrameC& f, MarchState& m, fl
         // asked again from HERE, the remaining track is shorter and the bound may apply.
         const int ke = horizon_retry(f, m);
         if (ke < 1) {                        // above everything in reach already: the march ends before this segment
-            if (STATS) cnt[ST_HEIGHT] += steps_after(f, m, ka + 1);
+            if (STATS) cnt[ST_HEIGHT] += steps_after<BOUNDED>(f, m, ka + 1, smax);
             go = false;
             return;
         }
@@ -811,11 +816,11 @@ __device__ __forceinline__ void march_segment(const FrameC& f, MarchState& m, fl
     if (SCAN == 3 && (MRTX_SEG_MASK & 1) != 0 && CF(f)->mip2 != nullptr) sg.jhi = last_kept_step<STATS, MRTX_PMASK_Q>(f, m, sg, cnt);   // A/B: the trial segment
     PROF_END(6);
     PROF_BEGIN(7);
-    if (STATS) cnt[ST_HEIGHT] += count_in_steps<PRIMARY>(f, oa, ob, oc, da, db, dc, smax, ka, 1, sg.jlo - 1);
+    if (STATS) cnt[ST_HEIGHT] += count_in_steps<PRIMARY, BOUNDED>(f, oa, ob, oc, da, db, dc, smax, ka, 1, sg.jlo - 1);
     if (__ballot(sg.exact) != 0ull)
-        step_loop<WIDE, PRIMARY, STATS, true, 1, CP>(f, oa, ob, oc, da, db, dc, smax, sg, ka, go, hit, sk_hit, cnt);
+        step_loop<WIDE, PRIMARY, STATS, true, 1, CP, BOUNDED>(f, oa, ob, oc, da, db, dc, smax, sg, ka, go, hit, sk_hit, cnt);
     else
-        step_loop<WIDE, PRIMARY, STATS, false, BATCH, CP>(f, oa, ob, oc, da, db, dc, smax, sg, ka, go, hit, sk_hit, cnt);
+        step_loop<WIDE, PRIMARY, STATS, false, BATCH, CP, BOUNDED>(f, oa, ob, oc, da, db, dc, smax, sg, ka, go, hit, sk_hit, cnt);
     PROF_END(7);
 #ifdef MRTX_PROF
 #if !defined(MRTX_PROF_SPREAD) && !defined(MRTX_PROF_TRIAL) && !defined(MRTX_PROF_FULLIV)
@@ -828,20 +833,20 @@ __device__ __forceinline__ void march_segment(const FrameC& f, MarchState& m, fl
     cnt[8] += 1; cnt[9] += (uint32_t)__popcll(__ballot(true));
 #endif
 #endif
-    segment_tail<PRIMARY, STATS>(f, m, smax, sg, go, rowB, colB, q2B, cnt);
+    segment_tail<PRIMARY, STATS, BOUNDED>(f, m, smax, sg, go, rowB, colB, q2B, cnt);
 }
 
 // Coarse march s_k = k*step, k = 1, 2, ...; returns true and s_k at the first sample at/below the surface.
 // PRIMARY: stop when s_k > smax (left the bounding sphere); shadow rays: stop when r^2 > R^2.
 // A lane drops out of the exec mask when it hits or leaves, and the wave leaves the loop when no lane is still
-// marching.  f.kmax is a multiple of SEG_N.
-template <bool WIDE, bool PRIMARY, bool STATS, int BATCH, int SCAN = PRIMARY ? 1 : 0>
+// marching.  f.kmax is a multiple of SEG_N.  BOUNDED (shadow rays): the steps end before s_k >= smax as well.
+template <bool WIDE, bool PRIMARY, bool STATS, int BATCH, int SCAN = PRIMARY ? 1 : 0, bool BOUNDED = false>
 __device__ __forceinline__ bool march(const FrameC& f, float oa, float ob, float oc, float da, float db, float dc,
                                       float smax, Seg& sg, float& sk_hit, uint32_t* cnt) {
     MarchState m;
     bool hit = false;
-    bool go = march_begin<PRIMARY, STATS>(f, oa, ob, oc, da, db, dc, m, cnt);
-    while (go) march_segment<WIDE, PRIMARY, STATS, BATCH, 0, SCAN>(f, m, smax, sg, go, hit, sk_hit, cnt);
+    bool go = march_begin<PRIMARY, STATS, false, BOUNDED>(f, oa, ob, oc, da, db, dc, m, cnt, smax);
+    while (go) march_segment<WIDE, PRIMARY, STATS, BATCH, 0, SCAN, BOUNDED>(f, m, smax, sg, go, hit, sk_hit, cnt);
     return hit;
 }
 
@@ -2596,6 +2601,113 @@ __global__ void __launch_bounds__(64) scatter_flux_kernel(const ScatterC q) {
     q.out[(int64_t)p * q.m + k] = s * q.inv_k;
 }
 
+// Terrain line of sight (DESIGN.md sections 3.12 and 4.13).  One probe: does the raised target end T see the raised observer
+// end O?  The march starts at the lower end (|P|^2 in float32; the target on a tie) and heads for the other one, so a swap of
+// the two ends marches the same ray (O - T == -(T - O) exactly); it is a shadow ray's march -- steps, skip intervals,
+// horizon-mip cut, below test -- that also ends before the first step with s_k >= L.  A lower end outside the bounding sphere
+// marches from where the segment enters the sphere, or not at all when the segment misses it.  true: clear.
+template <bool STATS, bool WIDE>
+__device__ __forceinline__ bool sight_probe(const FrameC& f, float Ta, float Tb, float Tc, float Oa, float Ob, float Oc,
+                                            uint32_t* cnt) {
+    if (STATS) cnt[ST_SHADOW]++;
+    const float rT = fmaf(Tc, Tc, fmaf(Tb, Tb, Ta * Ta)), rO = fmaf(Oc, Oc, fmaf(Ob, Ob, Oa * Oa));
+    const bool from_t = rT <= rO;
+    float oa = from_t ? Ta : Oa, ob = from_t ? Tb : Ob, oc = from_t ? Tc : Oc;
+    const float ta = from_t ? Oa - Ta : Ta - Oa, tb = from_t ? Ob - Tb : Tb - Ob, tc = from_t ? Oc - Tc : Tc - Oc;
+    const float L2 = fmaf(tc, tc, fmaf(tb, tb, ta * ta));
+    if (!(L2 > 0.0f)) return true;                          // the two ends coincide
+    const float L = sqrt_sh(L2);
+    const float inv = rcp_cr(L);
+    const float da = ta * inv, db = tb * inv, dc = tc * inv;
+    float smax = L;
+    const float q0 = from_t ? rT : rO;
+    if (q0 > f.R2f) {                                       // the lower end lies outside the bounding sphere
+        const float b = fmaf(oc, dc, fmaf(ob, db, oa * da));
+        const float c = q0 - f.R2f;
+        const float disc = fmaf(b, b, -c);
+        if (!(b < 0.0f) || !(disc >= 0.0f)) return true;   // heads away from the sphere, or misses it
+        const float s_in = c / (sqrtf(disc) - b);           // the nearer root of s^2 + 2 b s + c, without cancellation
+        if (!(s_in < L)) return true;                       // the segment ends before the sphere
+        oa = fmaf(s_in, da, oa); ob = fmaf(s_in, db, ob); oc = fmaf(s_in, dc, oc);
+        smax = L - s_in;
+    }
+    Seg ssg;
+    float sk_occ;
+    return !march<WIDE, false, STATS, MRTX_STEP_BATCH, 2, true>(f, oa, ob, oc, da, db, dc, smax, ssg, sk_occ, cnt);
+}
+
+// the raised end of a vertex: P = fmaf(hs, u, o), o = the lifted origin fmaf(scene_eps, n, p) of light_sample
+__device__ __forceinline__ void sight_end(const FrameC& f, const Vertex& v, float ua, float ub, float uc, float hs, float& Pa,
+                                          float& Pb, float& Pc) {
+    const float eps = CF(f)->scene_eps;
+    Pa = fmaf(hs, ua, fmaf(eps, v.na, v.pa));
+    Pb = fmaf(hs, ub, fmaf(eps, v.nb, v.pb));
+    Pc = fmaf(hs, uc, fmaf(eps, v.nc, v.pc));
+}
+
+// Per target the extra mast height (metres) at which it sees the observer: 0 if it does at its own height, otherwise a
+// bisection over t in [0, 1] of the mast t * mast_max (n_bis - 1 probes after the one at t = 1), +inf when even mast_max
+// is blocked.  Lane = target; a wave = 64 neighbouring nodes of one row (or 64 consecutive points), so with one observer its
+// rays leave nearby points for one end point.  The observer's vertex is formed per lane with the target's own code.
+template <bool STATS, bool WIDE>
+__global__ void __launch_bounds__(64) sight_kernel(const FrameC f, const SightC q) {
+    const int lane = threadIdx.x;
+    const int row = (int)(blockIdx.x / (unsigned)q.waves_x);
+    const int col = (int)(blockIdx.x % (unsigned)q.waves_x) * 64 + lane;
+    const bool in = row < q.g.rows && col < q.g.cols;
+    uint32_t cnt_store[STATS ? ST_N : 1];
+    uint32_t* const cnt = STATS ? cnt_store : nullptr;
+    if (STATS) {
+#pragma unroll
+        for (int i = 0; i < ST_N; i++) cnt[i] = 0;
+    }
+    if (in) {
+        Vertex vt, vo;
+        (void)illum_vertex<STATS, WIDE>(f, q.g, row, col, vt, cnt);
+        const int oi = q.n_obs == 1 ? 0 : col;
+        (void)illum_vertex<STATS, WIDE>(f, q.obs, oi, oi, vo, cnt);   // obs.points = 1: both tables indexed by the observer
+        const float2 rt = reinterpret_cast<const float2*>(q.g.rtab)[q.g.points ? col : row];
+        const float2 ct = reinterpret_cast<const float2*>(q.g.ctab)[col];
+        const float2 ro = reinterpret_cast<const float2*>(q.obs.rtab)[oi];
+        const float2 co = reinterpret_cast<const float2*>(q.obs.ctab)[oi];
+        float Oa, Ob, Oc;
+        sight_end(f, vo, ro.y * co.x, ro.y * co.y, ro.x, q.obs_hs[oi], Oa, Ob, Oc);
+        const float ua = rt.y * ct.x, ub = rt.y * ct.y, uc = rt.x;
+        // the target raised by target_h + t * mast_max metres
+        auto probe = [&](float t) {
+            const float hs = (float)((q.target_h_m + (double)t * q.mast_max_m) / q.radius_m * q.R);
+            float Ta, Tb, Tc;
+            sight_end(f, vt, ua, ub, uc, hs, Ta, Tb, Tc);
+            return sight_probe<STATS, WIDE>(f, Ta, Tb, Tc, Oa, Ob, Oc, cnt);
+        };
+        float m = 0.0f;
+        if (!probe(0.0f)) {
+            m = __builtin_inff();
+            if (q.n_bis > 0 && probe(1.0f)) {
+                float lo = 0.0f, hi = 1.0f;
+                for (int i = 1; i < q.n_bis; i++) {
+                    const float mid = 0.5f * (lo + hi);             // dyadic, at most 23 fraction bits: exact
+                    const bool clear = probe(mid);
+                    hi = clear ? mid : hi;
+                    lo = clear ? lo : mid;
+                }
+                m = (float)((double)hi * q.mast_max_m);
+            }
+        }
+        q.out[(int64_t)row * q.g.cols + col] = m;
+    }
+    if (STATS) {
+        const int which[4] = {ST_SHADOW, ST_HEIGHT, ST_FETCH, ST_MIP};
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            uint32_t c = cnt[which[i]];
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) c += __shfl_xor(c, m, 64);
+            if (lane == 0) atomicAdd(&CF(f)->stats[which[i]], (unsigned long long)c);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // D6 behind a queue: what is left of a path after render_kernel<MODE 2> (set_uint("path_seg_range", 2, 4),
 // moon_renderer.py:583).
@@ -3939,6 +4051,24 @@ hipError_t mrtx_launch_horizon_sun(const FrameC& f, HorizonSunC q, hipStream_t s
     const dim3 grid((unsigned)q.g.rows), block(64);
     if (f.dem_wide) hipLaunchKernelGGL((mrtx::horizon_sun_kernel<true>), grid, block, 0, st, f, q);
     else hipLaunchKernelGGL((mrtx::horizon_sun_kernel<false>), grid, block, 0, st, f, q);
+    return hipGetLastError();
+}
+
+// Terrain line of sight (sight_kernel): one lane per target, q.g.rows rows of q.g.cols targets, 64 targets of a row per wave.
+hipError_t mrtx_launch_sight(const FrameC& f, SightC q, bool stats, hipStream_t st) {
+    if (q.g.rows < 1 || q.g.cols < 1 || q.n_bis < 0 || q.n_bis > 24 || (q.n_obs != 1 && q.n_obs != q.g.cols) || !q.g.rtab ||
+        !q.g.ctab || !q.obs.rtab || !q.obs.ctab || !q.obs_hs || !q.out || !q.obs.points)
+        return hipErrorInvalidValue;
+    if ((uint64_t)q.g.rows * (uint64_t)q.g.cols > (1ull << 31)) return hipErrorInvalidValue;
+    q.waves_x = (q.g.cols + 63) / 64;
+    const uint64_t waves = (uint64_t)q.g.rows * (uint64_t)q.waves_x;
+    if (waves > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)waves), block(64);
+    const bool wide = f.dem_wide != 0;
+    if (stats) { if (wide) hipLaunchKernelGGL((mrtx::sight_kernel<true, true>), grid, block, 0, st, f, q);
+                 else hipLaunchKernelGGL((mrtx::sight_kernel<true, false>), grid, block, 0, st, f, q); }
+    else { if (wide) hipLaunchKernelGGL((mrtx::sight_kernel<false, true>), grid, block, 0, st, f, q);
+           else hipLaunchKernelGGL((mrtx::sight_kernel<false, false>), grid, block, 0, st, f, q); }
     return hipGetLastError();
 }
 

@@ -582,6 +582,71 @@ class MoonRT:
             stats["newton_cap_hits"] = stats.get("newton_cap_hits", 0) + int(st.reserved)
         return out if out is not None else res
 
+    # ---- Terrain line of sight
+    @staticmethod
+    def _observer(observer):
+        o = np.asarray(observer, np.float64)
+        if o.shape != (3,):
+            raise ValueError("observer must be one (lat, lon, height_m) triple")
+        return o
+
+    def viewshed(self, observer, lat=(90.0, -90.0), lon=(-180.0, 180.0), shape=(180, 360), target_height_m=0.0, mast_max_m=0.0,
+                 n_bis=0, radius_m=1737400.0, rows=None, stats=None, band_bytes=256 << 20):
+        """(rows, w) float32 map over the nodes of illumination_map's grid: per node the extra mast height, metres, at which a
+        target raised target_height_m there sees the observer (lat, lon, height_m): 0 where it does already, +inf where even
+        mast_max_m does not (n_bis = 0: a plain viewshed, 0 or +inf); otherwise the bisection's n_bis probes narrow it to
+        mast_max_m / 2^(n_bis - 1).  radius_m = the metres of D = 1 (1737400 * the DEM's radius_scale).  Bands of at most
+        band_bytes go through one device buffer; `stats`, if a dict, receives the summed counters."""
+        o = self._observer(observer)
+        h, w = int(shape[0]), int(shape[1])
+        r0, r1 = (0, h) if rows is None else (int(rows[0]), int(rows[1]))
+        g = _lib.MrtxSightGrid(o[0], o[1], o[2], float(target_height_m), float(mast_max_m), float(radius_m), float(lat[0]),
+                               float(lat[1]), float(lon[0]), float(lon[1]), h, w, r0, r1, int(n_bis), 0)
+        out = np.empty((max(r1 - r0, 0), w), np.float32)
+        step = max(1, int(band_bytes) // (4 * max(w, 1)))
+        if r1 - r0 <= step:      # one band: straight into the host array
+            st = MrtxStats()
+            self._check(self._lib.mrtx_sight_grid(self._ctx, C.byref(g), None, out.ctypes.data, C.byref(st)), "mrtx_sight_grid")
+            self._add_stats(stats, st)
+            return out
+        buf = DeviceBuffer(4 * step * w, self.config()["device"])
+        try:
+            for a in range(r0, r1, step):
+                g.row_begin, g.row_end = a, min(a + step, r1)
+                st = MrtxStats()
+                self._check(self._lib.mrtx_sight_grid(self._ctx, C.byref(g), buf.ptr, None, C.byref(st)), "mrtx_sight_grid")
+                self._add_stats(stats, st)
+                out[a - r0:g.row_end - r0] = buf.download(np.float32, (g.row_end - a, w))
+        finally:
+            buf.free()
+        return out
+
+    def line_of_sight(self, lat_deg, lon_deg, observer, target_height_m=0.0, mast_max_m=0.0, n_bis=0, radius_m=1737400.0,
+                      stats=None, chunk_bytes=256 << 20):
+        """(N,) float32 extra mast heights, metres, of N targets (degrees) toward `observer`: one (lat, lon, height_m) triple
+        shared by all, or an (N, 3) array, one per target.  As viewshed; a target on a grid node gives that node's value.
+        Calls hold at most chunk_bytes of output each (targets split between calls)."""
+        la, lo = self._points(lat_deg, lon_deg)
+        obs = np.asarray(observer, np.float64)
+        if obs.shape == (3,):
+            obs = obs.reshape(1, 3)
+        elif obs.shape != (la.size, 3):
+            raise ValueError("observer must be one (lat, lon, height_m) triple or one per target, (N, 3)")
+        obs = np.ascontiguousarray(obs)
+        shared = obs.shape[0] == 1
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        out = np.empty(la.size, np.float32)
+        step = max(1, min(int(chunk_bytes) // 4, 1 << 31))
+        for a in range(0, la.size, step):
+            b = min(a + step, la.size)
+            st = MrtxStats()
+            op, no = (obs.ctypes.data, 1) if shared else (obs[a:].ctypes.data, b - a)
+            self._check(self._lib.mrtx_sight_points(self._ctx, pts[a:].ctypes.data, b - a, op, no, float(target_height_m),
+                                                    float(mast_max_m), float(radius_m), int(n_bis), None, out[a:].ctypes.data,
+                                                    C.byref(st)), "mrtx_sight_points")
+            self._add_stats(stats, st)
+        return out
+
     @staticmethod
     def _add_stats(acc, st):
         if isinstance(acc, dict):
