@@ -10,9 +10,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/moonrt.h"
@@ -57,8 +59,7 @@ hipError_t mrtx_launch_illum_series(const FrameC& f, IllumSeriesC q, bool stats,
 hipError_t mrtx_launch_horizon(const FrameC& f, HorizonC h, bool stats, hipStream_t st);
 hipError_t mrtx_launch_horizon_sun(const FrameC& f, HorizonSunC q, hipStream_t st);
 hipError_t mrtx_launch_sight(const FrameC& f, SightC q, bool stats, hipStream_t st);
-hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, hipStream_t st);
-hipError_t mrtx_launch_thermal_scatter(const FrameC& f, const ThermalC& q, hipStream_t st);
+hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, bool ext, hipStream_t st);
 hipError_t mrtx_launch_view_hits(const FrameC& f, const ViewC& q, bool stats, hipStream_t st);
 hipError_t mrtx_launch_scatter_flux(const ScatterC& q, hipStream_t st);
 
@@ -1242,91 +1243,11 @@ static void illum_sc(double deg, float* sc) {
     sc[1] = (float)std::cos(r);
 }
 
-// Everything after the argument checks: state, tables, one launch into `dev_out`, counters.  rtab / ctab are host tables of
-// (sin, cos) pairs: n_r and n_c entries.  A series (mrtx_illum_series) passes `lights`, 8 floats per epoch, and `first` (per
-// point, or null): then rows = points, cols = the window's length, and the context's own light and Moon frame are not used.
-static int illum_run(mrtx_ctx* c, const std::vector<float>& rtab, const std::vector<float>& ctab, int rows, int cols, bool points,
-                     int n_sun, void* dev_out, float* host_out, MrtxStats* out, const std::vector<float>* lights = nullptr,
-                     const int32_t* first = nullptr) {
-    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
-    if (!lights && !c->moon_set) return fail(c, MRTX_E_STATE, "no moon frame: call mrtx_set_moon_frame first");
-    if (!lights && !c->light_set) return fail(c, MRTX_E_STATE, "no light: call mrtx_set_light first");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (!(c->prm.flags & MRTX_F_NO_SKIP)) { const int rc_ = ensure_mip(c); if (rc_ != MRTX_OK) return rc_; }
-    FrameC f;
-    FrameCold cold;
-    std::memset(&cold, 0, sizeof cold);
-    build_frame(c, f, cold);
-    if (!c->illum_cold) HIPCHK(c, hipMalloc((void**)&c->illum_cold, sizeof(FrameCold)));
-    if (!c->illum_stats) HIPCHK(c, hipMalloc((void**)&c->illum_stats, 16 * sizeof(unsigned long long)));
-    cold.accum = nullptr; cold.hits = nullptr; cold.stats = c->illum_stats; cold.stats_paths = nullptr;
-    f.cold = c->illum_cold;
-    const bool stats = (c->prm.flags & MRTX_F_COUNT_STATS) != 0;
-    if (c->prm.flags & MRTX_F_FORCE_WIDE) f.dem_wide = 1;
-    if (c->prm.flags & MRTX_F_NO_SKIP) f.mip = nullptr;   // (build_frame leaves the horizon mip out as well)
-    // one device block: sample table (64 pairs), row table, column table[, epoch lights (16-byte aligned: the tables above hold
-    // 4 floats per point), first epochs]
-    const size_t n_lights = lights ? lights->size() : 0, n_first = first ? (size_t)rows : 0;
-    const size_t tab_bytes = (128 + rtab.size() + ctab.size() + n_lights + n_first) * sizeof(float);
-    if (tab_bytes > c->illum_tab_bytes) {
-        if (c->illum_tab) { HIPCHK(c, hipFree(c->illum_tab)); c->illum_tab = nullptr; c->illum_tab_bytes = 0; }
-        HIPCHK(c, hipMalloc((void**)&c->illum_tab, tab_bytes));
-        c->illum_tab_bytes = tab_bytes;
-    }
-    std::vector<float> host((size_t)128 + rtab.size() + ctab.size() + n_lights + n_first, 0.0f);
-    mrtx_illum_sun_samples(n_sun, host.data());
-    std::copy(rtab.begin(), rtab.end(), host.begin() + 128);
-    std::copy(ctab.begin(), ctab.end(), host.begin() + 128 + (ptrdiff_t)rtab.size());
-    const size_t lights_at = 128 + rtab.size() + ctab.size(), first_at = lights_at + n_lights;
-    if (lights) std::copy(lights->begin(), lights->end(), host.begin() + (ptrdiff_t)lights_at);
-    if (first) std::memcpy(host.data() + first_at, first, n_first * sizeof(int32_t));
-    const size_t out_bytes = (size_t)rows * (size_t)cols * 16;
-    if (!dev_out) {
-        if (out_bytes > c->illum_out_bytes) {
-            if (c->illum_out) { HIPCHK(c, hipFree(c->illum_out)); c->illum_out = nullptr; c->illum_out_bytes = 0; }
-            HIPCHK(c, hipMalloc((void**)&c->illum_out, out_bytes));
-            c->illum_out_bytes = out_bytes;
-        }
-        dev_out = c->illum_out;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->illum_cold, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->illum_tab, host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
-    if (stats) HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
-    IllumC g;
-    std::memset(&g, 0, sizeof g);
-    g.sun = c->illum_tab; g.rtab = c->illum_tab + 128; g.ctab = g.rtab + rtab.size();
-    g.out = (float*)dev_out; g.rows = rows; g.cols = cols; g.points = points ? 1 : 0; g.n_sun = n_sun;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    if (lights) {
-        IllumSeriesC q;
-        q.g = g;
-        q.lights = c->illum_tab + lights_at;
-        q.first = first ? reinterpret_cast<const int32_t*>(c->illum_tab + first_at) : nullptr;
-        HIPCHK(c, mrtx_launch_illum_series(f, q, stats, c->stream));
-    } else {
-        HIPCHK(c, mrtx_launch_illum(f, g, stats, c->stream));
-    }
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));     // also: the pageable tables above are no longer read
-    float ms = 0.0f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    if (host_out) HIPCHK(c, hipMemcpy(host_out, dev_out, out_bytes, hipMemcpyDeviceToHost));
-    if (out) {
-        std::memset(out, 0, sizeof *out);
-        out->kernel_ms = ms;
-        out->launches = 1;
-        if (stats) {
-            unsigned long long h[16];
-            HIPCHK(c, hipMemcpy(h, c->illum_stats, sizeof h, hipMemcpyDeviceToHost));
-            out->shadow_rays = h[2]; out->height_samples = h[3]; out->dem_fetches = h[6]; out->mip_fetches = h[7];
-        }
-    }
-    return MRTX_OK;
-}
-
-int mrtx_illum_grid(mrtx_ctx* c, const MrtxIllumGrid* g, void* dev_out, float* host_out, MrtxStats* out) {
-    if (!c) return MRTX_E_INVALID;
-    if (!g) return fail(c, MRTX_E_INVALID, "null grid");
+// ---- What every terrain query shares: its tables, frame, staging, output and finish ---------------------------------------
+// The band of a lat/lon map (MrtxIllumGrid, or MrtxSightGrid's targets) checked and as the stage's tables: rtab = the rows'
+// (sin lat, cos lat), ctab = the columns' (sin lon, cos lon).  The illumination grid's n_sun is checked among them.
+extern "C++" template <class G>
+static int grid_tables(mrtx_ctx* c, const G* g, std::vector<float>& rtab, std::vector<float>& ctab) {
     if (!std::isfinite(g->lat_north) || !std::isfinite(g->lat_south) || !(g->lat_north > g->lat_south) || g->lat_north > 90.0 ||
         g->lat_south < -90.0)
         return fail(c, MRTX_E_INVALID, "latitudes must satisfy 90 >= lat_north > lat_south >= -90");
@@ -1336,24 +1257,23 @@ int mrtx_illum_grid(mrtx_ctx* c, const MrtxIllumGrid* g, void* dev_out, float* h
     if (g->h < 1 || g->w < 1) return fail(c, MRTX_E_INVALID, "empty grid (%d x %d)", g->h, g->w);
     if (g->row_begin < 0 || g->row_end > g->h || g->row_begin >= g->row_end)
         return fail(c, MRTX_E_INVALID, "bad band [%d, %d) of %d rows", g->row_begin, g->row_end, g->h);
-    if (!illum_n_ok(g->n_sun)) return fail(c, MRTX_E_INVALID, "n_sun must be 1, 2, 4, ..., 64 (got %d)", g->n_sun);
+    if constexpr (std::is_same<G, MrtxIllumGrid>::value)
+        if (!illum_n_ok(g->n_sun)) return fail(c, MRTX_E_INVALID, "n_sun must be 1, 2, 4, ..., 64 (got %d)", g->n_sun);
     if ((int64_t)(g->row_end - g->row_begin) * (int64_t)g->w > (int64_t)1 << 31)
         return fail(c, MRTX_E_INVALID, "a band holds at most 2^31 nodes: split the map into more bands");
-    if (!dev_out && !host_out) return fail(c, MRTX_E_INVALID, "no output buffer");
     const int rows = g->row_end - g->row_begin;
-    std::vector<float> rtab((size_t)rows * 2), ctab((size_t)g->w * 2);
+    rtab.assign((size_t)rows * 2, 0.0f);
+    ctab.assign((size_t)g->w * 2, 0.0f);
     const double dlat = (g->lat_north - g->lat_south) / (double)g->h, dlon = (g->lon_east - g->lon_west) / (double)g->w;
     for (int i = 0; i < rows; i++) illum_sc(g->lat_north - ((double)(g->row_begin + i) + 0.5) * dlat, &rtab[(size_t)i * 2]);
     for (int j = 0; j < g->w; j++) illum_sc(g->lon_west + ((double)j + 0.5) * dlon, &ctab[(size_t)j * 2]);
-    return illum_run(c, rtab, ctab, rows, g->w, false, g->n_sun, dev_out, host_out, out);
+    return MRTX_OK;
 }
 
-int mrtx_illum_points(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_sun, float* host_out4, MrtxStats* out) {
-    if (!c) return MRTX_E_INVALID;
-    if (n < 1) return fail(c, MRTX_E_INVALID, "n must be >= 1 (got %d)", n);
-    if (!latlon || !host_out4) return fail(c, MRTX_E_INVALID, "null point list or output");
-    if (!illum_n_ok(n_sun)) return fail(c, MRTX_E_INVALID, "n_sun must be 1, 2, 4, ..., 64 (got %d)", n_sun);
-    std::vector<float> rtab((size_t)n * 2), ctab((size_t)n * 2);
+// A point list checked and as the stage's tables: rtab = n (sin lat, cos lat) pairs, ctab = n (sin lon, cos lon) pairs
+static int point_tables(mrtx_ctx* c, const double* latlon, int32_t n, std::vector<float>& rtab, std::vector<float>& ctab) {
+    rtab.assign((size_t)n * 2, 0.0f);
+    ctab.assign((size_t)n * 2, 0.0f);
     for (int32_t i = 0; i < n; i++) {
         const double la = latlon[2 * (size_t)i], lo = latlon[2 * (size_t)i + 1];
         if (!std::isfinite(la) || !std::isfinite(lo) || la > 90.0 || la < -90.0 || std::fabs(lo) > 1e6)
@@ -1361,6 +1281,160 @@ int mrtx_illum_points(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_su
         illum_sc(la, &rtab[(size_t)i * 2]);
         illum_sc(lo, &ctab[(size_t)i * 2]);
     }
+    return MRTX_OK;
+}
+
+// grow one of the stage's device buffers to at least `bytes`
+static int stage_buffer(mrtx_ctx* c, float*& p, size_t& cap, size_t bytes) {
+    if (bytes > cap) {
+        if (p) { HIPCHK(c, hipFree(p)); p = nullptr; cap = 0; }
+        HIPCHK(c, hipMalloc((void**)&p, bytes));
+        cap = bytes;
+    }
+    return MRTX_OK;
+}
+
+// The frame of a terrain launch: the context's DEM and march parameters (and the horizon mip when the launch marches), the
+// stage's own cold block and counters.  sky: the single-epoch illumination calls, which also read the context's Moon frame
+// and light.  Called after every argument check.
+static int stage_frame(mrtx_ctx* c, FrameC& f, FrameCold& cold, bool march, bool sky = false) {
+    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
+    if (sky && !c->moon_set) return fail(c, MRTX_E_STATE, "no moon frame: call mrtx_set_moon_frame first");
+    if (sky && !c->light_set) return fail(c, MRTX_E_STATE, "no light: call mrtx_set_light first");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (march && !(c->prm.flags & MRTX_F_NO_SKIP)) { const int rc_ = ensure_mip(c); if (rc_ != MRTX_OK) return rc_; }
+    std::memset(&cold, 0, sizeof cold);
+    build_frame(c, f, cold);
+    if (!c->illum_cold) HIPCHK(c, hipMalloc((void**)&c->illum_cold, sizeof(FrameCold)));
+    if (!c->illum_stats) HIPCHK(c, hipMalloc((void**)&c->illum_stats, 16 * sizeof(unsigned long long)));
+    cold.accum = nullptr; cold.hits = nullptr; cold.stats = c->illum_stats; cold.stats_paths = nullptr;
+    f.cold = c->illum_cold;
+    if (c->prm.flags & MRTX_F_FORCE_WIDE) f.dem_wide = 1;
+    if (c->prm.flags & MRTX_F_NO_SKIP) f.mip = nullptr;   // (build_frame leaves the horizon mip out as well)
+    return MRTX_OK;
+}
+
+// n 4-byte words (float or int32) of host memory for stage_tables
+struct HostSeg {
+    const void* p;
+    size_t n;
+    HostSeg(const void* p_, size_t n_) : p(p_), n(n_) {}
+    HostSeg(const std::vector<float>& v) : p(v.data()), n(v.size()) {}
+};
+
+// The launch's tables in one device block, c->illum_tab: each segment at an offset rounded up to 16 bytes (the float4 loads
+// of the epoch lights), copied straight from the caller's memory, which must stay put until stage_finish.  dev[i] = segment
+// i's device address.  Called after stage_out, so that every buffer is grown before the first copy is queued.
+static int stage_tables(mrtx_ctx* c, std::initializer_list<HostSeg> segs, float** dev) {
+    size_t words = 0;
+    for (const HostSeg& s : segs) words += (s.n + 3) & ~(size_t)3;
+    const int rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, std::max(words * 4, (size_t)16));
+    if (rc != MRTX_OK) return rc;
+    float* d = c->illum_tab;
+    for (const HostSeg& s : segs) {
+        if (s.n) HIPCHK(c, hipMemcpyAsync(d, s.p, s.n * 4, hipMemcpyHostToDevice, c->stream));
+        *dev++ = d;
+        d += (s.n + 3) & ~(size_t)3;
+    }
+    return MRTX_OK;
+}
+
+// where the launch writes: the caller's dev_out, or else c->illum_out grown to `bytes` (read back by stage_finish)
+static int stage_out(mrtx_ctx* c, void*& dev_out, size_t bytes) {
+    if (dev_out) return MRTX_OK;
+    const int rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, bytes);
+    dev_out = c->illum_out;
+    return rc;
+}
+
+// right before the launch: the cold block (if any) and zeroed counters (if asked) queued, then the start event
+static int stage_start(mrtx_ctx* c, const FrameCold* cold, bool zero) {
+    if (cold) HIPCHK(c, hipMemcpyAsync(c->illum_cold, cold, sizeof *cold, hipMemcpyHostToDevice, c->stream));
+    if (zero) HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    return MRTX_OK;
+}
+
+// the counter slot of a launch's rays (mrtx_kernels.hip's ST_SHADOW, ST_BOUNCE), or none when it did not count
+enum StageRays { kNoRays = -1, kShadowRays = 2, kBounceRays = 8 };
+
+// right after the launch: the end event, wait, time, read back, counters (rays: reported as shadow_rays or bounce_rays)
+static int stage_finish(mrtx_ctx* c, const void* dev_out, float* host_out, size_t out_bytes, MrtxStats* out, StageRays rays) {
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // also: the pageable tables are no longer read
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (host_out) HIPCHK(c, hipMemcpy(host_out, dev_out, out_bytes, hipMemcpyDeviceToHost));
+    if (out) {
+        std::memset(out, 0, sizeof *out);
+        out->kernel_ms = ms;
+        out->launches = 1;
+        if (rays != kNoRays) {
+            unsigned long long h[16];
+            HIPCHK(c, hipMemcpy(h, c->illum_stats, sizeof h, hipMemcpyDeviceToHost));
+            (rays == kBounceRays ? out->bounce_rays : out->shadow_rays) = h[rays];
+            out->height_samples = h[3]; out->dem_fetches = h[6]; out->mip_fetches = h[7];
+        }
+    }
+    return MRTX_OK;
+}
+
+// ---- Sun illumination: maps, points and series ---------------------------------------------------------------------------
+// Everything after the argument checks: state, tables, one launch into `dev_out`, counters.  rtab / ctab: n_r and n_c
+// (sin, cos) pairs.  A series (mrtx_illum_series) passes `lights`, 8 floats per epoch, and `first` (per point, or null): then
+// rows = points, cols = the window's length, and the context's own light and Moon frame are not used.
+static int illum_run(mrtx_ctx* c, const std::vector<float>& rtab, const std::vector<float>& ctab, int rows, int cols, bool points,
+                     int n_sun, void* dev_out, float* host_out, MrtxStats* out, const std::vector<float>* lights = nullptr,
+                     const int32_t* first = nullptr) {
+    FrameC f;
+    FrameCold cold;
+    int rc = stage_frame(c, f, cold, true, !lights);
+    if (rc != MRTX_OK) return rc;
+    const bool stats = (c->prm.flags & MRTX_F_COUNT_STATS) != 0;
+    float sun[128];
+    mrtx_illum_sun_samples(n_sun, sun);
+    const size_t out_bytes = (size_t)rows * (size_t)cols * 16;
+    float* d[5];
+    if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK ||
+        (rc = stage_tables(c, {{sun, 2 * (size_t)n_sun}, rtab, ctab,
+                               {lights ? lights->data() : nullptr, lights ? lights->size() : 0}, {first, first ? (size_t)rows : 0}},
+                           d)) != MRTX_OK)
+        return rc;
+    IllumC g;
+    std::memset(&g, 0, sizeof g);
+    g.sun = d[0]; g.rtab = d[1]; g.ctab = d[2];
+    g.out = (float*)dev_out; g.rows = rows; g.cols = cols; g.points = points ? 1 : 0; g.n_sun = n_sun;
+    if ((rc = stage_start(c, &cold, stats)) != MRTX_OK) return rc;
+    if (lights) {
+        IllumSeriesC q;
+        q.g = g;
+        q.lights = d[3];
+        q.first = first ? reinterpret_cast<const int32_t*>(d[4]) : nullptr;
+        HIPCHK(c, mrtx_launch_illum_series(f, q, stats, c->stream));
+    } else {
+        HIPCHK(c, mrtx_launch_illum(f, g, stats, c->stream));
+    }
+    return stage_finish(c, dev_out, host_out, out_bytes, out, stats ? kShadowRays : kNoRays);
+}
+
+int mrtx_illum_grid(mrtx_ctx* c, const MrtxIllumGrid* g, void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!g) return fail(c, MRTX_E_INVALID, "null grid");
+    std::vector<float> rtab, ctab;
+    const int rc = grid_tables(c, g, rtab, ctab);
+    if (rc != MRTX_OK) return rc;
+    if (!dev_out && !host_out) return fail(c, MRTX_E_INVALID, "no output buffer");
+    return illum_run(c, rtab, ctab, g->row_end - g->row_begin, g->w, false, g->n_sun, dev_out, host_out, out);
+}
+
+int mrtx_illum_points(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_sun, float* host_out4, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (n < 1) return fail(c, MRTX_E_INVALID, "n must be >= 1 (got %d)", n);
+    if (!latlon || !host_out4) return fail(c, MRTX_E_INVALID, "null point list or output");
+    if (!illum_n_ok(n_sun)) return fail(c, MRTX_E_INVALID, "n_sun must be 1, 2, 4, ..., 64 (got %d)", n_sun);
+    std::vector<float> rtab, ctab;
+    const int rc = point_tables(c, latlon, n, rtab, ctab);
+    if (rc != MRTX_OK) return rc;
     return illum_run(c, rtab, ctab, 1, n, true, n_sun, nullptr, host_out4, out);
 }
 
@@ -1401,17 +1475,10 @@ int mrtx_illum_series(mrtx_ctx* c, const double* latlon, int32_t n_points, const
             return fail(c, MRTX_E_INVALID, "point %d: window [%lld, %lld) runs outside the %d epochs", p, (long long)f0,
                         (long long)(f0 + count), n_epochs);
     }
-    std::vector<float> rtab((size_t)n_points * 2), ctab((size_t)n_points * 2);
-    for (int32_t i = 0; i < n_points; i++) {
-        const double la = latlon[2 * (size_t)i], lo = latlon[2 * (size_t)i + 1];
-        if (!std::isfinite(la) || !std::isfinite(lo) || la > 90.0 || la < -90.0 || std::fabs(lo) > 1e6)
-            return fail(c, MRTX_E_INVALID, "point %d: latitude must lie in [-90, 90] and longitude be finite", i);
-        illum_sc(la, &rtab[(size_t)i * 2]);
-        illum_sc(lo, &ctab[(size_t)i * 2]);
-    }
-    std::vector<float> lights;
-    const int rc = epoch_lights(c, ep, n_epochs, lights);
+    std::vector<float> rtab, ctab, lights;
+    int rc = point_tables(c, latlon, n_points, rtab, ctab);
     if (rc != MRTX_OK) return rc;
+    if ((rc = epoch_lights(c, ep, n_epochs, lights)) != MRTX_OK) return rc;
     return illum_run(c, rtab, ctab, n_points, count, true, n_sun, dev_out, host_out, out, &lights, first);
 }
 
@@ -1419,62 +1486,22 @@ int mrtx_illum_series(mrtx_ctx* c, const double* latlon, int32_t n_points, const
 static bool horizon_az_ok(int32_t n_az) { return n_az >= 4 && n_az <= 4096 && (n_az & (n_az - 1)) == 0; }
 static int log2_of(int32_t n) { int l = 0; while ((1 << l) < n) l++; return l; }
 
-// the point list as the illumination stage's tables: n (sin lat, cos lat) pairs, then n (sin lon, cos lon) pairs
-static int point_tables(mrtx_ctx* c, const double* latlon, int32_t n, std::vector<float>& tab) {
-    tab.assign((size_t)n * 4, 0.0f);
-    for (int32_t i = 0; i < n; i++) {
-        const double la = latlon[2 * (size_t)i], lo = latlon[2 * (size_t)i + 1];
-        if (!std::isfinite(la) || !std::isfinite(lo) || la > 90.0 || la < -90.0 || std::fabs(lo) > 1e6)
-            return fail(c, MRTX_E_INVALID, "point %d: latitude must lie in [-90, 90] and longitude be finite", i);
-        illum_sc(la, &tab[(size_t)i * 2]);
-        illum_sc(lo, &tab[((size_t)n + i) * 2]);
-    }
+// the horizon and output arguments of mrtx_horizon_sun and the thermal calls: where each lives, and the horizons' size
+static int horizon_args(mrtx_ctx* c, const void* dev_horizon, const float* host_horizon, int32_t n, int32_t n_az,
+                        const void* dev_out, const float* host_out) {
+    if ((dev_horizon == nullptr) == (host_horizon == nullptr))
+        return fail(c, MRTX_E_INVALID, "give exactly one of dev_horizon and host_horizon");
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    if ((int64_t)n * (int64_t)n_az > (int64_t)1 << 31) return fail(c, MRTX_E_INVALID, "at most 2^31 horizon samples per call");
     return MRTX_OK;
 }
 
-// grow one of the stage's device buffers to at least `bytes`
-static int stage_buffer(mrtx_ctx* c, float*& p, size_t& cap, size_t bytes) {
-    if (bytes > cap) {
-        if (p) { HIPCHK(c, hipFree(p)); p = nullptr; cap = 0; }
-        HIPCHK(c, hipMalloc((void**)&p, bytes));
-        cap = bytes;
-    }
-    return MRTX_OK;
-}
-
-// the frame of a horizon launch: the context's DEM and march parameters, the illumination stage's own cold block and counters
-// (the context's light and Moon frame are not read).  Called after every argument check.
-static int horizon_frame(mrtx_ctx* c, FrameC& f, FrameCold& cold, bool march) {
-    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (march && !(c->prm.flags & MRTX_F_NO_SKIP)) { const int rc_ = ensure_mip(c); if (rc_ != MRTX_OK) return rc_; }
-    std::memset(&cold, 0, sizeof cold);
-    build_frame(c, f, cold);
-    if (!c->illum_cold) HIPCHK(c, hipMalloc((void**)&c->illum_cold, sizeof(FrameCold)));
-    if (!c->illum_stats) HIPCHK(c, hipMalloc((void**)&c->illum_stats, 16 * sizeof(unsigned long long)));
-    cold.accum = nullptr; cold.hits = nullptr; cold.stats = c->illum_stats; cold.stats_paths = nullptr;
-    f.cold = c->illum_cold;
-    if (c->prm.flags & MRTX_F_FORCE_WIDE) f.dem_wide = 1;
-    if (c->prm.flags & MRTX_F_NO_SKIP) f.mip = nullptr;
-    return MRTX_OK;
-}
-
-// after the launch (between c->ev0 and c->ev1): wait, time, read back, counters
-static int horizon_finish(mrtx_ctx* c, bool stats, const void* dev_out, float* host_out, size_t out_bytes, MrtxStats* out) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));     // also: the pageable tables are no longer read
-    float ms = 0.0f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    if (host_out) HIPCHK(c, hipMemcpy(host_out, dev_out, out_bytes, hipMemcpyDeviceToHost));
-    if (out) {
-        std::memset(out, 0, sizeof *out);
-        out->kernel_ms = ms;
-        out->launches = 1;
-        if (stats) {
-            unsigned long long h[16];
-            HIPCHK(c, hipMemcpy(h, c->illum_stats, sizeof h, hipMemcpyDeviceToHost));
-            out->shadow_rays = h[2]; out->height_samples = h[3]; out->dem_fetches = h[6]; out->mip_fetches = h[7];
-        }
-    }
+// every entry of a host horizon table an elevation in [-90, 90] degrees (a device table is not scanned)
+static int horizon_entries(mrtx_ctx* c, const float* host_horizon, int32_t n, int32_t n_az) {
+    const size_t nh = host_horizon ? (size_t)n * (size_t)n_az : 0;
+    for (size_t i = 0; i < nh; i++)
+        if (!(host_horizon[i] >= -90.0f && host_horizon[i] <= 90.0f))
+            return fail(c, MRTX_E_INVALID, "horizon entry %zu is not an elevation in [-90, 90] degrees", i);
     return MRTX_OK;
 }
 
@@ -1488,31 +1515,24 @@ int mrtx_horizon_points(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_
     if ((int64_t)n * (int64_t)n_az > (int64_t)1 << 31)
         return fail(c, MRTX_E_INVALID, "a call holds at most 2^31 outputs: split the points into more calls");
     if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
-    std::vector<float> tab;
-    int rc = point_tables(c, latlon, n, tab);
+    std::vector<float> rtab, ctab;
+    int rc = point_tables(c, latlon, n, rtab, ctab);
     if (rc != MRTX_OK) return rc;
     FrameC f;
     FrameCold cold;
-    if ((rc = horizon_frame(c, f, cold, true)) != MRTX_OK) return rc;
+    if ((rc = stage_frame(c, f, cold, true)) != MRTX_OK) return rc;
     const bool stats = (c->prm.flags & MRTX_F_COUNT_STATS) != 0;
-    const size_t tab_bytes = tab.size() * sizeof(float), out_bytes = (size_t)n * (size_t)n_az * sizeof(float);
-    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, tab_bytes)) != MRTX_OK) return rc;
-    if (!dev_out) {
-        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, out_bytes)) != MRTX_OK) return rc;
-        dev_out = c->illum_out;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->illum_cold, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->illum_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
-    if (stats) HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
+    const size_t out_bytes = (size_t)n * (size_t)n_az * sizeof(float);
+    float* d[2];
+    if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK || (rc = stage_tables(c, {rtab, ctab}, d)) != MRTX_OK) return rc;
     HorizonC h;
     std::memset(&h, 0, sizeof h);
-    h.g.rtab = c->illum_tab; h.g.ctab = c->illum_tab + 2 * (size_t)n;
+    h.g.rtab = d[0]; h.g.ctab = d[1];
     h.g.rows = n; h.g.cols = n; h.g.points = 1;
     h.out = (float*)dev_out; h.az_log2 = log2_of(n_az); h.n_bis = n_bis;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if ((rc = stage_start(c, &cold, stats)) != MRTX_OK) return rc;
     HIPCHK(c, mrtx_launch_horizon(f, h, stats, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    return horizon_finish(c, stats, dev_out, host_out, out_bytes, out);
+    return stage_finish(c, dev_out, host_out, out_bytes, out, stats ? kShadowRays : kNoRays);
 }
 
 int mrtx_horizon_sun(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon, const float* host_horizon,
@@ -1524,51 +1544,33 @@ int mrtx_horizon_sun(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az,
     if (m > (1 << 24)) return fail(c, MRTX_E_INVALID, "at most 2^24 epochs per call (got %d)", m);
     if (!horizon_az_ok(n_az)) return fail(c, MRTX_E_INVALID, "n_az must be 4, 8, ..., 4096 (got %d)", n_az);
     if (mode != 0 && mode != 1) return fail(c, MRTX_E_INVALID, "mode must be 0 (FULL) or 1 (SUMMARY) (got %d)", mode);
-    if ((dev_horizon == nullptr) == (host_horizon == nullptr))
-        return fail(c, MRTX_E_INVALID, "give exactly one of dev_horizon and host_horizon");
-    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
-    if ((int64_t)n * (int64_t)n_az > (int64_t)1 << 31) return fail(c, MRTX_E_INVALID, "at most 2^31 horizon samples per call");
+    int rc = horizon_args(c, dev_horizon, host_horizon, n, n_az, dev_out, host_out);
+    if (rc != MRTX_OK) return rc;
     if (mode == 0 && (int64_t)n * (int64_t)m > (int64_t)1 << 31)
         return fail(c, MRTX_E_INVALID, "FULL holds at most 2^31 outputs per call: split the points into more calls");
-    if (host_horizon) {
-        const size_t nh = (size_t)n * (size_t)n_az;
-        for (size_t i = 0; i < nh; i++)
-            if (!(host_horizon[i] >= -90.0f && host_horizon[i] <= 90.0f))
-                return fail(c, MRTX_E_INVALID, "horizon entry %zu is not an elevation in [-90, 90] degrees", i);
-    }
-    std::vector<float> tab, lights;
-    int rc = point_tables(c, latlon, n, tab);
-    if (rc != MRTX_OK) return rc;
+    if ((rc = horizon_entries(c, host_horizon, n, n_az)) != MRTX_OK) return rc;
+    std::vector<float> rtab, ctab, lights;
+    if ((rc = point_tables(c, latlon, n, rtab, ctab)) != MRTX_OK) return rc;
     if ((rc = epoch_lights(c, epochs, m, lights)) != MRTX_OK) return rc;
     FrameC f;
     FrameCold cold;
-    if ((rc = horizon_frame(c, f, cold, false)) != MRTX_OK) return rc;
-    // one device block: point tables (4 floats per point: the lights that follow are 16-byte aligned), epoch lights[, horizons]
+    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
     const size_t nh = host_horizon ? (size_t)n * (size_t)n_az : 0;
-    const size_t tab_bytes = (tab.size() + lights.size() + nh) * sizeof(float);
     const size_t out_bytes = mode == 0 ? (size_t)n * (size_t)m * sizeof(float) : (size_t)n * 16;
-    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, tab_bytes)) != MRTX_OK) return rc;
-    if (!dev_out) {
-        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, out_bytes)) != MRTX_OK) return rc;
-        dev_out = c->illum_out;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->illum_cold, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->illum_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->illum_tab + tab.size(), lights.data(), lights.size() * sizeof(float), hipMemcpyHostToDevice,
-                             c->stream));
-    if (nh) HIPCHK(c, hipMemcpyAsync(c->illum_tab + tab.size() + lights.size(), host_horizon, nh * sizeof(float),
-                                     hipMemcpyHostToDevice, c->stream));
+    float* d[4];
+    if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK ||
+        (rc = stage_tables(c, {rtab, ctab, lights, {host_horizon, nh}}, d)) != MRTX_OK)
+        return rc;
     HorizonSunC q;
     std::memset(&q, 0, sizeof q);
-    q.g.rtab = c->illum_tab; q.g.ctab = c->illum_tab + 2 * (size_t)n;
+    q.g.rtab = d[0]; q.g.ctab = d[1];
     q.g.rows = n; q.g.cols = n; q.g.points = 1;
-    q.lights = c->illum_tab + tab.size();
-    q.horizon = nh ? c->illum_tab + tab.size() + lights.size() : (const float*)dev_horizon;
+    q.lights = d[2];
+    q.horizon = host_horizon ? d[3] : (const float*)dev_horizon;
     q.out = (float*)dev_out; q.az_log2 = log2_of(n_az); q.m = m; q.mode = mode;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if ((rc = stage_start(c, &cold, false)) != MRTX_OK) return rc;
     HIPCHK(c, mrtx_launch_horizon_sun(f, q, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    return horizon_finish(c, false, dev_out, host_out, out_bytes, out);
+    return stage_finish(c, dev_out, host_out, out_bytes, out, kNoRays);
 }
 
 // ---- Terrain line of sight -------------------------------------------------------------------------
@@ -1587,46 +1589,37 @@ static int sight_check(mrtx_ctx* c, double target_h_m, double mast_max_m, double
     return MRTX_OK;
 }
 
-// Everything after the argument checks: the targets' tables (tgt: rows then columns, 2 floats each), the observers' point
+// Everything after the argument checks: the targets' tables (trt, tct: rows x cols nodes, or a point list), the observers'
 // tables and raised heights (scene units), one launch into the output, counters.
-static int sight_run(mrtx_ctx* c, const std::vector<float>& tgt, int rows, int cols, bool points, const std::vector<float>& obs,
-                     const std::vector<double>& obs_h_m, double target_h_m, double mast_max_m, double radius_m, int32_t n_bis,
-                     void* dev_out, float* host_out, MrtxStats* out) {
+static int sight_run(mrtx_ctx* c, const std::vector<float>& trt, const std::vector<float>& tct, int rows, int cols, bool points,
+                     const std::vector<float>& ort, const std::vector<float>& oct, const std::vector<double>& obs_h_m,
+                     double target_h_m, double mast_max_m, double radius_m, int32_t n_bis, void* dev_out, float* host_out,
+                     MrtxStats* out) {
     FrameC f;
     FrameCold cold;
     int rc;
-    if ((rc = horizon_frame(c, f, cold, true)) != MRTX_OK) return rc;
+    if ((rc = stage_frame(c, f, cold, true)) != MRTX_OK) return rc;
     const bool stats = (c->prm.flags & MRTX_F_COUNT_STATS) != 0;
     const int n_obs = (int)obs_h_m.size();
-    // one device block: target tables, observer tables, observer heights
-    std::vector<float> host(tgt.size() + obs.size() + (size_t)n_obs);
-    std::copy(tgt.begin(), tgt.end(), host.begin());
-    std::copy(obs.begin(), obs.end(), host.begin() + (ptrdiff_t)tgt.size());
-    float* hs = host.data() + tgt.size() + obs.size();
-    for (int i = 0; i < n_obs; i++) hs[i] = (float)(obs_h_m[(size_t)i] / radius_m * c->radius);
-    const size_t tab_bytes = host.size() * sizeof(float), out_bytes = (size_t)rows * (size_t)cols * sizeof(float);
-    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, tab_bytes)) != MRTX_OK) return rc;
-    if (!dev_out) {
-        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, out_bytes)) != MRTX_OK) return rc;
-        dev_out = c->illum_out;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->illum_cold, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->illum_tab, host.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
-    if (stats) HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
+    std::vector<float> hs((size_t)n_obs);
+    for (int i = 0; i < n_obs; i++) hs[(size_t)i] = (float)(obs_h_m[(size_t)i] / radius_m * c->radius);
+    const size_t out_bytes = (size_t)rows * (size_t)cols * sizeof(float);
+    float* d[5];
+    if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK || (rc = stage_tables(c, {trt, tct, ort, oct, hs}, d)) != MRTX_OK)
+        return rc;
     SightC q;
     std::memset(&q, 0, sizeof q);
-    q.g.rtab = c->illum_tab; q.g.ctab = c->illum_tab + 2 * (size_t)(points ? cols : rows);
+    q.g.rtab = d[0]; q.g.ctab = d[1];
     q.g.rows = rows; q.g.cols = cols; q.g.points = points ? 1 : 0;
-    q.obs.rtab = c->illum_tab + tgt.size(); q.obs.ctab = q.obs.rtab + 2 * (size_t)n_obs;
+    q.obs.rtab = d[2]; q.obs.ctab = d[3];
     q.obs.rows = n_obs; q.obs.cols = n_obs; q.obs.points = 1;
-    q.obs_hs = c->illum_tab + tgt.size() + obs.size();
+    q.obs_hs = d[4];
     q.out = (float*)dev_out;
     q.target_h_m = target_h_m; q.mast_max_m = mast_max_m; q.radius_m = radius_m; q.R = c->radius;
     q.n_obs = n_obs; q.n_bis = n_bis;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if ((rc = stage_start(c, &cold, stats)) != MRTX_OK) return rc;
     HIPCHK(c, mrtx_launch_sight(f, q, stats, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    return horizon_finish(c, stats, dev_out, host_out, out_bytes, out);
+    return stage_finish(c, dev_out, host_out, out_bytes, out, stats ? kShadowRays : kNoRays);
 }
 
 int mrtx_sight_grid(mrtx_ctx* c, const MrtxSightGrid* g, void* dev_out, float* host_out, MrtxStats* out) {
@@ -1637,28 +1630,12 @@ int mrtx_sight_grid(mrtx_ctx* c, const MrtxSightGrid* g, void* dev_out, float* h
     if (!sight_height_ok(g->obs_h_m)) return fail(c, MRTX_E_INVALID, "observer height must lie in [0, 1e9] m");
     int rc = sight_check(c, g->target_h_m, g->mast_max_m, g->radius_m, g->n_bis, dev_out, host_out);
     if (rc != MRTX_OK) return rc;
-    // the grid as mrtx_illum_grid checks it
-    if (!std::isfinite(g->lat_north) || !std::isfinite(g->lat_south) || !(g->lat_north > g->lat_south) || g->lat_north > 90.0 ||
-        g->lat_south < -90.0)
-        return fail(c, MRTX_E_INVALID, "latitudes must satisfy 90 >= lat_north > lat_south >= -90");
-    if (!std::isfinite(g->lon_west) || !std::isfinite(g->lon_east) || !(g->lon_east > g->lon_west) || std::fabs(g->lon_west) > 1e6 ||
-        std::fabs(g->lon_east) > 1e6)
-        return fail(c, MRTX_E_INVALID, "longitudes must be finite with lon_west < lon_east");
-    if (g->h < 1 || g->w < 1) return fail(c, MRTX_E_INVALID, "empty grid (%d x %d)", g->h, g->w);
-    if (g->row_begin < 0 || g->row_end > g->h || g->row_begin >= g->row_end)
-        return fail(c, MRTX_E_INVALID, "bad band [%d, %d) of %d rows", g->row_begin, g->row_end, g->h);
-    if ((int64_t)(g->row_end - g->row_begin) * (int64_t)g->w > (int64_t)1 << 31)
-        return fail(c, MRTX_E_INVALID, "a band holds at most 2^31 nodes: split the map into more bands");
-    const int rows = g->row_end - g->row_begin;
-    std::vector<float> tgt((size_t)rows * 2 + (size_t)g->w * 2);
-    const double dlat = (g->lat_north - g->lat_south) / (double)g->h, dlon = (g->lon_east - g->lon_west) / (double)g->w;
-    for (int i = 0; i < rows; i++) illum_sc(g->lat_north - ((double)(g->row_begin + i) + 0.5) * dlat, &tgt[(size_t)i * 2]);
-    for (int j = 0; j < g->w; j++) illum_sc(g->lon_west + ((double)j + 0.5) * dlon, &tgt[((size_t)rows + j) * 2]);
-    std::vector<float> obs;
+    std::vector<float> trt, tct, ort, oct;
+    if ((rc = grid_tables(c, g, trt, tct)) != MRTX_OK) return rc;
     const double ll[2] = {g->obs_lat, g->obs_lon};
-    if ((rc = point_tables(c, ll, 1, obs)) != MRTX_OK) return rc;
-    return sight_run(c, tgt, rows, g->w, false, obs, std::vector<double>(1, g->obs_h_m), g->target_h_m, g->mast_max_m,
-                     g->radius_m, g->n_bis, dev_out, host_out, out);
+    if ((rc = point_tables(c, ll, 1, ort, oct)) != MRTX_OK) return rc;
+    return sight_run(c, trt, tct, g->row_end - g->row_begin, g->w, false, ort, oct, std::vector<double>(1, g->obs_h_m),
+                     g->target_h_m, g->mast_max_m, g->radius_m, g->n_bis, dev_out, host_out, out);
 }
 
 int mrtx_sight_points(mrtx_ctx* c, const double* target_latlon, int32_t n, const double* observer_llh, int32_t n_observers,
@@ -1671,8 +1648,8 @@ int mrtx_sight_points(mrtx_ctx* c, const double* target_latlon, int32_t n, const
         return fail(c, MRTX_E_INVALID, "n_observers must be 1 or n (got %d for n = %d)", n_observers, n);
     int rc = sight_check(c, target_h_m, mast_max_m, radius_m, n_bis, dev_out, host_out);
     if (rc != MRTX_OK) return rc;
-    std::vector<float> tgt;
-    if ((rc = point_tables(c, target_latlon, n, tgt)) != MRTX_OK) return rc;
+    std::vector<float> trt, tct, ort, oct;
+    if ((rc = point_tables(c, target_latlon, n, trt, tct)) != MRTX_OK) return rc;
     std::vector<double> oll((size_t)n_observers * 2), oh((size_t)n_observers);
     for (int32_t i = 0; i < n_observers; i++) {
         const double* o = observer_llh + 3 * (size_t)i;
@@ -1681,9 +1658,8 @@ int mrtx_sight_points(mrtx_ctx* c, const double* target_latlon, int32_t n, const
         if (!sight_height_ok(o[2])) return fail(c, MRTX_E_INVALID, "observer %d: height must lie in [0, 1e9] m", i);
         oll[2 * (size_t)i] = o[0]; oll[2 * (size_t)i + 1] = o[1]; oh[(size_t)i] = o[2];
     }
-    std::vector<float> obs;
-    if ((rc = point_tables(c, oll.data(), n_observers, obs)) != MRTX_OK) return rc;
-    return sight_run(c, tgt, 1, n, true, obs, oh, target_h_m, mast_max_m, radius_m, n_bis, dev_out, host_out, out);
+    if ((rc = point_tables(c, oll.data(), n_observers, ort, oct)) != MRTX_OK) return rc;
+    return sight_run(c, trt, tct, 1, n, true, ort, oct, oh, target_h_m, mast_max_m, radius_m, n_bis, dev_out, host_out, out);
 }
 
 // ---- Regolith surface temperatures ---------------------------------------------------------------
@@ -1774,14 +1750,11 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
             x_max = std::max(x_max, (double)host_extra[i]);
         }
     }
-    if ((dev_horizon == nullptr) == (host_horizon == nullptr))
-        return fail(c, MRTX_E_INVALID, "give exactly one of dev_horizon and host_horizon");
-    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
-    if ((int64_t)n * (int64_t)n_az > (int64_t)1 << 31) return fail(c, MRTX_E_INVALID, "at most 2^31 horizon samples per call");
+    int rc = horizon_args(c, dev_horizon, host_horizon, n, n_az, dev_out, host_out);
+    if (rc != MRTX_OK) return rc;
     const MrtxThermalModel& md = *model;
     double dmax = 0.0;
-    int rc = thermal_model_ok(c, md, m, mode, &dmax);
-    if (rc != MRTX_OK) return rc;
+    if ((rc = thermal_model_ok(c, md, m, mode, &dmax)) != MRTX_OK) return rc;
     const int64_t width = mode == 0 ? (int64_t)m - md.n_spin : mode == 2 ? (int64_t)m : mode == 3 ? 2 * ((int64_t)m - md.n_spin) : 4;
     if ((int64_t)n * width > (int64_t)1 << 31)
         return fail(c, MRTX_E_INVALID, "a call holds at most 2^31 outputs: split the points into more calls");
@@ -1804,48 +1777,29 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
         if (!(t_eq <= 450.0))
             return fail(c, MRTX_E_INVALID, "the radiative-equilibrium temperature %.1f K exceeds 450 K, the model's range", t_eq);
     }
-    if (host_horizon) {
-        const size_t nh = (size_t)n * (size_t)n_az;
-        for (size_t i = 0; i < nh; i++)
-            if (!(host_horizon[i] >= -90.0f && host_horizon[i] <= 90.0f))
-                return fail(c, MRTX_E_INVALID, "horizon entry %zu is not an elevation in [-90, 90] degrees", i);
-    }
-    std::vector<float> tab, lights;
-    if ((rc = point_tables(c, latlon, n, tab)) != MRTX_OK) return rc;
+    if ((rc = horizon_entries(c, host_horizon, n, n_az)) != MRTX_OK) return rc;
+    std::vector<float> rtab, ctab, lights;
+    if ((rc = point_tables(c, latlon, n, rtab, ctab)) != MRTX_OK) return rc;
     if ((rc = epoch_lights(c, epochs, m, lights)) != MRTX_OK) return rc;
     FrameC f;
     FrameCold cold;
-    if ((rc = horizon_frame(c, f, cold, false)) != MRTX_OK) return rc;
-    // one device block: point tables, epoch lights, fluxes[, horizons]
+    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
     std::vector<float> fl((size_t)m);
     for (int32_t k = 0; k < m; k++) fl[k] = (float)flux[k];
     const size_t nh = host_horizon ? (size_t)n * (size_t)n_az : 0;
     const size_t nx = host_extra ? (size_t)n * (size_t)m : 0;
-    const size_t tab_bytes = (tab.size() + lights.size() + fl.size() + nh + nx) * sizeof(float);
     const size_t out_bytes = (size_t)n * (size_t)width * sizeof(float);
-    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, tab_bytes)) != MRTX_OK) return rc;
-    if (!dev_out) {
-        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, out_bytes)) != MRTX_OK) return rc;
-        dev_out = c->illum_out;
-    }
-    float* const d_lights = c->illum_tab + tab.size();
-    float* const d_flux = d_lights + lights.size();
-    float* const d_hz = d_flux + fl.size();
-    HIPCHK(c, hipMemcpyAsync(c->illum_cold, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->illum_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_lights, lights.data(), lights.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_flux, fl.data(), fl.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (nh) HIPCHK(c, hipMemcpyAsync(d_hz, host_horizon, nh * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    float* const d_x = d_hz + nh;
-    if (nx) HIPCHK(c, hipMemcpyAsync(d_x, host_extra, nx * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
+    float* d[6];
+    if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK ||
+        (rc = stage_tables(c, {rtab, ctab, lights, fl, {host_horizon, nh}, {host_extra, nx}}, d)) != MRTX_OK)
+        return rc;
     ThermalC q;
     std::memset(&q, 0, sizeof q);
-    q.g.rtab = c->illum_tab; q.g.ctab = c->illum_tab + 2 * (size_t)n;
+    q.g.rtab = d[0]; q.g.ctab = d[1];
     q.g.rows = n; q.g.cols = n; q.g.points = 1;
-    q.horizon = nh ? d_hz : (const float*)dev_horizon;
-    q.lights = d_lights; q.flux = d_flux; q.out = (float*)dev_out; q.caps = c->illum_stats;
-    q.xflux = nx ? d_x : (const float*)dev_extra;
+    q.horizon = host_horizon ? d[4] : (const float*)dev_horizon;
+    q.lights = d[2]; q.flux = d[3]; q.out = (float*)dev_out; q.caps = c->illum_stats;
+    q.xflux = host_extra ? d[5] : (const float*)dev_extra;
     q.az_log2 = log2_of(n_az); q.m = m; q.mode = mode;
     const int nn = md.n_nodes;
     q.n_nodes = nn; q.n_sub = md.n_sub; q.n_spin = md.n_spin; q.block = md.block; q.n_reset = md.n_reset; q.ref = md.ref_node;
@@ -1862,12 +1816,9 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
         if (i < nn - 1) q.qdz[i] = (float)(md.q_geo * md.dz[i]);
         if (i > 0 && i < nn - 1) q.a[i] = (float)(delta * 2.0 / (md.rho[i] * (md.dz[i - 1] + md.dz[i])));
     }
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    if (ext) HIPCHK(c, mrtx_launch_thermal_scatter(f, q, c->stream));
-    else HIPCHK(c, mrtx_launch_thermal(f, q, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    rc = horizon_finish(c, false, dev_out, host_out, out_bytes, out);
-    if (rc != MRTX_OK) return rc;
+    if ((rc = stage_start(c, &cold, true)) != MRTX_OK) return rc;      // the counters: q.caps
+    HIPCHK(c, mrtx_launch_thermal(f, q, ext, c->stream));
+    if ((rc = stage_finish(c, dev_out, host_out, out_bytes, out, kNoRays)) != MRTX_OK) return rc;
     unsigned long long cnt[2] = {0, 0};      // Newton cap hits, (point, epoch)s whose column left [20, 450] K
     HIPCHK(c, hipMemcpy(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost));
     if (out) out->reserved = cnt[0] > 0xffffffffull ? 0xffffffffu : (uint32_t)cnt[0];
@@ -1915,42 +1866,26 @@ int mrtx_view_hits(mrtx_ctx* c, const double* latlon, int32_t n, int32_t k, void
     if ((int64_t)n * (2 * (int64_t)k + 1) > (int64_t)1 << 31)
         return fail(c, MRTX_E_INVALID, "a call holds at most 2^31 outputs: split the points into more calls");
     if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
-    std::vector<float> tab;
-    int rc = point_tables(c, latlon, n, tab);
+    std::vector<float> rtab, ctab, dirs((size_t)k * 2);
+    int rc = point_tables(c, latlon, n, rtab, ctab);
     if (rc != MRTX_OK) return rc;
     FrameC f;
     FrameCold cold;
-    if ((rc = horizon_frame(c, f, cold, true)) != MRTX_OK) return rc;
+    if ((rc = stage_frame(c, f, cold, true)) != MRTX_OK) return rc;
     const bool stats = (c->prm.flags & MRTX_F_COUNT_STATS) != 0;
-    // one device block: point tables (4 floats per point), then the K direction pairs
-    tab.resize(tab.size() + 2 * (size_t)k);
-    mrtx_view_dir_samples(k, tab.data() + 4 * (size_t)n);
-    const size_t tab_bytes = tab.size() * sizeof(float), out_bytes = (size_t)n * (2 * (size_t)k + 1) * sizeof(float);
-    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, tab_bytes)) != MRTX_OK) return rc;
-    if (!dev_out) {
-        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, out_bytes)) != MRTX_OK) return rc;
-        dev_out = c->illum_out;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->illum_cold, &cold, sizeof cold, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->illum_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
-    if (stats) HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
+    mrtx_view_dir_samples(k, dirs.data());
+    const size_t out_bytes = (size_t)n * (2 * (size_t)k + 1) * sizeof(float);
+    float* d[3];
+    if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK || (rc = stage_tables(c, {rtab, ctab, dirs}, d)) != MRTX_OK) return rc;
     ViewC q;
     std::memset(&q, 0, sizeof q);
-    q.g.rtab = c->illum_tab; q.g.ctab = c->illum_tab + 2 * (size_t)n;
+    q.g.rtab = d[0]; q.g.ctab = d[1];
     q.g.rows = n; q.g.cols = n; q.g.points = 1;
-    q.dirs = c->illum_tab + 4 * (size_t)n;
+    q.dirs = d[2];
     q.out = (float*)dev_out; q.K = k;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if ((rc = stage_start(c, &cold, stats)) != MRTX_OK) return rc;
     HIPCHK(c, mrtx_launch_view_hits(f, q, stats, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    rc = horizon_finish(c, false, dev_out, host_out, out_bytes, out);
-    if (rc != MRTX_OK) return rc;
-    if (out && stats) {
-        unsigned long long h[16];
-        HIPCHK(c, hipMemcpy(h, c->illum_stats, sizeof h, hipMemcpyDeviceToHost));
-        out->bounce_rays = h[8]; out->height_samples = h[3]; out->dem_fetches = h[6]; out->mip_fetches = h[7];
-    }
-    return MRTX_OK;
+    return stage_finish(c, dev_out, host_out, out_bytes, out, stats ? kBounceRays : kNoRays);
 }
 
 int mrtx_scatter_flux(mrtx_ctx* c, const int32_t* index, int32_t n, int32_t k, const void* dev_exitance,
@@ -1976,35 +1911,27 @@ int mrtx_scatter_flux(mrtx_ctx* c, const int32_t* index, int32_t n, int32_t k, c
     for (size_t i = 0; i < ni; i++)
         if (index[i] < -1 || index[i] >= n_hits)
             return fail(c, MRTX_E_INVALID, "index entry %zu = %d lies outside the hit list [0, %d) (-1: sky)", i, index[i], n_hits);
-    if (host_exitance) {
-        const size_t ne = (size_t)n_hits * (size_t)m * 2;
-        for (size_t i = 0; i < ne; i++)
-            if (!(std::isfinite(host_exitance[i]) && host_exitance[i] >= 0.0f))
-                return fail(c, MRTX_E_INVALID, "exitance entry %zu must be finite and >= 0", i);
-    }
+    const size_t ne = host_exitance ? (size_t)n_hits * (size_t)m * 2 : 0;
+    for (size_t i = 0; i < ne; i++)
+        if (!(std::isfinite(host_exitance[i]) && host_exitance[i] >= 0.0f))
+            return fail(c, MRTX_E_INVALID, "exitance entry %zu must be finite and >= 0", i);
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    // one device block: the index table (padded to 4 entries), then the host exitance
-    const size_t ni4 = (ni + 3) & ~(size_t)3, ne = host_exitance ? (size_t)n_hits * (size_t)m * 2 : 0;
-    const size_t tab_bytes = (ni4 + ne) * 4, out_bytes = (size_t)n * (size_t)m * sizeof(float);
+    const size_t out_bytes = (size_t)n * (size_t)m * sizeof(float);
+    float* d[2];
     int rc;
-    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, std::max(tab_bytes, (size_t)16))) != MRTX_OK) return rc;
-    if (!dev_out) {
-        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, out_bytes)) != MRTX_OK) return rc;
-        dev_out = c->illum_out;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->illum_tab, index, ni * 4, hipMemcpyHostToDevice, c->stream));
-    if (ne) HIPCHK(c, hipMemcpyAsync(c->illum_tab + ni4, host_exitance, ne * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK ||
+        (rc = stage_tables(c, {{index, ni}, {host_exitance, ne}}, d)) != MRTX_OK)
+        return rc;
     ScatterC q;
     std::memset(&q, 0, sizeof q);
-    q.idx = reinterpret_cast<const int32_t*>(c->illum_tab);
-    q.ex = host_exitance ? c->illum_tab + ni4 : (const float*)dev_exitance;
+    q.idx = reinterpret_cast<const int32_t*>(d[0]);
+    q.ex = host_exitance ? d[1] : (const float*)dev_exitance;   // (n_hits = 0: never read, but not null)
     q.out = (float*)dev_out;
     q.n = n; q.K = k; q.m = m; q.chunks = (m + 63) / 64;
     q.omah = (float)(1.0 - albedo_h); q.eps = (float)emissivity; q.inv_k = (float)(1.0 / k);
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
     HIPCHK(c, mrtx_launch_scatter_flux(q, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    return horizon_finish(c, false, dev_out, host_out, out_bytes, out);
+    return stage_finish(c, dev_out, host_out, out_bytes, out, kNoRays);
 }
 
 int mrtx_samples_done(mrtx_ctx* c, uint32_t* out) {

@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include <string.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "mrtx_device.h"
 
@@ -2000,6 +2001,33 @@ __device__ __forceinline__ float group_sum(float v, int n) {
     for (int m = 1; m < n; m <<= 1) v += __shfl_xor(v, m, 64);
     return v;
 }
+// The counters of the terrain kernels: each lane counts into its own zeroed cnt[ST_N]; at the end the wave's sums of four of
+// them -- `first` (ST_SHADOW, or ST_BOUNCE for view rays), ST_HEIGHT, ST_FETCH, ST_MIP -- go to the stats block from lane 0.
+template <bool STATS>
+__device__ __forceinline__ void stage_flush(const FrameC& f, const uint32_t* cnt, int first, int lane) {
+    if (!STATS) return;
+    const int which[4] = {first, ST_HEIGHT, ST_FETCH, ST_MIP};
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        uint32_t c = cnt[which[i]];
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) c += __shfl_xor(c, m, 64);
+        if (lane == 0) atomicAdd(&CF(f)->stats[which[i]], (unsigned long long)c);
+    }
+}
+// A point's local frame from its table entries, U = u, E = (c_lon, -s_lon, 0) from ct = (s_lon, c_lon) and
+// N = (-s_lat s_lon, -s_lat c_lon, c_lat), and the lifted origin o = fmaf(scene_eps, n, p) of its vertex v (light_sample's)
+struct PointFrame {
+    float ua, ub, uc, Na, Nb, Nc, oa, ob, oc;
+    float2 ct;
+};
+__device__ __forceinline__ PointFrame point_frame(const FrameC& f, const IllumC& g, int row, int col, const Vertex& v) {
+    const float2 rt = reinterpret_cast<const float2*>(g.rtab)[g.points ? col : row];   // (s_lat, c_lat)
+    const float2 ct = reinterpret_cast<const float2*>(g.ctab)[col];                    // (s_lon, c_lon)
+    const float eps = CF(f)->scene_eps;
+    return {rt.y * ct.x, rt.y * ct.y, rt.x, -(rt.x * ct.x), -(rt.x * ct.y), rt.y,
+            fmaf(eps, v.na, v.pa), fmaf(eps, v.nb, v.pb), fmaf(eps, v.nc, v.pc), ct};
+}
 // the node's surface vertex and D (what every sample of the node shares)
 template <bool STATS, bool WIDE>
 __device__ __forceinline__ float illum_vertex(const FrameC& f, const IllumC& g, int row, int col, Vertex& v, uint32_t* cnt) {
@@ -2050,12 +2078,8 @@ __global__ void __launch_bounds__(64) illum_kernel(const FrameC f, const IllumC 
     const int col = wx * pw + (p & (pw - 1));
     const int row = wy * ((64 >> (MRTX_ILLUM_MAP == 0 ? g.n_log2 : 0)) >> g.pw_log2) + (p >> g.pw_log2);
     const bool in = row < g.rows && col < g.cols;
-    uint32_t cnt_store[STATS ? ST_N : 1];
+    uint32_t cnt_store[STATS ? ST_N : 1] = {};
     uint32_t* const cnt = STATS ? cnt_store : nullptr;
-    if (STATS) {
-#pragma unroll
-        for (int i = 0; i < ST_N; i++) cnt[i] = 0;
-    }
     float lit = 0.0f, irr = 0.0f, mu = 0.0f, D = 0.0f;
     if (in) {
         Vertex v;
@@ -2095,16 +2119,7 @@ __global__ void __launch_bounds__(64) illum_kernel(const FrameC f, const IllumC 
     const float inv_n = 1.0f / (float)n;   // a power of two: the scalings below are exact
     if (in && s == 0)
         reinterpret_cast<float4*>(g.out)[(int64_t)row * g.cols + col] = make_float4(lit * inv_n, irr * inv_n, mu, D);
-    if (STATS) {
-        const int which[4] = {ST_SHADOW, ST_HEIGHT, ST_FETCH, ST_MIP};
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            uint32_t c = cnt[which[i]];
-#pragma unroll
-            for (int m = 1; m < 64; m <<= 1) c += __shfl_xor(c, m, 64);
-            if (lane == 0) atomicAdd(&CF(f)->stats[which[i]], (unsigned long long)c);
-        }
-    }
+    stage_flush<STATS>(f, cnt, ST_SHADOW, lane);
 }
 
 // Sun illumination over many dates (DESIGN.md sections 3.7 and 4.9): entry (point, j) of a series is illum_kernel's output at
@@ -2123,12 +2138,8 @@ __global__ void __launch_bounds__(64) illum_series_kernel(const FrameC f, const 
     const int j = wx * pw + (p & (pw - 1));                                         // epoch within the window
     const int pt = wy * ((64 >> g.n_log2) >> g.pw_log2) + (p >> g.pw_log2);         // point
     const bool in = pt < g.rows && j < g.cols;
-    uint32_t cnt_store[STATS ? ST_N : 1];
+    uint32_t cnt_store[STATS ? ST_N : 1] = {};
     uint32_t* const cnt = STATS ? cnt_store : nullptr;
-    if (STATS) {
-#pragma unroll
-        for (int i = 0; i < ST_N; i++) cnt[i] = 0;
-    }
     float lit = 0.0f, irr = 0.0f, mu = 0.0f, D = 0.0f;
     if (in) {
         const int64_t k = (int64_t)(q.first ? q.first[pt] : 0) + j;
@@ -2147,16 +2158,7 @@ __global__ void __launch_bounds__(64) illum_series_kernel(const FrameC f, const 
     const float inv_n = 1.0f / (float)n;   // a power of two: the scalings below are exact
     if (in && s == 0)
         reinterpret_cast<float4*>(g.out)[(int64_t)pt * g.cols + j] = make_float4(lit * inv_n, irr * inv_n, mu, D);
-    if (STATS) {
-        const int which[4] = {ST_SHADOW, ST_HEIGHT, ST_FETCH, ST_MIP};
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            uint32_t c = cnt[which[i]];
-#pragma unroll
-            for (int m = 1; m < 64; m <<= 1) c += __shfl_xor(c, m, 64);
-            if (lane == 0) atomicAdd(&CF(f)->stats[which[i]], (unsigned long long)c);
-        }
-    }
+    stage_flush<STATS>(f, cnt, ST_SHADOW, lane);
 }
 
 // Terrain horizons (DESIGN.md sections 3.8 and 4.10): per (point, azimuth) a bisection over the elevation whose n_bis probes
@@ -2171,68 +2173,48 @@ __global__ void __launch_bounds__(64) horizon_kernel(const FrameC f, const Horiz
     const int n_az = 1 << h.az_log2;
     const int pt = (int)(gid >> h.az_log2), az = (int)(gid & (int64_t)(n_az - 1));
     const bool in = pt < h.g.rows;
-    uint32_t cnt_store[STATS ? ST_N : 1];
+    uint32_t cnt_store[STATS ? ST_N : 1] = {};
     uint32_t* const cnt = STATS ? cnt_store : nullptr;
-    if (STATS) {
-#pragma unroll
-        for (int i = 0; i < ST_N; i++) cnt[i] = 0;
-    }
     if (in) {
         Vertex v;
         (void)illum_vertex<STATS, WIDE>(f, h.g, pt, pt, v, cnt);    // g.points = 1: both tables indexed by the point
-        const float2 rt = reinterpret_cast<const float2*>(h.g.rtab)[pt];   // (s_lat, c_lat)
-        const float2 ct = reinterpret_cast<const float2*>(h.g.ctab)[pt];   // (s_lon, c_lon)
-        // local frame: U = u, E = (c_lon, -s_lon, 0), N = (-s_lat s_lon, -s_lat c_lon, c_lat)
-        const float ua = rt.y * ct.x, ub = rt.y * ct.y, uc = rt.x;
-        const float Na = -(rt.x * ct.x), Nb = -(rt.x * ct.y), Nc = rt.y;
+        const PointFrame p = point_frame(f, h.g, pt, pt, v);
         float cp, sp;
         sincos_turn((float)az * (1.0f / (float)n_az), cp, sp);     // a / n_az: exact
-        const float ha = fmaf(cp, Na, sp * ct.y), hb = fmaf(cp, Nb, -(sp * ct.x)), hc = cp * Nc;
-        const float eps = CF(f)->scene_eps;
-        const float oa = fmaf(eps, v.na, v.pa), ob = fmaf(eps, v.nb, v.pb), oc = fmaf(eps, v.nc, v.pc);
+        const float ha = fmaf(cp, p.Na, sp * p.ct.y), hb = fmaf(cp, p.Nb, -(sp * p.ct.x)), hc = cp * p.Nc;
         float lo = 0.0f, hi = 1.0f;
         for (int i = 0; i < h.n_bis; i++) {
             const float mid = 0.5f * (lo + hi);                     // dyadic, at most 24 fraction bits: exact
             float ce, se;
             sincos_turn((mid - 0.5f) * 0.5f, ce, se);               // e in (-1/4, 1/4) turn: quadrants -1 and 0
-            const float da = fmaf(se, ua, ce * ha), db = fmaf(se, ub, ce * hb), dc = fmaf(se, uc, ce * hc);
+            const float da = fmaf(se, p.ua, ce * ha), db = fmaf(se, p.ub, ce * hb), dc = fmaf(se, p.uc, ce * hc);
             bool clear = false;
             if (fmaf(v.nc, dc, fmaf(v.nb, db, v.na * da)) > 0.0f) {
                 if (STATS) cnt[ST_SHADOW]++;
                 Seg ssg;
                 float sk_occ;
-                clear = !march<WIDE, false, STATS, MRTX_STEP_BATCH, 2>(f, oa, ob, oc, da, db, dc, 0.0f, ssg, sk_occ, cnt);
+                clear = !march<WIDE, false, STATS, MRTX_STEP_BATCH, 2>(f, p.oa, p.ob, p.oc, da, db, dc, 0.0f, ssg, sk_occ, cnt);
             }
             hi = clear ? mid : hi;
             lo = clear ? lo : mid;
         }
         h.out[gid] = (hi - 0.5f) * 180.0f;
     }
-    if (STATS) {
-        const int which[4] = {ST_SHADOW, ST_HEIGHT, ST_FETCH, ST_MIP};
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            uint32_t c = cnt[which[i]];
-#pragma unroll
-            for (int m = 1; m < 64; m <<= 1) c += __shfl_xor(c, m, 64);
-            if (lane == 0) atomicAdd(&CF(f)->stats[which[i]], (unsigned long long)c);
-        }
-    }
+    stage_flush<STATS>(f, cnt, ST_SHADOW, lane);
 }
 
 // The visible share of the light's disc above a point's horizon, from the epoch's (Lb.xyz, rL2) l0,
-// the lifted origin o, the local frame (U = u, N, and E from ct = (s_lon, c_lon)) and the point's horizon row hz of n_az
-// samples.  (la, lb, lc): the unit direction to the light centre as light_sample forms it (illum_mu's l).
-__device__ __forceinline__ float disc_fraction(const float4 l0, float oa, float ob, float oc, float ua, float ub, float uc,
-                                               float Na, float Nb, float Nc, const float2 ct, const float* hz, int n_az,
-                                               float& la, float& lb, float& lc) {
+// the point's frame p (its lifted origin, U, N and E) and its horizon row hz of n_az samples.  (la, lb, lc): the unit
+// direction to the light centre as light_sample forms it (illum_mu's l).
+__device__ __forceinline__ float disc_fraction(const float4 l0, const PointFrame& p, const float* hz, int n_az, float& la,
+                                               float& lb, float& lc) {
     constexpr float kDeg = 57.2957795130823209f, kInvTurn = 0.159154943091895336f, kInvPi = 0.318309886183790672f;
-    const float ta = l0.x - oa, tb = l0.y - ob, tc = l0.z - oc;
+    const float ta = l0.x - p.oa, tb = l0.y - p.ob, tc = l0.z - p.oc;
     const float inv_dist = rcp_cr(sqrt_sh(fmaf(tc, tc, fmaf(tb, tb, ta * ta))));
     la = ta * inv_dist; lb = tb * inv_dist; lc = tc * inv_dist;
-    const float xu = fmaf(uc, lc, fmaf(ub, lb, ua * la));
-    const float xn = fmaf(Nc, lc, fmaf(Nb, lb, Na * la));
-    const float xe = fmaf(-ct.x, lb, ct.y * la);
+    const float xu = fmaf(p.uc, lc, fmaf(p.ub, lb, p.ua * la));
+    const float xn = fmaf(p.Nc, lc, fmaf(p.Nb, lb, p.Na * la));
+    const float xe = fmaf(-p.ct.x, lb, p.ct.y * la);
     const float es = atan2f(xu, sqrtf(fmaf(xe, xe, xn * xn))) * kDeg;
     float ph = atan2f(xe, xn) * kInvTurn;                   // turns from north through east, [-1/2, 1/2]
     ph = ph < 0.0f ? ph + 1.0f : ph;
@@ -2266,12 +2248,7 @@ __global__ void __launch_bounds__(64) horizon_sun_kernel(const FrameC f, const H
     const int n_az = 1 << q.az_log2;
     Vertex v;
     (void)illum_vertex<false, WIDE>(f, q.g, pt, pt, v, nullptr);
-    const float2 rt = reinterpret_cast<const float2*>(q.g.rtab)[pt];
-    const float2 ct = reinterpret_cast<const float2*>(q.g.ctab)[pt];
-    const float ua = rt.y * ct.x, ub = rt.y * ct.y, uc = rt.x;
-    const float Na = -(rt.x * ct.x), Nb = -(rt.x * ct.y), Nc = rt.y;
-    const float eps = CF(f)->scene_eps;
-    const float oa = fmaf(eps, v.na, v.pa), ob = fmaf(eps, v.nb, v.pb), oc = fmaf(eps, v.nc, v.pc);
+    const PointFrame p = point_frame(f, q.g, pt, pt, v);
     const float* const hz = q.horizon + ((int64_t)pt << q.az_log2);
     const float4* const lights = reinterpret_cast<const float4*>(q.lights);
     double sum = 0.0;
@@ -2283,7 +2260,7 @@ __global__ void __launch_bounds__(64) horizon_sun_kernel(const FrameC f, const H
         float fr = 0.0f;
         if (in) {
             float la, lb, lc;
-            fr = disc_fraction(lights[2 * (int64_t)k], oa, ob, oc, ua, ub, uc, Na, Nb, Nc, ct, hz, n_az, la, lb, lc);
+            fr = disc_fraction(lights[2 * (int64_t)k], p, hz, n_az, la, lb, lc);
             if (q.mode == 0) q.out[(int64_t)pt * q.m + k] = fr;
         }
         if (q.mode != 0) {
@@ -2345,18 +2322,13 @@ __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const Therm
     const int n = q.n_nodes;
     Vertex v;
     (void)illum_vertex<false, WIDE>(f, q.g, pt, pt, v, nullptr);
-    const float2 rt = reinterpret_cast<const float2*>(q.g.rtab)[pt];
-    const float2 ct = reinterpret_cast<const float2*>(q.g.ctab)[pt];
-    const float ua = rt.y * ct.x, ub = rt.y * ct.y, uc = rt.x;
-    const float Na = -(rt.x * ct.x), Nb = -(rt.x * ct.y), Nc = rt.y;
-    const float eps = CF(f)->scene_eps;
-    const float oa = fmaf(eps, v.na, v.pa), ob = fmaf(eps, v.nb, v.pb), oc = fmaf(eps, v.nc, v.pc);
+    const PointFrame p = point_frame(f, q.g, pt, pt, v);
     const float* const hz = q.horizon + ((int64_t)pt << q.az_log2);
     const float4* const lights = reinterpret_cast<const float4*>(q.lights);
     // Q_abs of epoch k: (1 - A(theta)) S_k f max(mu, 0), exactly 0 when f == 0 or mu <= 0; EXT: mv = A(theta) S_k f max(mu, 0)
     auto sunlit = [&](int k, float& mv) -> float {
         float la, lb, lc;
-        const float fr = disc_fraction(lights[2 * (int64_t)k], oa, ob, oc, ua, ub, uc, Na, Nb, Nc, ct, hz, n_az, la, lb, lc);
+        const float fr = disc_fraction(lights[2 * (int64_t)k], p, hz, n_az, la, lb, lc);
         const float mu = fmaf(v.nc, lc, fmaf(v.nb, lb, v.na * la));      // illum_mu's expression
         if (!(fr > 0.0f) || !(mu > 0.0f)) { mv = 0.0f; return 0.0f; }
         const float th = acosf(fminf(mu, 1.0f)) * kDeg;
@@ -2518,20 +2490,15 @@ __global__ void __launch_bounds__(64) view_hits_kernel(const FrameC f, const Vie
     constexpr float kDeg = 57.2957795130823209f;
     const int lane = threadIdx.x;
     const int64_t gid = (int64_t)blockIdx.x * 64 + lane;
-    uint32_t cnt_store[STATS ? ST_N : 1];
+    uint32_t cnt_store[STATS ? ST_N : 1] = {};
     uint32_t* const cnt = STATS ? cnt_store : nullptr;
-    if (STATS) {
-#pragma unroll
-        for (int i = 0; i < ST_N; i++) cnt[i] = 0;
-    }
     if (gid < (int64_t)q.g.rows * q.K) {
         const int pt = (int)(gid / q.K), j = (int)(gid % q.K);
         Vertex v;
         (void)illum_vertex<STATS, WIDE>(f, q.g, pt, pt, v, cnt);    // g.points = 1: both tables indexed by the point
         float b1a, b1b, b1c, b2a, b2b, b2c;
         duff_basis(v.na, v.nb, v.nc, b1a, b1b, b1c, b2a, b2b, b2c);
-        const float eps = CF(f)->scene_eps;
-        const float oa = fmaf(eps, v.na, v.pa), ob = fmaf(eps, v.nb, v.pb), oc = fmaf(eps, v.nc, v.pc);
+        const PointFrame p = point_frame(f, q.g, pt, pt, v);
         const float2 uh = reinterpret_cast<const float2*>(q.dirs)[j];
         const float rr = sqrt_sh(uh.x), zz = sqrt_sh(1.0f - uh.x);
         float cph, sph;
@@ -2544,28 +2511,19 @@ __global__ void __launch_bounds__(64) view_hits_kernel(const FrameC f, const Vie
         Seg sg;
         float hi = 0.0f;
         float2 o = make_float2(__builtin_nanf(""), __builtin_nanf(""));
-        if (march<WIDE, false, STATS, MRTX_STEP_BATCH>(f, oa, ob, oc, da, db, dc, 0.0f, sg, hi, cnt)) {
+        if (march<WIDE, false, STATS, MRTX_STEP_BATCH>(f, p.oa, p.ob, p.oc, da, db, dc, 0.0f, sg, hi, cnt)) {
             const int bk = (int)rintf(hi * f.inv_step);
             float lo = (float)(bk - 1) * f.step;
-            refine<WIDE>(f, sg, oa, ob, oc, da, db, dc, lo, hi);
+            refine<WIDE>(f, sg, p.oa, p.ob, p.oc, da, db, dc, lo, hi);
             if (STATS) { cnt[ST_HEIGHT] += (uint32_t)f.nbis; cnt[ST_FETCH] += (uint32_t)f.nbis; }
-            const float ha = fmaf(lo, da, oa), hb = fmaf(lo, db, ob), hc = fmaf(lo, dc, oc);
+            const float ha = fmaf(lo, da, p.oa), hb = fmaf(lo, db, p.ob), hc = fmaf(lo, dc, p.oc);
             float lat, lon;
             latlon(ha, hb, hc, fmaf(hb, hb, ha * ha), lat, lon);
             o = make_float2(lat * kDeg, lon * kDeg);
         }
         reinterpret_cast<float2*>(q.out)[gid] = o;
     }
-    if (STATS) {
-        const int which[4] = {ST_BOUNCE, ST_HEIGHT, ST_FETCH, ST_MIP};
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            uint32_t c = cnt[which[i]];
-#pragma unroll
-            for (int m = 1; m < 64; m <<= 1) c += __shfl_xor(c, m, 64);
-            if (lane == 0) atomicAdd(&CF(f)->stats[which[i]], (unsigned long long)c);
-        }
-    }
+    stage_flush<STATS>(f, cnt, ST_BOUNCE, lane);
 }
 
 // The terrain share of each point: its hits (non-NaN latitudes) over K, exact for a power of two.  One lane per point.
@@ -2636,13 +2594,11 @@ __device__ __forceinline__ bool sight_probe(const FrameC& f, float Ta, float Tb,
     return !march<WIDE, false, STATS, MRTX_STEP_BATCH, 2, true>(f, oa, ob, oc, da, db, dc, smax, ssg, sk_occ, cnt);
 }
 
-// the raised end of a vertex: P = fmaf(hs, u, o), o = the lifted origin fmaf(scene_eps, n, p) of light_sample
-__device__ __forceinline__ void sight_end(const FrameC& f, const Vertex& v, float ua, float ub, float uc, float hs, float& Pa,
-                                          float& Pb, float& Pc) {
-    const float eps = CF(f)->scene_eps;
-    Pa = fmaf(hs, ua, fmaf(eps, v.na, v.pa));
-    Pb = fmaf(hs, ub, fmaf(eps, v.nb, v.pb));
-    Pc = fmaf(hs, uc, fmaf(eps, v.nc, v.pc));
+// the raised end of a point: P = fmaf(hs, u, o), o its lifted origin
+__device__ __forceinline__ void sight_end(const PointFrame& p, float hs, float& Pa, float& Pb, float& Pc) {
+    Pa = fmaf(hs, p.ua, p.oa);
+    Pb = fmaf(hs, p.ub, p.ob);
+    Pc = fmaf(hs, p.uc, p.oc);
 }
 
 // Per target the extra mast height (metres) at which it sees the observer: 0 if it does at its own height, otherwise a
@@ -2655,29 +2611,21 @@ __global__ void __launch_bounds__(64) sight_kernel(const FrameC f, const SightC 
     const int row = (int)(blockIdx.x / (unsigned)q.waves_x);
     const int col = (int)(blockIdx.x % (unsigned)q.waves_x) * 64 + lane;
     const bool in = row < q.g.rows && col < q.g.cols;
-    uint32_t cnt_store[STATS ? ST_N : 1];
+    uint32_t cnt_store[STATS ? ST_N : 1] = {};
     uint32_t* const cnt = STATS ? cnt_store : nullptr;
-    if (STATS) {
-#pragma unroll
-        for (int i = 0; i < ST_N; i++) cnt[i] = 0;
-    }
     if (in) {
         Vertex vt, vo;
         (void)illum_vertex<STATS, WIDE>(f, q.g, row, col, vt, cnt);
         const int oi = q.n_obs == 1 ? 0 : col;
         (void)illum_vertex<STATS, WIDE>(f, q.obs, oi, oi, vo, cnt);   // obs.points = 1: both tables indexed by the observer
-        const float2 rt = reinterpret_cast<const float2*>(q.g.rtab)[q.g.points ? col : row];
-        const float2 ct = reinterpret_cast<const float2*>(q.g.ctab)[col];
-        const float2 ro = reinterpret_cast<const float2*>(q.obs.rtab)[oi];
-        const float2 co = reinterpret_cast<const float2*>(q.obs.ctab)[oi];
+        const PointFrame pt = point_frame(f, q.g, row, col, vt), po = point_frame(f, q.obs, oi, oi, vo);
         float Oa, Ob, Oc;
-        sight_end(f, vo, ro.y * co.x, ro.y * co.y, ro.x, q.obs_hs[oi], Oa, Ob, Oc);
-        const float ua = rt.y * ct.x, ub = rt.y * ct.y, uc = rt.x;
+        sight_end(po, q.obs_hs[oi], Oa, Ob, Oc);
         // the target raised by target_h + t * mast_max metres
         auto probe = [&](float t) {
             const float hs = (float)((q.target_h_m + (double)t * q.mast_max_m) / q.radius_m * q.R);
             float Ta, Tb, Tc;
-            sight_end(f, vt, ua, ub, uc, hs, Ta, Tb, Tc);
+            sight_end(pt, hs, Ta, Tb, Tc);
             return sight_probe<STATS, WIDE>(f, Ta, Tb, Tc, Oa, Ob, Oc, cnt);
         };
         float m = 0.0f;
@@ -2696,16 +2644,7 @@ __global__ void __launch_bounds__(64) sight_kernel(const FrameC f, const SightC 
         }
         q.out[(int64_t)row * q.g.cols + col] = m;
     }
-    if (STATS) {
-        const int which[4] = {ST_SHADOW, ST_HEIGHT, ST_FETCH, ST_MIP};
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            uint32_t c = cnt[which[i]];
-#pragma unroll
-            for (int m = 1; m < 64; m <<= 1) c += __shfl_xor(c, m, 64);
-            if (lane == 0) atomicAdd(&CF(f)->stats[which[i]], (unsigned long long)c);
-        }
-    }
+    stage_flush<STATS>(f, cnt, ST_SHADOW, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3978,6 +3917,14 @@ hipError_t mrtx_launch_render(const FrameC& f, int S, bool stats, int mode, bool
     return hipGetLastError();
 }
 
+// Runs launch(a, b) with a and b as std::integral_constant<bool>, so that the lambda can name the kernel instantiation it
+// launches (kernel<a(), b()>): the four instantiations a pair of run-time flags such as (stats, wide) selects.
+template <class L>
+static void pick2(bool a, bool b, L&& launch) {
+    if (a) { if (b) launch(std::true_type{}, std::true_type{}); else launch(std::true_type{}, std::false_type{}); }
+    else { if (b) launch(std::false_type{}, std::true_type{}); else launch(std::false_type{}, std::false_type{}); }
+}
+
 // The Sun illumination stage (illum_kernel): one wave per block of nodes -- 64 / n_sun nodes (MRTX_ILLUM_MAP 0) or 64 (1) in a
 // PW x PH block, PW as render_geometry picks it for as many pixels.  g.rows x g.cols nodes; g.pw_log2 and g.waves_x are set here.
 hipError_t mrtx_launch_illum(const FrameC& f, IllumC g, bool stats, hipStream_t st) {
@@ -3993,11 +3940,9 @@ hipError_t mrtx_launch_illum(const FrameC& f, IllumC g, bool stats, hipStream_t 
     const uint64_t waves = (uint64_t)g.waves_x * (uint64_t)((g.rows + PH - 1) / PH);
     if (waves > 0xFFFFFFFFull) return hipErrorInvalidValue;
     const dim3 grid((unsigned)waves), block(64);
-    const bool wide = f.dem_wide != 0;
-    if (stats) { if (wide) hipLaunchKernelGGL((mrtx::illum_kernel<true, true>), grid, block, 0, st, f, g);
-                 else hipLaunchKernelGGL((mrtx::illum_kernel<true, false>), grid, block, 0, st, f, g); }
-    else { if (wide) hipLaunchKernelGGL((mrtx::illum_kernel<false, true>), grid, block, 0, st, f, g);
-           else hipLaunchKernelGGL((mrtx::illum_kernel<false, false>), grid, block, 0, st, f, g); }
+    pick2(stats, f.dem_wide != 0, [&](auto s, auto w) {
+        hipLaunchKernelGGL((mrtx::illum_kernel<s(), w()>), grid, block, 0, st, f, g);
+    });
     return hipGetLastError();
 }
 
@@ -4020,11 +3965,9 @@ hipError_t mrtx_launch_illum_series(const FrameC& f, IllumSeriesC q, bool stats,
     const uint64_t waves = (uint64_t)g.waves_x * (uint64_t)((g.rows + PH - 1) / PH);
     if (waves > 0xFFFFFFFFull) return hipErrorInvalidValue;
     const dim3 grid((unsigned)waves), block(64);
-    const bool wide = f.dem_wide != 0;
-    if (stats) { if (wide) hipLaunchKernelGGL((mrtx::illum_series_kernel<true, true>), grid, block, 0, st, f, q);
-                 else hipLaunchKernelGGL((mrtx::illum_series_kernel<true, false>), grid, block, 0, st, f, q); }
-    else { if (wide) hipLaunchKernelGGL((mrtx::illum_series_kernel<false, true>), grid, block, 0, st, f, q);
-           else hipLaunchKernelGGL((mrtx::illum_series_kernel<false, false>), grid, block, 0, st, f, q); }
+    pick2(stats, f.dem_wide != 0, [&](auto s, auto w) {
+        hipLaunchKernelGGL((mrtx::illum_series_kernel<s(), w()>), grid, block, 0, st, f, q);
+    });
     return hipGetLastError();
 }
 
@@ -4035,11 +3978,9 @@ hipError_t mrtx_launch_horizon(const FrameC& f, HorizonC h, bool stats, hipStrea
     const uint64_t lanes = (uint64_t)h.g.rows << h.az_log2;
     if (lanes > (1ull << 31)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((lanes + 63) / 64)), block(64);
-    const bool wide = f.dem_wide != 0;
-    if (stats) { if (wide) hipLaunchKernelGGL((mrtx::horizon_kernel<true, true>), grid, block, 0, st, f, h);
-                 else hipLaunchKernelGGL((mrtx::horizon_kernel<true, false>), grid, block, 0, st, f, h); }
-    else { if (wide) hipLaunchKernelGGL((mrtx::horizon_kernel<false, true>), grid, block, 0, st, f, h);
-           else hipLaunchKernelGGL((mrtx::horizon_kernel<false, false>), grid, block, 0, st, f, h); }
+    pick2(stats, f.dem_wide != 0, [&](auto s, auto w) {
+        hipLaunchKernelGGL((mrtx::horizon_kernel<s(), w()>), grid, block, 0, st, f, h);
+    });
     return hipGetLastError();
 }
 
@@ -4064,37 +4005,24 @@ hipError_t mrtx_launch_sight(const FrameC& f, SightC q, bool stats, hipStream_t 
     const uint64_t waves = (uint64_t)q.g.rows * (uint64_t)q.waves_x;
     if (waves > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const dim3 grid((unsigned)waves), block(64);
-    const bool wide = f.dem_wide != 0;
-    if (stats) { if (wide) hipLaunchKernelGGL((mrtx::sight_kernel<true, true>), grid, block, 0, st, f, q);
-                 else hipLaunchKernelGGL((mrtx::sight_kernel<true, false>), grid, block, 0, st, f, q); }
-    else { if (wide) hipLaunchKernelGGL((mrtx::sight_kernel<false, true>), grid, block, 0, st, f, q);
-           else hipLaunchKernelGGL((mrtx::sight_kernel<false, false>), grid, block, 0, st, f, q); }
+    pick2(stats, f.dem_wide != 0, [&](auto s, auto w) {
+        hipLaunchKernelGGL((mrtx::sight_kernel<s(), w()>), grid, block, 0, st, f, q);
+    });
     return hipGetLastError();
 }
 
-// Regolith surface temperatures (thermal_kernel): one lane per point, 64 per wave.
-hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, hipStream_t st) {
-    if (q.g.rows < 1 || q.az_log2 < 2 || q.az_log2 > 12 || q.m < 1 || q.mode < 0 || q.mode > 2 || q.n_nodes < 3 ||
+// Regolith surface temperatures (thermal_kernel): one lane per point, 64 per wave.  ext: the same column with an extra
+// absorbed flux and the EXITANCE mode 3 (mrtx_thermal_scatter, section 3.11).
+hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, bool ext, hipStream_t st) {
+    if (q.g.rows < 1 || q.az_log2 < 2 || q.az_log2 > 12 || q.m < 1 || q.mode < 0 || q.mode > (ext ? 3 : 2) || q.n_nodes < 3 ||
         q.n_nodes > MRTX_THERMAL_NODES || q.n_sub < 1 || q.block < 1 || q.n_spin < 0 || q.n_reset < 0 || q.ref < 0 ||
         q.ref >= q.n_nodes - 1 || (q.mode != 2 && q.n_spin >= q.m) || !q.g.points || !q.horizon || !q.lights || !q.flux ||
         !q.out || !q.caps)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)((q.g.rows + 63) / 64)), block(64);
-    if (f.dem_wide) hipLaunchKernelGGL((mrtx::thermal_kernel<true, false>), grid, block, 0, st, f, q);
-    else hipLaunchKernelGGL((mrtx::thermal_kernel<false, false>), grid, block, 0, st, f, q);
-    return hipGetLastError();
-}
-
-// The same column with an extra absorbed flux and the EXITANCE mode (mrtx_thermal_scatter, section 3.11).
-hipError_t mrtx_launch_thermal_scatter(const FrameC& f, const ThermalC& q, hipStream_t st) {
-    if (q.g.rows < 1 || q.az_log2 < 2 || q.az_log2 > 12 || q.m < 1 || q.mode < 0 || q.mode > 3 || q.n_nodes < 3 ||
-        q.n_nodes > MRTX_THERMAL_NODES || q.n_sub < 1 || q.block < 1 || q.n_spin < 0 || q.n_reset < 0 || q.ref < 0 ||
-        q.ref >= q.n_nodes - 1 || (q.mode != 2 && q.n_spin >= q.m) || !q.g.points || !q.horizon || !q.lights || !q.flux ||
-        !q.out || !q.caps)
-        return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((q.g.rows + 63) / 64)), block(64);
-    if (f.dem_wide) hipLaunchKernelGGL((mrtx::thermal_kernel<true, true>), grid, block, 0, st, f, q);
-    else hipLaunchKernelGGL((mrtx::thermal_kernel<false, true>), grid, block, 0, st, f, q);
+    pick2(f.dem_wide != 0, ext, [&](auto w, auto e) {
+        hipLaunchKernelGGL((mrtx::thermal_kernel<w(), e()>), grid, block, 0, st, f, q);
+    });
     return hipGetLastError();
 }
 
@@ -4104,13 +4032,9 @@ hipError_t mrtx_launch_view_hits(const FrameC& f, const ViewC& q, bool stats, hi
         (int64_t)q.g.rows * q.K > 0x7fffffffLL)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)(((int64_t)q.g.rows * q.K + 63) / 64)), block(64);
-    if (stats) {
-        if (f.dem_wide) hipLaunchKernelGGL((mrtx::view_hits_kernel<true, true>), grid, block, 0, st, f, q);
-        else hipLaunchKernelGGL((mrtx::view_hits_kernel<false, true>), grid, block, 0, st, f, q);
-    } else {
-        if (f.dem_wide) hipLaunchKernelGGL((mrtx::view_hits_kernel<true, false>), grid, block, 0, st, f, q);
-        else hipLaunchKernelGGL((mrtx::view_hits_kernel<false, false>), grid, block, 0, st, f, q);
-    }
+    pick2(stats, f.dem_wide != 0, [&](auto s, auto w) {
+        hipLaunchKernelGGL((mrtx::view_hits_kernel<w(), s()>), grid, block, 0, st, f, q);
+    });
     hipLaunchKernelGGL(mrtx::view_share_kernel, dim3((unsigned)((q.g.rows + 63) / 64)), block, 0, st, q);
     return hipGetLastError();
 }

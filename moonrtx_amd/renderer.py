@@ -265,21 +265,27 @@ class MoonRT:
         h, w = int(shape[0]), int(shape[1])
         r0, r1 = (0, h) if rows is None else (int(rows[0]), int(rows[1]))
         g = _lib.MrtxIllumGrid(float(lat[0]), float(lat[1]), float(lon[0]), float(lon[1]), h, w, r0, r1, int(n_sun), 0)
-        out = np.empty((max(r1 - r0, 0), w, 4), np.float32)
-        step = max(1, int(band_bytes) // (16 * max(w, 1)))
+        return self._band_map("mrtx_illum_grid", g, np.empty((max(r1 - r0, 0), w, 4), np.float32), 16, band_bytes, stats)
+
+    def _band_map(self, name, g, out, node_bytes, band_bytes, stats):
+        """Rows [g.row_begin, g.row_end) of a map of node_bytes per node into `out` through the grid call `name`: in one call
+        straight into `out` when they fit in band_bytes, else in bands of that size through one device buffer."""
+        r0, r1, w = g.row_begin, g.row_end, g.w
+        step = max(1, int(band_bytes) // (node_bytes * max(w, 1)))
+        call = getattr(self._lib, name)
         if r1 - r0 <= step:      # one band: straight into the host array
             st = MrtxStats()
-            self._check(self._lib.mrtx_illum_grid(self._ctx, C.byref(g), None, out.ctypes.data, C.byref(st)), "mrtx_illum_grid")
+            self._check(call(self._ctx, C.byref(g), None, out.ctypes.data, C.byref(st)), name)
             self._add_stats(stats, st)
             return out
-        buf = DeviceBuffer(16 * step * w, self.config()["device"])
+        buf = DeviceBuffer(node_bytes * step * w, self.config()["device"])
         try:
             for a in range(r0, r1, step):
                 g.row_begin, g.row_end = a, min(a + step, r1)
                 st = MrtxStats()
-                self._check(self._lib.mrtx_illum_grid(self._ctx, C.byref(g), buf.ptr, None, C.byref(st)), "mrtx_illum_grid")
+                self._check(call(self._ctx, C.byref(g), buf.ptr, None, C.byref(st)), name)
                 self._add_stats(stats, st)
-                out[a - r0:g.row_end - r0] = buf.download(np.float32, (g.row_end - a, w, 4))
+                out[a - r0:g.row_end - r0] = buf.download(np.float32, (g.row_end - a,) + out.shape[1:])
         finally:
             buf.free()
         return out
@@ -318,9 +324,7 @@ class MoonRT:
             count = int(count)
         pts = np.ascontiguousarray(np.stack([la, lo], -1))
         out = np.empty((la.size, max(count, 0), 4), np.float32)
-        step = max(1, min(int(chunk_bytes) // (16 * max(count, 1)), (1 << 31) // max(count, 1)))
-        for a in range(0, la.size, step):
-            b = min(a + step, la.size)
+        for a, b in self._chunks(la.size, max(count, 1), chunk_bytes, 16, empty_call=False):
             st = MrtxStats()
             fp = None if first is None else first[a:].ctypes.data
             self._check(self._lib.mrtx_illum_series(self._ctx, pts[a:].ctypes.data, b - a, ep.ctypes.data, ep.shape[0], fp, count,
@@ -366,9 +370,7 @@ class MoonRT:
         if out is not None and out.nbytes < la.size * max(n_az, 0) * 4:
             raise ValueError("the device buffer is smaller than N x n_az float32")
         host = np.empty((la.size, max(n_az, 0)), np.float32) if out is None else None
-        step = max(1, min(int(chunk_bytes) // (4 * max(n_az, 1)), (1 << 31) // max(n_az, 1)))
-        for a in range(0, max(la.size, 1), step):
-            b = min(a + step, la.size)
+        for a, b in self._chunks(la.size, max(n_az, 1), chunk_bytes):
             st = MrtxStats()
             dev = None if out is None else out.ptr + a * n_az * 4
             hp = None if out is not None else host[a:].ctypes.data
@@ -386,27 +388,13 @@ class MoonRT:
         la, lo = self._points(lat_deg, lon_deg)
         ep = self._epochs(epochs)
         m = ep.shape[0]
-        if isinstance(horizon, DeviceBuffer):
-            if n_az is None:
-                raise ValueError("n_az is required with a device buffer")
-            n_az = int(n_az)
-            if horizon.nbytes < la.size * n_az * 4:
-                raise ValueError("the device buffer is smaller than N x n_az float32")
-            hz = None
-        else:
-            hz = np.ascontiguousarray(horizon, np.float32)
-            if hz.ndim != 2 or hz.shape[0] != la.size:
-                raise ValueError("horizon must be an (N, n_az) array")
-            n_az = hz.shape[1]
+        n_az, hz_at = self._horizon_arg(horizon, la.size, n_az)
         pts = np.ascontiguousarray(np.stack([la, lo], -1))
         width = 4 if summary else m
         res = np.empty((la.size, width), np.float32)
-        step = la.size if summary else max(1, min(int(chunk_bytes) // (4 * max(m, 1)), (1 << 31) // max(m, 1)))
-        for a in range(0, max(la.size, 1), max(step, 1)):
-            b = min(a + step, la.size)
+        for a, b in self._chunks(la.size, None if summary else max(m, 1), chunk_bytes):
             st = MrtxStats()
-            dh = None if hz is not None else horizon.ptr + a * n_az * 4
-            hh = None if hz is None else hz[a:].ctypes.data
+            dh, hh = hz_at(a)
             self._check(self._lib.mrtx_horizon_sun(self._ctx, pts[a:].ctypes.data, b - a, n_az, dh, hh, ep.ctypes.data, m,
                                                    1 if summary else 0, None, res[a:].ctypes.data, C.byref(st)),
                         "mrtx_horizon_sun")
@@ -441,33 +429,17 @@ class MoonRT:
         if fl.size != m:
             raise ValueError("flux must hold one value per epoch")
         model = self.thermal_grid() if model is None else model
-        if isinstance(horizon, DeviceBuffer):
-            if n_az is None:
-                raise ValueError("n_az is required with a device buffer")
-            n_az = int(n_az)
-            if horizon.nbytes < la.size * n_az * 4:
-                raise ValueError("the device buffer is smaller than N x n_az float32")
-            hz = None
-        else:
-            hz = np.ascontiguousarray(horizon, np.float32)
-            if hz.ndim != 2 or hz.shape[0] != la.size:
-                raise ValueError("horizon must be an (N, n_az) array")
-            n_az = hz.shape[1]
+        n_az, hz_at = self._horizon_arg(horizon, la.size, n_az)
         pts = np.ascontiguousarray(np.stack([la, lo], -1))
         width = {"full": max(m - int(model.n_spin), 1), "summary": 4, "flux": m}[mode]
         res = np.empty((la.size, width), np.float32)
-        step = la.size if mode == "summary" else max(1, min(int(chunk_bytes) // (4 * width), (1 << 31) // width))
-        for a in range(0, max(la.size, 1), max(step, 1)):
-            b = min(a + step, la.size)
+        for a, b in self._chunks(la.size, None if mode == "summary" else width, chunk_bytes):
             st = MrtxStats()
-            dh = None if hz is not None else horizon.ptr + a * n_az * 4
-            hh = None if hz is None else hz[a:].ctypes.data
+            dh, hh = hz_at(a)
             self._check(self._lib.mrtx_thermal(self._ctx, pts[a:].ctypes.data, b - a, n_az, dh, hh, ep.ctypes.data,
                                                fl.ctypes.data, m, C.byref(model), modes[mode], None, res[a:].ctypes.data,
                                                C.byref(st)), "mrtx_thermal")
-            self._add_stats(stats, st)
-            if isinstance(stats, dict):
-                stats["newton_cap_hits"] = stats.get("newton_cap_hits", 0) + int(st.reserved)
+            self._add_stats(stats, st, {"newton_cap_hits": "reserved"})
         return res
 
     @staticmethod
@@ -488,18 +460,14 @@ class MoonRT:
         hits = np.empty((la.size, max(k, 0), 2), np.float32)
         share = np.empty(la.size, np.float32)
         width = 2 * max(k, 1) + 1
-        step = max(1, min(int(chunk_bytes) // (4 * width), (1 << 31) // width))
-        for a in range(0, max(la.size, 1), step):
-            b = min(a + step, la.size)
+        for a, b in self._chunks(la.size, width, chunk_bytes):
             buf = np.empty((b - a) * width, np.float32) if b > a else np.empty(width, np.float32)
             st = MrtxStats()
             self._check(self._lib.mrtx_view_hits(self._ctx, pts[a:].ctypes.data, b - a, k, None, buf.ctypes.data, C.byref(st)),
                         "mrtx_view_hits")
             hits[a:b] = buf[:(b - a) * 2 * k].reshape(b - a, k, 2)
             share[a:b] = buf[(b - a) * 2 * k:(b - a) * width]
-            self._add_stats(stats, st)
-            if isinstance(stats, dict):
-                stats["bounce_rays"] = stats.get("bounce_rays", 0) + int(st.bounce_rays)
+            self._add_stats(stats, st, {"bounce_rays": "bounce_rays"})
         return hits, share
 
     def scatter_flux(self, index, exitance, albedo_h, emissivity, n_hits=None, m=None, out=None, stats=None):
@@ -548,17 +516,8 @@ class MoonRT:
         if fl.size != m:
             raise ValueError("flux must hold one value per epoch")
         model = self.thermal_grid() if model is None else model
-        if isinstance(horizon, DeviceBuffer):
-            if n_az is None:
-                raise ValueError("n_az is required with a device buffer")
-            n_az, dh, hh = int(n_az), horizon.ptr, None
-            if horizon.nbytes < la.size * n_az * 4:
-                raise ValueError("the device buffer is smaller than N x n_az float32")
-        else:
-            hz = np.ascontiguousarray(horizon, np.float32)
-            if hz.ndim != 2 or hz.shape[0] != la.size:
-                raise ValueError("horizon must be an (N, n_az) array")
-            n_az, dh, hh = hz.shape[1], None, hz.ctypes.data
+        n_az, hz_at = self._horizon_arg(horizon, la.size, n_az)
+        dh, hh = hz_at(0)
         dx = hx = None
         x_len = 0
         if isinstance(extra_flux, DeviceBuffer):
@@ -577,9 +536,7 @@ class MoonRT:
                                                    fl.ctypes.data, m, C.byref(model), modes[mode], dx, hx, x_len,
                                                    None if out is None else out.ptr, None if res is None else res.ctypes.data,
                                                    C.byref(st)), "mrtx_thermal_scatter")
-        self._add_stats(stats, st)
-        if isinstance(stats, dict):
-            stats["newton_cap_hits"] = stats.get("newton_cap_hits", 0) + int(st.reserved)
+        self._add_stats(stats, st, {"newton_cap_hits": "reserved"})
         return out if out is not None else res
 
     # ---- Terrain line of sight
@@ -602,24 +559,7 @@ class MoonRT:
         r0, r1 = (0, h) if rows is None else (int(rows[0]), int(rows[1]))
         g = _lib.MrtxSightGrid(o[0], o[1], o[2], float(target_height_m), float(mast_max_m), float(radius_m), float(lat[0]),
                                float(lat[1]), float(lon[0]), float(lon[1]), h, w, r0, r1, int(n_bis), 0)
-        out = np.empty((max(r1 - r0, 0), w), np.float32)
-        step = max(1, int(band_bytes) // (4 * max(w, 1)))
-        if r1 - r0 <= step:      # one band: straight into the host array
-            st = MrtxStats()
-            self._check(self._lib.mrtx_sight_grid(self._ctx, C.byref(g), None, out.ctypes.data, C.byref(st)), "mrtx_sight_grid")
-            self._add_stats(stats, st)
-            return out
-        buf = DeviceBuffer(4 * step * w, self.config()["device"])
-        try:
-            for a in range(r0, r1, step):
-                g.row_begin, g.row_end = a, min(a + step, r1)
-                st = MrtxStats()
-                self._check(self._lib.mrtx_sight_grid(self._ctx, C.byref(g), buf.ptr, None, C.byref(st)), "mrtx_sight_grid")
-                self._add_stats(stats, st)
-                out[a - r0:g.row_end - r0] = buf.download(np.float32, (g.row_end - a, w))
-        finally:
-            buf.free()
-        return out
+        return self._band_map("mrtx_sight_grid", g, np.empty((max(r1 - r0, 0), w), np.float32), 4, band_bytes, stats)
 
     def line_of_sight(self, lat_deg, lon_deg, observer, target_height_m=0.0, mast_max_m=0.0, n_bis=0, radius_m=1737400.0,
                       stats=None, chunk_bytes=256 << 20):
@@ -636,9 +576,7 @@ class MoonRT:
         shared = obs.shape[0] == 1
         pts = np.ascontiguousarray(np.stack([la, lo], -1))
         out = np.empty(la.size, np.float32)
-        step = max(1, min(int(chunk_bytes) // 4, 1 << 31))
-        for a in range(0, la.size, step):
-            b = min(a + step, la.size)
+        for a, b in self._chunks(la.size, 1, chunk_bytes, empty_call=False):
             st = MrtxStats()
             op, no = (obs.ctypes.data, 1) if shared else (obs[a:].ctypes.data, b - a)
             self._check(self._lib.mrtx_sight_points(self._ctx, pts[a:].ctypes.data, b - a, op, no, float(target_height_m),
@@ -648,10 +586,38 @@ class MoonRT:
         return out
 
     @staticmethod
-    def _add_stats(acc, st):
+    def _add_stats(acc, st, extra=None):
+        """Sum the counters of one call into the dict `acc` (if it is one); extra = {key: MrtxStats field} of the call's own."""
         if isinstance(acc, dict):
             for k in ("shadow_rays", "height_samples", "dem_fetches", "mip_fetches", "kernel_ms", "launches"):
                 acc[k] = acc.get(k, 0) + getattr(st, k)
+            for k, field in (extra or {}).items():
+                acc[k] = acc.get(k, 0) + int(getattr(st, field))
+
+    @staticmethod
+    def _chunks(n, per, chunk_bytes, out_bytes=4, empty_call=True):
+        """The [a, b) point ranges of a point query's calls: each holds at most chunk_bytes and 2^31 outputs, `per` outputs of
+        out_bytes per point (per = None: one call for all).  With N = 0 the query makes one call with no points when
+        empty_call, which the library refuses (horizon, horizon_sun, surface_temperature, view_hits: an empty query is an
+        error), and no call otherwise (illumination_series, line_of_sight: an empty result)."""
+        step = max(n, 1) if per is None else max(1, min(int(chunk_bytes) // (out_bytes * per), (1 << 31) // per))
+        return [(a, min(a + step, n)) for a in range(0, max(n, 1) if empty_call else n, step)]
+
+    @staticmethod
+    def _horizon_arg(horizon, n, n_az):
+        """(n_az, at) of a `horizon` argument -- the (N, n_az) float32 array of MoonRT.horizon, or a DeviceBuffer holding it
+        (then n_az is required) -- with at(a) = the (device, host) pointers of the horizons from point a on."""
+        if isinstance(horizon, DeviceBuffer):
+            if n_az is None:
+                raise ValueError("n_az is required with a device buffer")
+            n_az = int(n_az)
+            if horizon.nbytes < n * n_az * 4:
+                raise ValueError("the device buffer is smaller than N x n_az float32")
+            return n_az, lambda a: (horizon.ptr + a * n_az * 4, None)
+        hz = np.ascontiguousarray(horizon, np.float32)
+        if hz.ndim != 2 or hz.shape[0] != n:
+            raise ValueError("horizon must be an (N, n_az) array")
+        return hz.shape[1], lambda a: (None, hz[a:].ctypes.data)
 
     def config(self):
         """The configuration the context runs with, defaults filled in (mrtx_get_config): device, width, height, rank, world,

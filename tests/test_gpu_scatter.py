@@ -206,6 +206,15 @@ def test_gather_is_the_ordered_numpy_reduction(native_lib):
     assert np.all(got[3] == 0.0)
 
 
+def test_gather_without_hits_is_zero(native_lib):
+    # every ray sees sky, so the hit list is empty: a (0, m, 2) host exitance is a valid table and Q_sec is 0
+    rt = make(scene(), np.ones((90, 180), np.float32), 0)
+    got = rt.scatter_flux(np.full((5, 16), -1, np.int32), np.zeros((0, 7, 2), np.float32), thermal.albedo_hemispherical(),
+                          thermal.EMISSIVITY)
+    rt.close()
+    assert got.shape == (5, 7) and np.all(got == 0.0)
+
+
 def test_extra_flux_drives_the_column_as_the_model_says(native_lib, crater_case):
     c = crater_case
     md = c["md"]
