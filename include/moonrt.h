@@ -426,6 +426,49 @@ int mrtx_sight_points(mrtx_ctx* ctx, const double* target_latlon, int32_t n, con
                       double target_h_m, double mast_max_m, double radius_m, int32_t n_bis, void* dev_out, float* host_out,
                       MrtxStats* out);
 
+/* ---- Least-cost traverses (additive to ABI 7) ----------------------------------------------------
+ * A window of the DEM's own texel lattice: node (i, j), 0 <= i < rows, 0 <= j < cols, is texel (row0 + i stride,
+ * (col0 + j stride) mod W) of the (H, W) DEM, its height that texel's D.  stride >= 1; the last row lies inside the DEM; the
+ * columns are distinct ((cols - 1) stride < W).  wrap = 1 (only with cols stride == W and cols >= 3) joins column cols - 1 to
+ * column 0.  No edge crosses the pole.  At most 2^31 nodes.  Each node has 8 neighbours, directions 0..7 = N, NE, E, SE, S,
+ * SW, W, NW as the step from a node v to its neighbour u.  The edge u -> v weighs, in float32 in this order (section 3.13):
+ *   dh = (D_v - D_u) * Rm;  g = dh / L;  not driven if |g| > max_grade;
+ *   c = (L + climb * max(dh, 0)) + descent * max(-dh, 0);  m = 0.5 (P_u + P_v) (1 without penalties);  w = c * m;
+ *   not driven if w is infinite.
+ * Rm = (float)radius_m, the metres of D = 1; L = the edge's length from mrtx_traverse_lengths.  The cost field is float64, the
+ * least fixed point of d[v] = min(src[v], min over u of d[u] + (double)w(u -> v)) (+inf where unreachable). */
+typedef struct MrtxTraverse {
+    int32_t row0, col0, rows, cols, stride, wrap;
+    double radius_m;        /* metres of D = 1 (> 0) */
+    double max_grade;       /* rise over run (> 0; +inf: no slope limit) */
+    double climb_cost;      /* metres of cost per metre climbed (>= 0, finite) */
+    double descent_cost;    /* metres of cost per metre descended (>= 0, finite) */
+    int32_t reserved;       /* 0 */
+} MrtxTraverse;
+/* Host only, no context: the window's per-row float32 edge lengths, metres, rows x 3 floats (L_ew, L_ns, L_dg): L_ew[i] along
+ * row i, L_ns[i] from row i to row i + 1, L_dg[i] from row i to row i + 1 one column over (0 in the last row).  Each is the
+ * float64 great-circle distance between the two texel centres on a sphere of radius_m, rounded once to float32.  An N-S or
+ * diagonal edge uses the length of its upper (northern) row.  MRTX_E_INVALID for a bad window or a length that is not a
+ * finite positive float32. */
+int mrtx_traverse_lengths(const MrtxTraverse* t, int32_t dem_h, int32_t dem_w, float* out3);
+/* The cost field and the predecessors of a window from n_src >= 1 sources: src_ij = n_src (i, j) nodes, src_cost = their start
+ * costs (finite, >= 0; null: all 0; duplicates: the smallest wins).  Penalties: at most one of dev_penalty / host_penalty,
+ * rows x cols float32, each finite in [1e-3, 1e6] or +inf (impassable); a host table is checked before any device call, a
+ * device table in the kernel (a bad entry: MRTX_E_INVALID after the launch).  Output: exactly one of dev_cost / host_cost
+ * (rows x cols float64, 8-byte aligned) and exactly one of dev_pred / host_pred (rows x cols uint8); the device tables
+ * must not overlap.  pred: 8 = a source whose cost is its
+ * start cost; else the first direction k whose neighbour u is in the window with d[u] < d[v], a driven edge u -> v and
+ * d[u] + (double)w(u -> v) == d[v]; 255 = unreachable, 254 = none found.  Needs a DEM, neither a light nor a Moon frame; leaves
+ * the light, Moon frame and render state as they were.  out: launches (tile relaxation launches) and kernel_ms;
+ * tile_visits (optional): workgroups that relaxed a tile, which depends on scheduling. */
+int mrtx_traverse(mrtx_ctx* ctx, const MrtxTraverse* t, const int32_t* src_ij, const double* src_cost, int32_t n_src,
+                  const void* dev_penalty, const float* host_penalty, void* dev_cost, double* host_cost, void* dev_pred,
+                  uint8_t* host_pred, uint64_t* tile_visits, MrtxStats* out);
+/* The window's node heights: rows x cols float32 D (texel (row0 + i stride, (col0 + j stride) mod W), read directly) into
+ * exactly one of dev_out / host_out, so that a route's heights need not reach into the context's DEM later.  The window is
+ * checked as mrtx_traverse checks it; needs a DEM.  out: launches, kernel_ms. */
+int mrtx_traverse_heights(mrtx_ctx* ctx, const MrtxTraverse* t, void* dev_out, float* host_out, MrtxStats* out);
+
 /* Math conformance probe (ABI 7): the kernels' domain-restricted reciprocal (v_rcp_f32 + Newton steps) and square root (v_sqrt_f32 + a
  * +-1 ulp residual fix) against the compiler's IEEE expansions of 1.0f / x and sqrtf(x), ON THE DEVICE, for the n float bit patterns
  * from lo_bits on: which = 0 one Newton step, 1 two steps (what the kernels use), 2 the square root.  mismatches = how many differ;

@@ -52,6 +52,14 @@ class MrtxSightGrid(C.Structure):
                 ("row_begin", C.c_int32), ("row_end", C.c_int32), ("n_bis", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MrtxTraverse(C.Structure):
+    """A window of the DEM's texel lattice and the effort model of a least-cost traverse (mrtx_traverse, DESIGN.md section
+    3.13)."""
+    _fields_ = [("row0", C.c_int32), ("col0", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("stride", C.c_int32),
+                ("wrap", C.c_int32), ("radius_m", C.c_double), ("max_grade", C.c_double), ("climb_cost", C.c_double),
+                ("descent_cost", C.c_double), ("reserved", C.c_int32)]
+
+
 class MrtxIllumEpoch(C.Structure):
     """One date of a Sun-illumination series (mrtx_illum_series): what mrtx_set_light and
     mrtx_set_moon_frame would set for it."""
@@ -142,6 +150,10 @@ SIGNATURES = {
     "mrtx_sight_grid": (C.c_int, [_VP, C.POINTER(MrtxSightGrid), _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_sight_points": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _VP,
                                     _VP, C.POINTER(MrtxStats)]),
+    "mrtx_traverse_lengths": (C.c_int, [C.POINTER(MrtxTraverse), C.c_int32, C.c_int32, _VP]),
+    "mrtx_traverse": (C.c_int, [_VP, C.POINTER(MrtxTraverse), _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
+                                C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
+    "mrtx_traverse_heights": (C.c_int, [_VP, C.POINTER(MrtxTraverse), _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_thermal": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                C.POINTER(MrtxStats)]),
     "mrtx_view_dir_samples": (C.c_int, [C.c_int32, _VP]),

@@ -5,6 +5,7 @@
 // float32 per-launch constant block (FrameC) from it right before every launch.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -15,6 +16,7 @@
 #include <new>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/moonrt.h"
@@ -62,6 +64,10 @@ hipError_t mrtx_launch_sight(const FrameC& f, SightC q, bool stats, hipStream_t 
 hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, bool ext, hipStream_t st);
 hipError_t mrtx_launch_view_hits(const FrameC& f, const ViewC& q, bool stats, hipStream_t st);
 hipError_t mrtx_launch_scatter_flux(const ScatterC& q, hipStream_t st);
+hipError_t mrtx_launch_traverse_init(const TraverseC& q, hipStream_t st);
+hipError_t mrtx_launch_traverse_relax(const TraverseC& q, hipStream_t st);
+hipError_t mrtx_launch_traverse_pred(const TraverseC& q, hipStream_t st);
+hipError_t mrtx_launch_traverse_heights(const TraverseC& q, float* out, hipStream_t st);
 
 struct mrtx_ctx {
     MrtxConfig cfg{};
@@ -148,6 +154,7 @@ struct mrtx_ctx {
     unsigned long long* illum_stats = nullptr;   // ST_N counters
     float* illum_tab = nullptr; size_t illum_tab_bytes = 0;    // sample table + (sin, cos) tables
     float* illum_out = nullptr; size_t illum_out_bytes = 0;    // float4 per node when the caller gives no device buffer
+    float* trav_buf = nullptr; size_t trav_bytes = 0;         // mrtx_traverse: tile flags, and the outputs the caller wants on the host
     std::string err;
 };
 
@@ -645,6 +652,7 @@ void mrtx_destroy(mrtx_ctx* c) {
     if (c->illum_stats) (void)hipFree(c->illum_stats);
     if (c->illum_tab) (void)hipFree(c->illum_tab);
     if (c->illum_out) (void)hipFree(c->illum_out);
+    if (c->trav_buf) (void)hipFree(c->trav_buf);
     if (c->stream2) { (void)hipStreamSynchronize(c->stream2); put_stream(c->cfg.device, c->stream2); }
     put_event(c->cfg.device, c->ov_done[0]); put_event(c->cfg.device, c->ov_done[1]); put_event(c->cfg.device, c->ov_join);
     put_event(c->cfg.device, c->ev0);
@@ -1660,6 +1668,223 @@ int mrtx_sight_points(mrtx_ctx* c, const double* target_latlon, int32_t n, const
     }
     if ((rc = point_tables(c, oll.data(), n_observers, ort, oct)) != MRTX_OK) return rc;
     return sight_run(c, trt, tct, 1, n, true, ort, oct, oh, target_h_m, mast_max_m, radius_m, n_bis, dev_out, host_out, out);
+}
+
+// ---- Least-cost traverses ---------------------------------------------------------------------------
+// The checks that need no DEM: the effort model, the window's own numbers, the node count
+static int traverse_params(mrtx_ctx* c, const MrtxTraverse* t) {
+    if (t->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    if (t->rows < 1 || t->cols < 1) return fail(c, MRTX_E_INVALID, "empty window (%d x %d)", t->rows, t->cols);
+    if ((int64_t)t->rows * (int64_t)t->cols > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "a window holds at most 2^31 nodes (got %d x %d)", t->rows, t->cols);
+    if (t->stride < 1) return fail(c, MRTX_E_INVALID, "stride must be >= 1 (got %d)", t->stride);
+    if (t->row0 < 0 || t->col0 < 0) return fail(c, MRTX_E_INVALID, "row0 and col0 must be >= 0");
+    if (t->wrap != 0 && t->wrap != 1) return fail(c, MRTX_E_INVALID, "wrap must be 0 or 1 (got %d)", t->wrap);
+    if (t->wrap && t->cols < 3) return fail(c, MRTX_E_INVALID, "a wrapped window needs cols >= 3 (got %d)", t->cols);
+    if (!std::isfinite(t->radius_m) || !(t->radius_m > 0.0) || !std::isfinite((float)t->radius_m))
+        return fail(c, MRTX_E_INVALID, "radius_m must be finite and > 0 (also as a float32)");
+    if (!((float)t->max_grade > 0.0f)) return fail(c, MRTX_E_INVALID, "max_grade must be > 0 (as a float32; +inf: no limit)");
+    if (!std::isfinite(t->climb_cost) || !(t->climb_cost >= 0.0) || !std::isfinite((float)t->climb_cost) ||
+        !std::isfinite(t->descent_cost) || !(t->descent_cost >= 0.0) || !std::isfinite((float)t->descent_cost))
+        return fail(c, MRTX_E_INVALID, "climb_cost and descent_cost must be finite and >= 0 (also as float32)");
+    return MRTX_OK;
+}
+
+// The checks against the DEM's shape (H, W), then the rows x 3 lengths into out3 (each finite and > 0 as a float32)
+static int traverse_window(mrtx_ctx* c, const MrtxTraverse* t, int32_t H, int32_t W, float* out3) {
+    if (H < 2 || W < 2) return fail(c, MRTX_E_INVALID, "the DEM must be at least 2 x 2 (got %d x %d)", H, W);
+    if (t->row0 + (int64_t)(t->rows - 1) * t->stride >= H)
+        return fail(c, MRTX_E_INVALID, "the window's last row %lld lies outside the DEM's %d rows",
+                    (long long)(t->row0 + (int64_t)(t->rows - 1) * t->stride), H);
+    if (t->col0 >= W) return fail(c, MRTX_E_INVALID, "col0 = %d lies outside the DEM's %d columns", t->col0, W);
+    if (t->wrap && (int64_t)t->cols * t->stride != W)
+        return fail(c, MRTX_E_INVALID, "wrap = 1 needs cols x stride == W (%lld != %d)", (long long)t->cols * t->stride, W);
+    if (!t->wrap && (int64_t)(t->cols - 1) * t->stride >= W)
+        return fail(c, MRTX_E_INVALID, "the window's columns repeat: (cols - 1) x stride must be < W = %d", W);
+    const double dphi = (double)t->stride * kPiD / (double)H, dlam = (double)t->stride * 2.0 * kPiD / (double)W;
+    const double sl = std::sin(0.5 * dlam), sp = std::sin(0.5 * dphi);
+    for (int32_t i = 0; i < t->rows; i++) {
+        const double r = (double)t->row0 + (double)i * t->stride;
+        const double p1 = 0.5 * kPiD - (r + 0.5) * (kPiD / (double)H), p2 = p1 - dphi;
+        const double c1 = std::cos(p1), c2 = std::cos(p2);
+        const double hav[3] = {c1 * c1 * sl * sl, sp * sp, sp * sp + c1 * c2 * sl * sl};     // haversines of the three edges
+        for (int k = 0; k < 3; k++) {
+            const bool last = i == t->rows - 1 && k > 0;
+            const float L = last ? 0.0f : (float)(2.0 * t->radius_m * std::asin(std::sqrt(std::min(hav[k], 1.0))));
+            if (!last && !(std::isfinite(L) && L > 0.0f))
+                return fail(c, MRTX_E_INVALID, "row %d: edge length %d is %g, not a finite positive float32", i, k, (double)L);
+            if (out3) out3[3 * (size_t)i + k] = L;
+        }
+    }
+    return MRTX_OK;
+}
+
+int mrtx_traverse_lengths(const MrtxTraverse* t, int32_t dem_h, int32_t dem_w, float* out3) {
+    if (!t || !out3) return MRTX_E_INVALID;
+    const int rc = traverse_params(nullptr, t);
+    return rc != MRTX_OK ? rc : traverse_window(nullptr, t, dem_h, dem_w, out3);
+}
+
+// The caller's device tables: the costs are read and written as 64-bit atomics (8-byte aligned), the penalties as floats
+// (4-byte aligned); no two of them may overlap (the kernels read the penalties while they write costs and codes)
+static bool traverse_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return a && b && x < y + nb && y < x + na;
+}
+static int traverse_dev_buffers(mrtx_ctx* c, const MrtxTraverse* t, const void* dev_penalty, const void* dev_cost,
+                                const void* dev_pred) {
+    const size_t N = (size_t)t->rows * (size_t)t->cols;
+    if (dev_cost && (reinterpret_cast<uintptr_t>(dev_cost) & 7))
+        return fail(c, MRTX_E_INVALID, "dev_cost must be 8-byte aligned (float64, read and written atomically)");
+    if (dev_penalty && (reinterpret_cast<uintptr_t>(dev_penalty) & 3))
+        return fail(c, MRTX_E_INVALID, "dev_penalty must be 4-byte aligned (float32)");
+    if (traverse_overlap(dev_cost, 8 * N, dev_pred, N) || traverse_overlap(dev_penalty, 4 * N, dev_cost, 8 * N) ||
+        traverse_overlap(dev_penalty, 4 * N, dev_pred, N))
+        return fail(c, MRTX_E_INVALID, "dev_penalty, dev_cost and dev_pred must not overlap");
+    return MRTX_OK;
+}
+
+static bool traverse_penalty_ok(float p) { return (p >= 1e-3f && p <= 1e6f) || p == INFINITY; }
+
+// the relaxation launches one batch at a time; the change counter of the batch's last launch is read after each batch
+static const int kTraverseBatch = 8;
+
+int mrtx_traverse(mrtx_ctx* c, const MrtxTraverse* t, const int32_t* src_ij, const double* src_cost, int32_t n_src,
+                  const void* dev_penalty, const float* host_penalty, void* dev_cost, double* host_cost, void* dev_pred,
+                  uint8_t* host_pred, uint64_t* tile_visits, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!t) return fail(c, MRTX_E_INVALID, "null window");
+    int rc = traverse_params(c, t);
+    if (rc != MRTX_OK) return rc;
+    if (dev_penalty && host_penalty) return fail(c, MRTX_E_INVALID, "give at most one of dev_penalty and host_penalty");
+    if ((dev_cost == nullptr) == (host_cost == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_cost and host_cost");
+    if ((dev_pred == nullptr) == (host_pred == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_pred and host_pred");
+    if ((rc = traverse_dev_buffers(c, t, dev_penalty, dev_cost, dev_pred)) != MRTX_OK) return rc;
+    if (n_src < 1 || !src_ij) return fail(c, MRTX_E_INVALID, "need n_src >= 1 sources (got %d)", n_src);
+    // the sources, duplicates reduced to their smallest start cost (-0 made +0: the kernels order costs by their bits)
+    std::vector<std::pair<int64_t, double>> src((size_t)n_src);
+    for (int32_t k = 0; k < n_src; k++) {
+        const int32_t i = src_ij[2 * (size_t)k], j = src_ij[2 * (size_t)k + 1];
+        const double s = src_cost ? src_cost[k] : 0.0;
+        if (i < 0 || i >= t->rows || j < 0 || j >= t->cols)
+            return fail(c, MRTX_E_INVALID, "source %d: node (%d, %d) lies outside the %d x %d window", k, i, j, t->rows, t->cols);
+        if (!std::isfinite(s) || !(s >= 0.0)) return fail(c, MRTX_E_INVALID, "source %d: start cost must be finite and >= 0", k);
+        src[(size_t)k] = {(int64_t)i * t->cols + j, s + 0.0};
+    }
+    std::sort(src.begin(), src.end());
+    std::vector<int64_t> sn;
+    std::vector<double> sc;
+    for (const auto& e : src)
+        if (sn.empty() || sn.back() != e.first) { sn.push_back(e.first); sc.push_back(e.second); }
+    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
+    std::vector<float> len((size_t)t->rows * 3);
+    if ((rc = traverse_window(c, t, c->dem_h, c->dem_w, len.data())) != MRTX_OK) return rc;
+    const size_t N = (size_t)t->rows * (size_t)t->cols;
+    if (host_penalty)
+        for (size_t n = 0; n < N; n++)
+            if (!traverse_penalty_ok(host_penalty[n]))
+                return fail(c, MRTX_E_INVALID, "penalty %zu must be finite in [1e-3, 1e6] or +inf (got %g)", n, (double)host_penalty[n]);
+    int TS = 32;        // MOONRT_TRAVERSE_TILE: the tile edge, 8, 16 or 32 (the same field in every case)
+    if (const char* e = std::getenv("MOONRT_TRAVERSE_TILE")) {
+        TS = std::atoi(e);
+        if (TS != 8 && TS != 16 && TS != 32) return fail(c, MRTX_E_INVALID, "MOONRT_TRAVERSE_TILE must be 8, 16 or 32 (got %s)", e);
+    }
+    // ---- device work from here
+    FrameC f;
+    FrameCold cold;
+    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
+    const int tiles_x = (t->cols + TS - 1) / TS, tiles_y = (t->rows + TS - 1) / TS;
+    const size_t tiles = (size_t)tiles_x * (size_t)tiles_y;
+    const size_t cost_b = host_cost ? N * 8 : 0, pred_b = host_pred ? (N + 15) & ~(size_t)15 : 0;
+    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, cost_b + pred_b + 2 * tiles * 4)) != MRTX_OK) return rc;
+    char* tb = reinterpret_cast<char*>(c->trav_buf);
+    double* d_cost = host_cost ? reinterpret_cast<double*>(tb) : static_cast<double*>(dev_cost);
+    uint8_t* d_pred = host_pred ? reinterpret_cast<uint8_t*>(tb + cost_b) : static_cast<uint8_t*>(dev_pred);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(tb + cost_b + pred_b);
+    const size_t np = host_penalty ? N : 0;
+    float* d[4];
+    if ((rc = stage_tables(c, {len, {sn.data(), 2 * sn.size()}, {sc.data(), 2 * sc.size()}, {host_penalty, np}}, d)) != MRTX_OK)
+        return rc;
+    TraverseC q;
+    std::memset(&q, 0, sizeof q);
+    q.dem = f.dem; q.dem_pitch = f.dem_pitch; q.dem_w = c->dem_w;
+    q.row0 = t->row0; q.col0 = t->col0; q.rows = t->rows; q.cols = t->cols; q.stride = t->stride; q.wrap = t->wrap;
+    q.len = d[0];
+    q.src_node = reinterpret_cast<const int64_t*>(d[1]); q.src_cost = reinterpret_cast<const double*>(d[2]);
+    q.n_src = (int32_t)sn.size();
+    q.pen = host_penalty ? d[3] : static_cast<const float*>(dev_penalty);
+    q.d = d_cost; q.pred = d_pred;
+    q.rm = (float)t->radius_m; q.gmax = (float)t->max_grade; q.a_up = (float)t->climb_cost; q.a_dn = (float)t->descent_cost;
+    q.tile = TS; q.tiles_x = tiles_x; q.tiles_y = tiles_y;
+    q.visits = c->illum_stats;                                       // [0] tile visits, [1] bad device penalties
+    q.changed = reinterpret_cast<uint32_t*>(c->illum_stats + 2);     // kTraverseBatch per-launch change counters
+    uint32_t* fa = flags;
+    uint32_t* fb = flags + tiles;
+    HIPCHK(c, hipMemsetAsync(flags, 0, 2 * tiles * 4, c->stream));
+    if ((rc = stage_start(c, nullptr, true)) != MRTX_OK) return rc;
+    q.flag_in = fa;
+    HIPCHK(c, mrtx_launch_traverse_init(q, c->stream));
+    unsigned long long cnt[2] = {0, 0};
+    if (dev_penalty) {
+        HIPCHK(c, hipMemcpyAsync(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (cnt[1])
+            return fail(c, MRTX_E_INVALID, "%llu entries of the device penalty table are not finite in [1e-3, 1e6] or +inf", cnt[1]);
+    }
+    uint32_t launches = 0;
+    for (;;) {      // no launch cap: the relaxation only lowers costs, and reaches its fixed point
+        HIPCHK(c, hipMemsetAsync(q.changed, 0, kTraverseBatch * sizeof(uint32_t), c->stream));
+        for (int s = 0; s < kTraverseBatch; s++) {
+            q.flag_in = fa; q.flag_out = fb; q.slot = s;
+            HIPCHK(c, mrtx_launch_traverse_relax(q, c->stream));
+            std::swap(fa, fb);
+            launches++;
+        }
+        uint32_t last = 0;
+        HIPCHK(c, hipMemcpyAsync(&last, q.changed + (kTraverseBatch - 1), sizeof last, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (last == 0) break;       // a whole launch lowered nothing: every later one is empty too
+    }
+    HIPCHK(c, mrtx_launch_traverse_pred(q, c->stream));
+    // finish: time, the float64 and uint8 read-backs, the counters
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (host_cost) HIPCHK(c, hipMemcpy(host_cost, d_cost, N * 8, hipMemcpyDeviceToHost));
+    if (host_pred) HIPCHK(c, hipMemcpy(host_pred, d_pred, N, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost));
+    if (tile_visits) *tile_visits = cnt[0];
+    if (out) {
+        std::memset(out, 0, sizeof *out);
+        out->kernel_ms = ms;
+        out->launches = launches;
+    }
+    return MRTX_OK;
+}
+
+// The window's node heights D (rows x cols float32), gathered on the device: what a route's heights are read from
+int mrtx_traverse_heights(mrtx_ctx* c, const MrtxTraverse* t, void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!t) return fail(c, MRTX_E_INVALID, "null window");
+    int rc = traverse_params(c, t);
+    if (rc != MRTX_OK) return rc;
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 3)) return fail(c, MRTX_E_INVALID, "dev_out must be 4-byte aligned");
+    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
+    if ((rc = traverse_window(c, t, c->dem_h, c->dem_w, nullptr)) != MRTX_OK) return rc;
+    FrameC f;
+    FrameCold cold;
+    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
+    const size_t bytes = (size_t)t->rows * (size_t)t->cols * sizeof(float);
+    if ((rc = stage_out(c, dev_out, bytes)) != MRTX_OK) return rc;
+    TraverseC q;
+    std::memset(&q, 0, sizeof q);
+    q.dem = f.dem; q.dem_pitch = f.dem_pitch; q.dem_w = c->dem_w;
+    q.row0 = t->row0; q.col0 = t->col0; q.rows = t->rows; q.cols = t->cols; q.stride = t->stride; q.wrap = t->wrap;
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_traverse_heights(q, static_cast<float*>(dev_out), c->stream));
+    return stage_finish(c, dev_out, host_out, bytes, out, kNoRays);
 }
 
 // ---- Regolith surface temperatures ---------------------------------------------------------------

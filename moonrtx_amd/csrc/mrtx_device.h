@@ -283,3 +283,26 @@ struct SightC {
     int32_t n_bis;          // 0 .. 24
     int32_t waves_x;        // waves per row of targets (set by the launcher)
 };
+
+// Least-cost traverses (mrtx_traverse, DESIGN.md sections 3.13 and 4.14; kernels in mrtx_traverse.hip).  A window of the DEM's
+// texel lattice, rows x cols nodes, node n = i * cols + j; the relaxation works on tiles of TS x TS nodes, one workgroup each.
+struct TraverseC {
+    const float* dem;           // the context's padded DEM (FrameC::dem's layout), always addressed with 64-bit offsets
+    int64_t dem_pitch;          // w + 4 elements
+    int32_t dem_w;              // W: columns wrap modulo W
+    int32_t row0, col0, rows, cols, stride, wrap;
+    const float* len;           // rows x 3 float32 (L_ew, L_ns, L_dg), mrtx_traverse_lengths
+    const float* pen;           // rows x cols float32 penalties, or null (m = 1)
+    double* d;                  // rows x cols float64 costs
+    uint8_t* pred;              // rows x cols predecessor codes
+    float rm, gmax, a_up, a_dn; // (float) of radius_m, max_grade, climb_cost, descent_cost
+    int32_t tile, tiles_x, tiles_y;   // tile edge TS (8, 16 or 32) and the tile grid
+    uint32_t* flag_in;          // per tile: relax it in this launch (cleared by the tile's workgroup)
+    uint32_t* flag_out;         // per tile: relax it in the next launch
+    uint32_t* changed;          // per launch slot of a batch: workgroups that lowered a cost
+    int32_t slot;               // this launch's slot
+    unsigned long long* visits; // [0] tile visits, [1] bad device penalty entries
+    const int64_t* src_node;    // the sources, duplicates reduced on the host: node index and start cost
+    const double* src_cost;
+    int32_t n_src;
+};

@@ -105,10 +105,12 @@ class MoonRT:
             raise ValueError("elevation must be a 2-D float32 array")
         self._check(self._lib.mrtx_upload_dem(self._ctx, a.ctypes.data, a.shape[0], a.shape[1]), "mrtx_upload_dem")
         self._keepalive.pop("dem", None)
+        self._dem_shape = (int(a.shape[0]), int(a.shape[1]))
 
     def bind_dem(self, buf, h, w):
         """Ingest a device-resident float32 (h, w) DEM; the context makes its own row-pair copy (8 B per texel)."""
         self._check(self._lib.mrtx_bind_dem_device(self._ctx, buf.ptr, h, w), "mrtx_bind_dem_device")
+        self._dem_shape = (int(h), int(w))
 
     def upload_color(self, rgba):
         if rgba is None:
@@ -584,6 +586,133 @@ class MoonRT:
                                                     C.byref(st)), "mrtx_sight_points")
             self._add_stats(stats, st)
         return out
+
+    # ---- Least-cost traverses
+    def _dem_hw(self):
+        hw = getattr(self, "_dem_shape", None)
+        if hw is None:
+            raise MoonRTError("no displacement map: call upload_dem or bind_dem first")
+        return hw
+
+    def traverse_nodes(self, window):
+        """(lat, lon, grid) of a traverse window (row0, col0, rows, cols[, stride[, wrap]]) on the DEM in place: lat (rows,)
+        and lon (cols,) float64 degrees of its nodes, the texel centres (lon in [-180, 180)), and grid = dict(lat=, lon=,
+        shape=), the arguments with which illumination_map / viewshed sample the same positions node for node (their
+        longitudes continue past 180 where the window does; with stride > 1 a window on the DEM's first or last row puts
+        lat beyond +-90, which those calls refuse)."""
+        from .traverse import window_dict
+        w = window_dict(window)
+        H, W = self._dem_hw()
+        s = w["stride"]
+        lat = 90.0 - (w["row0"] + np.arange(w["rows"]) * s + 0.5) * (180.0 / H)
+        lon = -180.0 + ((w["col0"] + np.arange(w["cols"]) * s) % W + 0.5) * (360.0 / W)
+        la_n = 90.0 - (w["row0"] + 0.5 - 0.5 * s) * (180.0 / H)
+        lo_w = -180.0 + (w["col0"] + 0.5 - 0.5 * s) * (360.0 / W)
+        grid = {"lat": (la_n, la_n - w["rows"] * s * (180.0 / H)), "lon": (lo_w, lo_w + w["cols"] * s * (360.0 / W)),
+                "shape": (w["rows"], w["cols"])}
+        return lat, lon, grid
+
+    def snap_to_nodes(self, window, lat_deg, lon_deg):
+        """(N, 2) int32 (i, j) of the window nodes nearest to N points: the row whose centre latitude is nearest, the column
+        whose centre longitude is nearest around the circle (halves round up to the larger index); ValueError if one lies
+        outside the window."""
+        from .traverse import window_dict
+        w = window_dict(window)
+        H, W = self._dem_hw()
+        s = w["stride"]
+        la = np.atleast_1d(np.asarray(lat_deg, np.float64))
+        lo = np.atleast_1d(np.asarray(lon_deg, np.float64))
+        i = np.floor(((90.0 - la) * (H / 180.0) - 0.5 - w["row0"]) / s + 0.5).astype(np.int64)
+        cc = ((lo + 180.0) * (W / 360.0) - 0.5 - w["col0"]) % W           # texel columns east of col0
+        j = np.floor(cc / s + 0.5).astype(np.int64)
+        if w["wrap"]:
+            j %= w["cols"]
+        else:       # nearer to the window's first column going round the circle the other way
+            j = np.where(j >= w["cols"], np.where((W - cc) / s <= 0.5, 0, j), j)
+        bad = (i < 0) | (i >= w["rows"]) | (j < 0) | (j >= w["cols"])
+        if bad.any():
+            k = int(np.argmax(bad))
+            raise ValueError(f"point ({la[k]}, {lo[k]}) lies outside the window")
+        return np.ascontiguousarray(np.stack([i, j], -1).astype(np.int32))
+
+    def traverse(self, window, sources=None, penalty=None, max_slope_deg=20.0, climb_cost=8.0, descent_cost=0.0,
+                 radius_m=1737400.0, start_cost=None, stats=None, nodes=None, heights=True):
+        """The least-cost field over a window (row0, col0, rows, cols[, stride[, wrap]]) of the DEM's texel lattice
+        (mrtx_traverse) from its sources: `sources` = an (N, 2) array of (lat, lon) degrees, each
+        snapped to its nearest node (snap_to_nodes), or `nodes` = an (N, 2) array of explicit (i, j) nodes -- exactly one of
+        the two; start_cost = N start costs (default 0).  penalty: None, a (rows, cols) float32 map or a DeviceBuffer
+        holding one (see moonrtx_amd.traverse for builders).  The effort of a step is its length plus climb_cost per metre
+        climbed and descent_cost per metre descended (the defaults: Naismith's rule, 8 m of walking per metre of ascent);
+        steps steeper than max_slope_deg are not driven.  radius_m = the metres of D = 1.  Returns a
+        moonrtx_amd.traverse.TraverseField; with `heights` it holds the window's node heights (mrtx_traverse_heights), so that
+        routes read their heights from the field and not from the context, which may be closed or hold another DEM by then.
+        `stats`, if a dict, receives kernel_ms, launches and tile_visits of the traverse."""
+        from . import traverse as tv
+        w = tv.window_dict(window)
+        H, W = self._dem_hw()
+        if (sources is None) == (nodes is None):
+            raise ValueError("give exactly one of sources ((lat, lon) degrees) and nodes ((i, j) indices)")
+        if nodes is not None:
+            ij = np.asarray(nodes)
+            if not np.issubdtype(ij.dtype, np.integer):
+                raise ValueError("nodes must be integer (i, j) indices")
+            ij = np.ascontiguousarray(ij.reshape(-1, 2) if ij.ndim == 1 else ij, np.int32)
+        else:
+            ll = np.asarray(sources, np.float64)
+            ll = ll.reshape(1, -1) if ll.ndim == 1 else ll
+            if ll.ndim != 2 or ll.shape[1] != 2:
+                raise ValueError("sources must be (N, 2) (lat, lon) degrees")
+            ij = self.snap_to_nodes(w, ll[:, 0], ll[:, 1])
+        if ij.ndim != 2 or ij.shape[1] != 2:
+            raise ValueError("nodes must be (N, 2) (i, j) indices")
+        cost0 = None if start_cost is None else np.ascontiguousarray(np.broadcast_to(np.asarray(start_cost, np.float64),
+                                                                                      (ij.shape[0],)))
+        t = self._traverse_window(w, radius_m, tv.max_slope_grade(max_slope_deg), climb_cost, descent_cost)
+        lengths = np.empty((max(w["rows"], 1), 3), np.float32)
+        rc = self._lib.mrtx_traverse_lengths(C.byref(t), H, W, lengths.ctypes.data)
+        if rc != 0:
+            raise MoonRTError(f"mrtx_traverse_lengths failed ({rc}): bad window or lengths")
+        dev_pen = host_pen = None
+        if isinstance(penalty, DeviceBuffer):
+            if penalty.nbytes < 4 * w["rows"] * w["cols"]:
+                raise ValueError("the penalty buffer is smaller than rows x cols float32")
+            dev_pen = penalty.ptr
+        elif penalty is not None:
+            pen = np.ascontiguousarray(penalty, np.float32)
+            if pen.shape != (w["rows"], w["cols"]):
+                raise ValueError(f"penalty must be a (rows, cols) = {(w['rows'], w['cols'])} map")
+            host_pen = pen.ctypes.data
+        cost = np.empty((w["rows"], w["cols"]), np.float64)
+        pred = np.empty((w["rows"], w["cols"]), np.uint8)
+        visits = C.c_uint64()
+        st = MrtxStats()
+        self._check(self._lib.mrtx_traverse(self._ctx, C.byref(t), ij.ctypes.data, None if cost0 is None else cost0.ctypes.data,
+                                            ij.shape[0], dev_pen, host_pen, None, cost.ctypes.data, None, pred.ctypes.data,
+                                            C.byref(visits), C.byref(st)), "mrtx_traverse")
+        if isinstance(stats, dict):
+            stats["kernel_ms"] = stats.get("kernel_ms", 0) + st.kernel_ms
+            stats["launches"] = stats.get("launches", 0) + st.launches
+            stats["tile_visits"] = stats.get("tile_visits", 0) + int(visits.value)
+        lat, lon, _ = self.traverse_nodes(w)
+        D = self.traverse_heights(w) if heights else None
+        return tv.TraverseField(cost, pred, w, lengths, radius_m, lat, lon, D=D)
+
+    @staticmethod
+    def _traverse_window(w, radius_m=1737400.0, max_grade=1.0, climb_cost=0.0, descent_cost=0.0):
+        return _lib.MrtxTraverse(w["row0"], w["col0"], w["rows"], w["cols"], w["stride"], w["wrap"], float(radius_m),
+                                 float(max_grade), float(climb_cost), float(descent_cost), 0)
+
+    def traverse_heights(self, window, stats=None):
+        """(rows, cols) float32 D of a traverse window's nodes, copied from the context's DEM (mrtx_traverse_heights):
+        (D - 1) x radius_m is a node's height above the sphere in metres."""
+        from .traverse import window_dict
+        w = window_dict(window)
+        D = np.empty((w["rows"], w["cols"]), np.float32)
+        st = MrtxStats()
+        self._check(self._lib.mrtx_traverse_heights(self._ctx, C.byref(self._traverse_window(w)), None, D.ctypes.data,
+                                                    C.byref(st)), "mrtx_traverse_heights")
+        self._add_stats(stats, st)
+        return D
 
     @staticmethod
     def _add_stats(acc, st, extra=None):
