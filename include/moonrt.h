@@ -469,6 +469,49 @@ int mrtx_traverse(mrtx_ctx* ctx, const MrtxTraverse* t, const int32_t* src_ij, c
  * checked as mrtx_traverse checks it; needs a DEM.  out: launches, kernel_ms. */
 int mrtx_traverse_heights(mrtx_ctx* ctx, const MrtxTraverse* t, void* dev_out, float* host_out, MrtxStats* out);
 
+/* ---- Terrain relief: slope, roughness and landing hazard (additive to ABI 7) -----------------------
+ * A window of the DEM's texel lattice as MrtxTraverse's, never wrapped: node (i, j) is texel (row0 + i stride,
+ * (col0 + j stride) mod W); the last row lies inside the DEM and the columns are distinct.  A node's footprint is the
+ * (2 ri + 1) x (2 rj + 1) lattice nodes (i + di, j + dj), |di| <= ri, |dj| <= rj, 1 <= ri, rj <= 32, (2 rj + 1) stride <= W,
+ * read straight from the DEM: it may reach outside the window, its columns wrap modulo W, and a node whose footprint would
+ * leave the DEM's rows [0, H) gets four NaNs -- so a node's bits do not depend on the window it is computed in.  Per node the
+ * least-squares plane c + aj dj + ai di through z = (double)D - 1 over the footprint and the residual about it, all sums
+ * float64 left folds in the order of section 3.14; output float4 (grade, rms_m, ge, gn): ge = aj kx[i] the gradient to the east
+ * and gn = -(ai ky[i]) to the north (rise over run), grade = sqrtf((float)(ge ge + gn gn)), rms_m = the root mean square
+ * residual in metres.  At most 2^31 nodes. */
+typedef struct MrtxRelief {
+    int32_t row0, col0, rows, cols, stride;
+    int32_t ri, rj;         /* the footprint's half-heights in lattice nodes, 1 .. 32 */
+    int32_t reserved;       /* 0 */
+    double radius_m;        /* metres of D = 1 (> 0) */
+} MrtxRelief;
+/* Host only, no context: the window's per-row metric scales, rows x 2 float64 (kx, ky): kx[i] = radius_m over the distance
+ * along row i between neighbouring lattice nodes, radius_m cos(lat_i) stride 2 pi / W, and ky[i] = radius_m over the N-S
+ * distance between neighbouring lattice rows, radius_m stride pi / H; lat_i the latitude of row i's texel centres.  The window
+ * and the footprint are checked against the (dem_h, dem_w) DEM as mrtx_relief checks them; MRTX_E_INVALID if they are bad or a
+ * scale is not finite and positive. */
+int mrtx_relief_scales(const MrtxRelief* r, int32_t dem_h, int32_t dem_w, double* out2);
+/* The relief map of a window: rows x cols float4 into exactly one of dev_out (16-byte aligned) and host_out.  Needs a DEM,
+ * neither a light nor a Moon frame; leaves the light, Moon frame and render state as they were.  out: launches, kernel_ms;
+ * with MRTX_F_COUNT_STATS dem_fetches = the texels the definition reads, (2 ri + 1)(2 rj + 1) per node that is not NaN. */
+int mrtx_relief(mrtx_ctx* ctx, const MrtxRelief* r, void* dev_out, float* host_out, MrtxStats* out);
+/* The safe share of a landing ellipse over a relief map of rows x cols float4 (exactly one of dev_relief, 16-byte aligned, and
+ * host_relief): per node (float)safe / (float)total, float32, where total counts the nodes of the (2 Ri + 1) x (2 Rj + 1) box
+ * around it that lie inside the map (wrap = 1: column cols - 1 joins column 0, needs cols >= 3; a box wider than the circle
+ * holds every column once) and safe those with grade <= grade_max and rms_m <= rms_max (a NaN node is unsafe).
+ * 0 <= Ri, Rj <= 1024; the thresholds are >= 0 (+inf: no limit).  Output: rows x cols float32 into exactly one of dev_out and
+ * host_out; device tables must not overlap.  Needs no DEM.  out: launches, kernel_ms. */
+typedef struct MrtxReliefShare {
+    int32_t rows, cols;
+    int32_t Ri, Rj;         /* the box's half-heights in map nodes, 0 .. 1024 */
+    int32_t wrap;           /* 1: the map closes the circle of longitude */
+    int32_t reserved;       /* 0 */
+    double grade_max;       /* rise over run */
+    double rms_max;         /* metres */
+} MrtxReliefShare;
+int mrtx_relief_share(mrtx_ctx* ctx, const MrtxReliefShare* s, const void* dev_relief, const float* host_relief, void* dev_out,
+                      float* host_out, MrtxStats* out);
+
 /* Math conformance probe (ABI 7): the kernels' domain-restricted reciprocal (v_rcp_f32 + Newton steps) and square root (v_sqrt_f32 + a
  * +-1 ulp residual fix) against the compiler's IEEE expansions of 1.0f / x and sqrtf(x), ON THE DEVICE, for the n float bit patterns
  * from lo_bits on: which = 0 one Newton step, 1 two steps (what the kernels use), 2 the square root.  mismatches = how many differ;

@@ -60,6 +60,18 @@ class MrtxTraverse(C.Structure):
                 ("descent_cost", C.c_double), ("reserved", C.c_int32)]
 
 
+class MrtxRelief(C.Structure):
+    """A window of the DEM's texel lattice and the footprint of a relief map (mrtx_relief)."""
+    _fields_ = [("row0", C.c_int32), ("col0", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("stride", C.c_int32),
+                ("ri", C.c_int32), ("rj", C.c_int32), ("reserved", C.c_int32), ("radius_m", C.c_double)]
+
+
+class MrtxReliefShare(C.Structure):
+    """The box and the thresholds of a landing ellipse's safe share (mrtx_relief_share)."""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("Ri", C.c_int32), ("Rj", C.c_int32), ("wrap", C.c_int32),
+                ("reserved", C.c_int32), ("grade_max", C.c_double), ("rms_max", C.c_double)]
+
+
 class MrtxIllumEpoch(C.Structure):
     """One date of a Sun-illumination series (mrtx_illum_series): what mrtx_set_light and
     mrtx_set_moon_frame would set for it."""
@@ -154,6 +166,9 @@ SIGNATURES = {
     "mrtx_traverse": (C.c_int, [_VP, C.POINTER(MrtxTraverse), _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
                                 C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
     "mrtx_traverse_heights": (C.c_int, [_VP, C.POINTER(MrtxTraverse), _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_relief_scales": (C.c_int, [C.POINTER(MrtxRelief), C.c_int32, C.c_int32, _VP]),
+    "mrtx_relief": (C.c_int, [_VP, C.POINTER(MrtxRelief), _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_relief_share": (C.c_int, [_VP, C.POINTER(MrtxReliefShare), _VP, _VP, _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_thermal": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                C.POINTER(MrtxStats)]),
     "mrtx_view_dir_samples": (C.c_int, [C.c_int32, _VP]),

@@ -68,6 +68,9 @@ hipError_t mrtx_launch_traverse_init(const TraverseC& q, hipStream_t st);
 hipError_t mrtx_launch_traverse_relax(const TraverseC& q, hipStream_t st);
 hipError_t mrtx_launch_traverse_pred(const TraverseC& q, hipStream_t st);
 hipError_t mrtx_launch_traverse_heights(const TraverseC& q, float* out, hipStream_t st);
+hipError_t mrtx_launch_relief(const ReliefC& q, int tile, hipStream_t st);
+hipError_t mrtx_launch_relief_share(const ShareC& q, hipStream_t st);
+size_t mrtx_relief_tile_lds(int th, int tw, int ri, int rj);
 
 struct mrtx_ctx {
     MrtxConfig cfg{};
@@ -1885,6 +1888,137 @@ int mrtx_traverse_heights(mrtx_ctx* c, const MrtxTraverse* t, void* dev_out, flo
     if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
     HIPCHK(c, mrtx_launch_traverse_heights(q, static_cast<float*>(dev_out), c->stream));
     return stage_finish(c, dev_out, host_out, bytes, out, kNoRays);
+}
+
+// ---- Terrain relief: slope, roughness, landing hazard -------------------------------------------
+// The checks that need no DEM: the window's own numbers, the footprint, the node count, the radius
+static int relief_params(mrtx_ctx* c, const MrtxRelief* r) {
+    if (r->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    if (r->rows < 1 || r->cols < 1) return fail(c, MRTX_E_INVALID, "empty window (%d x %d)", r->rows, r->cols);
+    if ((int64_t)r->rows * (int64_t)r->cols > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "a window holds at most 2^31 nodes (got %d x %d)", r->rows, r->cols);
+    if (r->stride < 1) return fail(c, MRTX_E_INVALID, "stride must be >= 1 (got %d)", r->stride);
+    if (r->row0 < 0 || r->col0 < 0) return fail(c, MRTX_E_INVALID, "row0 and col0 must be >= 0");
+    if (r->ri < 1 || r->ri > 32 || r->rj < 1 || r->rj > 32)
+        return fail(c, MRTX_E_INVALID, "the footprint's ri and rj must lie in 1 .. 32 (got %d, %d)", r->ri, r->rj);
+    if (!std::isfinite(r->radius_m) || !(r->radius_m > 0.0) || !std::isfinite((float)r->radius_m))
+        return fail(c, MRTX_E_INVALID, "radius_m must be finite and > 0 (also as a float32)");
+    return MRTX_OK;
+}
+
+// The checks against the DEM's shape (H, W), then the rows x 2 scales (kx, ky) into out2 (each finite and > 0)
+static int relief_window(mrtx_ctx* c, const MrtxRelief* r, int32_t H, int32_t W, double* out2) {
+    if (H < 2 || W < 2) return fail(c, MRTX_E_INVALID, "the DEM must be at least 2 x 2 (got %d x %d)", H, W);
+    if (r->row0 + (int64_t)(r->rows - 1) * r->stride >= H)
+        return fail(c, MRTX_E_INVALID, "the window's last row %lld lies outside the DEM's %d rows",
+                    (long long)(r->row0 + (int64_t)(r->rows - 1) * r->stride), H);
+    if (r->col0 >= W) return fail(c, MRTX_E_INVALID, "col0 = %d lies outside the DEM's %d columns", r->col0, W);
+    if ((int64_t)(r->cols - 1) * r->stride >= W)
+        return fail(c, MRTX_E_INVALID, "the window's columns repeat: (cols - 1) x stride must be < W = %d", W);
+    if ((int64_t)(2 * r->rj + 1) * r->stride > W)
+        return fail(c, MRTX_E_INVALID, "the footprint goes round the circle: (2 rj + 1) x stride must be <= W = %d", W);
+    const double dphi = (double)r->stride * kPiD / (double)H, dlam = (double)r->stride * 2.0 * kPiD / (double)W;
+    for (int32_t i = 0; i < r->rows; i++) {
+        const double row = (double)r->row0 + (double)i * r->stride;
+        const double lat = 0.5 * kPiD - (row + 0.5) * (kPiD / (double)H);
+        const double kx = r->radius_m / (r->radius_m * std::cos(lat) * dlam), ky = r->radius_m / (r->radius_m * dphi);
+        if (!(std::isfinite(kx) && kx > 0.0 && std::isfinite(ky) && ky > 0.0))
+            return fail(c, MRTX_E_INVALID, "row %d: the scales (%g, %g) are not finite and positive", i, kx, ky);
+        if (out2) { out2[2 * (size_t)i] = kx; out2[2 * (size_t)i + 1] = ky; }
+    }
+    return MRTX_OK;
+}
+
+int mrtx_relief_scales(const MrtxRelief* r, int32_t dem_h, int32_t dem_w, double* out2) {
+    if (!r || !out2) return MRTX_E_INVALID;
+    const int rc = relief_params(nullptr, r);
+    return rc != MRTX_OK ? rc : relief_window(nullptr, r, dem_h, dem_w, out2);
+}
+
+// Q(r) = r (r + 1)(2 r + 1) / 3 = the sum of d^2 over d = -r .. r, an exact integer
+static int64_t relief_q(int64_t r) { return r * (r + 1) * (2 * r + 1) / 3; }
+
+int mrtx_relief(mrtx_ctx* c, const MrtxRelief* r, void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!r) return fail(c, MRTX_E_INVALID, "null window");
+    int rc = relief_params(c, r);
+    if (rc != MRTX_OK) return rc;
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 15)) return fail(c, MRTX_E_INVALID, "dev_out must be 16-byte aligned (float4)");
+    // MOONRT_RELIEF_TILE: the nodes a workgroup stages, 16 (16 x 16), 32 (32 x 32) or 64 (64 rows x 16 columns), or 0 = the
+    // kernel that reads every footprint straight from global memory; the same bits in every case
+    int tile = r->ri > 4 ? 32 : 16;
+    if (const char* e = std::getenv("MOONRT_RELIEF_TILE")) {
+        tile = std::atoi(e);
+        if ((tile != 0 || std::strcmp(e, "0") != 0) && tile != 16 && tile != 32 && tile != 64)
+            return fail(c, MRTX_E_INVALID, "MOONRT_RELIEF_TILE must be 0, 16, 32 or 64 (got %s)", e);
+    }
+    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
+    std::vector<double> scale((size_t)r->rows * 2);
+    if ((rc = relief_window(c, r, c->dem_h, c->dem_w, scale.data())) != MRTX_OK) return rc;
+    FrameC f;
+    FrameCold cold;
+    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
+    const bool stats = (c->prm.flags & MRTX_F_COUNT_STATS) != 0;
+    const size_t bytes = (size_t)r->rows * (size_t)r->cols * 16;
+    float* d[1];
+    if ((rc = stage_out(c, dev_out, bytes)) != MRTX_OK || (rc = stage_tables(c, {{scale.data(), 2 * scale.size()}}, d)) != MRTX_OK)
+        return rc;
+    ReliefC q;
+    std::memset(&q, 0, sizeof q);
+    q.dem = f.dem; q.dem_pitch = f.dem_pitch; q.dem_h = c->dem_h; q.dem_w = c->dem_w;
+    q.row0 = r->row0; q.col0 = r->col0; q.rows = r->rows; q.cols = r->cols; q.stride = r->stride; q.ri = r->ri; q.rj = r->rj;
+    q.scale = reinterpret_cast<const double*>(d[0]);
+    const int64_t nj = 2 * r->rj + 1, ni = 2 * r->ri + 1;
+    q.inv_n = 1.0 / (double)(ni * nj);
+    q.inv_xj = 1.0 / (double)(ni * relief_q(r->rj));
+    q.inv_xi = 1.0 / (double)(nj * relief_q(r->ri));
+    q.rm = (float)r->radius_m;
+    q.out = static_cast<float4*>(dev_out);
+    q.fetches = stats ? c->illum_stats + 6 : nullptr;
+    if ((rc = stage_start(c, nullptr, stats)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_relief(q, tile, c->stream));
+    return stage_finish(c, dev_out, host_out, bytes, out, stats ? kShadowRays : kNoRays);
+}
+
+int mrtx_relief_share(mrtx_ctx* c, const MrtxReliefShare* s, const void* dev_relief, const float* host_relief, void* dev_out,
+                      float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!s) return fail(c, MRTX_E_INVALID, "null share");
+    if (s->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    if (s->rows < 1 || s->cols < 1) return fail(c, MRTX_E_INVALID, "empty map (%d x %d)", s->rows, s->cols);
+    if ((int64_t)s->rows * (int64_t)s->cols > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "a map holds at most 2^31 nodes (got %d x %d)", s->rows, s->cols);
+    if (s->Ri < 0 || s->Ri > 1024 || s->Rj < 0 || s->Rj > 1024)
+        return fail(c, MRTX_E_INVALID, "the box's Ri and Rj must lie in 0 .. 1024 (got %d, %d)", s->Ri, s->Rj);
+    if (s->wrap != 0 && s->wrap != 1) return fail(c, MRTX_E_INVALID, "wrap must be 0 or 1 (got %d)", s->wrap);
+    if (s->wrap && s->cols < 3) return fail(c, MRTX_E_INVALID, "a wrapped map needs cols >= 3 (got %d)", s->cols);
+    if (!(s->grade_max >= 0.0) || !(s->rms_max >= 0.0)) return fail(c, MRTX_E_INVALID, "grade_max and rms_max must be >= 0 (+inf: no limit)");
+    if ((dev_relief == nullptr) == (host_relief == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_relief and host_relief");
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    if (dev_relief && (reinterpret_cast<uintptr_t>(dev_relief) & 15)) return fail(c, MRTX_E_INVALID, "dev_relief must be 16-byte aligned (float4)");
+    if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 3)) return fail(c, MRTX_E_INVALID, "dev_out must be 4-byte aligned (float32)");
+    const size_t N = (size_t)s->rows * (size_t)s->cols;
+    if (traverse_overlap(dev_relief, 16 * N, dev_out, 4 * N)) return fail(c, MRTX_E_INVALID, "dev_relief and dev_out must not overlap");
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    int rc;
+    float* d[1] = {nullptr};
+    if ((rc = stage_out(c, dev_out, 4 * N)) != MRTX_OK || (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, 4 * N)) != MRTX_OK ||
+        (rc = stage_tables(c, {{host_relief, host_relief ? 4 * N : 0}}, d)) != MRTX_OK)
+        return rc;
+    ShareC q;
+    std::memset(&q, 0, sizeof q);
+    q.relief = host_relief ? reinterpret_cast<const float4*>(d[0]) : static_cast<const float4*>(dev_relief);
+    q.sat = reinterpret_cast<uint32_t*>(c->trav_buf);
+    q.out = static_cast<float*>(dev_out);
+    q.rows = s->rows; q.cols = s->cols; q.Ri = s->Ri; q.Rj = s->Rj; q.wrap = s->wrap;
+    q.gmax = (float)s->grade_max; q.smax = (float)s->rms_max;
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_relief_share(q, c->stream));
+    if ((rc = stage_finish(c, dev_out, host_out, 4 * N, out, kNoRays)) != MRTX_OK) return rc;
+    if (out) out->launches = 3;
+    return MRTX_OK;
 }
 
 // ---- Regolith surface temperatures ---------------------------------------------------------------

@@ -306,3 +306,29 @@ struct TraverseC {
     const double* src_cost;
     int32_t n_src;
 };
+
+// Terrain relief (mrtx_relief, DESIGN.md sections 3.14 and 4.15; kernels in mrtx_relief.hip).  A window of the DEM's texel
+// lattice as in TraverseC, never wrapped; the footprint of a node is the (2 ri + 1) x (2 rj + 1) lattice nodes around it, read
+// straight from the DEM (rows outside [0, dem_h) make the node NaN, columns wrap modulo dem_w).
+struct ReliefC {
+    const float* dem;           // the context's padded DEM (FrameC::dem's layout), always addressed with 64-bit offsets
+    int64_t dem_pitch;          // w + 4 elements
+    int32_t dem_h, dem_w;
+    int32_t row0, col0, rows, cols, stride, ri, rj;
+    int32_t tiles_x;            // the tile grid's width (the tiled kernels)
+    const double* scale;        // rows x 2 float64 (kx, ky), mrtx_relief_scales
+    double inv_n, inv_xj, inv_xi;   // the plane fit's three reciprocals, formed on the host
+    float rm;                   // (float)radius_m
+    float4* out;                // rows x cols (grade, rms_m, ge, gn)
+    unsigned long long* fetches;    // the counter of the texels the spec reads, or null
+};
+
+// The safe share of a landing ellipse (mrtx_relief_share): integer box sums of the predicate grade <= gmax && rms_m <= smax
+// over a rows x cols relief map, through a summed-area table of uint32 counts.
+struct ShareC {
+    const float4* relief;       // rows x cols (grade, rms_m, ge, gn)
+    uint32_t* sat;              // rows x cols: row prefix sums after share_rows_kernel, the table after share_cols_kernel
+    float* out;                 // rows x cols float32 safe / total
+    int32_t rows, cols, Ri, Rj, wrap;
+    float gmax, smax;
+};

@@ -5,6 +5,7 @@ minus the Tk window.  The PlotOptiX-named surface (set_data / set_displacement /
 lives in moonrtx_amd/tkoptix.py and is a thin adapter over this class.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -713,6 +714,62 @@ class MoonRT:
                                                     C.byref(st)), "mrtx_traverse_heights")
         self._add_stats(stats, st)
         return D
+
+    # ---- Terrain relief: slope, roughness, landing hazard
+    def relief(self, window, footprint_m=None, footprint_nodes=None, radius_m=1737400.0, stats=None):
+        """Slope and roughness under a footprint, per node of a window (row0, col0, rows, cols[, stride]) of the DEM's texel
+        lattice (mrtx_relief).  Exactly one of footprint_nodes = (ri, rj), the footprint's half-heights
+        in lattice nodes (1 .. 32), and footprint_m, its width in metres: then ri follows from the N-S spacing of the rows, and
+        the window is split into row bands over which rj = max(1, round(footprint_m / 2 / L_ew)) is constant, one call per
+        band (a footprint reads the DEM, not the window, so the bands join exactly).  radius_m = the metres of D = 1.
+        Returns a moonrtx_amd.relief.ReliefMap; `stats`, if a dict, receives the summed counters."""
+        from . import relief as rl
+        w = rl.window_dict(window)
+        if w["wrap"]:
+            raise ValueError("a relief window is never wrapped: its footprints read across the seam by themselves")
+        H, W = self._dem_hw()
+        if (footprint_m is None) == (footprint_nodes is None):
+            raise ValueError("give exactly one of footprint_m and footprint_nodes = (ri, rj)")
+        if footprint_nodes is not None:
+            ri, rj = (int(v) for v in footprint_nodes)
+            bands = [(0, w["rows"], rj)]
+        else:
+            ri, bands = rl.footprint_bands(self._lib, w, footprint_m, radius_m, (H, W))
+        table = np.empty((w["rows"], w["cols"], 4), np.float32)
+        for a, n, rj in bands:
+            st = MrtxStats()
+            t = rl.relief_window(w, ri, rj, radius_m, rows=(a, n))
+            self._check(self._lib.mrtx_relief(self._ctx, C.byref(t), None, table[a:].ctypes.data, C.byref(st)), "mrtx_relief")
+            self._add_stats(stats, st)
+        lat, lon, _ = self.traverse_nodes(w)
+        return rl.ReliefMap(table, w, radius_m, ri, bands, w["cols"] * w["stride"] == W, lat, lon)
+
+    def landing_share(self, relief, max_slope_deg, max_rms_m, ellipse_m=None, ellipse_nodes=None, stats=None):
+        """The safe share of a landing ellipse around every node of a ReliefMap (mrtx_relief_share): (rows, cols) float32,
+        the fraction of the map's nodes in the (2 Ri + 1) x (2 Rj + 1) box around the node with slope <= max_slope_deg and
+        roughness <= max_rms_m (NaN nodes are unsafe; nodes outside the map do not count, and the columns join across +-180
+        when the map goes round the circle).  Exactly one of ellipse_nodes = (Ri, Rj), 0 .. 1024, and ellipse_m, the box's
+        width in metres, turned into nodes with the map's N-S spacing and the E-W spacing of its middle row."""
+        from . import relief as rl
+        from .traverse import max_slope_grade
+        w = relief.window
+        if (ellipse_m is None) == (ellipse_nodes is None):
+            raise ValueError("give exactly one of ellipse_m and ellipse_nodes = (Ri, Rj)")
+        if ellipse_nodes is not None:
+            Ri, Rj = (int(v) for v in ellipse_nodes)
+        else:
+            k = rl.scales(self._lib, rl.relief_window(w, radius_m=relief.radius_m), self._dem_hw())
+            half = 0.5 * float(ellipse_m) / relief.radius_m
+            Ri, Rj = int(math.floor(half * k[0, 1] + 0.5)), int(math.floor(half * k[w["rows"] // 2, 0] + 0.5))
+        s = _lib.MrtxReliefShare(w["rows"], w["cols"], Ri, Rj, 1 if relief.closes_circle and w["cols"] >= 3 else 0, 0,
+                                 max_slope_grade(max_slope_deg), float(max_rms_m))
+        table = np.ascontiguousarray(relief.table, np.float32)
+        out = np.empty((w["rows"], w["cols"]), np.float32)
+        st = MrtxStats()
+        self._check(self._lib.mrtx_relief_share(self._ctx, C.byref(s), None, table.ctypes.data, None, out.ctypes.data,
+                                                C.byref(st)), "mrtx_relief_share")
+        self._add_stats(stats, st)
+        return out
 
     @staticmethod
     def _add_stats(acc, st, extra=None):

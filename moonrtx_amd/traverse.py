@@ -153,6 +153,32 @@ def penalty_from_temperature(t_max, limit_k, soft_k=None):
     return _clamp(p)
 
 
+def _grade_and(relief, field):
+    """(grade-like array) of a ReliefMap's field or of a plain array."""
+    return np.asarray(getattr(relief, field) if hasattr(relief, field) else relief, np.float64)
+
+
+def penalty_from_slope(relief, max_slope_deg, weight=4.0):
+    """Keep off steep ground at the scale of the vehicle: +inf where the footprint's grade (MoonRT.relief's `grade`, or a
+    plain array of grades) exceeds the limit or is NaN, else P = 1 + weight grade / tan(max_slope_deg), rising from 1 on
+    level ground to 1 + weight at the limit."""
+    g = _grade_and(relief, "grade")
+    gmax = max_slope_grade(max_slope_deg)
+    p = 1.0 + float(weight) * (g / gmax)
+    return _clamp(np.where(g > gmax, np.inf, p))
+
+
+def penalty_from_roughness(relief, max_rms_m, weight=4.0):
+    """Keep off rough ground: +inf where the footprint's roughness (MoonRT.relief's `rms_m`, or a plain array, metres) exceeds
+    max_rms_m or is NaN, else P = 1 + weight rms_m / max_rms_m."""
+    r = _grade_and(relief, "rms_m")
+    m = float(max_rms_m)
+    if not m > 0.0:
+        raise ValueError("max_rms_m must be > 0")
+    p = 1.0 + float(weight) * (r / m)
+    return _clamp(np.where(r > m, np.inf, p))
+
+
 def _clamp(p):
     p = np.asarray(p, np.float64)
     out = np.where(np.isinf(p), np.inf, np.clip(p, P_MIN, P_MAX)).astype(np.float32)

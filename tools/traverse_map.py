@@ -10,7 +10,9 @@ texel lattice from one or more starts, and the route to one target.
 --window ROW0 COL0 ROWS COLS [STRIDE [WRAP]] is a block of DEM texels (rows from the north, columns from -180), every STRIDE-th
 one; WRAP 1 (with COLS x STRIDE = the DEM's width) joins its last column to its first, for caps around a pole.  Starts and the
 target snap to their nearest node.  --sight OBS_LAT OBS_LON OBS_H closes every node that does not see an observer raised
-OBS_H metres (a viewshed over the same nodes).  The .npy holds the (rows, cols) float64 costs (+inf: unreachable); the CSV the
+OBS_H metres (a viewshed over the same nodes).  --footprint M closes every node whose slope over a vehicle footprint M metres
+across (MoonRT.relief) exceeds --max-slope and makes steeper ground dearer; with it, --max-rms M does the same for the
+roughness about the footprint's plane.  The .npy holds the (rows, cols) float64 costs (+inf: unreachable); the CSV the
 route, one node per line.  Synthetic LOLA-like DEM unless --elevation-file is given; heights are metres on the DEM's own
 radius (1737.4 km x its radius_scale)."""
 import argparse, os, sys
@@ -30,6 +32,9 @@ ap.add_argument("--climb", type=float, default=8.0, help="metres of effort per m
 ap.add_argument("--descent", type=float, default=0.0, help="metres of effort per metre descended")
 ap.add_argument("--sight", type=float, nargs=3, default=None, metavar=("OBS_LAT", "OBS_LON", "OBS_H"))
 ap.add_argument("--target-height", type=float, default=2.0, help="the rover's antenna height for --sight, metres")
+ap.add_argument("--footprint", type=float, default=None, metavar="M",
+                help="vehicle footprint, metres: slope (and --max-rms) limits at that scale")
+ap.add_argument("--max-rms", type=float, default=None, metavar="M", help="roughness limit over --footprint, metres")
 ap.add_argument("--downscale", type=int, default=2)
 ap.add_argument("--dem-size", type=int, nargs=2, default=None, help="synthetic DEM (h, w); default 46080/downscale x 92160/downscale")
 ap.add_argument("--elevation-file", default=None)
@@ -40,6 +45,8 @@ if not 4 <= len(a.window) <= 6:
     ap.error("--window takes ROW0 COL0 ROWS COLS [STRIDE [WRAP]]")
 if a.route and a.to is None:
     ap.error("--route needs --to")
+if a.max_rms is not None and a.footprint is None:
+    ap.error("--max-rms needs --footprint")
 
 if a.elevation_file:
     from moonrtx_amd.ingest import load_elevation_data
@@ -66,6 +73,13 @@ if a.sight is not None:
     view = rt.viewshed(tuple(a.sight), target_height_m=a.target_height, radius_m=radius_m, **grid)
     penalty = tv.penalty_from_viewshed(view)
     print(f"line of sight to {tuple(a.sight)}: {float(np.isfinite(penalty).mean()):.4f} of the nodes stay open")
+if a.footprint is not None:
+    relief = rt.relief(window[:5], footprint_m=a.footprint, radius_m=radius_m)
+    hazard = tv.penalty_from_slope(relief, a.max_slope)
+    if a.max_rms is not None:
+        hazard = np.maximum(hazard, tv.penalty_from_roughness(relief, a.max_rms))
+    penalty = hazard if penalty is None else np.where(np.isinf(penalty), penalty, hazard)
+    print(f"{a.footprint:g} m footprint: {float(np.isfinite(penalty).mean()):.4f} of the nodes stay open")
 st = {}
 f = rt.traverse(window, np.array(a.start, np.float64), penalty=penalty, max_slope_deg=a.max_slope, climb_cost=a.climb,
                 descent_cost=a.descent, radius_m=radius_m, stats=st)
