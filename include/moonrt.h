@@ -512,6 +512,33 @@ typedef struct MrtxReliefShare {
 int mrtx_relief_share(mrtx_ctx* ctx, const MrtxReliefShare* s, const void* dev_relief, const float* host_relief, void* dev_out,
                       float* host_out, MrtxStats* out);
 
+/* ---- Mast-height horizons and joint windows (additive to ABI 7) ----------------------------------
+ * mrtx_horizon_points from a raised origin: point p marches from P = fmaf(hs, u, o), hs = (float)(height_m[p] / radius_m * R),
+ * the raised end of mrtx_sight_points (so a mast top is one point for the horizon and for the line of sight).  height_m: n
+ * doubles, each finite in [0, 1e4] metres; radius_m > 0 the metres of D = 1.  Azimuths, bisection and probe directions are
+ * mrtx_horizon_points'; a point with hs == 0 is that call's bit for bit (output and counters), a point with hs > 0 marches
+ * every probe (no n . d > 0 test: a mast top sees below its facet's plane, and the horizon's dip is negative), from where the
+ * probe enters the bounding sphere when P lies outside it (clear when it misses the sphere).  Output, limits and state as
+ * mrtx_horizon_points: n x n_az float32 into exactly one of dev_out and host_out.  out may be NULL. */
+int mrtx_horizon_raised(mrtx_ctx* ctx, const double* latlon_deg, const double* height_m, double radius_m, int32_t n,
+                        int32_t n_az, int32_t n_bis, void* dev_out, float* host_out, MrtxStats* out);
+/* Two bodies against one set of horizons, reduced per point: f_a and f_b are, bit for bit,
+ * mrtx_horizon_sun FULL's fractions for the epoch tables epochs_a and epochs_b (m epochs each, the same dates); per epoch
+ * ok_a = f_a >= (float)min_a, ok_b = f_b >= (float)min_b, both = ok_a && ok_b.  min_a, min_b in (0, 1]; m <= 2^24;
+ * horizons from exactly one of dev_horizon and host_horizon.  Output: n x 8 float32, point-major, into exactly one of dev_out
+ * (16-byte aligned) and host_out:
+ *   [0] share of epochs with ok_a        [1] longest run of consecutive epochs with !ok_a
+ *   [2] share with ok_b                  [3] longest run with !ok_b
+ *   [4] share with both                  [5] longest run with both
+ *   [6] index of the first epoch of that run (the earliest such run; -1 if [5] is 0)
+ *   [7] longest run with !both
+ * Shares are (float)(count / (double)m); runs and the index are exact float counts.  No n x m buffer is allocated.  Needs a
+ * DEM, but neither a light nor a Moon frame; leaves the light, Moon frame and render state as they were.  out: launches,
+ * kernel_ms. */
+int mrtx_horizon_windows(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t n_az, const void* dev_horizon,
+                         const float* host_horizon, const MrtxIllumEpoch* epochs_a, const MrtxIllumEpoch* epochs_b, int32_t m,
+                         double min_a, double min_b, void* dev_out, float* host_out, MrtxStats* out);
+
 /* Math conformance probe (ABI 7): the kernels' domain-restricted reciprocal (v_rcp_f32 + Newton steps) and square root (v_sqrt_f32 + a
  * +-1 ulp residual fix) against the compiler's IEEE expansions of 1.0f / x and sqrtf(x), ON THE DEVICE, for the n float bit patterns
  * from lo_bits on: which = 0 one Newton step, 1 two steps (what the kernels use), 2 the square root.  mismatches = how many differ;

@@ -159,6 +159,10 @@ SIGNATURES = {
     "mrtx_horizon_points": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_horizon_sun": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP,
                                    C.POINTER(MrtxStats)]),
+    "mrtx_horizon_raised": (C.c_int, [_VP, _VP, _VP, C.c_double, C.c_int32, C.c_int32, C.c_int32, _VP, _VP,
+                                      C.POINTER(MrtxStats)]),
+    "mrtx_horizon_windows": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, C.c_double, C.c_double,
+                                       _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_sight_grid": (C.c_int, [_VP, C.POINTER(MrtxSightGrid), _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_sight_points": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _VP,
                                     _VP, C.POINTER(MrtxStats)]),

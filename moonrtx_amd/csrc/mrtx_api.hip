@@ -60,6 +60,8 @@ hipError_t mrtx_launch_illum(const FrameC& f, IllumC g, bool stats, hipStream_t 
 hipError_t mrtx_launch_illum_series(const FrameC& f, IllumSeriesC q, bool stats, hipStream_t st);
 hipError_t mrtx_launch_horizon(const FrameC& f, HorizonC h, bool stats, hipStream_t st);
 hipError_t mrtx_launch_horizon_sun(const FrameC& f, HorizonSunC q, hipStream_t st);
+hipError_t mrtx_launch_horizon_raised(const FrameC& f, HorizonRaisedC q, bool stats, hipStream_t st);
+hipError_t mrtx_launch_horizon_windows(const FrameC& f, HorizonWindowsC q, hipStream_t st);
 hipError_t mrtx_launch_sight(const FrameC& f, SightC q, bool stats, hipStream_t st);
 hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, bool ext, hipStream_t st);
 hipError_t mrtx_launch_view_hits(const FrameC& f, const ViewC& q, bool stats, hipStream_t st);
@@ -1581,6 +1583,88 @@ int mrtx_horizon_sun(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az,
     q.out = (float*)dev_out; q.az_log2 = log2_of(n_az); q.m = m; q.mode = mode;
     if ((rc = stage_start(c, &cold, false)) != MRTX_OK) return rc;
     HIPCHK(c, mrtx_launch_horizon_sun(f, q, c->stream));
+    return stage_finish(c, dev_out, host_out, out_bytes, out, kNoRays);
+}
+
+// ---- Mast-height horizons and joint windows --------------------------------------------------------
+int mrtx_horizon_raised(mrtx_ctx* c, const double* latlon, const double* height_m, double radius_m, int32_t n, int32_t n_az,
+                        int32_t n_bis, void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!latlon || !height_m) return fail(c, MRTX_E_INVALID, "null point list or height list");
+    if (n < 1) return fail(c, MRTX_E_INVALID, "n must be >= 1 (got %d)", n);
+    if (!horizon_az_ok(n_az)) return fail(c, MRTX_E_INVALID, "n_az must be 4, 8, ..., 4096 (got %d)", n_az);
+    if (n_bis < 1 || n_bis > 24) return fail(c, MRTX_E_INVALID, "n_bis must lie in [1, 24] (got %d)", n_bis);
+    if (!std::isfinite(radius_m) || !(radius_m > 0.0)) return fail(c, MRTX_E_INVALID, "radius_m must be finite and > 0");
+    if ((int64_t)n * (int64_t)n_az > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "a call holds at most 2^31 outputs: split the points into more calls");
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    std::vector<float> hs((size_t)n);
+    for (int32_t i = 0; i < n; i++) {
+        const double h = height_m[i];
+        if (!std::isfinite(h) || h < 0.0 || h > 1e4) return fail(c, MRTX_E_INVALID, "point %d: height must lie in [0, 1e4] m", i);
+        hs[(size_t)i] = (float)(h / radius_m * c->radius);
+        if (!std::isfinite(hs[(size_t)i])) return fail(c, MRTX_E_INVALID, "point %d: height / radius_m is out of range", i);
+    }
+    std::vector<float> rtab, ctab;
+    int rc = point_tables(c, latlon, n, rtab, ctab);
+    if (rc != MRTX_OK) return rc;
+    FrameC f;
+    FrameCold cold;
+    if ((rc = stage_frame(c, f, cold, true)) != MRTX_OK) return rc;
+    const bool stats = (c->prm.flags & MRTX_F_COUNT_STATS) != 0;
+    const size_t out_bytes = (size_t)n * (size_t)n_az * sizeof(float);
+    float* d[3];
+    if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK || (rc = stage_tables(c, {rtab, ctab, hs}, d)) != MRTX_OK) return rc;
+    HorizonRaisedC q;
+    std::memset(&q, 0, sizeof q);
+    q.h.g.rtab = d[0]; q.h.g.ctab = d[1];
+    q.h.g.rows = n; q.h.g.cols = n; q.h.g.points = 1;
+    q.h.out = (float*)dev_out; q.h.az_log2 = log2_of(n_az); q.h.n_bis = n_bis;
+    q.hs = d[2];
+    if ((rc = stage_start(c, &cold, stats)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_horizon_raised(f, q, stats, c->stream));
+    return stage_finish(c, dev_out, host_out, out_bytes, out, stats ? kShadowRays : kNoRays);
+}
+
+int mrtx_horizon_windows(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon,
+                         const float* host_horizon, const MrtxIllumEpoch* epochs_a, const MrtxIllumEpoch* epochs_b, int32_t m,
+                         double min_a, double min_b, void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!latlon || !epochs_a || !epochs_b) return fail(c, MRTX_E_INVALID, "null point list or epoch table");
+    if (n < 1 || m < 1) return fail(c, MRTX_E_INVALID, "n and m must be >= 1 (got %d, %d)", n, m);
+    // the runs and the start index are float counts, exact up to 2^24
+    if (m > (1 << 24)) return fail(c, MRTX_E_INVALID, "at most 2^24 epochs per call (got %d)", m);
+    if (!horizon_az_ok(n_az)) return fail(c, MRTX_E_INVALID, "n_az must be 4, 8, ..., 4096 (got %d)", n_az);
+    if (!(min_a > 0.0 && min_a <= 1.0) || !(min_b > 0.0 && min_b <= 1.0))
+        return fail(c, MRTX_E_INVALID, "min_a and min_b must lie in (0, 1]");
+    if (!((float)min_a > 0.0f) || !((float)min_b > 0.0f))
+        return fail(c, MRTX_E_INVALID, "min_a and min_b must be positive as float32");
+    int rc = horizon_args(c, dev_horizon, host_horizon, n, n_az, dev_out, host_out);
+    if (rc != MRTX_OK) return rc;
+    if (dev_out && ((uintptr_t)dev_out & 15)) return fail(c, MRTX_E_INVALID, "dev_out must be 16-byte aligned");
+    if ((rc = horizon_entries(c, host_horizon, n, n_az)) != MRTX_OK) return rc;
+    std::vector<float> rtab, ctab, lights_a, lights_b;
+    if ((rc = point_tables(c, latlon, n, rtab, ctab)) != MRTX_OK) return rc;
+    if ((rc = epoch_lights(c, epochs_a, m, lights_a)) != MRTX_OK) return rc;
+    if ((rc = epoch_lights(c, epochs_b, m, lights_b)) != MRTX_OK) return rc;
+    FrameC f;
+    FrameCold cold;
+    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
+    const size_t nh = host_horizon ? (size_t)n * (size_t)n_az : 0;
+    const size_t out_bytes = (size_t)n * 32;
+    float* d[5];
+    if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK ||
+        (rc = stage_tables(c, {rtab, ctab, lights_a, lights_b, {host_horizon, nh}}, d)) != MRTX_OK)
+        return rc;
+    HorizonWindowsC q;
+    std::memset(&q, 0, sizeof q);
+    q.g.rtab = d[0]; q.g.ctab = d[1];
+    q.g.rows = n; q.g.cols = n; q.g.points = 1;
+    q.lights_a = d[2]; q.lights_b = d[3];
+    q.horizon = host_horizon ? d[4] : (const float*)dev_horizon;
+    q.out = (float*)dev_out; q.min_a = (float)min_a; q.min_b = (float)min_b; q.az_log2 = log2_of(n_az); q.m = m;
+    if ((rc = stage_start(c, &cold, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_horizon_windows(f, q, c->stream));
     return stage_finish(c, dev_out, host_out, out_bytes, out, kNoRays);
 }
 

@@ -215,6 +215,26 @@ struct HorizonSunC {
     int32_t mode;           // 0 FULL, 1 SUMMARY
 };
 
+// Raised horizons (mrtx_horizon_raised): HorizonC and per point the raise of its march origin.  A
+// struct of its own, so that horizon_kernel's arguments stay as they were.
+struct HorizonRaisedC {
+    HorizonC h;
+    const float* hs;        // per point: (float)(height_m / radius_m * R), >= 0
+};
+
+// Joint windows of two bodies against one set of horizons (mrtx_horizon_windows): HorizonSunC's point
+// list and horizons, two epoch-light tables of m epochs each and the two thresholds.  One wave per point.
+struct HorizonWindowsC {
+    IllumC g;               // the point list (g.rows points), as in HorizonC
+    const float* horizon;   // n_points x n_az float32 elevations (degrees)
+    const float* lights_a;  // 8 floats per epoch, as IllumSeriesC's
+    const float* lights_b;
+    float* out;             // n_points x 8 float32 (two float4 per point)
+    float min_a, min_b;     // ok = f >= min
+    int32_t az_log2;        // log2(n_az)
+    int32_t m;              // epochs
+};
+
 // Regolith surface temperatures (mrtx_thermal): per point the absorbed flux of every epoch from its
 // vertex, its horizon row and the epoch's light constants, and a 1D heat-conduction column stepped through the epochs.  One
 // lane per point; the column lives in registers, so the node count is capped at compile time.  The layer tables are shared by

@@ -2166,8 +2166,13 @@ __global__ void __launch_bounds__(64) illum_series_kernel(const FrameC f, const 
 // escapes (light_sample's origin, illum_sample's march).  Lane = (point, azimuth), point-major: one wave = 64 consecutive
 // azimuths of one point (64 / n_az points when n_az < 64), so the 64 lanes leave one origin.  Steep probes end after a few
 // steps; the last probes graze the horizon and run the length of the bounding shell.
-template <bool STATS, bool WIDE>
-__global__ void __launch_bounds__(64) horizon_kernel(const FrameC f, const HorizonC h) {
+// RAISED (DESIGN.md sections 3.15 and 4.16, horizon_raised_kernel): point pt marches from sight_end(p, hs[pt]).  hs == 0 is
+// the plain probe, bit for bit; hs > 0 drops the facet test (a mast top sees below its facet's plane) and, when the raised
+// origin lies outside the bounding sphere, marches from where the probe enters it, as sight_probe does (clear when it heads
+// away from the sphere or misses it).  RAISED = false compiles to the kernel as it was.
+__device__ __forceinline__ void sight_end(const PointFrame& p, float hs, float& Pa, float& Pb, float& Pc);
+template <bool STATS, bool WIDE, bool RAISED>
+__device__ __forceinline__ void horizon_body(const FrameC& f, const HorizonC& h, const float* hs_tab) {
     const int lane = threadIdx.x;
     const int64_t gid = (int64_t)blockIdx.x * 64 + lane;
     const int n_az = 1 << h.az_log2;
@@ -2182,6 +2187,13 @@ __global__ void __launch_bounds__(64) horizon_kernel(const FrameC f, const Horiz
         float cp, sp;
         sincos_turn((float)az * (1.0f / (float)n_az), cp, sp);     // a / n_az: exact
         const float ha = fmaf(cp, p.Na, sp * p.ct.y), hb = fmaf(cp, p.Nb, -(sp * p.ct.x)), hc = cp * p.Nc;
+        // the march origin: the lifted origin, or the mast top above it; q0 > R^2: that one lies outside the bounding sphere
+        const float hs = RAISED ? hs_tab[pt] : 0.0f;
+        const bool up = RAISED && hs > 0.0f;
+        float Oa = p.oa, Ob = p.ob, Oc = p.oc;
+        if (up) sight_end(p, hs, Oa, Ob, Oc);
+        const float q0 = RAISED ? fmaf(Oc, Oc, fmaf(Ob, Ob, Oa * Oa)) : 0.0f;
+        const bool outside = up && q0 > f.R2f;
         float lo = 0.0f, hi = 1.0f;
         for (int i = 0; i < h.n_bis; i++) {
             const float mid = 0.5f * (lo + hi);                     // dyadic, at most 24 fraction bits: exact
@@ -2189,11 +2201,26 @@ __global__ void __launch_bounds__(64) horizon_kernel(const FrameC f, const Horiz
             sincos_turn((mid - 0.5f) * 0.5f, ce, se);               // e in (-1/4, 1/4) turn: quadrants -1 and 0
             const float da = fmaf(se, p.ua, ce * ha), db = fmaf(se, p.ub, ce * hb), dc = fmaf(se, p.uc, ce * hc);
             bool clear = false;
-            if (fmaf(v.nc, dc, fmaf(v.nb, db, v.na * da)) > 0.0f) {
+            if (up || fmaf(v.nc, dc, fmaf(v.nb, db, v.na * da)) > 0.0f) {
                 if (STATS) cnt[ST_SHADOW]++;
-                Seg ssg;
-                float sk_occ;
-                clear = !march<WIDE, false, STATS, MRTX_STEP_BATCH, 2>(f, p.oa, p.ob, p.oc, da, db, dc, 0.0f, ssg, sk_occ, cnt);
+                float oa = Oa, ob = Ob, oc = Oc;
+                bool meets = true;
+                if (outside) {
+                    const float b = fmaf(Oc, dc, fmaf(Ob, db, Oa * da));
+                    const float c = q0 - f.R2f;
+                    const float disc = fmaf(b, b, -c);
+                    meets = b < 0.0f && disc >= 0.0f;              // heads for the sphere and meets it
+                    if (meets) {
+                        const float s_in = c / (sqrtf(disc) - b);   // the nearer root of s^2 + 2 b s + c, without cancellation
+                        oa = fmaf(s_in, da, Oa); ob = fmaf(s_in, db, Ob); oc = fmaf(s_in, dc, Oc);
+                    }
+                }
+                clear = true;
+                if (meets) {
+                    Seg ssg;
+                    float sk_occ;
+                    clear = !march<WIDE, false, STATS, MRTX_STEP_BATCH, 2>(f, oa, ob, oc, da, db, dc, 0.0f, ssg, sk_occ, cnt);
+                }
             }
             hi = clear ? mid : hi;
             lo = clear ? lo : mid;
@@ -2201,6 +2228,14 @@ __global__ void __launch_bounds__(64) horizon_kernel(const FrameC f, const Horiz
         h.out[gid] = (hi - 0.5f) * 180.0f;
     }
     stage_flush<STATS>(f, cnt, ST_SHADOW, lane);
+}
+template <bool STATS, bool WIDE>
+__global__ void __launch_bounds__(64) horizon_kernel(const FrameC f, const HorizonC h) {
+    horizon_body<STATS, WIDE, false>(f, h, nullptr);
+}
+template <bool STATS, bool WIDE>
+__global__ void __launch_bounds__(64) horizon_raised_kernel(const FrameC f, const HorizonRaisedC q) {
+    horizon_body<STATS, WIDE, true>(f, q.h, q.hs);
 }
 
 // The visible share of the light's disc above a point's horizon, from the epoch's (Lb.xyz, rL2) l0,
@@ -2293,6 +2328,76 @@ __global__ void __launch_bounds__(64) horizon_sun_kernel(const FrameC f, const H
             reinterpret_cast<float4*>(q.out)[pt] =
                 make_float4((float)(sum * inv_m), (float)((double)n_lit * inv_m), (float)((double)n_full * inv_m), (float)best);
         }
+    }
+}
+
+// Joint windows of two bodies against one set of horizons (DESIGN.md sections 3.15 and 4.16): horizon_sun_kernel's walk -- one
+// wave per point, the epochs 64 at a time, the vertex and frame once, the horizon row in L1 -- with disc_fraction evaluated for
+// both epoch tables and three masks (ok_a, ok_b, both) reduced in the wave: their counts from the ballots' popcounts, and four
+// runs (!ok_a, !ok_b, both, !both) by horizon_sun_kernel's scheme, the run that reaches a chunk's end carried into the next.
+// Everything carried is wave-uniform; the first epoch of the longest `both` run is kept with it (a later run of the same length
+// does not replace it).  No atomics, no LDS; lane 0 stores the point's two float4.
+// the run of set epochs that ends at this lane's epoch (0 if it is not set): back to the nearest unset epoch of the chunk, or
+// through the chunk's start into the run `cur` carried in.  set holds no lane past the last epoch.
+__device__ __forceinline__ int run_ending_here(unsigned long long set, int lane, bool in, int cur) {
+    const unsigned long long below = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
+    const unsigned long long brk = ~set & below;
+    const int run = brk ? lane - (63 - __clzll((long long)brk)) : lane + 1 + cur;
+    return in ? run : 0;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) v = max(v, __shfl_xor(v, s, 64));
+    return v;
+}
+template <bool WIDE>
+__global__ void __launch_bounds__(64) horizon_windows_kernel(const FrameC f, const HorizonWindowsC q) {
+    const int lane = threadIdx.x;
+    const int pt = (int)blockIdx.x;
+    const int n_az = 1 << q.az_log2;
+    Vertex v;
+    (void)illum_vertex<false, WIDE>(f, q.g, pt, pt, v, nullptr);
+    const PointFrame p = point_frame(f, q.g, pt, pt, v);
+    const float* const hz = q.horizon + ((int64_t)pt << q.az_log2);
+    const float4* const la4 = reinterpret_cast<const float4*>(q.lights_a);
+    const float4* const lb4 = reinterpret_cast<const float4*>(q.lights_b);
+    uint32_t n_a = 0, n_b = 0, n_ab = 0;                    // wave-uniform counts
+    int cur_a = 0, cur_b = 0, cur_ab = 0, cur_no = 0;       // the runs reaching the previous chunk's end
+    int best_a = 0, best_b = 0, best_ab = 0, best_no = 0, first_ab = -1;
+    for (int k0 = 0; k0 < q.m; k0 += 64) {
+        const int k = k0 + lane;
+        const bool in = k < q.m;
+        bool ok_a = false, ok_b = false;
+        if (in) {
+            float la, lb, lc;
+            ok_a = disc_fraction(la4[2 * (int64_t)k], p, hz, n_az, la, lb, lc) >= q.min_a;
+            ok_b = disc_fraction(lb4[2 * (int64_t)k], p, hz, n_az, la, lb, lc) >= q.min_b;
+        }
+        const unsigned long long ma = __ballot(ok_a), mb = __ballot(ok_b), valid = __ballot(in);
+        const unsigned long long mab = ma & mb;
+        n_a += (uint32_t)__popcll(ma); n_b += (uint32_t)__popcll(mb); n_ab += (uint32_t)__popcll(mab);
+        const int last = min(64, q.m - k0) - 1;
+        int ra = run_ending_here(valid & ~ma, lane, in, cur_a);
+        int rb = run_ending_here(valid & ~mb, lane, in, cur_b);
+        int rab = run_ending_here(mab, lane, in, cur_ab);
+        int rno = run_ending_here(valid & ~mab, lane, in, cur_no);
+        cur_a = __shfl(ra, last, 64); cur_b = __shfl(rb, last, 64);
+        cur_ab = __shfl(rab, last, 64); cur_no = __shfl(rno, last, 64);
+        best_a = max(best_a, wave_max(ra));
+        best_b = max(best_b, wave_max(rb));
+        best_no = max(best_no, wave_max(rno));
+        const int mx = wave_max(rab);
+        if (mx > best_ab) {                                 // wave-uniform; the lowest lane that ends a run of mx: the earliest
+            const unsigned long long at = __ballot(rab == mx);
+            best_ab = mx;
+            first_ab = k0 + (int)__builtin_ctzll(at) - mx + 1;
+        }
+    }
+    if (lane == 0) {
+        const double md = (double)q.m;                      // shares are (float)(count / (double)m): a division, as specified
+        float4* const o = reinterpret_cast<float4*>(q.out) + 2 * (int64_t)pt;
+        o[0] = make_float4((float)((double)n_a / md), (float)best_a, (float)((double)n_b / md), (float)best_b);
+        o[1] = make_float4((float)((double)n_ab / md), (float)best_ab, (float)first_ab, (float)best_no);
     }
 }
 
@@ -3992,6 +4097,31 @@ hipError_t mrtx_launch_horizon_sun(const FrameC& f, HorizonSunC q, hipStream_t s
     const dim3 grid((unsigned)q.g.rows), block(64);
     if (f.dem_wide) hipLaunchKernelGGL((mrtx::horizon_sun_kernel<true>), grid, block, 0, st, f, q);
     else hipLaunchKernelGGL((mrtx::horizon_sun_kernel<false>), grid, block, 0, st, f, q);
+    return hipGetLastError();
+}
+
+// Raised horizons (horizon_raised_kernel): mrtx_launch_horizon's lane mapping, with the per-point raise table q.hs.
+hipError_t mrtx_launch_horizon_raised(const FrameC& f, HorizonRaisedC q, bool stats, hipStream_t st) {
+    const HorizonC& h = q.h;
+    if (h.g.rows < 1 || h.az_log2 < 2 || h.az_log2 > 12 || h.n_bis < 1 || h.n_bis > 24 || !h.g.points || !h.out || !q.hs)
+        return hipErrorInvalidValue;
+    const uint64_t lanes = (uint64_t)h.g.rows << h.az_log2;
+    if (lanes > (1ull << 31)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((lanes + 63) / 64)), block(64);
+    pick2(stats, f.dem_wide != 0, [&](auto s, auto w) {
+        hipLaunchKernelGGL((mrtx::horizon_raised_kernel<s(), w()>), grid, block, 0, st, f, q);
+    });
+    return hipGetLastError();
+}
+
+// Joint windows (horizon_windows_kernel): one wave per point.
+hipError_t mrtx_launch_horizon_windows(const FrameC& f, HorizonWindowsC q, hipStream_t st) {
+    if (q.g.rows < 1 || q.az_log2 < 2 || q.az_log2 > 12 || q.m < 1 || q.m > (1 << 24) || !q.g.points || !q.horizon ||
+        !q.lights_a || !q.lights_b || !q.out)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)q.g.rows), block(64);
+    if (f.dem_wide) hipLaunchKernelGGL((mrtx::horizon_windows_kernel<true>), grid, block, 0, st, f, q);
+    else hipLaunchKernelGGL((mrtx::horizon_windows_kernel<false>), grid, block, 0, st, f, q);
     return hipGetLastError();
 }
 

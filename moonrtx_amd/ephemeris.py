@@ -521,3 +521,51 @@ def sun_epochs(times, observer=None):
     of calculate_moon_ephemeris -> scene_from_ephemeris, the values tools/illumination_map.py sets per date."""
     rows = [epoch_of_scene(scene_from_ephemeris(calculate_moon_ephemeris(t, False, observer), 16, 16)) for t in times]
     return np.array(rows, np.float64).reshape(-1, 14)
+
+
+EARTH_RADIUS_KM = 6378.137          # the equatorial radius: the disc whose visible share mrtx_horizon_sun returns
+
+
+def _moon_rows(u, v):
+    """The Moon frame's rows (east-90, longitude-0, north) from a row's u and v, as the library forms them (moon_rows)."""
+    ez = np.asarray(u, float) / np.linalg.norm(u)
+    v0 = np.asarray(v, float) - float(np.dot(v, ez)) * ez
+    v0 = v0 / np.linalg.norm(v0)
+    return np.stack([np.cross(ez, v0), v0, ez])
+
+
+def earth_distance_km(t):
+    """The Earth-Moon centre distance, km, of the series calculate_moon_ephemeris uses, at a timezone-aware datetime."""
+    if t.tzinfo is None:
+        raise ValueError("times must be timezone-aware")
+    dt_utc = t.astimezone(timezone.utc)
+    jde = julian_day(dt_utc) + tt_minus_utc(dt_utc) / 86400.0
+    return float(moon_position((jde - 2451545.0) / 36525.0)[2])
+
+
+def sun_earth_epochs(times, observer=None):
+    """(sun, earth): sun_epochs(times, observer) and earth_epochs(times, observer) from one pass over the dates."""
+    from .scene import MOON_RADIUS_KM
+    sun = np.empty((len(times), 14), np.float64)
+    earth = np.empty((len(times), 14), np.float64)
+    for i, t in enumerate(times):
+        e = calculate_moon_ephemeris(t, False, observer)
+        s = scene_from_ephemeris(e, 16, 16)
+        sun[i] = earth[i] = epoch_of_scene(s)
+        scale = float(s.radius) / MOON_RADIUS_KM
+        b, l = math.radians(e.libr_lat_geo), math.radians(e.libr_long_geo)
+        d_body = np.array([math.cos(b) * math.sin(l), math.cos(b) * math.cos(l), math.sin(b)])
+        M = _moon_rows(earth[i, 8:11], earth[i, 11:14])
+        earth[i, 0:3] = earth[i, 5:8] + (earth_distance_km(t) * scale) * (M.T @ d_body)
+        earth[i, 3] = EARTH_RADIUS_KM * scale
+        earth[i, 4] = 0.0
+    return sun, earth
+
+
+def earth_epochs(times, observer=None):
+    """(m, 14) float64 epochs whose "light" is the Earth: the Moon frame of sun_epochs for the same
+    date, so that one set of horizons serves both tables; the Earth's centre placed from the Moon's centre toward the
+    geocentric sub-Earth point (libr_lat_geo, libr_long_geo) at the ephemeris' Earth-Moon distance, in scene units;
+    light_radius = the Earth's equatorial radius in scene units, light_radiance = 0.  MoonRT.horizon_sun then returns the
+    visible share of the Earth's disc from each point, the parallax of the surface point included."""
+    return sun_earth_epochs(times, observer)[1]

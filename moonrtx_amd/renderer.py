@@ -361,15 +361,26 @@ class MoonRT:
             raise ValueError(f"n_az must be 4, 8, ..., 4096 (got {n_az})")
         return np.arange(n, dtype=np.float64) * (360.0 / n)
 
-    def horizon(self, lat_deg, lon_deg, n_az=256, n_bis=14, stats=None, out=None, chunk_bytes=256 << 20):
+    def horizon(self, lat_deg, lon_deg, n_az=256, n_bis=14, stats=None, out=None, chunk_bytes=256 << 20, height_m=None,
+                radius_m=1737400.0):
         """(N, n_az) float32: the terrain's horizon elevation, degrees, seen from N points (degrees) at horizon_azimuths(n_az),
         found by n_bis bisection probes that are each an illumination sample's visibility decision.
         out = a DeviceBuffer of at least N * n_az * 4 bytes: the horizons are written there (point-major) and `out` is
         returned.  Calls hold at most chunk_bytes of output each (points split between calls); `stats`, if a dict, receives
-        the summed counters."""
+        the summed counters.  height_m (one value, or one per point, metres in [0, 1e4]): the horizon seen from a mast top that
+        high above each point, line_of_sight's raised end (section 3.15; radius_m = the metres of D = 1); a height of 0 gives
+        the ground's horizon bit for bit, None makes the ground-only call."""
         la, lo = self._points(lat_deg, lon_deg)
         n_az = int(n_az)
         pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        hts = None
+        if height_m is not None:
+            hts = np.asarray(height_m, np.float64)
+            if hts.ndim == 0:
+                hts = np.full(la.size, float(hts))
+            hts = np.ascontiguousarray(hts.ravel())
+            if hts.size != la.size:
+                raise ValueError("height_m must be one height or one per point")
         if out is not None and out.nbytes < la.size * max(n_az, 0) * 4:
             raise ValueError("the device buffer is smaller than N x n_az float32")
         host = np.empty((la.size, max(n_az, 0)), np.float32) if out is None else None
@@ -377,10 +388,43 @@ class MoonRT:
             st = MrtxStats()
             dev = None if out is None else out.ptr + a * n_az * 4
             hp = None if out is not None else host[a:].ctypes.data
-            self._check(self._lib.mrtx_horizon_points(self._ctx, pts[a:].ctypes.data, b - a, n_az, int(n_bis), dev, hp,
-                                                      C.byref(st)), "mrtx_horizon_points")
+            if hts is None:
+                self._check(self._lib.mrtx_horizon_points(self._ctx, pts[a:].ctypes.data, b - a, n_az, int(n_bis), dev, hp,
+                                                          C.byref(st)), "mrtx_horizon_points")
+            else:
+                self._check(self._lib.mrtx_horizon_raised(self._ctx, pts[a:].ctypes.data, hts[a:].ctypes.data, float(radius_m),
+                                                          b - a, n_az, int(n_bis), dev, hp, C.byref(st)), "mrtx_horizon_raised")
             self._add_stats(stats, st)
         return out if out is not None else host
+
+    WINDOW_COLUMNS = ("share_a", "longest_out_a", "share_b", "longest_out_b", "share_both", "longest_both", "first_both",
+                      "longest_out_both")
+
+    def horizon_windows(self, lat_deg, lon_deg, horizon, epochs_a, epochs_b, min_a=0.5, min_b=1.0, n_az=None, stats=None,
+                        chunk_bytes=256 << 20):
+        """Two bodies against the horizons of `horizon`, reduced per point on the device: with f_a,
+        f_b horizon_sun's fractions for the epoch tables epochs_a, epochs_b (the same m dates), ok_a = f_a >= min_a,
+        ok_b = f_b >= min_b and both = ok_a and ok_b, the (N, 8) float32 columns WINDOW_COLUMNS: the share of epochs with ok_a
+        and the longest run of epochs without it, the same for b, the share with both, the longest run with both and the index
+        of its first epoch (the earliest such run; -1 if there is none), the longest run without both.  Runs are in epochs.
+        `horizon` as for horizon_sun.  No (N, m) table exists anywhere; calls hold at most chunk_bytes of horizons and
+        output."""
+        la, lo = self._points(lat_deg, lon_deg)
+        ea, eb = self._epochs(epochs_a), self._epochs(epochs_b)
+        if ea.shape != eb.shape:
+            raise ValueError("epochs_a and epochs_b must hold the same number of epochs")
+        m = ea.shape[0]
+        n_az, hz_at = self._horizon_arg(horizon, la.size, n_az)
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        res = np.empty((la.size, 8), np.float32)
+        for a, b in self._chunks(la.size, max(int(n_az), 0) + 8, chunk_bytes):
+            st = MrtxStats()
+            dh, hh = hz_at(a)
+            self._check(self._lib.mrtx_horizon_windows(self._ctx, pts[a:].ctypes.data, b - a, n_az, dh, hh, ea.ctypes.data,
+                                                       eb.ctypes.data, m, float(min_a), float(min_b), None,
+                                                       res[a:].ctypes.data, C.byref(st)), "mrtx_horizon_windows")
+            self._add_stats(stats, st)
+        return res
 
     def horizon_sun(self, lat_deg, lon_deg, horizon, epochs, summary=False, stats=None, n_az=None, chunk_bytes=256 << 20):
         """The Sun against the horizons of `horizon`: per (point, epoch) the fraction of the light's

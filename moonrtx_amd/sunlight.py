@@ -92,11 +92,25 @@ class IlluminationStatistics(NamedTuple):
     stats: dict                   # summed counters and kernel times of the horizon and the Sun calls
 
 
-def illumination_statistics(rt, lat, lon, start, days, step_min=60, n_az=256, n_bis=14, observer=None, chunk=65536):
+def _heights(height_m, radius_m, n):
+    """kw(a, b): the keywords MoonRT.horizon takes for points [a, b) of n with mast tops height_m (None: the ground-only call;
+    one height, or one per point) -- section 3.15."""
+    if height_m is None:
+        return lambda a, b: {}
+    h = np.asarray(height_m, np.float64)
+    h = np.full(n, float(h)) if h.ndim == 0 else h.ravel()
+    if h.size != n:
+        raise ValueError("height_m must be one height or one per point")
+    return lambda a, b: {"height_m": h[a:b], "radius_m": radius_m}
+
+
+def illumination_statistics(rt, lat, lon, start, days, step_min=60, n_az=256, n_bis=14, observer=None, chunk=65536,
+                            height_m=None, radius_m=1737400.0):
     """Long-term Sun statistics of the points (lat, lon in degrees) from `start` (timezone-aware) over `days` at `step_min`
     minutes (DESIGN.md sections 3.8 and 3.9): each point's horizon is computed once (MoonRT.horizon, n_az azimuths, n_bis
     probes), then compared with the Sun on every date (MoonRT.horizon_sun, SUMMARY).  Points are streamed `chunk` at a time;
-    their horizons stay in a device buffer.  Returns IlluminationStatistics."""
+    their horizons stay in a device buffer.  height_m (one height or one per point, metres): the statistics of a mast top
+    that high above each point (section 3.15; radius_m = the metres of D = 1).  Returns IlluminationStatistics."""
     from .renderer import DeviceBuffer
     la = np.atleast_1d(np.asarray(lat, np.float64)).ravel()
     lo = np.atleast_1d(np.asarray(lon, np.float64)).ravel()
@@ -111,15 +125,67 @@ def illumination_statistics(rt, lat, lon, start, days, step_min=60, n_az=256, n_
     chunk = max(1, min(int(chunk), la.size, (1 << 31) // int(n_az)))
     out = np.empty((la.size, 4), np.float32)
     stats = {}
+    raised = _heights(height_m, radius_m, la.size)
     buf = DeviceBuffer(chunk * int(n_az) * 4, rt.config()["device"])
     try:
         for a in range(0, la.size, chunk):
             b = min(a + chunk, la.size)
-            rt.horizon(la[a:b], lo[a:b], n_az=n_az, n_bis=n_bis, stats=stats, out=buf)
+            rt.horizon(la[a:b], lo[a:b], n_az=n_az, n_bis=n_bis, stats=stats, out=buf, **raised(a, b))
             out[a:b] = rt.horizon_sun(la[a:b], lo[a:b], buf, ep, summary=True, stats=stats, n_az=n_az)
     finally:
         buf.free()
     return IlluminationStatistics(out[:, 0], out[:, 1], out[:, 2], out[:, 3].astype(np.float64) * (step_min / 60.0), times, stats)
+
+
+class SiteWindows(NamedTuple):
+    times: list                   # the dates used
+    sun_share: np.ndarray         # (N,) share of the dates with at least min_sun of the Sun's disc above the horizon
+    longest_no_sun_h: np.ndarray  # (N,) longest run of consecutive dates without that, hours (run x step)
+    earth_share: np.ndarray       # (N,) share of the dates with at least min_earth of the Earth's disc above the horizon
+    longest_no_earth_h: np.ndarray  # (N,) longest run of consecutive dates without that, hours
+    both_share: np.ndarray        # (N,) share of the dates with both
+    longest_both_h: np.ndarray    # (N,) the longest unbroken working window: consecutive dates with both, hours
+    best_start: np.ndarray        # (N,) int: index into `times` of that window's first date (the earliest such; -1: none)
+    longest_outage_h: np.ndarray  # (N,) longest run of consecutive dates without both, hours
+    stats: dict                   # summed counters and kernel times of the horizon and the windows calls
+
+
+def site_windows(rt, lat, lon, start, days, step_min=60, height_m=0.0, min_sun=0.5, min_earth=1.0, n_az=256, n_bis=14,
+                 observer=None, chunk=65536, radius_m=1737400.0):
+    """For how long can a lander work at the points (lat, lon in degrees) without a break -- Sun on the panel AND the Earth in
+    view -- from `start` (timezone-aware) over `days` at `step_min` minutes?  Each point's horizon
+    is computed once from a mast top height_m above it (one height or one per point; MoonRT.horizon), then held against the
+    Sun (ephemeris.sun_epochs) and the Earth (ephemeris.earth_epochs) on every date and reduced on the device
+    (MoonRT.horizon_windows): a date counts for the Sun when at least min_sun of its disc is above the horizon, for the Earth
+    when at least min_earth of its disc is.  Points are streamed `chunk` at a time; their horizons stay in a device buffer
+    and no (points x dates) table is ever formed.  Returns SiteWindows."""
+    from .renderer import DeviceBuffer
+    la = np.atleast_1d(np.asarray(lat, np.float64)).ravel()
+    lo = np.atleast_1d(np.asarray(lon, np.float64)).ravel()
+    if la.shape != lo.shape:
+        raise ValueError("lat and lon must have the same number of points")
+    m = int(round(days * 1440.0 / step_min))
+    if m < 1:
+        raise ValueError("days / step_min gives no date")
+    times = [start + timedelta(minutes=k * step_min) for k in range(m)]
+    ep_sun, ep_earth = ephemeris.sun_earth_epochs(times, observer)
+    rt.horizon_azimuths(n_az)       # checks n_az
+    raised = _heights(0.0 if height_m is None else height_m, radius_m, la.size)
+    chunk = max(1, min(int(chunk), la.size, (1 << 31) // int(n_az)))
+    out = np.empty((la.size, 8), np.float32)
+    stats = {}
+    buf = DeviceBuffer(chunk * int(n_az) * 4, rt.config()["device"])
+    try:
+        for a in range(0, la.size, chunk):
+            b = min(a + chunk, la.size)
+            rt.horizon(la[a:b], lo[a:b], n_az=n_az, n_bis=n_bis, stats=stats, out=buf, **raised(a, b))
+            out[a:b] = rt.horizon_windows(la[a:b], lo[a:b], buf, ep_sun, ep_earth, min_a=min_sun, min_b=min_earth, n_az=n_az,
+                                          stats=stats)
+    finally:
+        buf.free()
+    hours = step_min / 60.0
+    run = lambda j: out[:, j].astype(np.float64) * hours     # noqa: E731
+    return SiteWindows(times, out[:, 0], run(1), out[:, 2], run(3), out[:, 4], run(5), out[:, 6].astype(np.int64), run(7), stats)
 
 
 class SurfaceTemperatures(NamedTuple):
