@@ -398,6 +398,26 @@ int mrtx_thermal_scatter(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int
                          const MrtxThermalModel* model, int32_t mode, const void* dev_extra, const float* host_extra,
                          int64_t extra_len, void* dev_out, float* host_out, MrtxStats* out);
 
+/* ---- Subsurface temperature columns and ice-stability depths (additive to ABI 7) -----------------
+ * The free sublimation rate of a volatile, kg m^-2 s^-1: ln E(T) = b[0] - b[1] / T + b[2] ln T + b[3] T (the vapour-pressure
+ * law with the Hertz-Knudsen factor sqrt(M / (2 pi R T)) folded in by the host: moonrtx_amd.volatiles.law). */
+typedef struct MrtxVolatile { double b[4]; } MrtxVolatile;
+/* mrtx_thermal_scatter with two more modes (modes 0-3, species NULL: its outputs, counters, refusals and range flag, bit for
+ * bit).  mode 4 (COLUMN): n x (m - n_spin) x n_nodes float32, point-major, then epoch, then node: (float)T_i of every node
+ * after each recorded epoch's steps, where FULL samples node 0; at most 2^31 outputs per call.  mode 5 (VOLATILE, species
+ * required): n x n_nodes x 2 float64, 8-byte aligned, point-major: per node (E_mean_i, T_max_i).  After each recorded epoch's
+ * steps, per node: tf = (float)T_i, Td = (double)tf, x = fma(b3, Td, fma(b2, log(Td), b0 - b1 / Td)), S_i = S_i + exp(x) (a
+ * float64 left fold from 0 in epoch order), M_i = fmaxf(M_i, tf); the output is S_i / (double)(m - n_spin) and (double)M_i.  E
+ * is taken at the float32-rounded temperature, which is exactly what COLUMN stores; spin-up epochs contribute nothing.  The
+ * extra-flux table, the host checks, out->reserved and the [20, 450] K range flag are mrtx_thermal_scatter's.  Refused: a
+ * species outside mode 5 or none in it; a non-finite coefficient; a law that does not strictly increase on [20, 450] K
+ * (b1 / T^2 + b2 / T + b3 > 0 on the 1 K grid); x(450 K) > 700; an unaligned dev_out in mode 5.  mrtx_thermal and
+ * mrtx_thermal_scatter refuse modes 4 and 5.  Needs a DEM; leaves the light, Moon frame and render state as they were. */
+int mrtx_thermal_column(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t n_az, const void* dev_horizon,
+                        const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux_Wm2, int32_t m,
+                        const MrtxThermalModel* model, int32_t mode, const void* dev_extra, const float* host_extra,
+                        int64_t extra_len, const MrtxVolatile* species, void* dev_out, void* host_out, MrtxStats* out);
+
 /* ---- Terrain line of sight (additive to ABI 7) --------------------------------------------------
  * An end is a surface point (lat, lon, degrees) raised h >= 0 metres along its radial unit vector u, from the lifted vertex of
  * mrtx_horizon_points: P = fmaf(hs, u, o) with hs = (float)(h / radius_m * R), R the context's Moon radius and radius_m the

@@ -91,6 +91,12 @@ class MrtxThermalModel(C.Structure):
                 ("emissivity", C.c_double), ("sigma", C.c_double), ("q_geo", C.c_double), ("albedo", C.c_double * 3)]
 
 
+class MrtxVolatile(C.Structure):
+    """The free sublimation rate of a volatile, ln E(T) = b0 - b1 / T + b2 ln T + b3 T in kg m^-2 s^-1 (mrtx_thermal_column's
+    VOLATILE; volatiles.law builds it)."""
+    _fields_ = [("b", C.c_double * 4)]
+
+
 F_COUNT_STATS = 1
 F_FORCE_WIDE = 2
 F_NO_SKIP = 4
@@ -181,6 +187,8 @@ SIGNATURES = {
                                     C.c_double, _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_thermal_scatter": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                        C.c_int64, _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_thermal_column": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
+                                      C.c_int64, C.POINTER(MrtxVolatile), _VP, _VP, C.POINTER(MrtxStats)]),
 }
 
 _lib = None

@@ -2164,21 +2164,51 @@ static int thermal_model_ok(mrtx_ctx* c, const MrtxThermalModel& md, int32_t m, 
     return MRTX_OK;
 }
 
-// mrtx_thermal and, with ext, mrtx_thermal_scatter (section 3.11: mode 3 EXITANCE and the extra flux table, exactly one of
-// dev_extra and host_extra or neither, with at least n x m entries)
+// the sublimation law of VOLATILE (section 3.16): finite, strictly increasing on [20, 450] K (the 1 K grid, as
+// thermal_model_ok scans c(T)), and exp(x) finite at the top of the range
+static int volatile_ok(mrtx_ctx* c, const MrtxVolatile& sp) {
+    const double* b = sp.b;
+    for (int i = 0; i < 4; i++)
+        if (!std::isfinite(b[i])) return fail(c, MRTX_E_INVALID, "the species' coefficient b[%d] must be finite", i);
+    for (int T = 20; T <= 450; T++) {
+        const double t = (double)T;
+        if (!(b[1] / (t * t) + b[2] / t + b[3] > 0.0))
+            return fail(c, MRTX_E_INVALID, "the species' law must increase on [20, 450] K: d ln E / dT <= 0 at %d K", T);
+    }
+    const double x_top = std::fma(b[3], 450.0, std::fma(b[2], std::log(450.0), b[0] - b[1] / 450.0));
+    if (!(x_top <= 700.0))
+        return fail(c, MRTX_E_INVALID, "the species' ln E(450 K) = %g exceeds 700: exp would overflow", x_top);
+    return MRTX_OK;
+}
+
+// what each entry point accepts: mrtx_thermal modes 0-2; mrtx_thermal_scatter (section 3.11) also mode 3 EXITANCE and the
+// extra flux table, exactly one of dev_extra and host_extra or neither, with at least n x m entries; mrtx_thermal_column
+// (section 3.16) also modes 4 COLUMN and 5 VOLATILE, the latter with a species
+enum ThermalEntry { kThermal = 0, kThermalScatter = 1, kThermalColumn = 2 };
+
 static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon,
                        const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux, int32_t m,
-                       const MrtxThermalModel* model, int32_t mode, void* dev_out, float* host_out, MrtxStats* out, bool ext,
-                       const void* dev_extra, const float* host_extra, int64_t extra_len) {
+                       const MrtxThermalModel* model, int32_t mode, void* dev_out, void* host_out, MrtxStats* out,
+                       ThermalEntry entry, const void* dev_extra, const float* host_extra, int64_t extra_len,
+                       const MrtxVolatile* species) {
+    const bool ext = entry != kThermal;
     if (!c) return MRTX_E_INVALID;
     if (!latlon || !epochs || !flux || !model) return fail(c, MRTX_E_INVALID, "null point list, epoch table, flux or model");
     if (n < 1 || m < 1) return fail(c, MRTX_E_INVALID, "n and m must be >= 1 (got %d, %d)", n, m);
     if (m > (1 << 24)) return fail(c, MRTX_E_INVALID, "at most 2^24 epochs per call (got %d)", m);
     if (!horizon_az_ok(n_az)) return fail(c, MRTX_E_INVALID, "n_az must be 4, 8, ..., 4096 (got %d)", n_az);
-    if (!ext && (mode < 0 || mode > 2))
+    if (entry == kThermal && (mode < 0 || mode > 2))
         return fail(c, MRTX_E_INVALID, "mode must be 0 (FULL), 1 (SUMMARY) or 2 (FLUX) (got %d)", mode);
-    if (ext && (mode < 0 || mode > 3))
+    if (entry == kThermalScatter && (mode < 0 || mode > 3))
         return fail(c, MRTX_E_INVALID, "mode must be 0 (FULL), 1 (SUMMARY), 2 (FLUX) or 3 (EXITANCE) (got %d)", mode);
+    if (entry == kThermalColumn && (mode < 0 || mode > 5))
+        return fail(c, MRTX_E_INVALID,
+                    "mode must be 0 (FULL), 1 (SUMMARY), 2 (FLUX), 3 (EXITANCE), 4 (COLUMN) or 5 (VOLATILE) (got %d)", mode);
+    if ((mode == 5) != (species != nullptr))
+        return fail(c, MRTX_E_INVALID, "a species is required in mode 5 (VOLATILE) and must be null in every other mode");
+    if (species) { const int rc_ = volatile_ok(c, *species); if (rc_ != MRTX_OK) return rc_; }
+    if (mode == 5 && ((uintptr_t)dev_out & 7))
+        return fail(c, MRTX_E_INVALID, "VOLATILE writes float64 pairs: dev_out must be 8-byte aligned");
     if (dev_extra && host_extra) return fail(c, MRTX_E_INVALID, "give at most one of dev_extra and host_extra");
     const bool have_extra = dev_extra || host_extra;
     if (have_extra && extra_len < (int64_t)n * (int64_t)m)
@@ -2193,12 +2223,14 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
             x_max = std::max(x_max, (double)host_extra[i]);
         }
     }
-    int rc = horizon_args(c, dev_horizon, host_horizon, n, n_az, dev_out, host_out);
+    int rc = horizon_args(c, dev_horizon, host_horizon, n, n_az, dev_out, static_cast<const float*>(host_out));
     if (rc != MRTX_OK) return rc;
     const MrtxThermalModel& md = *model;
     double dmax = 0.0;
     if ((rc = thermal_model_ok(c, md, m, mode, &dmax)) != MRTX_OK) return rc;
-    const int64_t width = mode == 0 ? (int64_t)m - md.n_spin : mode == 2 ? (int64_t)m : mode == 3 ? 2 * ((int64_t)m - md.n_spin) : 4;
+    // outputs per point; VOLATILE's are float64
+    const int64_t width = mode == 0 ? (int64_t)m - md.n_spin : mode == 2 ? (int64_t)m : mode == 3 ? 2 * ((int64_t)m - md.n_spin) :
+                          mode == 4 ? ((int64_t)m - md.n_spin) * md.n_nodes : mode == 5 ? 2 * (int64_t)md.n_nodes : 4;
     if ((int64_t)n * width > (int64_t)1 << 31)
         return fail(c, MRTX_E_INVALID, "a call holds at most 2^31 outputs: split the points into more calls");
     double s_max = 0.0;
@@ -2231,7 +2263,7 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
     for (int32_t k = 0; k < m; k++) fl[k] = (float)flux[k];
     const size_t nh = host_horizon ? (size_t)n * (size_t)n_az : 0;
     const size_t nx = host_extra ? (size_t)n * (size_t)m : 0;
-    const size_t out_bytes = (size_t)n * (size_t)width * sizeof(float);
+    const size_t out_bytes = (size_t)n * (size_t)width * (mode == 5 ? sizeof(double) : sizeof(float));
     float* d[6];
     if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK ||
         (rc = stage_tables(c, {rtab, ctab, lights, fl, {host_horizon, nh}, {host_extra, nx}}, d)) != MRTX_OK)
@@ -2244,6 +2276,7 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
     q.lights = d[2]; q.flux = d[3]; q.out = (float*)dev_out; q.caps = c->illum_stats;
     q.xflux = host_extra ? d[5] : (const float*)dev_extra;
     q.az_log2 = log2_of(n_az); q.m = m; q.mode = mode;
+    if (species) for (int i = 0; i < 4; i++) q.vb[i] = species->b[i];
     const int nn = md.n_nodes;
     q.n_nodes = nn; q.n_sub = md.n_sub; q.n_spin = md.n_spin; q.block = md.block; q.n_reset = md.n_reset; q.ref = md.ref_node;
     const double delta = md.spacing_s / md.n_sub;
@@ -2261,7 +2294,7 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
     }
     if ((rc = stage_start(c, &cold, true)) != MRTX_OK) return rc;      // the counters: q.caps
     HIPCHK(c, mrtx_launch_thermal(f, q, ext, c->stream));
-    if ((rc = stage_finish(c, dev_out, host_out, out_bytes, out, kNoRays)) != MRTX_OK) return rc;
+    if ((rc = stage_finish(c, dev_out, static_cast<float*>(host_out), out_bytes, out, kNoRays)) != MRTX_OK) return rc;
     unsigned long long cnt[2] = {0, 0};      // Newton cap hits, (point, epoch)s whose column left [20, 450] K
     HIPCHK(c, hipMemcpy(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost));
     if (out) out->reserved = cnt[0] > 0xffffffffull ? 0xffffffffu : (uint32_t)cnt[0];
@@ -2276,16 +2309,25 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
 int mrtx_thermal(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon, const float* host_horizon,
                  const MrtxIllumEpoch* epochs, const double* flux, int32_t m, const MrtxThermalModel* model, int32_t mode,
                  void* dev_out, float* host_out, MrtxStats* out) {
-    return thermal_run(c, latlon, n, n_az, dev_horizon, host_horizon, epochs, flux, m, model, mode, dev_out, host_out, out, false,
-                       nullptr, nullptr, 0);
+    return thermal_run(c, latlon, n, n_az, dev_horizon, host_horizon, epochs, flux, m, model, mode, dev_out, host_out, out,
+                       kThermal, nullptr, nullptr, 0, nullptr);
 }
 
 int mrtx_thermal_scatter(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon,
                          const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux, int32_t m,
                          const MrtxThermalModel* model, int32_t mode, const void* dev_extra, const float* host_extra,
                          int64_t extra_len, void* dev_out, float* host_out, MrtxStats* out) {
-    return thermal_run(c, latlon, n, n_az, dev_horizon, host_horizon, epochs, flux, m, model, mode, dev_out, host_out, out, true,
-                       dev_extra, host_extra, extra_len);
+    return thermal_run(c, latlon, n, n_az, dev_horizon, host_horizon, epochs, flux, m, model, mode, dev_out, host_out, out,
+                       kThermalScatter, dev_extra, host_extra, extra_len, nullptr);
+}
+
+// ---- Subsurface temperature columns and volatile loss rates --------------------------------------
+int mrtx_thermal_column(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon,
+                        const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux, int32_t m,
+                        const MrtxThermalModel* model, int32_t mode, const void* dev_extra, const float* host_extra,
+                        int64_t extra_len, const MrtxVolatile* species, void* dev_out, void* host_out, MrtxStats* out) {
+    return thermal_run(c, latlon, n, n_az, dev_horizon, host_horizon, epochs, flux, m, model, mode, dev_out, host_out, out,
+                       kThermalColumn, dev_extra, host_extra, extra_len, species);
 }
 
 // ---- Terrain-scattered sunlight and infrared -------------------------------------------------------

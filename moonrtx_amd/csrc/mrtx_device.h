@@ -245,12 +245,13 @@ struct ThermalC {
     const float* horizon;       // n_points x n_az float32 elevations (degrees)
     const float* lights;        // 8 floats per epoch, as IllumSeriesC's
     const float* flux;          // per epoch the solar flux at the Moon, W m^-2
-    float* out;                 // mode 0: n x (m - n_spin) float32 surface temperatures; 1: n float4; 2: n x m float32 fluxes
+    float* out;                 // mode 0: n x (m - n_spin) float32 surface temperatures; 1: n float4; 2: n x m float32 fluxes;
+                                // 4: n x (m - n_spin) x n_nodes float32; 5: n x n_nodes double2 (8-byte aligned)
     unsigned long long* caps;   // two counters, zeroed by the host: [0] surface solves that reached the Newton cap, [1] the
                                 // (point, epoch)s after whose steps a node was non-finite or outside [20, 450] K
     int32_t az_log2;            // log2(n_az)
     int32_t m;                  // epochs, spin-up included
-    int32_t mode;               // 0 FULL, 1 SUMMARY, 2 FLUX
+    int32_t mode;               // 0 FULL, 1 SUMMARY, 2 FLUX, 3 EXITANCE (EXT), 4 COLUMN, 5 VOLATILE (COL, section 3.16)
     int32_t n_nodes;            // 3 .. MRTX_THERMAL_NODES
     int32_t n_sub;              // explicit steps per epoch
     int32_t n_spin;             // spin-up epochs (stepped, not recorded), < m outside FLUX
@@ -269,6 +270,8 @@ struct ThermalC {
     float qdz[MRTX_THERMAL_NODES];  // Q x dz_i: the steady step of link i (the bottom node's step: i = N - 2)
     // thermal_kernel<EXT = true> only (mrtx_thermal_scatter, section 3.11); mode 3 (EXITANCE) writes n x (m - n_spin) float2
     const float* xflux;             // null, or n x m float32 extra absorbed flux, point-major
+    // thermal_kernel<WIDE, true, 2> only (mrtx_thermal_column's VOLATILE, section 3.16)
+    double vb[4];                   // ln E(T) = vb[0] - vb[1] / T + vb[2] ln T + vb[3] T
 };
 
 // What terrain a point sees (mrtx_view_hits).

@@ -2412,11 +2412,17 @@ __global__ void __launch_bounds__(64) horizon_windows_kernel(const FrameC f, con
 // to Q_abs in every epoch (spin-up and the start included), and mode 3 (EXITANCE), which records per epoch the reflected
 // sunlight M_vis = A(theta) S f max(mu, 0) and the emission eps sigma T0^4 after the epoch's steps.  EXT = false is the
 // mrtx_thermal kernel unchanged.
+// COL (section 3.16, mrtx_thermal_column; EXT's column, modes 4 and 5 only): what the column holds below the surface.  COL = 1
+// (COLUMN) stores (float)T_i of every node after each recorded epoch's steps.  COL = 2 (VOLATILE) keeps per node a float64 sum
+// of the free sublimation rate E((float)T_i), evaluated once per recorded epoch, and a float32 maximum: 3 registers per node
+// beside the column's own, and the point's n_nodes (mean E, T_max) pairs at the end.  COL = 0 is the kernel of modes 0-3,
+// its machine code unchanged.
 // After each epoch's steps the column is checked once (not per step, which would cost a share of the step itself): a node
 // that is not finite or lies outside [20, 450] K, the range the step bound and the heat capacity were checked on, counts
 // that (point, epoch) in q.caps[1]; the host then refuses the call's results (sections 3.10, 3.11).
-template <bool WIDE, bool EXT>
+template <bool WIDE, bool EXT, int COL = 0>
 __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const ThermalC q) {
+    static_assert(COL == 0 || EXT, "the subsurface modes run EXT's column");
     constexpr int NN = MRTX_THERMAL_NODES;
     constexpr float kDeg = 57.2957795130823209f;
     const int lane = threadIdx.x;
@@ -2450,10 +2456,12 @@ __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const Therm
         return qa;
     };
     float mv = 0.0f;
-    if (q.mode == 2) {
-        if (in)
-            for (int k = 0; k < q.m; k++) q.out[(int64_t)pt * q.m + k] = absorbed(k, mv);
-        return;
+    if constexpr (COL == 0) {
+        if (q.mode == 2) {
+            if (in)
+                for (int k = 0; k < q.m; k++) q.out[(int64_t)pt * q.m + k] = absorbed(k, mv);
+            return;
+        }
     }
     // the uniform start: ((<Q_abs> over the spin-up epochs + Q) / (eps sigma))^(1/4)
     double qs = 0.0;
@@ -2492,6 +2500,12 @@ __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const Therm
     float t_max = -INFINITY, t_min = INFINITY;
     int in_block = 0, blocks = 0;
     const int m_rec = q.m - q.n_spin;
+    double e_sum[COL == 2 ? NN : 1];        // VOLATILE: the left fold of E((float)T_i) and the maximum of (float)T_i per node
+    float n_max[COL == 2 ? NN : 1];
+    if constexpr (COL == 2) {
+#pragma unroll
+        for (int i = 0; i < NN; i++) { e_sum[i] = 0.0; n_max[i] = -INFINITY; }
+    }
     for (int k = 0; k < q.m; k++) {
         const float qa = absorbed(k, mv);
         for (int s = 0; s < q.n_sub; s++) {
@@ -2553,7 +2567,7 @@ __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const Therm
                     blocks++;
                 }
             }
-        } else {
+        } else if constexpr (COL == 0) {
             double tb = 0.0;
 #pragma unroll
             for (int i = 2; i < NN; i++) tb = i == n - 1 ? T[i] : tb;
@@ -2567,11 +2581,37 @@ __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const Therm
                     reinterpret_cast<float2*>(q.out)[(int64_t)pt * m_rec + (k - q.n_spin)] =
                         make_float2(mv, q.es * ((ts * ts) * (ts * ts)));
             }
+        } else if constexpr (COL == 1) {
+            // node i of recorded epoch k - n_spin: at most 2^31 outputs per call, so the index needs 64 bits
+            float* const o = q.out + ((int64_t)pt * m_rec + (k - q.n_spin)) * n;
+#pragma unroll
+            for (int i = 0; i < NN; i++)
+                if (in && i < n) o[i] = (float)T[i];
+        } else {
+            // E at the float32-rounded temperature (what COLUMN stores): x = b0 - b1 / T + b2 ln T + b3 T, once per epoch
+#pragma unroll
+            for (int i = 0; i < NN; i++) {
+                if (i < n) {
+                    const float tf = (float)T[i];
+                    const double td = (double)tf;
+                    const double x = fma(q.vb[3], td, fma(q.vb[2], log(td), q.vb[0] - q.vb[1] / td));
+                    e_sum[i] = e_sum[i] + exp(x);
+                    n_max[i] = fmaxf(n_max[i], tf);
+                }
+            }
         }
     }
-    if (in && q.mode == 1) {
-        const double inv = 1.0 / (double)m_rec;
-        reinterpret_cast<float4*>(q.out)[pt] = make_float4(t_max, t_min, (float)(sum_s * inv), (float)(sum_b * inv));
+    if constexpr (COL == 0) {
+        if (in && q.mode == 1) {
+            const double inv = 1.0 / (double)m_rec;
+            reinterpret_cast<float4*>(q.out)[pt] = make_float4(t_max, t_min, (float)(sum_s * inv), (float)(sum_b * inv));
+        }
+    }
+    if constexpr (COL == 2) {
+        double2* const o = reinterpret_cast<double2*>(q.out) + (int64_t)pt * n;
+#pragma unroll
+        for (int i = 0; i < NN; i++)
+            if (in && i < n) o[i] = make_double2(e_sum[i] / (double)m_rec, (double)n_max[i]);
     }
     caps = in ? caps : 0u;
     out_of_range = in ? out_of_range : 0u;
@@ -4142,17 +4182,25 @@ hipError_t mrtx_launch_sight(const FrameC& f, SightC q, bool stats, hipStream_t 
 }
 
 // Regolith surface temperatures (thermal_kernel): one lane per point, 64 per wave.  ext: the same column with an extra
-// absorbed flux and the EXITANCE mode 3 (mrtx_thermal_scatter, section 3.11).
+// absorbed flux and the EXITANCE mode 3 (mrtx_thermal_scatter, section 3.11), and the subsurface modes 4 (COLUMN) and
+// 5 (VOLATILE) of mrtx_thermal_column (section 3.16), which have instantiations of their own.
 hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, bool ext, hipStream_t st) {
-    if (q.g.rows < 1 || q.az_log2 < 2 || q.az_log2 > 12 || q.m < 1 || q.mode < 0 || q.mode > (ext ? 3 : 2) || q.n_nodes < 3 ||
+    if (q.g.rows < 1 || q.az_log2 < 2 || q.az_log2 > 12 || q.m < 1 || q.mode < 0 || q.mode > (ext ? 5 : 2) || q.n_nodes < 3 ||
         q.n_nodes > MRTX_THERMAL_NODES || q.n_sub < 1 || q.block < 1 || q.n_spin < 0 || q.n_reset < 0 || q.ref < 0 ||
         q.ref >= q.n_nodes - 1 || (q.mode != 2 && q.n_spin >= q.m) || !q.g.points || !q.horizon || !q.lights || !q.flux ||
         !q.out || !q.caps)
         return hipErrorInvalidValue;
+    if (q.mode == 4 && (int64_t)q.g.rows * (q.m - q.n_spin) * q.n_nodes > (int64_t)1 << 31) return hipErrorInvalidValue;
+    if (q.mode == 5 && ((uintptr_t)q.out & 7)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((q.g.rows + 63) / 64)), block(64);
-    pick2(f.dem_wide != 0, ext, [&](auto w, auto e) {
-        hipLaunchKernelGGL((mrtx::thermal_kernel<w(), e()>), grid, block, 0, st, f, q);
-    });
+    if (q.mode >= 4)
+        pick2(f.dem_wide != 0, q.mode == 5, [&](auto w, auto v) {
+            hipLaunchKernelGGL((mrtx::thermal_kernel<w(), true, v() ? 2 : 1>), grid, block, 0, st, f, q);
+        });
+    else
+        pick2(f.dem_wide != 0, ext, [&](auto w, auto e) {
+            hipLaunchKernelGGL((mrtx::thermal_kernel<w(), e()>), grid, block, 0, st, f, q);
+        });
     return hipGetLastError();
 }
 

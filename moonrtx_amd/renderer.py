@@ -586,6 +586,64 @@ class MoonRT:
         self._add_stats(stats, st, {"newton_cap_hits": "reserved"})
         return out if out is not None else res
 
+    @staticmethod
+    def thermal_depths(model=None):
+        """The node depths z_i of a MrtxThermalModel in metres, (n_nodes,) float64: z_0 = 0 and z_{i+1} = z_i + dz[i] (the
+        model of thermal_grid() unless given)."""
+        model = MoonRT.thermal_grid() if model is None else model
+        n = int(model.n_nodes)
+        return np.concatenate([[0.0], np.cumsum(np.array(model.dz[:n - 1], np.float64))])
+
+    def thermal_column(self, lat_deg, lon_deg, horizon, epochs, flux, model=None, mode="column", extra_flux=None, species=None,
+                       stats=None, n_az=None, out=None):
+        """surface_temperature_scatter with the subsurface modes of DESIGN.md section 3.16, in one call.  Its modes ("full",
+        "summary", "flux", "exitance") give its bits; "column": (N, m - n_spin, n_nodes) float32, every node's temperature
+        after each recorded epoch (node 0 is "full"); "volatile": (N, n_nodes, 2) float64 (E_mean, T_max) per node, the mean
+        over the recorded epochs of the free sublimation rate of `species` (a volatiles.Species, an MrtxVolatile or its four
+        coefficients; kg m^-2 s^-1) and the node's highest temperature.  thermal_depths(model) gives the nodes' depths.
+        out = a DeviceBuffer: the output is written there and `out` returned."""
+        modes = {"full": 0, "summary": 1, "flux": 2, "exitance": 3, "column": 4, "volatile": 5}
+        if mode not in modes:
+            raise ValueError(f"mode must be one of {sorted(modes)} (got {mode!r})")
+        if (mode == "volatile") != (species is not None):
+            raise ValueError("species is required in mode 'volatile' and must be None otherwise")
+        sp = None
+        if species is not None:
+            from . import volatiles
+            sp = species if isinstance(species, _lib.MrtxVolatile) else volatiles.law(species)
+        la, lo = self._points(lat_deg, lon_deg)
+        ep = self._epochs(epochs)
+        m = ep.shape[0]
+        fl = np.ascontiguousarray(np.asarray(flux, np.float64).ravel())
+        if fl.size != m:
+            raise ValueError("flux must hold one value per epoch")
+        model = self.thermal_grid() if model is None else model
+        n_az, hz_at = self._horizon_arg(horizon, la.size, n_az)
+        dh, hh = hz_at(0)
+        dx = hx = None
+        x_len = 0
+        if isinstance(extra_flux, DeviceBuffer):
+            dx, x_len = extra_flux.ptr, extra_flux.nbytes // 4
+        elif extra_flux is not None:
+            xf = np.ascontiguousarray(extra_flux, np.float32)
+            hx, x_len = xf.ctypes.data, xf.size
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        rec, nn = max(m - int(model.n_spin), 1), max(int(model.n_nodes), 1)
+        shape = {"full": (la.size, rec), "summary": (la.size, 4), "flux": (la.size, m), "exitance": (la.size, rec, 2),
+                 "column": (la.size, rec, nn), "volatile": (la.size, nn, 2)}[mode]
+        dtype = np.float64 if mode == "volatile" else np.float32
+        if out is not None and out.nbytes < int(np.prod(shape)) * np.dtype(dtype).itemsize:
+            raise ValueError("the device buffer is smaller than the output")
+        res = np.empty(shape, dtype) if out is None else None
+        st = MrtxStats()
+        self._check(self._lib.mrtx_thermal_column(self._ctx, pts.ctypes.data, la.size, n_az, dh, hh, ep.ctypes.data,
+                                                  fl.ctypes.data, m, C.byref(model), modes[mode], dx, hx, x_len,
+                                                  None if sp is None else C.byref(sp), None if out is None else out.ptr,
+                                                  None if res is None else res.ctypes.data, C.byref(st)),
+                    "mrtx_thermal_column")
+        self._add_stats(stats, st, {"newton_cap_hits": "reserved"})
+        return out if out is not None else res
+
     # ---- Terrain line of sight (DESIGN.md section 3.12)
     @staticmethod
     def _observer(observer):

@@ -209,6 +209,16 @@ def surface_temperatures(rt, lat, lon, start, days, step_min=60, spinup_lunation
     hits' own columns in EXITANCE mode, the gather and the points' columns with that extra flux.  Device tables stay under
     about `budget_bytes` per group of points; `q_sec_mean` also returns each point's mean extra flux over the recorded dates
     (stats["q_sec_mean"]; it downloads the flux).  `alloc(nbytes)` replaces the device allocation (tests)."""
+    out, times, stats, _ = _columns(rt, lat, lon, start, days, step_min, spinup_lunations, n_az, n_bis, observer, chunk, thermal,
+                                    scatter, budget_bytes, q_sec_mean, alloc, None)
+    return SurfaceTemperatures(out[:, 0], out[:, 1], out[:, 2], out[:, 3], times, stats)
+
+
+def _columns(rt, lat, lon, start, days, step_min, spinup_lunations, n_az, n_bis, observer, chunk, thermal, scatter, budget_bytes,
+             q_sec_mean, alloc, species):
+    """The flow surface_temperatures and ice_stability share: the dates, the model, and per chunk of points the horizons and
+    the columns.  species = None: the points' columns run in SUMMARY, (N, 4) float32; a species: in VOLATILE
+    (MoonRT.thermal_column, section 3.16), (N, n_nodes, 2) float64.  Returns (out, the recorded dates, stats, model)."""
     from . import thermal as th
     la = np.atleast_1d(np.asarray(lat, np.float64)).ravel()
     lo = np.atleast_1d(np.asarray(lon, np.float64)).ravel()
@@ -226,12 +236,15 @@ def surface_temperatures(rt, lat, lon, start, days, step_min=60, spinup_lunation
     fl = ephemeris.sun_flux(all_times)
     rt.horizon_azimuths(n_az)       # checks n_az
     chunk = max(1, min(int(chunk), la.size, (1 << 31) // int(n_az)))
-    out = np.empty((la.size, 4), np.float32)
+    out = _columns_out(la.size, model, species)
     stats = {}
     if scatter:
-        return _scatter_temperatures(rt, la, lo, start, step, m_rec, model, n_az, n_bis, observer, chunk, int(scatter),
-                                     budget_bytes, q_sec_mean, alloc)
+        times, stats = _scatter_temperatures(rt, la, lo, start, step, m_rec, model, n_az, n_bis, observer, chunk, int(scatter),
+                                             budget_bytes, q_sec_mean, alloc, species, out)
+        return out, times, stats, model
     if thermal is not None:
+        if species is not None:
+            raise ValueError("thermal= replaces the SUMMARY call only")
         for a in range(0, la.size, chunk):
             b = min(a + chunk, la.size)
             hz = rt.horizon(la[a:b], lo[a:b], n_az=n_az, n_bis=n_bis, stats=stats)
@@ -243,11 +256,22 @@ def surface_temperatures(rt, lat, lon, start, days, step_min=60, spinup_lunation
             for a in range(0, la.size, chunk):
                 b = min(a + chunk, la.size)
                 rt.horizon(la[a:b], lo[a:b], n_az=n_az, n_bis=n_bis, stats=stats, out=buf)
-                out[a:b] = rt.surface_temperature(la[a:b], lo[a:b], buf, ep, fl, model=model, mode="summary", stats=stats,
-                                                  n_az=n_az)
+                if species is None:
+                    out[a:b] = rt.surface_temperature(la[a:b], lo[a:b], buf, ep, fl, model=model, mode="summary", stats=stats,
+                                                      n_az=n_az)
+                else:
+                    out[a:b] = rt.thermal_column(la[a:b], lo[a:b], buf, ep, fl, model=model, mode="volatile", species=species,
+                                                 stats=stats, n_az=n_az)
         finally:
             buf.free()
-    return SurfaceTemperatures(out[:, 0], out[:, 1], out[:, 2], out[:, 3], all_times[n_spin:], stats)
+    return out, all_times[n_spin:], stats, model
+
+
+def _columns_out(n, model, species):
+    """The array the points' final column call fills: SUMMARY's, or with a species VOLATILE's."""
+    if species is None:
+        return np.empty((n, 4), np.float32)
+    return np.empty((n, int(model.n_nodes), 2), np.float64)
 
 
 def compact_hits(hits):
@@ -280,10 +304,11 @@ def scatter_groups(hit_counts, m_hits, m_targets, n_az, budget_bytes):
 
 
 def _scatter_temperatures(rt, la, lo, start, step, m_rec, model, n_az, n_bis, observer, chunk, k, budget_bytes, q_sec_mean,
-                          alloc):
-    """surface_temperatures with scatter = K (section 3.11).  Per chunk of points: their view hits; per group of points that
-    fits the budget: their horizons, the hits' horizons, the hits' columns in EXITANCE mode over [own spin-up | the points'
-    spin-up | recorded], the gather, and the points' columns with the extra flux."""
+                          alloc, species, out):
+    """_columns with scatter = K (section 3.11).  Per chunk of points: their view hits; per group of points that fits the
+    budget: their horizons, the hits' horizons, the hits' columns in EXITANCE mode over [own spin-up | the points' spin-up |
+    recorded], the gather, and the points' columns with the extra flux (SUMMARY, or with a species VOLATILE) into `out`.
+    Returns (the recorded dates, stats)."""
     import time
     from . import thermal as th
     rt.view_samples(k)              # checks K
@@ -299,7 +324,6 @@ def _scatter_temperatures(rt, la, lo, start, step, m_rec, model, n_az, n_bis, ob
         from .renderer import DeviceBuffer
         device = rt.config()["device"]
         alloc = lambda nbytes: DeviceBuffer(max(int(nbytes), 4), device)     # noqa: E731
-    out = np.empty((la.size, 4), np.float32)
     stats = {"scatter_hits": 0, "view_factor": np.empty(la.size, np.float32), "stage_s": {}}
     if q_sec_mean:
         stats["q_sec_mean"] = np.zeros(la.size, np.float64)
@@ -348,10 +372,46 @@ def _scatter_temperatures(rt, la, lo, start, step, m_rec, model, n_az, n_bis, ob
                     if q_sec_mean:
                         qs = q.download(np.float32, (p1 - p0, m_t))
                         stats["q_sec_mean"][p0:p1] = qs[:, n_spin:].astype(np.float64).mean(axis=1)
-                out[p0:p1] = timed("columns", lambda: rt.surface_temperature_scatter(
-                    la[p0:p1], lo[p0:p1], hz_t, ep_t, fl_t, model=model, mode="summary", extra_flux=q, stats=stats,
-                    n_az=n_az))
+                if species is None:
+                    out[p0:p1] = timed("columns", lambda: rt.surface_temperature_scatter(
+                        la[p0:p1], lo[p0:p1], hz_t, ep_t, fl_t, model=model, mode="summary", extra_flux=q, stats=stats,
+                        n_az=n_az))
+                else:
+                    out[p0:p1] = timed("columns", lambda: rt.thermal_column(
+                        la[p0:p1], lo[p0:p1], hz_t, ep_t, fl_t, model=model, mode="volatile", extra_flux=q, species=species,
+                        stats=stats, n_az=n_az))
             finally:
                 for buf in bufs:
                     buf.free()
-    return SurfaceTemperatures(out[:, 0], out[:, 1], out[:, 2], out[:, 3], times[2 * n_spin:], stats)
+    return times[2 * n_spin:], stats
+
+
+class IceStability(NamedTuple):
+    depth_m: np.ndarray           # (N,) the shallowest depth at which buried ice is stable, m (0: at the surface; inf: nowhere)
+    loss_rate_surface: np.ndarray  # (N,) the retreat rate of exposed ice at the surface, m s^-1 (E_mean_0 / rho_solid)
+    e_mean: np.ndarray            # (N, n_nodes) time-mean free sublimation rate at every node, kg m^-2 s^-1
+    t_max_nodes: np.ndarray       # (N, n_nodes) highest temperature of every node over the recorded dates, K
+    z: np.ndarray                 # (n_nodes,) node depths, m
+    times: list                   # the recorded dates (the spin-up dates precede them)
+    stats: dict                   # summed counters and kernel times of every call made
+
+
+def ice_stability(rt, lat, lon, start, days, step_min=60, spinup_lunations=None, n_az=256, n_bis=14, observer=None,
+                  chunk=65536, species=None, scatter=0, rate_max=None, barrier_m=None, budget_bytes=8 << 30, alloc=None):
+    """How deep must ice of `species` (default volatiles.H2O) be buried at the points (lat, lon in degrees) to survive
+    ?  The run is surface_temperatures' -- the same dates, spin-up, horizons, chunks and, with
+    scatter = K, scatter groups -- with the points' final columns in VOLATILE mode: per node the mean over the recorded dates
+    of the free sublimation rate and the highest temperature.  volatiles.stability_depth turns the rates into a depth: the
+    shallowest at which the retreat rate E_mean / rho_solid is at most rate_max (default 1 mm per 10^9 years), with
+    barrier_m the diffusion length of an overlying dry lag (None: the exposed-ice criterion).  One species per call.  The
+    regolith's properties are the dry ones throughout: ice changes neither its conductivity nor its heat capacity, and the
+    rate is the time mean of the free rate, without pumping or recondensation.  Returns IceStability."""
+    from . import volatiles
+    species = volatiles.H2O if species is None else species
+    rate_max = volatiles.RATE_MAX if rate_max is None else float(rate_max)
+    out, times, stats, model = _columns(rt, lat, lon, start, days, step_min, spinup_lunations, n_az, n_bis, observer, chunk,
+                                        None, scatter, budget_bytes, False, alloc, species)
+    z = rt.thermal_depths(model)
+    e_mean = out[:, :, 0]
+    depth = volatiles.stability_depth(e_mean, z, species, rate_max=rate_max, barrier_m=barrier_m)
+    return IceStability(depth, e_mean[:, 0] / species.rho_solid, e_mean, out[:, :, 1], z, times, stats)

@@ -6,7 +6,8 @@ the thermal stage (DESIGN.md sections 3.8 and 3.10), headless.
       --step-min 60 --out temps.npy
   python tools/temperature_map.py --point -89.5 45.0 --days 30 > series.csv
 --scatter K adds the sunlight and infrared the surrounding terrain sends, from K view rays per point (section 3.11); with
---point it also prints the point's terrain view factor and its mean scattered flux.
+--point it also prints the point's terrain view factor and its mean scattered flux.  --point ... --depths prints every
+node's temperature per date (the COLUMN mode of section 3.16) instead of the surface's alone.
 The window's nodes are MoonRT.grid_nodes; temps.npy holds a (4, h, w) float32 array: the maximum, minimum and mean surface
 temperature over the dates and the mean temperature of the column's bottom node, K.  The column is spun up over
 --spinup-lunations lunations before the first date.  Synthetic LOLA-like DEM unless --elevation-file is given."""
@@ -34,8 +35,11 @@ ap.add_argument("--downscale", type=int, default=2)
 ap.add_argument("--dem-size", type=int, nargs=2, default=None, help="synthetic DEM (h, w); default 46080/downscale x 92160/downscale")
 ap.add_argument("--elevation-file", default=None)
 ap.add_argument("--scatter", type=int, default=0, help="K view rays per point for the terrain-scattered flux (0: none)")
+ap.add_argument("--depths", action="store_true", help="with --point: the whole column per date, one CSV column per node")
 ap.add_argument("--out", default="temps.npy")
 a = ap.parse_args()
+if a.depths and a.point is None:
+    ap.error("--depths goes with --point")
 if (a.window is None) == (a.point is None):
     ap.error("give exactly one of --window and --point")
 
@@ -78,16 +82,25 @@ if a.point is not None:
             ex = rt.surface_temperature_scatter(h_lat, h_lon, hz_h, ephemeris.sun_epochs(times_h, obs),
                                                 ephemeris.sun_flux(times_h), model, mode="exitance", stats=st)
             q = rt.scatter_flux(index, ex, thermal.albedo_hemispherical(), thermal.EMISSIVITY, stats=st)
-        ts = rt.surface_temperature_scatter([a.point[0]], [a.point[1]], hz, ephemeris.sun_epochs(times, obs),
-                                            ephemeris.sun_flux(times), model, mode="full", extra_flux=q, stats=st)[0]
+        col = rt.thermal_column if a.depths else rt.surface_temperature_scatter
+        ts = col([a.point[0]], [a.point[1]], hz, ephemeris.sun_epochs(times, obs), ephemeris.sun_flux(times), model,
+                 mode="column" if a.depths else "full", extra_flux=q, stats=st)[0]
         print(f"# terrain view factor {float(share[0]):.4f} ({h_lat.size} of {a.scatter} rays), mean scattered flux "
               f"{float(q[0, n_spin:].astype(np.float64).mean()):.3f} W m^-2 over the recorded dates", file=sys.stderr)
+    elif a.depths:
+        ts = rt.thermal_column([a.point[0]], [a.point[1]], hz, ephemeris.sun_epochs(times, obs), ephemeris.sun_flux(times),
+                               model, mode="column", stats=st)[0]
     else:
         ts = rt.surface_temperature([a.point[0]], [a.point[1]], hz, ephemeris.sun_epochs(times, obs),
                                     ephemeris.sun_flux(times), model, mode="full", stats=st)[0]
-    print("time_utc,surface_temperature_K")
-    for t, v in zip(times[model.n_spin:], ts):
-        print(f"{t.isoformat()},{v:.4f}")
+    if a.depths:
+        print("time_utc," + ",".join(f"T_K_at_{z:.4f}_m" for z in rt.thermal_depths(model)))
+        for t, v in zip(times[model.n_spin:], ts):
+            print(f"{t.isoformat()}," + ",".join(f"{x:.4f}" for x in v))
+    else:
+        print("time_utc,surface_temperature_K")
+        for t, v in zip(times[model.n_spin:], ts):
+            print(f"{t.isoformat()},{v:.4f}")
     print(f"# {len(times)} epochs ({model.n_spin} spin-up) x {model.n_sub} steps: {st['kernel_ms']:.3f} ms of kernels",
           file=sys.stderr)
 else:

@@ -2,7 +2,8 @@
 """Measure the surface-temperature stage on one GPU: thermal_kernel in SUMMARY over a polar window
 for a year of hourly epochs with the default spin-up, the same year without spin-up (the difference is the spin-up's share),
 and FULL / SUMMARY / FLUX on the first --small-points points.  Horizons come from horizon_kernel into a device buffer first.
-Kernel times come from the library's HIP events.
+--volatile times VOLATILE (mrtx_thermal_column, section 4.17) beside SUMMARY through mrtx_thermal on those points, --repeat
+runs each, alternating.  Kernel times come from the library's HIP events.
 
   python tools/thermal_bench.py --dem-size 23040 46080 --size 1024 1024 --days 365
 """
@@ -25,6 +26,7 @@ ap.add_argument("--spinup-lunations", type=int, default=thermal.SPINUP_LUNATIONS
 ap.add_argument("--small-points", type=int, default=65536, help="points of the FULL / FLUX / small SUMMARY measurements")
 ap.add_argument("--skip-large", action="store_true", help="only the small-point measurements")
 ap.add_argument("--repeat", type=int, default=2)
+ap.add_argument("--volatile", action="store_true", help="also VOLATILE beside SUMMARY on the small points, alternating")
 ap.add_argument("--out", default=None, help="write the numbers as JSON here")
 a = ap.parse_args()
 
@@ -75,6 +77,19 @@ for name, mode, e, f, model in (("small_full_month", "full", ep[:md.n_spin + m_f
         st = {}
         rt.surface_temperature(LA[:ns], LO[:ns], buf, e, f, model, mode=mode, stats=st, n_az=a.n_az)
         res.setdefault(name + "_ms", []).append(st["kernel_ms"])
+if a.volatile:
+    from moonrtx_amd import volatiles
+    for rep in range(a.repeat):
+        st = {}
+        rt.surface_temperature(LA[:ns], LO[:ns], buf, ep, fl, md, mode="summary", stats=st, n_az=a.n_az)
+        res.setdefault("alt_summary_ms", []).append(st["kernel_ms"])
+        st = {}
+        v_ = rt.thermal_column(LA[:ns], LO[:ns], buf, ep, fl, md, mode="volatile", species=volatiles.H2O, stats=st, n_az=a.n_az)
+        res.setdefault("alt_volatile_ms", []).append(st["kernel_ms"])
+    res["volatile_over_summary"] = min(res["alt_volatile_ms"]) / min(res["alt_summary_ms"])
+    depth = volatiles.stability_depth(v_[:, :, 0], MoonRT.thermal_depths(md))
+    res["volatile_depth_share"] = dict(surface=float((depth == 0.0).mean()), buried=float(np.isfinite(depth).mean()),
+                                       never=float(np.isinf(depth).mean()))
 if "summary_spin_ms" in res:
     res["spinup_share"] = 1.0 - min(res["summary_nospin_ms"]) / min(res["summary_spin_ms"])
 buf.free()
