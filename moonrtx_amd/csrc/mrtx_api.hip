@@ -360,11 +360,7 @@ void build_frame(const mrtx_ctx* c, FrameC& f, FrameCold& k) {
     k.hm_kcol = (float)(1.05 * (double)c->dem_w / (2.0 * kPiD));
     f.mip = c->mip; f.mip_pitch = c->mip_w + 2; f.mip_h = c->mip_h; f.mip_w = c->mip_w; f.mip_shift = c->mip_shift;
     f.dem_pitch = c->dem_w + 4;
-#if MRTX_DEM_PAIRS
     f.dem_maxidx = (uint32_t)((uint64_t)(c->dem_h + 4) * (uint64_t)(c->dem_w + 4) - 2);   // elements idx and idx+1 are read
-#else
-    f.dem_maxidx = (uint32_t)((uint64_t)(c->dem_h + 2) * (uint64_t)(c->dem_w + 4) + (uint64_t)(c->dem_w + 2));
-#endif
     f.dem_wide = ((uint64_t)(c->dem_h + 4) * (uint64_t)(c->dem_w + 4) * MRTX_DEM_ELEM_BYTES > 0xFFFFFFFFull) ? 1 : 0;
     f.tile_w = c->cfg.tile_w; f.tile_h = c->cfg.tile_h;
     f.tiles_x = c->tiles_x; f.tiles_y = c->tiles_y; f.tile_shift = c->tile_shift;
@@ -1072,16 +1068,8 @@ int mrtx_render_part(mrtx_ctx* c, int32_t n_blocks, int32_t part, int32_t n_part
         PathQ& pq = pqs[(size_t)s];
         const size_t set = overlap ? (size_t)(s & 1) : 0;     // ping-pong: sub-part s hands over through buffer set s % 2
         pq.ray0 = reinterpret_cast<float4*>(reinterpret_cast<char*>(c->path_rec) + set * n * MRTX_PATH_REC_BYTES); pq.ray1 = pq.ray0 + n; pq.ray2 = pq.ray1 + n;
-#if MRTX_C_AOS == 2
-        pq.c4 = pq.ray2 + n; pq.c0 = pq.c1 = pq.c2 = nullptr;
+        pq.c4 = pq.ray2 + n;
         pq.lane_of = reinterpret_cast<uint32_t*>(reinterpret_cast<float*>(pq.c4) + 3 * n);     // 12 bytes per sample
-#elif MRTX_C_AOS
-        pq.c4 = pq.ray2 + n; pq.c0 = pq.c1 = pq.c2 = nullptr;
-        pq.lane_of = reinterpret_cast<uint32_t*>(pq.c4 + n);
-#else
-        pq.c0 = reinterpret_cast<float*>(pq.ray2 + n); pq.c1 = pq.c0 + n; pq.c2 = pq.c1 + n; pq.c4 = nullptr;
-        pq.lane_of = reinterpret_cast<uint32_t*>(pq.c2 + n);
-#endif
         pq.npaths = c->path_npaths + set * ((size_t)c->path_cap + 64);
         pq.meta = c->path_meta + set * (size_t)c->path_cap;
         pq.counters = c->path_ctr + set * 8 * 16; pq.n_sub = c->path_nsub; pq.grp_log2 = c->path_grp_log2;
@@ -1228,8 +1216,6 @@ int mrtx_render_part(mrtx_ctx* c, int32_t n_blocks, int32_t part, int32_t n_part
             out->primary_hits = h[1]; out->shadow_rays = h[2];
             out->height_samples = h[3]; out->colour_fetches = h[4]; out->background_fetches = h[5];
             out->dem_fetches = h[6]; out->mip_fetches = h[7]; out->bounce_rays = h[8]; out->bounce_sun_hits = h[9];
-            if (std::getenv("MOONRT_DEBUG_STATS"))   // measurement builds (-DMRTX_PROF_MARGIN): the spare counter slots
-                std::fprintf(stderr, "libmoonrt debug stats[10..14]: %llu %llu %llu %llu %llu\n", h[10], h[11], h[12], h[13], h[14]);
         }
     }
     return MRTX_OK;

@@ -17,12 +17,10 @@ struct GridC {          // equirectangular grid: row 0 = +90 deg, column 0 = -18
     float row_scale, row_off, col_scale, col_off, wf;
 };
 
-// DEM layout in HBM (see dem_march() in mrtx_kernels.hip): 1 = row pairs, element (r, c) = float2 (D[r][c], D[r+1][c]),
-// so the 2x2 footprint of a bilinear evaluation is ONE 16-byte load; 0 = plain padded float32, two 8-byte loads.
-#ifndef MRTX_DEM_PAIRS
-#define MRTX_DEM_PAIRS 1
-#endif
-#define MRTX_DEM_ELEM_BYTES (MRTX_DEM_PAIRS ? 8 : 4)
+// DEM layout in HBM (see dem_march() in mrtx_kernels.hip): row pairs, element (r, c) = float2 (D[r][c], D[r+1][c]),
+// so the 2x2 footprint of a bilinear evaluation is ONE 16-byte load (plain padded float32, two 8-byte loads: retired,
+// DESIGN.md section 4.18).
+#define MRTX_DEM_ELEM_BYTES 8
 
 // Tile numbering.  Tile t belongs to rank t % world, and t counts the tiles in raster order with a cyclic shift of
 // `shift` columns per tile row: t = ty * tiles_x + (tx + shift * ty) % tiles_x.  With plain raster numbering and
@@ -137,15 +135,16 @@ struct FrameC {
 //             out about the ray: bit 6 = still marching after segment 1 (bits 8-31 = its horizon bound kend, the texel
 //             coordinates are those of the END of segment 1), bit 7 = hit inside segment 1 (bits 8-31 = the step k that
 //             landed at/below the surface, the coordinates are the origin's); neither = march from the origin
-//   c4 (c0/1/2 with MRTX_C_AOS = 0)  the sample's radiance so far (direct term / Sun disk / environment / overlay colour); path_kernel writes
+//   c4        the sample's radiance so far (direct term / Sun disk / environment / overlay colour); path_kernel writes
 //             the final value back when the path adds light, resolve_paths_kernel sums the 64 lanes in the butterfly
 //             order of the spec
 //   meta      per chunk: bit 31 = the chunk was deferred, bits 0-14 / 15-29 = pixel (x0, y0) of the wave's pixel block
 // A wave writes 1 KB (ray*) / 256 B (c*) contiguous per array.
 struct PathQ {
     float4* ray0; float4* ray1; float4* ray2;
-    float* c0; float* c1; float* c2;
-    float4* c4;                 // MRTX_C_AOS 1: the three of them as one float4 per sample (one 16-byte access instead of three sectors); 2: packed, 12 bytes per sample
+    float* c0; float* c1; float* c2;    // unused (null) since the three-array layout was retired; they stay because PathQ is a by-value kernel
+                                        // argument and taking them out changes the generated code of both kernels
+    float4* c4;                 // the running radiance, three floats PACKED: 12 bytes per sample (see c_load / c_store)
     uint32_t* lane_of;          // per ray record: lane + the state of its march after the trial segment (see above)
     uint8_t* npaths;            // per chunk: ray records it holds (0 for a chunk that was not deferred): zero before the launch
     uint32_t* meta;
@@ -161,14 +160,12 @@ struct PathQ {
     int32_t rare_min;           // ... and runs the rare steps (a continuation ray hit terrain; a vertex got its direct
                                 //     term) when at least this many lanes wait for them
 };
-// The running radiance of a sample as ONE float4 per sample (round 3): a path that adds light reads and writes one 64-byte sector
-// instead of three in three arrays -- path stage 5.41 -> 5.19 ms at cfg3, render and resolve unchanged (0 = the three float arrays)
-// 2 (round 4): the three floats PACKED, 12 bytes per sample -- resolve_paths_kernel streams a quarter less, the render kernel writes a
-// quarter less, a path's read-modify-write still touches one sector five times in eight: path stage 4.35 -> 4.28 ms, frame -0.12 ms
-#ifndef MRTX_C_AOS
-#define MRTX_C_AOS 2
-#endif
-#define MRTX_PATH_REC_BYTES (MRTX_C_AOS == 1 ? 68 : 64)  // per record: 3 x float4 + 3 x float (or one float4) + 1 word
+// The running radiance of a sample, the earlier layouts (retired).  Round 3: ONE float4 per sample instead of
+// three float arrays -- a path that adds light reads and writes one 64-byte sector instead of three: path stage 5.41 -> 5.19 ms at
+// cfg3, render and resolve unchanged.  Round 4, as shipped: the three floats PACKED, 12 bytes per sample -- resolve_paths_kernel
+// streams a quarter less, the render kernel writes a quarter less, a path's read-modify-write still touches one sector five times in
+// eight: path stage 4.35 -> 4.28 ms, frame -0.12 ms.
+#define MRTX_PATH_REC_BYTES 64  // per record: 3 x float4 + 3 x float + 1 word
 #define MRTX_REC_RESUME 64u
 #define MRTX_REC_HIT 128u
 

@@ -35,13 +35,6 @@
 #define MRTX_TRIAL_BATCH 1     // steps fetched together in the trial segment.  Round 4 (8 waves per SIMD, VALU issue 0.65): 1 step
 #endif                         // 16.20 ms against 16.34 with 2 -- the 64 continuation rays are incoherent, a speculated second step is
                                // mostly thrown away; the coherent marches keep MRTX_STEP_BATCH = 2 (1: 16.64 ms, 3: 16.68)
-#ifndef MRTX_ENV_PREFETCH
-#define MRTX_ENV_PREFETCH 0    // 1: render_kernel<MODE 2> fetches the environment texel of a continuation ray BEFORE its trial segment, so
-#endif                         // that the DRAM miss hides behind the march.  Bit-exact; measured on the star-map frame (gpurun_out/r4z): render
-                               // 17.28 ms against 17.06 -- the 19 % extra look-ups (rays that hit or march on) cost more than the hidden round: off
-#ifndef MRTX_TRIAL_SEGMENT
-#define MRTX_TRIAL_SEGMENT 1   // 0 = hand every continuation ray to path_kernel unmarched (A/B switch, see trace_sample)
-#endif
 
 namespace mrtx {
 
@@ -65,11 +58,7 @@ __device__ unsigned long long g_prof[16];
 #define PROF_END(i)
 #endif
 
-#ifdef MRTX_PROF_MARGIN   // measurement build: how far above the surface are the steps path_kernel evaluates? (slots 10-13 of stats[])
-enum { ST_PRIMARY = 0, ST_HITS, ST_SHADOW, ST_HEIGHT, ST_COLOUR, ST_BG, ST_FETCH, ST_MIP, ST_BOUNCE, ST_SUNHIT, ST_MALL, ST_M1, ST_M2, ST_M3, ST_N };
-#else
 enum { ST_PRIMARY = 0, ST_HITS, ST_SHADOW, ST_HEIGHT, ST_COLOUR, ST_BG, ST_FETCH, ST_MIP, ST_BOUNCE, ST_SUNHIT, ST_N };
-#endif
 
 // atan(q) ~= q * P(q^2) on [0,1], |err| <= 1.3e-7
 __device__ __forceinline__ float atan_poly(float q) {
@@ -215,39 +204,20 @@ __device__ __forceinline__ float4 nt_load4(const float4* p) {
     return make_float4(v.x, v.y, v.z, v.w);
 }
 
-// a sample's running radiance in the hand-over buffers (PathQ::c0/c1/c2, or one float4 per sample with MRTX_C_AOS)
+// a sample's running radiance in the hand-over buffers: PathQ::c4, three packed floats (12 bytes) per sample
 typedef float v3f __attribute__((ext_vector_type(3)));
 struct __attribute__((packed, aligned(4))) Tri { float x, y, z; };
 __device__ __forceinline__ void c_load(const PathQ& pq, uint32_t e, float& c0, float& c1, float& c2) {
-#if MRTX_C_AOS == 2
     const Tri v = reinterpret_cast<const Tri*>(pq.c4)[e]; c0 = v.x; c1 = v.y; c2 = v.z;
-#elif MRTX_C_AOS
-    const float4 v = pq.c4[e]; c0 = v.x; c1 = v.y; c2 = v.z;
-#else
-    c0 = pq.c0[e]; c1 = pq.c1[e]; c2 = pq.c2[e];
-#endif
 }
 __device__ __forceinline__ void c_store(const PathQ& pq, uint32_t e, float c0, float c1, float c2) {
-#if MRTX_C_AOS == 2
     { Tri v; v.x = c0; v.y = c1; v.z = c2; reinterpret_cast<Tri*>(pq.c4)[e] = v; }
-#elif MRTX_C_AOS
-    pq.c4[e] = make_float4(c0, c1, c2, 0.0f);
-#else
-    pq.c0[e] = c0; pq.c1[e] = c1; pq.c2[e] = c2;
-#endif
 }
 struct __attribute__((packed, aligned(4))) Pair { float x, y; };
 struct __attribute__((packed, aligned(8))) Quad { float a, b, c, d; };
 struct __attribute__((packed, aligned(8))) UQuad { uint32_t a, b, c, d; };
 
-// CP: cache policy of the load -- 0 plain, 1 non-temporal (a line the wave will not touch again: the incoherent marches)
-#ifndef MRTX_TRIAL_CP
-#define MRTX_TRIAL_CP 0
-#endif
-#ifndef MRTX_PATH_CP
-#define MRTX_PATH_CP 0
-#endif
-template <bool WIDE, int CP = 0>
+template <bool WIDE>
 __device__ __forceinline__ float dem_march(const FrameC& f, float rowf, float colf) {
     const float rfl = floorf(rowf), cfl = floorf(colf);
     const float fr = rowf - rfl, fc = colf - cfl;
@@ -256,35 +226,14 @@ __device__ __forceinline__ float dem_march(const FrameC& f, float rowf, float co
     const uint32_t r0p = (uint32_t)((int)rfl + 2), c0p = (uint32_t)((int)cfl + 2);
     const uint32_t idx = min(__umul24(r0p, (uint32_t)f.dem_pitch) + c0p, f.dem_maxidx);
     const char* base = reinterpret_cast<const char*>(f.dem);
-#if MRTX_DEM_PAIRS
     // row-pair layout: element (r, c) = (D[r][c], D[r+1][c]); elements (r0, c0) and (r0, c0+1) are adjacent, so the
     // whole 2x2 footprint is ONE 16-byte load -- half the gather instructions and L1 tag look-ups of two row loads
+    // (tried and retired, DESIGN.md section 4.18: two 8-byte loads from a plain float32 DEM, 14.82 ms against 14.03; non-temporal loads
+    // for the incoherent marches, path stage 6.85 ms against 5.4 -- the lines ARE reused)
     Quad q;
-    if (CP == 2) {
-        // TIMING-ONLY A/B (results wrong; -DMRTX_PATH_CP=2): what would path_kernel gain from a DEM of half the bytes per texel
-        // (16-bit codes: round-3 verdict item 6)?  The same gather, 8 bytes from a buffer addressed at 4 bytes per element, so
-        // that a 128-byte line covers 32 columns x 2 rows: an upper bound on the traffic effect, without any decode cost.
-        const Pair h = *reinterpret_cast<const Pair*>(WIDE ? base + ((uint64_t)idx << 2) : base + (idx << 2));
-        q.a = h.x; q.b = h.y; q.c = h.x; q.d = h.y;
-    } else if (CP == 1) {
-        const v4f v = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(WIDE ? base + ((uint64_t)idx << 3) : base + (idx << 3)));
-        q.a = v.x; q.b = v.y; q.c = v.z; q.d = v.w;
-    } else if (WIDE) q = *reinterpret_cast<const Quad*>(base + ((uint64_t)idx << 3));
+    if (WIDE) q = *reinterpret_cast<const Quad*>(base + ((uint64_t)idx << 3));
     else q = *reinterpret_cast<const Quad*>(base + (idx << 3));
     return lerp2(q.a, q.c, q.b, q.d, fr, fc);
-#else
-    Pair t, u;
-    if (WIDE) {
-        const char* p = base + ((uint64_t)idx << 2);
-        t = *reinterpret_cast<const Pair*>(p);
-        u = *reinterpret_cast<const Pair*>(p + ((uint64_t)(uint32_t)f.dem_pitch << 2));
-    } else {
-        const uint32_t off0 = idx << 2, off1 = off0 + ((uint32_t)f.dem_pitch << 2);
-        t = *reinterpret_cast<const Pair*>(base + off0);
-        u = *reinterpret_cast<const Pair*>(base + off1);
-    }
-    return lerp2(t.x, t.y, u.x, u.y, fr, fc);
-#endif
 }
 
 __device__ __forceinline__ int32_t wrapc(int32_t c, int32_t w) {
@@ -329,13 +278,9 @@ __device__ __forceinline__ void exact_rowcol(const FrameC& f, float pa, float pb
 // [jlo, jhi] (widened by a step each side and by 1e-5 in the bound, which dwarfs every rounding involved,
 // so approximate v_sqrt/v_rcp are fine here).  Steps outside it cannot hit and are not evaluated; the ray's
 // termination test is monotone, so it is enough to apply it at evaluated steps and at the segment end.
-// seg_setup in two phases, so that a caller can put OTHER work between the max-mip fetch and its use (fused_first_segment):
-// seg_anchors = the anchors, the quadratic and WHERE the max-mip is to be read; seg_interval = the skip interval from the cells.
-#ifndef MRTX_WIDE_TAP
-#define MRTX_WIDE_TAP 1       // a footprint of up to MRTX_TAP_COLS cells along the columns still gets its skip interval (see seg_anchors)
-#endif
+// seg_setup in two phases: seg_anchors = the anchors, the quadratic and WHERE the max-mip is to be read; seg_interval = the skip interval from the cells.
 #ifndef MRTX_TAP_COLS
-#define MRTX_TAP_COLS 4
+#define MRTX_TAP_COLS 4       // a footprint of up to MRTX_TAP_COLS cells along the columns still gets its skip interval (see seg_anchors)
 #endif
 struct MipTap { uint32_t off; bool usable, two_r, two_c; int ncol; };
 __device__ __forceinline__ void seg_anchors(const FrameC& f, float oa, float ob, float oc, float da, float db, float dc,
@@ -365,7 +310,7 @@ __device__ __forceinline__ void seg_anchors(const FrameC& f, float oa, float ob,
         // Columns shrink with cos(latitude): a ray that travels east-west at 30 degrees of latitude already covers more columns in
         // 16 steps than a cell is wide, and round 4 found 23 % of all camera and shadow segments of the cfg3 frame WITHOUT a skip
         // interval for that reason alone.  Up to four cells along the columns are therefore allowed (a second 16-byte load).
-        tap.usable = !sg.exact & (i1 - i0 <= 1) & (j1 - j0 <= (MRTX_WIDE_TAP ? MRTX_TAP_COLS - 1 : 1)) & (i0 >= -1) & (i1 <= f.mip_h) & (j0 >= -1) &
+        tap.usable = !sg.exact & (i1 - i0 <= 1) & (j1 - j0 <= MRTX_TAP_COLS - 1) & (i0 >= -1) & (i1 <= f.mip_h) & (j0 >= -1) &
                      (j1 <= f.mip_w);
         tap.two_r = i1 > i0; tap.two_c = j1 > j0; tap.ncol = j1 - j0 + 1;
 #ifdef MRTX_PROF_FULLIV
@@ -406,15 +351,13 @@ __device__ __forceinline__ void seg_setup(const FrameC& f, float oa, float ob, f
     if (tap.usable) {
         const Quad q = mip_fetch(f, tap);
         float more = 0.0f;       // D > 0 everywhere: zero is neutral for the maximum
-        if (MRTX_WIDE_TAP) {
 #pragma unroll
-            for (int c = 2; c < MRTX_TAP_COLS; c += 2) {      // columns j0 + c (and j0 + c + 1): the next two cells of the same row pair
-                if (tap.ncol > c) {
-                    const Quad q2 = *reinterpret_cast<const Quad*>(reinterpret_cast<const char*>(f.mip) + tap.off + 8u * (uint32_t)c);
-                    more = fmaxf(more, fmaxf(q2.a, tap.two_r ? q2.b : q2.a));
-                    if (tap.ncol > c + 1) more = fmaxf(more, fmaxf(q2.c, tap.two_r ? q2.d : q2.c));
-                    if (STATS) cnt[ST_MIP] += 4;
-                }
+        for (int c = 2; c < MRTX_TAP_COLS; c += 2) {      // columns j0 + c (and j0 + c + 1): the next two cells of the same row pair
+            if (tap.ncol > c) {
+                const Quad q2 = *reinterpret_cast<const Quad*>(reinterpret_cast<const char*>(f.mip) + tap.off + 8u * (uint32_t)c);
+                more = fmaxf(more, fmaxf(q2.a, tap.two_r ? q2.b : q2.a));
+                if (tap.ncol > c + 1) more = fmaxf(more, fmaxf(q2.c, tap.two_r ? q2.d : q2.c));
+                if (STATS) cnt[ST_MIP] += 4;
             }
         }
         seg_interval<STATS>(f, rq, sg, tap, q, cnt, more);
@@ -425,7 +368,7 @@ __device__ __forceinline__ void seg_setup(const FrameC& f, float oa, float ob, f
 // EXACTABLE = false: the caller knows (by ballot) that no lane of the wave is in an exact-fallback segment.
 // The quadratic needs no clamp: a non-seam, non-polar segment keeps (row, col) >= 0.5 texel inside
 // [-1, h) x [-1, w), and dem_march()'s unsigned index clamp keeps even a NaN inside the allocation.
-template <bool WIDE, bool EXACTABLE, int CP = 0>
+template <bool WIDE, bool EXACTABLE>
 __device__ __forceinline__ bool below_seg(const FrameC& f, const Seg& sg, float sk, float pa, float pb, float pc,
                                           float r2) {
     const float u = (sk - sg.sa) * f.inv_step;
@@ -435,7 +378,7 @@ __device__ __forceinline__ bool below_seg(const FrameC& f, const Seg& sg, float 
         float q2;
         exact_rowcol(f, pa, pb, pc, rowf, colf, q2);
     }
-    const float surf = f.Rf * dem_march<WIDE, CP>(f, rowf, colf);
+    const float surf = f.Rf * dem_march<WIDE>(f, rowf, colf);
     return r2 <= surf * surf;
 }
 
@@ -459,7 +402,7 @@ __device__ __forceinline__ bool below_seg(const FrameC& f, const Seg& sg, float 
 #endif
 // BOUNDED (shadow rays only; mrtx_sight_*): the ray also ends before the first step with s_k >= smax, the
 // segment's far end.  Every other caller leaves it false and compiles to the code it always had.
-template <bool WIDE, bool PRIMARY, bool STATS, bool EXACTABLE, int BATCH, int CP = 0, bool BOUNDED = false>
+template <bool WIDE, bool PRIMARY, bool STATS, bool EXACTABLE, int BATCH, bool BOUNDED = false>
 __device__ __forceinline__ void step_loop_from(const FrameC& f, float oa, float ob, float oc, float da, float db, float dc,
                                                float smax, const Seg& sg, int ka, int j, bool more, bool& go, bool& hit,
                                                float& sk_out, uint32_t* cnt) {
@@ -470,7 +413,7 @@ __device__ __forceinline__ void step_loop_from(const FrameC& f, float oa, float 
             const float pa = fmaf(sk, da, oa), pb = fmaf(sk, db, ob), pc = fmaf(sk, dc, oc);
             const float r2 = fmaf(pc, pc, fmaf(pb, pb, pa * pa));
             const bool in = (PRIMARY ? (sk <= smax) : (r2 <= f.R2f)) & (!BOUNDED || sk < smax) & (k <= f.kmax);
-            const bool bel = below_seg<WIDE, EXACTABLE, CP>(f, sg, sk, pa, pb, pc, r2);
+            const bool bel = below_seg<WIDE, EXACTABLE>(f, sg, sk, pa, pb, pc, r2);
             if (STATS) { cnt[ST_HEIGHT] += in ? 1u : 0u; cnt[ST_FETCH]++; }
 #ifdef MRTX_PROF
             cnt[11] += 1;                                    // wave-level step iterations
@@ -492,7 +435,7 @@ __device__ __forceinline__ void step_loop_from(const FrameC& f, float oa, float 
                 const float u = ((float)(ka + min(j + i, SEG_N)) * f.step - sg.sa) * f.inv_step;   // as below_seg()
                 const float rowf = fmaf(u, fmaf(u, sg.r2, sg.r1), sg.ra);
                 const float colf = fmaf(u, fmaf(u, sg.c2, sg.c1), sg.ca);
-                surf[i] = f.Rf * dem_march<WIDE, CP>(f, rowf, colf);
+                surf[i] = f.Rf * dem_march<WIDE>(f, rowf, colf);
             }
 #ifdef MRTX_PROF
             cnt[11] += 1;
@@ -519,12 +462,12 @@ __device__ __forceinline__ void step_loop_from(const FrameC& f, float oa, float 
     }
 }
 
-template <bool WIDE, bool PRIMARY, bool STATS, bool EXACTABLE, int BATCH, int CP = 0, bool BOUNDED = false>
+template <bool WIDE, bool PRIMARY, bool STATS, bool EXACTABLE, int BATCH, bool BOUNDED = false>
 __device__ __forceinline__ void step_loop(const FrameC& f, float oa, float ob, float oc, float da, float db, float dc,
                                           float smax, const Seg& sg, int ka, bool& go, bool& hit, float& sk_out,
                                           uint32_t* cnt) {
-    step_loop_from<WIDE, PRIMARY, STATS, EXACTABLE, BATCH, CP, BOUNDED>(f, oa, ob, oc, da, db, dc, smax, sg, ka, sg.jlo, sg.jlo <= sg.jhi,
-                                                           go, hit, sk_out, cnt);
+    step_loop_from<WIDE, PRIMARY, STATS, EXACTABLE, BATCH, BOUNDED>(f, oa, ob, oc, da, db, dc, smax, sg, ka, sg.jlo, sg.jlo <= sg.jhi,
+                                                                       go, hit, sk_out, cnt);
 }
 
 // STATS builds only: the spec counts a DEM evaluation at every step that is still inside; add the skipped ones.
@@ -783,7 +726,7 @@ __device__ __forceinline__ int first_kept_step(const FrameC& f, const MarchState
 // ONE 16-step segment of a march (the lanes that call it are still marching): anchors + skip interval, the steps
 // that can be at/below the surface, the termination test at the segment end.  `hit` / `sk_hit` are set by the step
 // that lands at/below the surface, `go` says whether the ray continues with the next segment.
-template <bool WIDE, bool PRIMARY, bool STATS, int BATCH, int CP = 0, int SCAN = PRIMARY ? 1 : 0, bool BOUNDED = false>
+template <bool WIDE, bool PRIMARY, bool STATS, int BATCH, int SCAN = PRIMARY ? 1 : 0, bool BOUNDED = false>
 __device__ __forceinline__ void march_segment(const FrameC& f, MarchState& m, float smax, Seg& sg, bool& go, bool& hit,
                                               float& sk_hit, uint32_t* cnt) {
     const float oa = m.oa, ob = m.ob, oc = m.oc, da = m.da, db = m.db, dc = m.dc;
@@ -819,12 +762,12 @@ __device__ __forceinline__ void march_segment(const FrameC& f, MarchState& m, fl
     PROF_BEGIN(7);
     if (STATS) cnt[ST_HEIGHT] += count_in_steps<PRIMARY, BOUNDED>(f, oa, ob, oc, da, db, dc, smax, ka, 1, sg.jlo - 1);
     if (__ballot(sg.exact) != 0ull)
-        step_loop<WIDE, PRIMARY, STATS, true, 1, CP, BOUNDED>(f, oa, ob, oc, da, db, dc, smax, sg, ka, go, hit, sk_hit, cnt);
+        step_loop<WIDE, PRIMARY, STATS, true, 1, BOUNDED>(f, oa, ob, oc, da, db, dc, smax, sg, ka, go, hit, sk_hit, cnt);
     else
-        step_loop<WIDE, PRIMARY, STATS, false, BATCH, CP, BOUNDED>(f, oa, ob, oc, da, db, dc, smax, sg, ka, go, hit, sk_hit, cnt);
+        step_loop<WIDE, PRIMARY, STATS, false, BATCH, BOUNDED>(f, oa, ob, oc, da, db, dc, smax, sg, ka, go, hit, sk_hit, cnt);
     PROF_END(7);
 #ifdef MRTX_PROF
-#if !defined(MRTX_PROF_SPREAD) && !defined(MRTX_PROF_TRIAL) && !defined(MRTX_PROF_FULLIV)
+#if !defined(MRTX_PROF_TRIAL) && !defined(MRTX_PROF_FULLIV)
     cnt[8] += 1;                                     // wave-level segments
     cnt[9] += (uint32_t)__popcll(__ballot(true));    // lanes alive in them
     cnt[PRIMARY ? 13 : 14] += (__ballot(sg.jlo <= sg.jhi) == 0ull) ? 1u : 0u;   // wave-level segments nobody steps in
@@ -847,7 +790,7 @@ __device__ __forceinline__ bool march(const FrameC& f, float oa, float ob, float
     MarchState m;
     bool hit = false;
     bool go = march_begin<PRIMARY, STATS, false, BOUNDED>(f, oa, ob, oc, da, db, dc, m, cnt, smax);
-    while (go) march_segment<WIDE, PRIMARY, STATS, BATCH, 0, SCAN, BOUNDED>(f, m, smax, sg, go, hit, sk_hit, cnt);
+    while (go) march_segment<WIDE, PRIMARY, STATS, BATCH, SCAN, BOUNDED>(f, m, smax, sg, go, hit, sk_hit, cnt);
     return hit;
 }
 
@@ -885,7 +828,6 @@ __device__ __forceinline__ void duff_basis(float na, float nb, float nc, float& 
 }
 
 // D7: nearest environment texel along a scene-frame direction
-// ... in two halves, so that a caller can issue the fetch long before it needs the texel: the texel's index, and its decoding
 __device__ __forceinline__ int64_t env_texel_index(const FrameC& f, float dx, float dy, float dz) {
     float el, az;
     latlon(dx, dy, dz, fmaf(dy, dy, dx * dx), el, az);
@@ -1074,11 +1016,9 @@ __device__ __forceinline__ bool continue_path(const FrameC& f, const Vertex& v, 
 // disk bounces onto the Moon small through its radiance 2.0 and by parking it, moon_renderer.py:109-111, :757-760),
 // then the environment texel along its direction; adds throughput x radiance.  Moon frame, float32: distance of the
 // disk centre from the ray.
-// PRE: the caller fetched the environment texel of this direction already (`pre_px`; render_kernel<MODE 2> issues the fetch before the
-// trial segment so that its latency hides behind the march): same texel, same result, no load here
-template <bool STATS, bool PRE = false>
+template <bool STATS>
 __device__ __forceinline__ bool escaped_radiance(const FrameC& f, float boa, float bob, float boc, float bda, float bdb,
-                                                 float bdc, float& e0, float& e1, float& e2, uint32_t* cnt, uint32_t pre_px = 0u) {
+                                                 float bdc, float& e0, float& e1, float& e2, uint32_t* cnt) {
     if (CF(f)->sun_on) {
         const float sa = CF(f)->Sb[0] - boa, sb = CF(f)->Sb[1] - bob, sc = CF(f)->Sb[2] - boc;
         const float bq = fmaf(sc, bdc, fmaf(sb, bdb, sa * bda));
@@ -1091,24 +1031,19 @@ __device__ __forceinline__ bool escaped_radiance(const FrameC& f, float boa, flo
         }
     }
     if (CF(f)->bg) {   // environment radiance along its direction (scene frame)
-        if (PRE) {
-            env_decode(pre_px, e0, e1, e2);
-            if (STATS) cnt[ST_BG]++;
-        } else {
-            float ex, ey, ez;
-            to_scene_dir(f, bda, bdb, bdc, ex, ey, ez);
-            env_lookup<STATS>(f, ex, ey, ez, e0, e1, e2, cnt);
-        }
+        float ex, ey, ez;
+        to_scene_dir(f, bda, bdb, bdc, ex, ey, ez);
+        env_lookup<STATS>(f, ex, ey, ez, e0, e1, e2, cnt);
         return true;
     }
     return false;
 }
-template <bool STATS, bool PRE = false>
+template <bool STATS>
 __device__ __forceinline__ void escaped_path(const FrameC& f, float boa, float bob, float boc, float bda, float bdb,
                                              float bdc, float t0r, float t1r, float t2r, float& c0, float& c1,
-                                             float& c2, uint32_t* cnt, uint32_t pre_px = 0u) {
+                                             float& c2, uint32_t* cnt) {
     float e0, e1, e2;
-    if (escaped_radiance<STATS, PRE>(f, boa, bob, boc, bda, bdb, bdc, e0, e1, e2, cnt, pre_px)) {
+    if (escaped_radiance<STATS>(f, boa, bob, boc, bda, bdb, bdc, e0, e1, e2, cnt)) {
         c0 = fmaf(t0r, e0, c0); c1 = fmaf(t1r, e1, c1); c2 = fmaf(t2r, e2, c2);
     }
 }
@@ -1171,110 +1106,15 @@ __device__ __forceinline__ float nearest_capsule(const FrameC& f, int lt, float 
     return which >= 0 ? best : -1.0e30f;
 }
 
-// ---- render_kernel<MODE 2>, an experiment that is NOT the shipped order (round 3; kept as an A/B switch with its measurement):
-// the shadow ray of the first vertex and the FIRST segment of its continuation ray marched TOGETHER.  Both rays leave the same
-// point (vertex + scene_epsilon * normal: light_sample and continue_path build it with the same expression), so its exact texel
-// coordinates and its horizon-mip cell are evaluated / fetched once; the two segment set-ups are issued back to back (both
-// max-mip fetches in flight together) and the step loop evaluates the next steps of BOTH rays per iteration, so that the trial
-// segment rides the memory rounds of the shadow march instead of adding ~4 dependent rounds of its own after it.  Per ray the
-// evaluations, their order and every counter are those of march_begin_at + march_segment: bit-identical (tools/quick_parity.py).
-// Measured at cfg3, S1, (2,4) (gpurun_out/r3b, profiles/r03_mode2_ab.md): render_kernel<MODE 2> 18.9 ms as shipped;
-//   MRTX_FUSED_TRIAL=1: 22.7 ms (147 VGPRs: 3 waves per SIMD instead of 4), 23.6 ms when held to 128 VGPRs (16 spilled);
-//   MRTX_FUSED_TRIAL=2 (only the origin's coordinates and horizon cell shared, marches in sequence): 19.0 ms -- 65 VALU per
-//   sample less buy nothing;
+// ---- render_kernel<MODE 2>, tried in round 3 and retired (profiles/r03_mode2_ab.md): the shadow ray of the
+// first vertex and the FIRST segment of its continuation ray marched TOGETHER, so that the trial segment rides the memory rounds of
+// the shadow march.  Bit-identical.  Measured at cfg3, S1, (2,4): render_kernel<MODE 2> 18.9 ms as shipped; fused first segment
+// 22.7 ms (147 VGPRs: 3 waves per SIMD instead of 4), 23.6 ms when held to 128 VGPRs (16 spilled); only the origin's coordinates and
+// horizon cell shared, the marches in sequence: 19.0 ms -- 65 VALU per sample less bought nothing;
 // and the shipped kernel under an occupancy cap (tools/occ_sweep.sh): 3 waves per SIMD 23.4 ms, 4 (as shipped) 18.9 ms, while a
-// launch bound of 5 / 6 waves (96 / 80 VGPRs, 22+ spilled) gives 22.2 / 23.3 ms.  The kernel is bound by the dependent-load
+// launch bound of 5 / 6 waves (96 / 80 VGPRs, 22+ spilled) gave 22.2 / 23.3 ms.  The kernel is bound by the dependent-load
 // rounds a wave goes through times the waves a SIMD can hold; two more live march states cost a wave slot, which is worth
 // more than the four rounds the fusion hides.
-#ifndef MRTX_FUSED_TRIAL
-#define MRTX_FUSED_TRIAL 0     // 1 = fused first segment, 2 = shared origin only, 0 = one march after the other (ships)
-#endif
-#if MRTX_FUSED_TRIAL == 1
-#if MRTX_WIDE_TAP
-#error "fused_first_segment reads one max-mip element pair per ray: build it with -DMRTX_WIDE_TAP=0"
-#endif
-template <bool WIDE, bool STATS>
-__device__ __forceinline__ void fused_first_segment(const FrameC& f, MarchState& ms, MarchState& mt, Seg& sgs, Seg& sgt,
-                                                    bool& go_s, bool& go_t, bool& hit_s, bool& hit_t, float& sk_s, float& sk_t,
-                                                    uint32_t* cnt) {
-    constexpr int B = 2;
-    float rBs, cBs, qBs, rBt, cBt, qBt;
-    MipTap tap_s, tap_t;
-    seg_anchors(f, ms.oa, ms.ob, ms.oc, ms.da, ms.db, ms.dc, ms.ka, ms.rowA, ms.colA, ms.q2A, sgs, rBs, cBs, qBs, tap_s);
-    seg_anchors(f, mt.oa, mt.ob, mt.oc, mt.da, mt.db, mt.dc, mt.ka, mt.rowA, mt.colA, mt.q2A, sgt, rBt, cBt, qBt, tap_t);
-    tap_s.usable &= go_s; tap_t.usable &= go_t;
-    if (f.mip != nullptr) {                                  // wave-uniform
-        tap_s.off = tap_s.usable ? tap_s.off : 0u; tap_t.off = tap_t.usable ? tap_t.off : 0u;
-        const Quad qs = mip_fetch(f, tap_s), qt = mip_fetch(f, tap_t);     // unconditional: both in flight together
-        if (tap_s.usable) seg_interval<STATS>(f, ms.rq, sgs, tap_s, qs, cnt);
-        if (tap_t.usable) seg_interval<STATS>(f, mt.rq, sgt, tap_t, qt, cnt);
-    }
-    sgs.jhi = max(min(sgs.jhi, ms.kend - ms.ka), sgs.jlo - 1);   // steps beyond kend cannot be at/below the surface
-    sgt.jhi = max(min(sgt.jhi, mt.kend - mt.ka), sgt.jlo - 1);
-    if (STATS) {
-        if (go_s) cnt[ST_HEIGHT] += count_in_steps<false>(f, ms.oa, ms.ob, ms.oc, ms.da, ms.db, ms.dc, 0.0f, ms.ka, 1, sgs.jlo - 1);
-        if (go_t) cnt[ST_HEIGHT] += count_in_steps<false>(f, mt.oa, mt.ob, mt.oc, mt.da, mt.db, mt.dc, 0.0f, mt.ka, 1, sgt.jlo - 1);
-    }
-    int js = sgs.jlo, jt = sgt.jlo;
-    bool more_s = go_s & (js <= sgs.jhi), more_t = go_t & (jt <= sgt.jhi);
-    if (__ballot((go_s & sgs.exact) | (go_t & sgt.exact)) == 0ull) {
-        // both rays step while both have lanes stepping; what is left of either one afterwards runs in its own loop below
-        while (__ballot(more_s) != 0ull && __ballot(more_t) != 0ull) {
-            float surf_s[B], surf_t[B];
-#pragma unroll
-            for (int i = 0; i < B; i++) {
-                // steps past jhi are evaluated at the segment's last step instead (inside the quadratic's range), as in step_loop
-                const float us = ((float)(ms.ka + min(js + i, SEG_N)) * f.step - sgs.sa) * f.inv_step;
-                surf_s[i] = f.Rf * dem_march<WIDE>(f, fmaf(us, fmaf(us, sgs.r2, sgs.r1), sgs.ra), fmaf(us, fmaf(us, sgs.c2, sgs.c1), sgs.ca));
-                const float ut = ((float)(mt.ka + min(jt + i, SEG_N)) * f.step - sgt.sa) * f.inv_step;
-                surf_t[i] = f.Rf * dem_march<WIDE>(f, fmaf(ut, fmaf(ut, sgt.r2, sgt.r1), sgt.ra), fmaf(ut, fmaf(ut, sgt.c2, sgt.c1), sgt.ca));
-            }
-            bool act = more_s;
-#pragma unroll
-            for (int i = 0; i < B; i++) {
-                const int k = ms.ka + js + i;
-                const float sk = (float)k * f.step;
-                const float pa = fmaf(sk, ms.da, ms.oa), pb = fmaf(sk, ms.db, ms.ob), pc = fmaf(sk, ms.dc, ms.oc);
-                const float r2 = fmaf(pc, pc, fmaf(pb, pb, pa * pa));
-                const bool in = (r2 <= f.R2f) & (k <= f.kmax);
-                const bool bel = r2 <= surf_s[i] * surf_s[i];
-                if (STATS) { cnt[ST_HEIGHT] += (act & in) ? 1u : 0u; cnt[ST_FETCH] += act ? 1u : 0u; }
-                hit_s = act ? (in & bel) : hit_s;
-                go_s = act ? (in & !bel) : go_s;
-                sk_s = act ? sk : sk_s;
-                act = act & go_s & (js + i + 1 <= sgs.jhi);
-            }
-            js += B; more_s = act;
-            act = more_t;
-#pragma unroll
-            for (int i = 0; i < B; i++) {
-                const int k = mt.ka + jt + i;
-                const float sk = (float)k * f.step;
-                const float pa = fmaf(sk, mt.da, mt.oa), pb = fmaf(sk, mt.db, mt.ob), pc = fmaf(sk, mt.dc, mt.oc);
-                const float r2 = fmaf(pc, pc, fmaf(pb, pb, pa * pa));
-                const bool in = (r2 <= f.R2f) & (k <= f.kmax);
-                const bool bel = r2 <= surf_t[i] * surf_t[i];
-                if (STATS) { cnt[ST_HEIGHT] += (act & in) ? 1u : 0u; cnt[ST_FETCH] += act ? 1u : 0u; }
-                hit_t = act ? (in & bel) : hit_t;
-                go_t = act ? (in & !bel) : go_t;
-                sk_t = act ? sk : sk_t;
-                act = act & go_t & (jt + i + 1 <= sgt.jhi);
-            }
-            jt += B; more_t = act;
-        }
-        if (__ballot(more_s) != 0ull)
-            step_loop_from<WIDE, false, STATS, false, MRTX_STEP_BATCH>(f, ms.oa, ms.ob, ms.oc, ms.da, ms.db, ms.dc, 0.0f, sgs, ms.ka, js, more_s, go_s, hit_s, sk_s, cnt);
-        if (__ballot(more_t) != 0ull)
-            step_loop_from<WIDE, false, STATS, false, MRTX_TRIAL_BATCH>(f, mt.oa, mt.ob, mt.oc, mt.da, mt.db, mt.dc, 0.0f, sgt, mt.ka, jt, more_t, go_t, hit_t, sk_t, cnt);
-    } else {                                                 // a lane needs exact texel coordinates at every step (seam / pole)
-        step_loop_from<WIDE, false, STATS, true, 1>(f, ms.oa, ms.ob, ms.oc, ms.da, ms.db, ms.dc, 0.0f, sgs, ms.ka, js, more_s, go_s, hit_s, sk_s, cnt);
-        step_loop_from<WIDE, false, STATS, true, 1>(f, mt.oa, mt.ob, mt.oc, mt.da, mt.db, mt.dc, 0.0f, sgt, mt.ka, jt, more_t, go_t, hit_t, sk_t, cnt);
-    }
-    segment_tail<false, STATS>(f, ms, 0.0f, sgs, go_s, rBs, cBs, qBs, cnt);
-    segment_tail<false, STATS>(f, mt, 0.0f, sgt, go_t, rBt, cBt, qBt, cnt);
-}
-
-#endif   // MRTX_FUSED_TRIAL == 1
 
 // ---- MODE 3 (sky-only tiles, environment map bound): the pixel-uniform shortcut.
 // A 4K pixel of the default view subtends 1/11 of a texel of the reference's 16k star map, so the 64 samples of most sky pixels
@@ -1323,30 +1163,23 @@ __device__ __forceinline__ bool sky_pixel_uniform(const FrameC& f, int x, int y,
     return uni;
 }
 
-// ---- LDS as the spill space of render_kernel<MODE 2> (round 4, MRTX_LDS_PARK).
+// ---- LDS as the spill space of render_kernel<MODE 2> (round 4).
 // The kernel's time follows the waves a SIMD holds (1 -> 2 -> 3 -> 4 waves: 52 -> 29 -> 23 -> 19 ms, profiles/r03_mode2_ab.md) and the
 // fifth wave needs <= 96 VGPRs; the compiler's own 96-VGPR code spills 17 registers to scratch and loses its load clustering.  What
 // is COLD while a march runs -- the first vertex (point, normal, albedo: 9), the sample's RNG key and the radiance the light sample
 // carries across the shadow march; the running radiance, throughput and key across the trial segment -- is parked in LDS instead:
-// lane-private 16-byte slots (ds_write_b128 / ds_read_b128, consecutive lanes = consecutive 16-byte slots: conflict-free), three
-// slots = 3 KB per wave, 60 KB per CU at 20 waves.  The values come back bit for bit, so nothing in the arithmetic changes.
+// lane-private 16-byte slots (ds_write_b128 / ds_read_b128, consecutive lanes = consecutive 16-byte slots: conflict-free).
+// The values come back bit for bit, so nothing in the arithmetic changes.
 // A compiler-level memory barrier on either side keeps LLVM from forwarding the stored values to the loads (which would keep them
 // in registers after all).
-#ifndef MRTX_LDS_PARK
-#define MRTX_LDS_PARK 1
-#endif
-#ifndef MRTX_PARK_SHARE_ORIGIN
-#define MRTX_PARK_SHARE_ORIGIN 1     // the shadow ray and the continuation ray leave the SAME point (vertex + scene_epsilon * normal): its exact
-#endif                               // texel coordinates and horizon cell are evaluated once and sit out the shadow march in a fourth slot
-#define MRTX_PARK_SLOTS (MRTX_PARK_SHARE_ORIGIN ? 4 : 3)
-#ifndef MRTX_WG_WAVES
-#define MRTX_WG_WAVES 1       // waves per workgroup of render_kernel (see there)
-#endif
+// The shadow ray and the continuation ray leave the SAME point (vertex + scene_epsilon * normal): its exact texel coordinates and
+// horizon cell are evaluated once and sit out the shadow march in a fourth slot -- 4 KB per wave.
+#define MRTX_PARK_SLOTS 4
 __device__ __forceinline__ void park_put(v4f* park, int slot, float a, float b, float c, float d) {
     const v4f v = {a, b, c, d};
-    park[slot * (64 * MRTX_WG_WAVES) + threadIdx.x] = v;
+    park[slot * 64 + threadIdx.x] = v;
 }
-__device__ __forceinline__ v4f park_get(const v4f* park, int slot) { return park[slot * (64 * MRTX_WG_WAVES) + threadIdx.x]; }
+__device__ __forceinline__ v4f park_get(const v4f* park, int slot) { return park[slot * 64 + threadIdx.x]; }
 __device__ __forceinline__ void park_fence() { asm volatile("" ::: "memory"); }
 
 struct SampleOut {
@@ -1366,13 +1199,12 @@ template <bool STATS, bool WIDE, int MODE, bool OVERLAY>
 __device__ __forceinline__ void trace_sample(const FrameC& f, int lt, int x, int y, uint32_t gs, SampleOut& o,
                                              uint32_t* cnt, bool lead = false, v4f* park = nullptr) {
     constexpr bool BOUNCE = MODE == 1, DEFER = MODE == 2;
-    constexpr bool PARK = DEFER && MRTX_LDS_PARK != 0;
     // (writing the hit record from here, as soon as it is known, instead of carrying it to the end of the wave was measured for the
-    // direct kernel: 13.33 ms against 13.21 -- its single late store stays.  render_kernel<MODE 2> with MRTX_LDS_PARK is held to 96
+    // direct kernel: 13.33 ms against 13.21 -- its single late store stays.  render_kernel<MODE 2>, which parks in LDS, is held to 96
     // VGPRs, where four registers carried through three marches do count: its launches hold ONE block, so the record of sample 0
     // (`lead`) IS the frame's hit record and goes to memory right here)
     auto emit_hit = [&](float h0, float h1, float h2, float h3) {
-        if (PARK) {
+        if (DEFER) {
             if (lead) reinterpret_cast<float4*>(CF(f)->hits)[(int64_t)y * f.W + x] = make_float4(h0, h1, h2, h3);
         } else {
             o.h0 = h0; o.h1 = h1; o.h2 = h2; o.h3 = h3;
@@ -1454,25 +1286,6 @@ __device__ __forceinline__ void trace_sample(const FrameC& f, int lt, int x, int
         hit = march<WIDE, true, STATS, BATCH>(f, pa, pb, pc, da, db, dc, smax, sg, hi, cnt);
         PROF_END(2);
         PROF_BEGIN(3);
-#ifdef MRTX_PROF_SPREAD   // measurement only: spread of the lanes' texel coordinates at the primary hit (would an LDS tile cover the wave?)
-        {
-            const float u = (hi - sg.sa) * f.inv_step;
-            float rw = fmaf(u, fmaf(u, sg.r2, sg.r1), sg.ra), cl = fmaf(u, fmaf(u, sg.c2, sg.c1), sg.ca);
-            float rmin = hit ? rw : 1e30f, rmax = hit ? rw : -1e30f, cmin = hit ? cl : 1e30f, cmax = hit ? cl : -1e30f;
-            for (int m = 1; m < 64; m <<= 1) {
-                rmin = fminf(rmin, __shfl_xor(rmin, m, 64)); rmax = fmaxf(rmax, __shfl_xor(rmax, m, 64));
-                cmin = fminf(cmin, __shfl_xor(cmin, m, 64)); cmax = fmaxf(cmax, __shfl_xor(cmax, m, 64));
-            }
-            const float er = rmax - rmin, ec = cmax - cmin;
-            if (__ballot(hit) != 0ull) {
-                const float e = fmaxf(er, ec);
-                cnt[13] += (e <= 8.0f) ? 1u : 0u;
-                cnt[14] += (e <= 16.0f) ? 1u : 0u;
-                cnt[15] += (e <= 28.0f) ? 1u : 0u;
-                cnt[9] += 1u;
-            }
-        }
-#endif
         if (hit) {
             // hi = (float)k * step of the first sample below; k recovered exactly (|k*step/step - k| << 0.5)
             const int k = (int)rintf(hi * f.inv_step);
@@ -1524,84 +1337,21 @@ __device__ __forceinline__ void trace_sample(const FrameC& f, int lt, int x, int
     float t0r = 1.0f, t1r = 1.0f, t2r = 1.0f;   // path throughput
     uint32_t seg = 1;
     float ul1 = u2, ul2 = u3;
-#if MRTX_FUSED_TRIAL && MRTX_TRIAL_SEGMENT && !defined(MRTX_PROF)
-    if (DEFER) {
-        // Vertex 1: its light sample's shadow ray and the first segment of its continuation ray share their origin and are
-        // marched together (fused_first_segment); then the rest of the shadow march.  Same evaluations, results and counters
-        // as direct_light() followed by the trial segment below (MRTX_FUSED_TRIAL = 0).
-        float so_a, so_b, so_c, sw_a, sw_b, sw_c, carried = 0.0f;
-        const bool have_s = light_sample(f, v, ul1, ul2, so_a, so_b, so_c, sw_a, sw_b, sw_c, carried);
-        if (STATS && have_s) cnt[ST_SHADOW]++;
-        const float k0 = t0r * v.al0, k1 = t1r * v.al1, k2 = t2r * v.al2;      // the direct term's weights: throughput BEFORE the bounce
-        const bool have_c = continue_path(f, v, ks, 1u, t0r, t1r, t2r, o.oa, o.ob, o.oc, o.da, o.db, o.dc);
-        if (STATS && have_c) cnt[ST_BOUNCE]++;
-        float row0, col0, q2o;
-        exact_rowcol(f, so_a, so_b, so_c, row0, col0, q2o);                     // ONE evaluation for both rays' origin
-        const bool hm_on = CF(f)->hmip != nullptr;                              // wave-uniform
-        const float cell = hm_on ? horizon_cell(f, row0, col0) : 0.0f;         // ... and one horizon-mip look-up
-        MarchState ms, mt;
-        ms.rowA = mt.rowA = row0; ms.colA = mt.colA = col0;
-        // an absent ray is a ray of length zero from the same origin: its set-up arithmetic stays finite and is discarded
-        // (b = 0 and a = 0 make horizon_kend's chord bound infinite, so it never cuts and never counts anything)
-        bool go_s = march_begin_at<false, STATS, false, true>(f, so_a, so_b, so_c, have_s ? sw_a : 0.0f, have_s ? sw_b : 0.0f,
-                                                              have_s ? sw_c : 0.0f, ms, cnt, cell) & have_s;
-        bool go_t = march_begin_at<false, STATS, false, true>(f, so_a, so_b, so_c, have_c ? o.da : 0.0f, have_c ? o.db : 0.0f,
-                                                              have_c ? o.dc : 0.0f, mt, cnt, cell) & have_c;
-        bool hit_s = false, hit_t = false;
-        float sk_s = 0.0f, sk_t = 0.0f;
-        Seg sgs, sgt;
-#if MRTX_FUSED_TRIAL == 2     // A/B: shared origin coordinates and horizon cell only, the two marches one after the other
-        while (go_s) march_segment<WIDE, false, STATS, BATCH, 0, 2>(f, ms, 0.0f, sgs, go_s, hit_s, sk_s, cnt);
-        if (go_t) march_segment<WIDE, false, STATS, MRTX_TRIAL_BATCH>(f, mt, 0.0f, sgt, go_t, hit_t, sk_t, cnt);
-#else
-        const bool any_s = __ballot(go_s) != 0ull, any_t = __ballot(go_t) != 0ull;
-        if (any_s && any_t) {
-            fused_first_segment<WIDE, STATS>(f, ms, mt, sgs, sgt, go_s, go_t, hit_s, hit_t, sk_s, sk_t, cnt);
-        } else if (any_t) {
-            if (go_t) march_segment<WIDE, false, STATS, MRTX_TRIAL_BATCH>(f, mt, 0.0f, sgt, go_t, hit_t, sk_t, cnt);
-        }
-        while (go_s) march_segment<WIDE, false, STATS, BATCH, 0, 2>(f, ms, 0.0f, sgs, go_s, hit_s, sk_s, cnt);
-#endif
-        const float wgt = (have_s && !hit_s) ? carried : 0.0f;
-        o.c0 = fmaf(k0, wgt, o.c0);
-        o.c1 = fmaf(k1, wgt, o.c1);
-        o.c2 = fmaf(k2, wgt, o.c2);
-        if (have_c) {
-            o.row = row0; o.col = col0;
-            o.t0 = t0r; o.t1 = t1r; o.t2 = t2r;
-            o.ks = ks; o.aux = 0u;
-            if (!go_t && !hit_t) {
-                escaped_path<STATS>(f, o.oa, o.ob, o.oc, o.da, o.db, o.dc, t0r, t1r, t2r, o.c0, o.c1, o.c2, cnt);
-            } else {
-                o.path = true;
-                if (hit_t) {
-                    o.aux = MRTX_REC_HIT | ((uint32_t)(int)rintf(sk_t * f.inv_step) << 8);
-                } else {
-                    o.aux = MRTX_REC_RESUME | ((uint32_t)mt.kend << 8);
-                    o.row = mt.rowA; o.col = mt.colA;
-                }
-            }
-        }
-        return;
-    }
-#endif
-    uint32_t ksl = ks;      // the sample's RNG key as the continuation uses it (PARK: the copy that came back from LDS)
-    float org_row = 0.0f, org_col = 0.0f, org_cell = 0.0f;   // PARK + MRTX_PARK_SHARE_ORIGIN: the lifted vertex on the DEM grid
+    uint32_t ksl = ks;      // the sample's RNG key as the continuation uses it (DEFER: the copy that came back from LDS)
+    float org_row = 0.0f, org_col = 0.0f, org_cell = 0.0f;   // DEFER: the lifted vertex on the DEM grid
     for (;;) {
         PROF_BEGIN(5);
         float wgt;
-        if (PARK) {
+        if (DEFER) {
             // direct_light() with the vertex, the key and the carried radiance parked in LDS while the shadow ray marches
             float oa, ob, oc, wa, wb, wc, carried = 0.0f;
             const bool have_s = light_sample(f, v, ul1, ul2, oa, ob, oc, wa, wb, wc, carried);
-#if MRTX_PARK_SHARE_ORIGIN
             // the origin's exact texel coordinates and horizon-mip cell: ONE evaluation / look-up for the shadow ray and, below,
             // for the continuation ray (continue_path builds its origin with the very expression light_sample uses)
             float q2o;
             exact_rowcol(f, oa, ob, oc, org_row, org_col, q2o);
             org_cell = CF(f)->hmip != nullptr ? horizon_cell(f, org_row, org_col) : 0.0f;
             park_put(park, 3, org_row, org_col, org_cell, 0.0f);
-#endif
             park_put(park, 0, v.pa, v.pb, v.pc, v.na);
             park_put(park, 1, v.nb, v.nc, v.al0, v.al1);
             park_put(park, 2, v.al2, __uint_as_float(ksl), carried, 0.0f);
@@ -1611,19 +1361,13 @@ __device__ __forceinline__ void trace_sample(const FrameC& f, int lt, int x, int
                 if (STATS) cnt[ST_SHADOW]++;
                 Seg ssg;
                 float sk_occ;
-#if MRTX_PARK_SHARE_ORIGIN
                 MarchState ms;
                 ms.rowA = org_row; ms.colA = org_col;
                 bool sgo = march_begin_at<false, STATS, false, true>(f, oa, ob, oc, wa, wb, wc, ms, cnt, org_cell);
-                while (sgo) march_segment<WIDE, false, STATS, MRTX_SHADOW_BATCH, 0, 2>(f, ms, 0.0f, ssg, sgo, occluded, sk_occ, cnt);
-#else
-                occluded = march<WIDE, false, STATS, BATCH, 2>(f, oa, ob, oc, wa, wb, wc, 0.0f, ssg, sk_occ, cnt);
-#endif
+                while (sgo) march_segment<WIDE, false, STATS, MRTX_SHADOW_BATCH, 2>(f, ms, 0.0f, ssg, sgo, occluded, sk_occ, cnt);
             }
             park_fence();
-#if MRTX_PARK_SHARE_ORIGIN
             { const v4f p3 = park_get(park, 3); org_row = p3.x; org_col = p3.y; org_cell = p3.z; }
-#endif
             const v4f p0 = park_get(park, 0), p1 = park_get(park, 1), p2 = park_get(park, 2);
             v.pa = p0.x; v.pb = p0.y; v.pc = p0.z; v.na = p0.w;
             v.nb = p1.x; v.nc = p1.y; v.al0 = p1.z; v.al1 = p1.w;
@@ -1641,22 +1385,20 @@ __device__ __forceinline__ void trace_sample(const FrameC& f, int lt, int x, int
             // whether to continue, build their continuation rays and locate the ray origins on the DEM grid -- is done
             // here at full occupancy; the queue record is a ray that is ready to march.
             if (continue_path(f, v, ksl, 1u, t0r, t1r, t2r, o.oa, o.ob, o.oc, o.da, o.db, o.dc)) {
-                constexpr bool SHARED = PARK && MRTX_PARK_SHARE_ORIGIN != 0;
-                if (SHARED) {
-                    o.row = org_row; o.col = org_col;
-                } else {
-                    float q2;
-                    exact_rowcol(f, o.oa, o.ob, o.oc, o.row, o.col, q2);
-                }
+                o.row = org_row; o.col = org_col;
                 o.t0 = t0r; o.t1 = t1r; o.t2 = t2r;
                 o.ks = ksl; o.aux = 0u;
                 if (STATS) cnt[ST_BOUNCE]++;
-#if MRTX_TRIAL_SEGMENT
                 // The FIRST segment of the continuation ray is marched right here: the 64 rays of the pixel still start
                 // within a texel of each other, every lane is busy, and four rays in five end inside it without touching
                 // the terrain again (they have cleared everything in reach, horizon_kend, or left the shell) -- those paths
                 // are finished in this wave.  A ray that hits, or is still marching after 16 steps, goes to path_kernel WITH
                 // what the segment found out: the step that landed below the surface, or the state at the segment's end.
+                // (Tried in round 4 and retired, DESIGN.md section 4.18: fetching the environment texel of the ray's direction BEFORE
+                // the segment, so that the DRAM miss hides behind the march -- 84 % of the continuation rays end in it by leaving the
+                // Moon and then read one texel of a 537 MB map.  Bit-exact; on the star-map frame render took 17.28 ms against 17.06:
+                // the 19 % extra look-ups, for rays that hit or march on, cost more than the hidden round.  Handing every ray over
+                // unmarched instead: render 11.2 + paths 11.1 = 22.3 ms against a 17.6 ms frame.)
 #ifdef MRTX_PROF
                 uint32_t tcnt[16];
 #pragma unroll
@@ -1671,35 +1413,20 @@ __device__ __forceinline__ void trace_sample(const FrameC& f, int lt, int x, int
                 }
                 MarchState tm;
                 tm.rowA = o.row; tm.colA = o.col;
-                // With an environment map bound (the reference's default, moon_renderer.py:604-607) 84 % of the continuation rays
-                // end in this segment by leaving the Moon, and each then reads one texel of a 537 MB map -- a DRAM miss at the very
-                // end of the wave's life.  The texel depends on the ray's direction alone: its fetch is issued HERE and lands while
-                // the segment is marched (a wasted 4-byte fetch for the rays that hit or march on).
-                constexpr bool ENVPRE = MRTX_ENV_PREFETCH != 0;
-                uint32_t env_px = 0u;
-                if (ENVPRE && CF(f)->bg != nullptr) {          // wave-uniform
-                    float ex, ey, ez;
-                    to_scene_dir(f, o.da, o.db, o.dc, ex, ey, ez);
-                    env_px = reinterpret_cast<const uint32_t*>(CF(f)->bg)[env_texel_index(f, ex, ey, ez)];
-                }
-                if (PARK) {     // the radiance so far, the throughput and the key sit out the trial segment in LDS
-                    park_put(park, 0, o.c0, o.c1, o.c2, o.t0);
-                    park_put(park, 1, o.t1, o.t2, __uint_as_float(o.ks), 0.0f);
-                    park_fence();
-                }
-                bool tgo = SHARED ? march_begin_at<false, STATS, false, true>(f, o.oa, o.ob, o.oc, o.da, o.db, o.dc, tm, tcnt, org_cell)
-                                  : march_begin_at<false, STATS>(f, o.oa, o.ob, o.oc, o.da, o.db, o.dc, tm, tcnt);
+                // the radiance so far, the throughput and the key sit out the trial segment in LDS
+                park_put(park, 0, o.c0, o.c1, o.c2, o.t0);
+                park_put(park, 1, o.t1, o.t2, __uint_as_float(o.ks), 0.0f);
+                park_fence();
+                bool tgo = march_begin_at<false, STATS, false, true>(f, o.oa, o.ob, o.oc, o.da, o.db, o.dc, tm, tcnt, org_cell);
                 bool thit = false;
                 Seg tsg;
                 float tsk = 0.0f;
-                if (tgo) march_segment<WIDE, false, STATS, MRTX_TRIAL_BATCH, MRTX_TRIAL_CP, 3>(f, tm, 0.0f, tsg, tgo, thit, tsk, tcnt);
-                if (PARK) {
-                    park_fence();
-                    const v4f p0 = park_get(park, 0), p1 = park_get(park, 1);
-                    o.c0 = p0.x; o.c1 = p0.y; o.c2 = p0.z; o.t0 = p0.w;
-                    o.t1 = p1.x; o.t2 = p1.y; o.ks = __float_as_uint(p1.z);
-                    t0r = o.t0; t1r = o.t1; t2r = o.t2;
-                }
+                if (tgo) march_segment<WIDE, false, STATS, MRTX_TRIAL_BATCH, 3>(f, tm, 0.0f, tsg, tgo, thit, tsk, tcnt);
+                park_fence();
+                const v4f p0 = park_get(park, 0), p1 = park_get(park, 1);
+                o.c0 = p0.x; o.c1 = p0.y; o.c2 = p0.z; o.t0 = p0.w;
+                o.t1 = p1.x; o.t2 = p1.y; o.ks = __float_as_uint(p1.z);
+                t0r = o.t0; t1r = o.t1; t2r = o.t2;
 #ifdef MRTX_PROF_TRIAL   // measurement only: the trial's step iterations and the lanes evaluating in them (slots 13 / 14), its cycles (15)
                 cnt[13] += tcnt[11]; cnt[14] += tcnt[12]; cnt[15] += tcnt[6] + tcnt[7];
 #endif
@@ -1708,8 +1435,7 @@ __device__ __forceinline__ void trace_sample(const FrameC& f, int lt, int x, int
                     for (int i = 0; i < ST_N; i++) cnt[i] += tcnt[i];
                 }
                 if (!tgo && !thit) {
-                    if (ENVPRE) escaped_path<STATS, true>(f, o.oa, o.ob, o.oc, o.da, o.db, o.dc, t0r, t1r, t2r, o.c0, o.c1, o.c2, cnt, env_px);
-                    else escaped_path<STATS>(f, o.oa, o.ob, o.oc, o.da, o.db, o.dc, t0r, t1r, t2r, o.c0, o.c1, o.c2, cnt);
+                    escaped_path<STATS>(f, o.oa, o.ob, o.oc, o.da, o.db, o.dc, t0r, t1r, t2r, o.c0, o.c1, o.c2, cnt);
                 } else {
                     o.path = true;
                     if (thit) {
@@ -1719,9 +1445,6 @@ __device__ __forceinline__ void trace_sample(const FrameC& f, int lt, int x, int
                         o.row = tm.rowA; o.col = tm.colA;
                     }
                 }
-#else
-                o.path = true;
-#endif
             }
         }
         if (!BOUNCE) break;
@@ -1753,16 +1476,13 @@ __device__ __forceinline__ float tree_sum(float v) {
 }
 
 // One wave = 64 (pixel, sample) pairs: P = 64/S pixels (PW x PH block) x S samples in adjacent lanes.
-// One workgroup = MRTX_WG_WAVES waves over a (MRTX_WG_TILE x MRTX_WG_TILE)-pixel sub-tile of a sharding
-// tile (never smaller than one wave's pixel block).  Measured at cfg3 (profiles/r01g_wgtile.txt):
-// 4 waves x 16x16 px 21.1 ms, 8x8 18.5, 4x4 17.2, 2x2 15.7; 1 wave x 1 px 15.15 ms.  Per-pixel march cost
-// varies ~20x between disc centre and limb, so the finest grain lets the dispatcher balance the CUs and
-// no wave slot waits on a slower sibling of its workgroup.
+// One workgroup = ONE wave over a (MRTX_WG_TILE x MRTX_WG_TILE)-pixel sub-tile of a sharding
+// tile (never smaller than the wave's pixel block).  Measured at cfg3 (profiles/r01g_wgtile.txt), when a workgroup
+// could still hold several waves (retired): 4 waves x 16x16 px 21.1 ms, 8x8 18.5, 4x4 17.2,
+// 2x2 15.7; 1 wave x 1 px 15.15 ms.  Per-pixel march cost varies ~20x between disc centre and limb, so the finest
+// grain lets the dispatcher balance the CUs and no wave slot waits on a slower sibling of its workgroup.
 #ifndef MRTX_WG_TILE
 #define MRTX_WG_TILE 1
-#endif
-#ifndef MRTX_WG_WAVES
-#define MRTX_WG_WAVES 1
 #endif
 #ifndef MRTX_SKY_WG_TILE
 #define MRTX_SKY_WG_TILE 8    // MODE 3: a wave walks an 8x8-pixel block (a sky sample is ~150 instructions: one pixel per
@@ -1803,24 +1523,22 @@ template <int S, bool STATS, bool WIDE, int MODE, bool OVERLAY>
                                  // needs 62 VGPRs under any bound up to 8 -- 8 waves per SIMD (rounds 2-3: 121-125 VGPRs, 4 waves; a bound of
                                  // 5 then meant 17 spilled registers and 22.2 ms against 18.9)
 #endif
-__global__ void __launch_bounds__(64 * MRTX_WG_WAVES, MODE == 1 ? MRTX_BOUNCE_WAVES(STATS, S) : MODE == 2 ? MRTX_MIN_WAVES_DEFER : MRTX_MIN_WAVES)
+__global__ void __launch_bounds__(64, MODE == 1 ? MRTX_BOUNCE_WAVES(STATS, S) : MODE == 2 ? MRTX_MIN_WAVES_DEFER : MRTX_MIN_WAVES)
 render_kernel(const FrameC f, const PathQ pq) {
     constexpr bool DEFER = MODE == 2;
     constexpr int P = 64 / S;
     constexpr int PW = P >= 64 ? 8 : P >= 32 ? 8 : P >= 16 ? 4 : P >= 8 ? 4 : P >= 4 ? 2 : P >= 2 ? 2 : 1;
     constexpr int PH = P / PW;
-    // workgroup tile edge in pixels: MRTX_WG_TILE, but at least two jobs wide so the 4 waves all have work
-    constexpr int WGMIN = MRTX_WG_WAVES > 2 ? 2 * PW : MRTX_WG_WAVES > 1 ? 2 * PH : PW;
+    // workgroup tile edge in pixels: MRTX_WG_TILE, but at least the wave's pixel block
     constexpr int WGTILE = MODE == 3 ? MRTX_SKY_WG_TILE : MRTX_WG_TILE;
-    constexpr int WGT = (WGMIN > WGTILE) ? WGMIN : WGTILE;
+    constexpr int WGT = (PW > WGTILE) ? PW : WGTILE;
     constexpr int WGS = WGT == 16 ? 4 : WGT == 8 ? 3 : WGT == 4 ? 2 : WGT == 2 ? 1 : 0;
     constexpr int JX = WGT / PW, JY = WGT / PH, NJOBS = JX * JY;
     __shared__ unsigned int lds_cnt[ST_N];
-    constexpr bool PARK = DEFER && MRTX_LDS_PARK != 0;
-    __shared__ v4f park_lds[PARK ? MRTX_PARK_SLOTS * 64 * MRTX_WG_WAVES : 1];
-    v4f* const park = PARK ? park_lds : nullptr;
+    __shared__ v4f park_lds[DEFER ? MRTX_PARK_SLOTS * 64 : 1];
+    v4f* const park = DEFER ? park_lds : nullptr;
 
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;   // wv is 0 (a workgroup is one wave); the compiler does not take that from the launch bound
     // XCD-aware remap: consecutive blockIdx values go to XCDs round-robin, so block b and b+8 share an XCD (and its
     // L2).  Two deals, chosen per launch on the host (f.xcd_share):
     //  0: XCD x gets tiles x, x+8, ... whole -- best L2 locality; 3056 tiles at cfg3 on one GPU average out (14.87 ms
@@ -1871,7 +1589,7 @@ render_kernel(const FrameC f, const PathQ pq) {
     const int p = lane / S, s = lane % S;
     // MODE 3: lane l looks at pixel (l % 8, l / 8) of the wave's 8 x 8 block first -- one texel for the whole pixel? (see
     // sky_pixel_uniform) -- and the jobs below take a pixel's verdict and texel from the lane that holds them
-    constexpr bool SKY_UNI = MODE == 3 && WGT == 8 && MRTX_WG_WAVES == 1;
+    constexpr bool SKY_UNI = MODE == 3 && WGT == 8;
     uint64_t sky_nu = ~0ull;             // lanes (= pixels of the 8 x 8 block) whose samples do NOT all read one texel
     auto sky_jobmask = [&](int jx_, int jy_) {   // the lanes that hold the PW x PH pixels of job (jx_, jy_)
         uint64_t mk = 0ull;
@@ -1898,7 +1616,7 @@ render_kernel(const FrameC f, const PathQ pq) {
             if (STATS) { cnt[ST_PRIMARY] += (uint32_t)S; cnt[ST_BG] += (uint32_t)S; }
         }
     }
-    for (int job = wv; job < NJOBS; job += MRTX_WG_WAVES) {
+    for (int job = wv; job < NJOBS; job++) {
         const int jx = job % JX, jy = job / JX;
         const int x = px0 + jx * PW + (p % PW), y = py0 + jy * PH + (p / PW);
         if (px0 + jx * PW >= f.W || py0 + jy * PH >= f.H) continue;  // wave-uniform
@@ -1913,7 +1631,7 @@ render_kernel(const FrameC f, const PathQ pq) {
         // A launch carries ONE block of S samples per pixel (mrtx_launch_render checks it; mrtx_render_part launches block after
         // block).  Round 4: with the block count a run-time value the compiler kept everything a sample can hand to the next
         // iteration -- running sums, hit record, hand-over fields, hoisted per-pixel invariants -- alive through every march:
-        // render_kernel<MODE 2> 121 VGPRs (4 waves per SIMD); with a trip count of one 73 (6 waves), 62 with MRTX_LDS_PARK (8).
+        // render_kernel<MODE 2> 121 VGPRs (4 waves per SIMD); with a trip count of one 73 (6 waves), 62 with the cold state parked in LDS (8).
         constexpr uint32_t n_blk = 1u;
         for (uint32_t blk = 0; blk < n_blk; blk++) {
             o.c0 = o.c1 = o.c2 = o.hitflag = 0.f;
@@ -1936,24 +1654,14 @@ render_kernel(const FrameC f, const PathQ pq) {
                 // lane_of maps a record back to its sample); the running radiance of all 64 samples in lane order
                 const uint64_t pm = __ballot(o.path);
                 const uint32_t es = chunk * 64u + __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
-#ifndef MRTX_AB_NOSTORE   // A/B only: how much of render_kernel<MODE 2> is the hand-over traffic (results are wrong without it)
                 if (o.path) {
                     nt_store4(pq.ray0 + es, o.oa, o.ob, o.oc, o.da);
                     nt_store4(pq.ray1 + es, o.db, o.dc, o.t0, o.t1);
                     nt_store4(pq.ray2 + es, o.t2, o.row, o.col, __uint_as_float(o.ks));
                     pq.lane_of[es] = (uint32_t)lane | o.aux;
                 }
-#if MRTX_C_AOS == 2
                 { float* const cp = reinterpret_cast<float*>(pq.c4) + 3u * (size_t)e;
                   __builtin_nontemporal_store(o.c0, cp); __builtin_nontemporal_store(o.c1, cp + 1); __builtin_nontemporal_store(o.c2, cp + 2); }
-#elif MRTX_C_AOS
-                nt_store4(pq.c4 + e, o.c0, o.c1, o.c2, 0.0f);
-#else
-                __builtin_nontemporal_store(o.c0, pq.c0 + e);
-                __builtin_nontemporal_store(o.c1, pq.c1 + e);
-                __builtin_nontemporal_store(o.c2, pq.c2 + e);
-#endif
-#endif
                 if (lane == 0) pq.npaths[chunk] = (uint8_t)__popcll(pm);
                 if (lane == 0) pq.meta[chunk] = 0x80000000u | (uint32_t)(px0 + jx * PW) | ((uint32_t)(py0 + jy * PH) << 15);
             } else {
@@ -1964,7 +1672,7 @@ render_kernel(const FrameC f, const PathQ pq) {
             s3 += tree_sum<S>(o.hitflag);
         }
         if (inb && s == 0) reinterpret_cast<float4*>(CF(f)->accum)[(int64_t)y * f.W + x] = make_float4(s0, s1, s2, s3);
-        if (!PARK && inb && s == 0) reinterpret_cast<float4*>(CF(f)->hits)[(int64_t)y * f.W + x] = make_float4(o.h0, o.h1, o.h2, o.h3);   // PARK: trace_sample stored it
+        if (!DEFER && inb && s == 0) reinterpret_cast<float4*>(CF(f)->hits)[(int64_t)y * f.W + x] = make_float4(o.h0, o.h1, o.h2, o.h3);   // DEFER: trace_sample stored it
     }
 
 #ifdef MRTX_PROF
@@ -1991,11 +1699,9 @@ render_kernel(const FrameC f, const PathQ pq) {
 // Sun illumination of the terrain (DESIGN.md sections 3.6 and 4.8): per node of a lat/lon band or a point list, the vertex
 // of the camera path's first hit (hit_vertex at p = R D(node) u) and n_sun light samples of the fixed table marched like its
 // shadow ray (light_sample + march, the body of direct_light with the visibility kept apart from what a sample carries).
-// MRTX_ILLUM_MAP 0: one wave = 64/n adjacent nodes x n samples in adjacent lanes (render_kernel's idea: the lanes march from
-// nearly one point in nearly one direction); 1: lane = node, the samples in a loop (the alternative, measured in 4.8).
-#ifndef MRTX_ILLUM_MAP
-#define MRTX_ILLUM_MAP 0
-#endif
+// One wave = 64/n adjacent nodes x n samples in adjacent lanes (render_kernel's idea: the lanes march from nearly one point in
+// nearly one direction).  Tried and retired (DESIGN.md sections 4.8 and 4.18; profiles/illum_a_summary.md): lane = node, the samples
+// in a loop -- the same bits, the whole-Moon map 8.7 ms against 4.6.
 // (sum over the n lanes of a node, the pairwise order of tree_sum<n>) for a run-time n
 __device__ __forceinline__ float group_sum(float v, int n) {
     for (int m = 1; m < n; m <<= 1) v += __shfl_xor(v, m, 64);
@@ -2067,16 +1773,12 @@ template <bool STATS, bool WIDE>
 __global__ void __launch_bounds__(64) illum_kernel(const FrameC f, const IllumC g) {
     const int lane = threadIdx.x;
     const int n = g.n_sun;
-#if MRTX_ILLUM_MAP == 0
     const int s = lane & (n - 1), p = lane >> g.n_log2;
-#else
-    const int s = 0, p = lane;
-#endif
     // the wave's node block: PW x PH nodes in raster order
     const int pw = 1 << g.pw_log2;
     const int wx = (int)(blockIdx.x % (unsigned)g.waves_x), wy = (int)(blockIdx.x / (unsigned)g.waves_x);
     const int col = wx * pw + (p & (pw - 1));
-    const int row = wy * ((64 >> (MRTX_ILLUM_MAP == 0 ? g.n_log2 : 0)) >> g.pw_log2) + (p >> g.pw_log2);
+    const int row = wy * ((64 >> g.n_log2) >> g.pw_log2) + (p >> g.pw_log2);
     const bool in = row < g.rows && col < g.cols;
     uint32_t cnt_store[STATS ? ST_N : 1] = {};
     uint32_t* const cnt = STATS ? cnt_store : nullptr;
@@ -2086,36 +1788,12 @@ __global__ void __launch_bounds__(64) illum_kernel(const FrameC f, const IllumC 
         D = illum_vertex<STATS, WIDE>(f, g, row, col, v, cnt);
         mu = illum_mu(f, FrameLight{f}, v);
         const float2* sun = reinterpret_cast<const float2*>(g.sun);
-#if MRTX_ILLUM_MAP == 0
         const float2 us = sun[s];
         float carried;
         if (illum_sample<STATS, WIDE>(f, FrameLight{f}, v, us.x, us.y, carried, cnt)) { lit = 1.0f; irr = carried; }
-#else
-        // the n samples in turn; their sum in tree_sum's pairwise order: part[t] holds the pending sum of 2^t samples
-        float part[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        for (int i = 0; i < n; i++) {
-            const float2 us = sun[i];
-            float carried, x = 0.0f;
-            if (illum_sample<STATS, WIDE>(f, FrameLight{f}, v, us.x, us.y, carried, cnt)) { lit += 1.0f; x = carried; }
-            if (STATS && i > 0) { cnt[ST_HEIGHT] += 5; cnt[ST_FETCH] += 5; }   // the spec counts the vertex per sample
-            bool pending = true;
-#pragma unroll
-            for (int t = 0; t < 7; t++) {
-                if (pending) {
-                    if ((i >> t) & 1) x = part[t] + x;
-                    else { part[t] = x; pending = false; }
-                }
-            }
-        }
-        irr = part[0];
-#pragma unroll
-        for (int t = 1; t < 7; t++) irr = g.n_log2 == t ? part[t] : irr;   // (no run-time index into a register array)
-#endif
     }
-#if MRTX_ILLUM_MAP == 0
     lit = group_sum(lit, n);    // a count: exact
     irr = group_sum(irr, n);
-#endif
     const float inv_n = 1.0f / (float)n;   // a power of two: the scalings below are exact
     if (in && s == 0)
         reinterpret_cast<float4*>(g.out)[(int64_t)row * g.cols + col] = make_float4(lit * inv_n, irr * inv_n, mu, D);
@@ -2814,11 +2492,10 @@ __global__ void __launch_bounds__(64) sight_kernel(const FrameC f, const SightC 
 #ifndef MRTX_PATH_STEPS
 #define MRTX_PATH_STEPS 2
 #endif
-#ifndef MRTX_PATH_WIDE
-#define MRTX_PATH_WIDE 0      // 1 = wide stepping while a wave drains (see the kernel body): bit-exact, measured SLOWER (path stage 5.44 ms
-                              // against 5.13 on one GPU, 0.98 / 0.91 ms for a rank of eight): the block costs three more spilled registers
-                              // in the main phase, more than the shorter drain gives back -- an A/B switch, off
-#endif
+// Tried in round 3 and retired: wide stepping while a wave drains -- once the queue is empty the lanes left
+// alone in a wave spread the next steps of a live lane's segment over the idle lanes, one round trip for up to 16 steps.  Bit-exact,
+// measured SLOWER (path stage 5.44 ms against 5.13 on one GPU, 0.98 / 0.91 ms for a rank of eight): the block cost three more spilled
+// registers in the main phase, more than the shorter drain gave back.
 #ifdef MRTX_PATH_PROF   // measurement build only (tools/path_prof.py): block executions and lane counts of path_kernel
 __device__ unsigned long long g_pprof[16];
 __device__ unsigned long long g_pprof_end[8192];   // end time of every persistent wave (tools/path_prof.py: the shape of the tail)
@@ -2840,9 +2517,6 @@ enum { PS_IDLE = 0, PS_NEEDSEG, PS_STEP, PS_BISECT, PS_ENDED, PS_HITWAIT, PS_SHA
 // dependent memory rounds a wave goes through (the mask trades ~1.6 step rounds per set-up for ~1.5 medium-mip rounds + 0.6), with
 // the memory system merely close to saturation at the same time.  Off by default (MRTX_PATH_MIP2 in mrtx_device.h); kept as a switch
 // because it is bit-exact and halves the path stage's HBM traffic, which a bandwidth-starved configuration might want.
-#if MRTX_PATH_MIP2 && MRTX_PATH_WIDE
-#error "MRTX_PATH_WIDE walks j .. jhi contiguously: build it with -DMRTX_PATH_MIP2=0"
-#endif
 template <bool STATS>
 __device__ __forceinline__ uint32_t step_mask(const FrameC& f, const MarchState& m, const Seg& sg, uint32_t todo, uint32_t* cnt) {
     const float* m2 = CF(f)->mip2;
@@ -2885,31 +2559,16 @@ __device__ __forceinline__ uint32_t step_mask(const FrameC& f, const MarchState&
 // VALU + the max-mip fetch) and STEP (its next step of the current segment is to be evaluated: ~45 VALU + one DEM
 // fetch); every iteration evaluates ONE step for all stepping lanes, and the set-up block runs when enough lanes
 // need it (or nobody is stepping).  Same evaluations, same order per ray as march_segment().
-// MRTX_PATH_PARK (round 4): the lanes' COLD state -- the current vertex (9 floats), the radiance its light sample carries, the path
-// throughput (3) and the sample's radiance so far (3) -- lives in LDS, four lane-private 16-byte slots (4 KB per wave), and is touched
-// only by the blocks that need it (refill, march over, the rare blocks).  path_kernel is bound by its waves' chains of dependent memory
-// rounds times the waves a SIMD holds (section 4.6 of DESIGN.md), so sixteen registers less looked like the price of a sixth wave.
-// MEASURED (cfg3, gpurun_out/r4x/path_park.log; path stage ms incl. resolve, two rounds): as shipped 4.98; parked at 5 waves (94
-// VGPRs, no scratch instead of 96 + 2 spilled) 4.98-5.04; at launch bounds 6 / 7 (80 / 72 VGPRs, 12 / 20 spilled: the set-up and
-// vertex blocks' temporaries are what fills the file, not the cold state) 5.36 / 6.10; with the step mask (MRTX_PATH_MIP2) on top
-// 4.97 / 5.00 / 4.96 at 5 / 6 / 7 waves.  Neither more resident waves, nor 46 % less traffic, nor both move the kernel: off (an A/B
-// switch; bit-exact, tools/quick_parity.py).
-#ifndef MRTX_PATH_PARK
-#define MRTX_PATH_PARK 0
-#endif
+// Tried in round 4 and retired: the lanes' COLD state -- the current vertex (9 floats), the radiance its light
+// sample carries, the path throughput (3) and the sample's radiance so far (3) -- parked in LDS, four lane-private 16-byte slots,
+// touched only by the blocks that need it: sixteen registers less looked like the price of a sixth wave.  Bit-exact.
+// MEASURED (cfg3; path stage ms incl. resolve, two rounds): as shipped 4.98; parked at 5 waves (94 VGPRs, no scratch instead of 96 +
+// 2 spilled) 4.98-5.04; at launch bounds 6 / 7 (80 / 72 VGPRs, 12 / 20 spilled: the set-up and vertex blocks' temporaries are what
+// fills the file, not the cold state) 5.36 / 6.10; with the step mask (MRTX_PATH_MIP2) on top 4.97 / 5.00 / 4.96 at 5 / 6 / 7 waves.
+// Neither more resident waves, nor 46 % less traffic, nor both moved the kernel.
 template <bool STATS, bool WIDE>
 __global__ void __launch_bounds__(64, STATS ? 2 : MRTX_PATH_WAVES) path_kernel(const FrameC f, const PathQ pq) {
     const uint32_t lane = threadIdx.x;
-#if MRTX_PATH_PARK
-    __shared__ float pk_lds[4 * 64 * 4];
-    float* const pk = pk_lds + lane * 4u;              // slot s, component c of this lane: pk[s * 256 + c]
-#define PKS(s, c) pk[(s) * 256 + (c)]
-    // slot 0: v.pa pb pc na | 1: v.nb nc al0 al1 | 2: v.al2, carried, t0r, t1r | 3: t2r, c0, c1, c2
-#define COLD_GET_T(a, b, c) do { a = PKS(2, 2); b = PKS(2, 3); c = PKS(3, 0); } while (0)
-#define COLD_SET_T(a, b, c) do { PKS(2, 2) = a; PKS(2, 3) = b; PKS(3, 0) = c; } while (0)
-#define COLD_GET_C(a, b, c) do { a = PKS(3, 1); b = PKS(3, 2); c = PKS(3, 3); } while (0)
-#define COLD_SET_C(a, b, c) do { PKS(3, 1) = a; PKS(3, 2) = b; PKS(3, 3) = c; } while (0)
-#endif
     // Work distribution.  The records of render block b (b % 8 = a group label: blocks with one label ran on one XCD and
     // cover neighbouring pixels of the same tiles, see the remap in render_kernel) are taken in GROUPS of G consecutive
     // blocks of one label, handed out by atomic counters in device memory -- one set of counters per label of THIS
@@ -2954,21 +2613,15 @@ __global__ void __launch_bounds__(64, STATS ? 2 : MRTX_PATH_WAVES) path_kernel(c
     uint32_t todo = 0u;           // the steps of the current segment still to be evaluated, bit jj - 1 for step jj >= j
 #endif
     float sk_hit = 0.0f;
-#if MRTX_PATH_PARK
-    float wgt = 0.0f;
-#else
     Vertex v;
     float t0r = 1.0f, t1r = 1.0f, t2r = 1.0f, c0 = 0.0f, c1 = 0.0f, c2 = 0.0f, carried = 0.0f, wgt = 0.0f;
-#endif
     // BISECT lanes (a continuation ray that hit: D3's bisection, one level per DEM fetch like any other step) keep the
     // bracket in registers that are dead meanwhile: lo in wgt, hi in sk_hit, the levels left in j
     float& bis_lo = wgt;
     float& bis_hi = sk_hit;
     m.oa = m.ob = m.oc = m.da = m.db = m.dc = 0.0f; m.rq.q0 = m.rq.b = m.rq.a = 0.0f; m.rowA = m.colA = m.q2A = 0.0f; m.ka = 0; m.kend = 0;
     sg.sa = sg.ra = sg.r1 = sg.r2 = sg.ca = sg.c1 = sg.c2 = 0.0f; sg.jlo = 1; sg.jhi = 0; sg.exact = false;
-#if !MRTX_PATH_PARK
     v.pa = v.pb = v.pc = v.na = v.nb = v.nc = v.al0 = v.al1 = v.al2 = 0.0f;
-#endif
 
     for (;;) {
         // Every lane waits for exactly one of four blocks -- refill, segment set-up, step, rare -- and the wave decides
@@ -3045,7 +2698,7 @@ __global__ void __launch_bounds__(64, STATS ? 2 : MRTX_PATH_WAVES) path_kernel(c
             if (fill_l) {
                 const float4 r0 = nt_load4(pq.ray0 + e), r1 = nt_load4(pq.ray1 + e), r2 = nt_load4(pq.ray2 + e);
                 const uint32_t aux = __builtin_nontemporal_load(pq.lane_of + e);
-                e = (e & ~63u) | (aux & 63u);            // from here on: the sample's slot in c0/c1/c2
+                e = (e & ~63u) | (aux & 63u);            // from here on: the sample's slot in c4
                 m.rowA = r2.y; m.colA = r2.z;
                 bool go = true;
                 j = 1;
@@ -3073,11 +2726,7 @@ __global__ void __launch_bounds__(64, STATS ? 2 : MRTX_PATH_WAVES) path_kernel(c
                 } else {
                     go = march_begin_at<false, STATS, true>(f, r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, m, cnt);
                 }
-#if MRTX_PATH_PARK
-                COLD_SET_T(r1.z, r1.w, r2.x);
-#else
                 t0r = r1.z; t1r = r1.w; t2r = r2.x;
-#endif
                 ks = __float_as_uint(r2.w);
                 hit = false; shadow = false; have_c = false;
                 seg = 1;
@@ -3124,86 +2773,18 @@ __global__ void __launch_bounds__(64, STATS ? 2 : MRTX_PATH_WAVES) path_kernel(c
             }
         }
         PPROF_T(10);
-#if MRTX_PATH_WIDE
-        // ---- DRAIN, wide stepping: once the queue is empty a wave ends when its last path does, and a marching path needs an
-        // iteration per MRTX_PATH_STEPS steps while most lanes idle.  With at most four lanes stepping, each of them borrows a
-        // quarter of the wave: lane 16 g + i evaluates step j + i of the g-th stepping lane's segment, and the owner takes the
-        // first step (in march order) that ends the march -- the same evaluations in the same order as one step at a time, a
-        // whole segment per iteration.  Results and counters unchanged (the steps behind the terminating one are not counted).
-        bool wide_done = false;
-        {
-            const uint64_t stepm = __ballot(state == PS_STEP);
-            const int nst = __popcll(stepm);
-            if (!more && nst > 0 && nst <= 4) {            // wave-uniform
-                const uint32_t grp = lane >> 4, sub16 = lane & 15u;
-                int src = -1;
-                {
-                    uint64_t mm = stepm;
-#pragma unroll
-                    for (uint32_t i = 0; i < 4; i++) {
-                        const int bpos = mm ? (int)__builtin_ctzll(mm) : -1;
-                        src = (i == grp) ? bpos : src;
-                        mm &= mm - 1ull;
-                    }
-                }
-                const bool has = src >= 0;
-                const int sl = has ? src : 0;
-                Seg wsg;
-                const float woa = __shfl(m.oa, sl, 64), wob = __shfl(m.ob, sl, 64), woc = __shfl(m.oc, sl, 64);
-                const float wda = __shfl(m.da, sl, 64), wdb = __shfl(m.db, sl, 64), wdc = __shfl(m.dc, sl, 64);
-                wsg.sa = __shfl(sg.sa, sl, 64); wsg.ra = __shfl(sg.ra, sl, 64); wsg.r1 = __shfl(sg.r1, sl, 64); wsg.r2 = __shfl(sg.r2, sl, 64);
-                wsg.ca = __shfl(sg.ca, sl, 64); wsg.c1 = __shfl(sg.c1, sl, 64); wsg.c2 = __shfl(sg.c2, sl, 64);
-                wsg.exact = __shfl((int)sg.exact, sl, 64) != 0;
-                wsg.jlo = 1; wsg.jhi = SEG_N;
-                const int wka = __shfl(m.ka, sl, 64), wj = __shfl(j, sl, 64), wjhi = __shfl(sg.jhi, sl, 64);
-                const int jj = wj + (int)sub16;
-                const bool valid = has && jj <= wjhi;
-                const int kk = wka + min(jj, wjhi);
-                const float wsk = (float)kk * f.step;
-                const float wpa = fmaf(wsk, wda, woa), wpb = fmaf(wsk, wdb, wob), wpc = fmaf(wsk, wdc, woc);
-                const float wr2 = fmaf(wpc, wpc, fmaf(wpb, wpb, wpa * wpa));
-                const bool win = (wr2 <= f.R2f) & (kk <= f.kmax);
-                const bool wbel = below_seg<WIDE, true, MRTX_PATH_CP>(f, wsg, wsk, wpa, wpb, wpc, wr2);
-                const uint64_t hm = __ballot(valid & win & wbel), om = __ballot(valid & !win);
-                if (state == PS_STEP) {
-                    const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(stepm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)stepm, 0u));   // < 4
-                    const uint32_t h16 = (uint32_t)(hm >> (16u * rk)) & 0xFFFFu, o16 = (uint32_t)(om >> (16u * rk)) & 0xFFFFu;
-                    const int nvalid = min(16, sg.jhi - j + 1);
-                    const uint32_t term = h16 | o16;
-                    if (term != 0u) {
-                        const int t = (int)__builtin_ctz(term);
-                        const bool is_hit = ((h16 >> t) & 1u) != 0u;
-                        if (STATS) { cnt[ST_HEIGHT] += (uint32_t)t + (is_hit ? 1u : 0u); cnt[ST_FETCH] += (uint32_t)t + 1u; }
-                        if (is_hit) { hit = true; sk_hit = (float)(m.ka + j + t) * f.step; }
-                        j += t + 1;
-                        state = PS_ENDED;
-                    } else {
-                        if (STATS) { cnt[ST_HEIGHT] += (uint32_t)nvalid; cnt[ST_FETCH] += (uint32_t)nvalid; }
-                        j += nvalid;
-                        if (j > sg.jhi) segend = true;
-                    }
-                }
-                wide_done = true;
-            }
-        }
-#else
-        const bool wide_done = false;
-#endif
         if (do_step) {
             // ---- the next MRTX_PATH_STEPS steps of every stepping lane: their DEM footprints are fetched together (one
             // memory round trip per iteration is what bounds this kernel), then the steps are tested in march order and
             // whatever follows the one that ends the march or the segment is dropped (its fetch is wasted).  Same
             // evaluations, same order, same results as one step at a time.  cfg3: 1 step 14.5 ms, 2 steps 13.3.
-            if ((state == PS_STEP && !wide_done) || state == PS_BISECT) {
+            if (state == PS_STEP || state == PS_BISECT) {
                 // A BISECT lane evaluates the mid-point of its bracket in slot 0 and, speculatively, the mid-point of the
                 // lower half in slot 1 (the next level if slot 0 turns out below the surface): the bisection of D3 rides the
                 // fetch rounds of the march instead of adding five of its own to the rare block.
                 const bool bis = state == PS_BISECT;
                 bool bel[MRTX_PATH_STEPS], in[MRTX_PATH_STEPS];
                 float sks[MRTX_PATH_STEPS];
-#ifdef MRTX_PROF_MARGIN
-                float mrg[MRTX_PATH_STEPS];
-#endif
                 const float mid0 = 0.5f * (bis_lo + bis_hi);
 #if MRTX_PATH_MIP2
                 // the next MRTX_PATH_STEPS steps the mask kept (a lane with fewer left repeats its last one: a wasted fetch)
@@ -3229,16 +2810,8 @@ __global__ void __launch_bounds__(64, STATS ? 2 : MRTX_PATH_WAVES) path_kernel(c
                     const float pa = fmaf(sk, m.da, m.oa), pb = fmaf(sk, m.db, m.ob), pc = fmaf(sk, m.dc, m.oc);
                     const float r2 = fmaf(pc, pc, fmaf(pb, pb, pa * pa));
                     in[i] = (r2 <= f.R2f) & (k <= f.kmax);
-                    bel[i] = below_seg<WIDE, true, MRTX_PATH_CP>(f, sg, sk, pa, pb, pc, r2);
+                    bel[i] = below_seg<WIDE, true>(f, sg, sk, pa, pb, pc, r2);
                     sks[i] = sk;
-#ifdef MRTX_PROF_MARGIN
-                    {
-                        const float uu = (sk - sg.sa) * f.inv_step;
-                        float rw = fmaf(uu, fmaf(uu, sg.r2, sg.r1), sg.ra), cl = fmaf(uu, fmaf(uu, sg.c2, sg.c1), sg.ca);
-                        if (sg.exact) { float q2; exact_rowcol(f, pa, pb, pc, rw, cl, q2); }
-                        mrg[i] = sqrtf(r2) / (f.Rf * dem_march<WIDE>(f, rw, cl)) - 1.0f;
-                    }
-#endif
                 }
                 bool act = !bis;
                 if (bis) {
@@ -3269,9 +2842,6 @@ __global__ void __launch_bounds__(64, STATS ? 2 : MRTX_PATH_WAVES) path_kernel(c
 #else
                     if (act) {
                         if (STATS) { cnt[ST_HEIGHT] += in[i] ? 1u : 0u; cnt[ST_FETCH]++; }
-#ifdef MRTX_PROF_MARGIN
-                        if (STATS) { cnt[ST_MALL]++; cnt[ST_M1] += mrg[i] > 1.0e-4f; cnt[ST_M2] += mrg[i] > 3.0e-4f; cnt[ST_M3] += mrg[i] > 1.0e-3f; }
-#endif
                         j++;
                         if (in[i] & bel[i]) { hit = true; sk_hit = sks[i]; state = PS_ENDED; act = false; }
                         else if (!in[i]) { state = PS_ENDED; act = false; }
@@ -3301,33 +2871,6 @@ __global__ void __launch_bounds__(64, STATS ? 2 : MRTX_PATH_WAVES) path_kernel(c
 
         // ---- march over
         if (state == PS_ENDED) {
-#if MRTX_PATH_PARK
-            if (shadow) {
-                wgt = hit ? 0.0f : PKS(2, 1);
-                state = PS_SHADE;
-            } else if (hit) {
-                if (!have_c) { float a, b, c_; c_load(pq, e, a, b, c_); COLD_SET_C(a, b, c_); have_c = true; }
-                const int bk = (int)rintf(sk_hit * f.inv_step);
-                bis_lo = (float)(bk - 1) * f.step;       // bis_hi is sk_hit already
-                j = f.nbis;
-                if (STATS) { cnt[ST_HEIGHT] += (uint32_t)f.nbis; cnt[ST_FETCH] += (uint32_t)f.nbis; }
-                state = f.nbis > 0 ? PS_BISECT : PS_HITWAIT;
-            } else if (CF(f)->bg) {
-                state = PS_ESCAPED;
-            } else {
-                float e0, e1, e2, a = 0.0f, b = 0.0f, c_ = 0.0f;
-                bool in_reg = false;
-                if (escaped_radiance<STATS>(f, m.oa, m.ob, m.oc, m.da, m.db, m.dc, e0, e1, e2, cnt)) {   // the Sun disk
-                    if (!have_c) { c_load(pq, e, a, b, c_); have_c = true; } else { COLD_GET_C(a, b, c_); }
-                    float t0, t1, t2;
-                    COLD_GET_T(t0, t1, t2);
-                    a = fmaf(t0, e0, a); b = fmaf(t1, e1, b); c_ = fmaf(t2, e2, c_);
-                    in_reg = true;
-                }
-                if (have_c) { if (!in_reg) COLD_GET_C(a, b, c_); c_store(pq, e, a, b, c_); }
-                state = PS_IDLE;
-            }
-#else
             if (shadow) {
                 wgt = hit ? 0.0f : carried;
                 state = PS_SHADE;
@@ -3353,7 +2896,6 @@ __global__ void __launch_bounds__(64, STATS ? 2 : MRTX_PATH_WAVES) path_kernel(c
                 if (have_c) c_store(pq, e, c0, c1, c2);
                 state = PS_IDLE;
             }
-#endif
         }
 
         // ---- the rare steps (~8 % of the paths reach them): a continuation ray that hit terrain gets its vertex and
@@ -3361,70 +2903,6 @@ __global__ void __launch_bounds__(64, STATS ? 2 : MRTX_PATH_WAVES) path_kernel(c
         // continued or ended (~250 VALU).  They wait until enough lanes need them -- or nothing is marching.
         PPROF_T(12);
         if (do_rare) {
-#if MRTX_PATH_PARK
-            if (state == PS_ESCAPED) {
-                float e0, e1, e2, a = 0.0f, b = 0.0f, c_ = 0.0f;
-                bool in_reg = false;
-                if (escaped_radiance<STATS>(f, m.oa, m.ob, m.oc, m.da, m.db, m.dc, e0, e1, e2, cnt)) {
-                    float t0, t1, t2;
-                    COLD_GET_T(t0, t1, t2);
-                    // a black texel adds nothing (fmaf(t, 0, c) == c for finite t): the sample's radiance need not be touched
-                    const bool nothing = (e0 == 0.0f) & (e1 == 0.0f) & (e2 == 0.0f) & ((t0 + t1 + t2) < __builtin_inff());
-                    if (!nothing) {
-                        if (!have_c) { c_load(pq, e, a, b, c_); have_c = true; } else { COLD_GET_C(a, b, c_); }
-                        a = fmaf(t0, e0, a); b = fmaf(t1, e1, b); c_ = fmaf(t2, e2, c_);
-                        in_reg = true;
-                    }
-                }
-                if (have_c) { if (!in_reg) COLD_GET_C(a, b, c_); c_store(pq, e, a, b, c_); }
-                state = PS_IDLE;
-            }
-            if (state == PS_HITWAIT) {
-                const float blo = bis_lo;                  // the bisected bracket's upper side (PS_BISECT)
-                Vertex v;
-                hit_vertex<STATS, WIDE>(f, fmaf(blo, m.da, m.oa), fmaf(blo, m.db, m.ob), fmaf(blo, m.dc, m.oc), v, cnt);
-                PKS(0, 0) = v.pa; PKS(0, 1) = v.pb; PKS(0, 2) = v.pc; PKS(0, 3) = v.na;
-                PKS(1, 0) = v.nb; PKS(1, 1) = v.nc; PKS(1, 2) = v.al0; PKS(1, 3) = v.al1; PKS(2, 0) = v.al2;
-                seg++;
-                const uint32_t d0 = 4u + 5u * (seg - 2u);   // the dimensions drawn when this segment was started
-                const float ul1 = u01(ks, d0 + 3u), ul2 = u01(ks, d0 + 4u);
-                float soa, sob, soc, swa, swb, swc, carried;
-                if (light_sample(f, v, ul1, ul2, soa, sob, soc, swa, swb, swc, carried)) {
-                    PKS(2, 1) = carried;
-                    if (STATS) cnt[ST_SHADOW]++;
-                    const bool go = march_begin<false, STATS, true>(f, soa, sob, soc, swa, swb, swc, m, cnt);
-                    hit = false; shadow = true;
-                    state = go ? PS_NEEDSEG : PS_ENDED;
-                } else {
-                    wgt = 0.0f;
-                    state = PS_SHADE;
-                }
-            }
-            park_fence();       // the vertex a lane parked above is READ BACK below (not kept in registers across the blocks)
-            if (state == PS_SHADE) {
-                Vertex v;
-                v.pa = PKS(0, 0); v.pb = PKS(0, 1); v.pc = PKS(0, 2); v.na = PKS(0, 3);
-                v.nb = PKS(1, 0); v.nc = PKS(1, 1); v.al0 = PKS(1, 2); v.al1 = PKS(1, 3); v.al2 = PKS(2, 0);
-                float t0r, t1r, t2r, c0, c1, c2;
-                COLD_GET_T(t0r, t1r, t2r);
-                COLD_GET_C(c0, c1, c2);
-                c0 = fmaf(t0r * v.al0, wgt, c0);
-                c1 = fmaf(t1r * v.al1, wgt, c1);
-                c2 = fmaf(t2r * v.al2, wgt, c2);
-                float boa, bob, boc, bda, bdb, bdc;
-                if (continue_path(f, v, ks, seg, t0r, t1r, t2r, boa, bob, boc, bda, bdb, bdc)) {
-                    COLD_SET_T(t0r, t1r, t2r);
-                    COLD_SET_C(c0, c1, c2);
-                    if (STATS) cnt[ST_BOUNCE]++;
-                    const bool go = march_begin<false, STATS, true>(f, boa, bob, boc, bda, bdb, bdc, m, cnt);
-                    hit = false; shadow = false;
-                    state = go ? PS_NEEDSEG : PS_ENDED;
-                } else {
-                    c_store(pq, e, c0, c1, c2);
-                    state = PS_IDLE;
-                }
-            }
-#else
             if (state == PS_ESCAPED) {
                 float e0, e1, e2;
                 if (escaped_radiance<STATS>(f, m.oa, m.ob, m.oc, m.da, m.db, m.dc, e0, e1, e2, cnt)) {
@@ -3470,7 +2948,6 @@ __global__ void __launch_bounds__(64, STATS ? 2 : MRTX_PATH_WAVES) path_kernel(c
                     state = PS_IDLE;
                 }
             }
-#endif
         }
         PPROF_T(13);
     }
@@ -3520,16 +2997,8 @@ __global__ void __launch_bounds__(256) resolve_paths_kernel(const FrameC f, cons
             acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (mt[u] & 0x80000000u) {                       // wave-uniform
                 const uint32_t e = (base + u) * 64u + lane;
-#if MRTX_C_AOS == 2
                 { const float* const cp = reinterpret_cast<const float*>(pq.c4) + 3u * (size_t)e;
                   a0[u] = __builtin_nontemporal_load(cp); a1[u] = __builtin_nontemporal_load(cp + 1); a2[u] = __builtin_nontemporal_load(cp + 2); }
-#elif MRTX_C_AOS
-                { const float4 v = nt_load4(pq.c4 + e); a0[u] = v.x; a1[u] = v.y; a2[u] = v.z; }
-#else
-                a0[u] = __builtin_nontemporal_load(pq.c0 + e);
-                a1[u] = __builtin_nontemporal_load(pq.c1 + e);
-                a2[u] = __builtin_nontemporal_load(pq.c2 + e);
-#endif
                 const uint32_t x = (mt[u] & 0x7FFFu) + (pp & ((1u << pq.pw_log2) - 1u));
                 const uint32_t y = ((mt[u] >> 15) & 0x7FFFu) + (pp >> pq.pw_log2);
                 if (ss == 0u && x < (uint32_t)f.W && y < (uint32_t)f.H) {
@@ -3878,7 +3347,7 @@ __global__ void probe_cr_kernel(uint32_t lo, uint64_t n, int which, unsigned lon
     }
 }
 
-// DEM (h, w) row-major -> padded (h+4, w+4): rows clamp, columns wrap (see dem_march)
+// DEM (h, w) row-major -> padded (h+4, w+4) row pairs: rows clamp, columns wrap (see dem_march)
 __global__ void pad_dem_kernel(const float* __restrict__ src, float* __restrict__ dst, int h, int w) {
     const int pitch = w + 4;
     const int64_t n = (int64_t)(h + 4) * pitch;
@@ -3887,12 +3356,7 @@ __global__ void pad_dem_kernel(const float* __restrict__ src, float* __restrict_
         const int r1 = r + 1 < 0 ? 0 : (r + 1 > h - 1 ? h - 1 : r + 1);
         r = r < 0 ? 0 : (r > h - 1 ? h - 1 : r);
         c = c < 0 ? c + w : (c > w - 1 ? c - w : c);
-#if MRTX_DEM_PAIRS
         reinterpret_cast<float2*>(dst)[i] = make_float2(src[(int64_t)r * w + c], src[(int64_t)r1 * w + c]);
-#else
-        (void)r1;
-        dst[i] = src[(int64_t)r * w + c];
-#endif
     }
 }
 
@@ -4000,9 +3464,8 @@ static void render_geometry(const FrameC& f, int S, int& xcd_share, unsigned& gr
     const int P = 64 / S;
     const int PW = P >= 32 ? 8 : P >= 8 ? 4 : P >= 2 ? 2 : 1;
     const int PH = P / PW;
-    const int wgmin = MRTX_WG_WAVES > 2 ? 2 * PW : MRTX_WG_WAVES > 1 ? 2 * PH : PW;
     const int wgtile = mode == 3 ? MRTX_SKY_WG_TILE : MRTX_WG_TILE;
-    const int wgt = (wgmin > wgtile) ? wgmin : wgtile;
+    const int wgt = (PW > wgtile) ? PW : wgtile;
     const int subs = (f.tile_w / wgt) * (f.tile_h / wgt);
     xcd_share = (MRTX_XCD_SHARE && (subs & 7) == 0 && f.n_active < MRTX_XCD_SHARE_BELOW) ? 1 : 0;   // see the remap in render_kernel
     const int groups = xcd_share ? f.n_active : (f.n_active + 8 * MRTX_XCD_TILE_RUN - 1) / (8 * MRTX_XCD_TILE_RUN) * (8 * MRTX_XCD_TILE_RUN);
@@ -4024,7 +3487,7 @@ hipError_t mrtx_launch_render(const FrameC& f, int S, bool stats, int mode, bool
     FrameC fr = f;
     int njobs, pwl; unsigned gx;
     render_geometry(f, S, fr.xcd_share, gx, njobs, pwl, mode);
-    const dim3 grid(gx), block(64 * MRTX_WG_WAVES);
+    const dim3 grid(gx), block(64);
     if (f.n_blocks != 1) return hipErrorInvalidValue;   // one block of S samples per launch (see render_kernel)
     if (grid.x == 0) return hipSuccess;
     PathQ q;
@@ -4070,13 +3533,13 @@ static void pick2(bool a, bool b, L&& launch) {
     else { if (b) launch(std::false_type{}, std::true_type{}); else launch(std::false_type{}, std::false_type{}); }
 }
 
-// The Sun illumination stage (illum_kernel): one wave per block of nodes -- 64 / n_sun nodes (MRTX_ILLUM_MAP 0) or 64 (1) in a
+// The Sun illumination stage (illum_kernel): one wave per block of nodes -- 64 / n_sun nodes in a
 // PW x PH block, PW as render_geometry picks it for as many pixels.  g.rows x g.cols nodes; g.pw_log2 and g.waves_x are set here.
 hipError_t mrtx_launch_illum(const FrameC& f, IllumC g, bool stats, hipStream_t st) {
     if (g.n_sun < 1 || g.n_sun > 64 || (g.n_sun & (g.n_sun - 1)) || g.rows < 1 || g.cols < 1) return hipErrorInvalidValue;
     g.n_log2 = 0;
     while ((1 << g.n_log2) < g.n_sun) g.n_log2++;
-    const int P = MRTX_ILLUM_MAP == 0 ? 64 >> g.n_log2 : 64;
+    const int P = 64 >> g.n_log2;
     int PW = P >= 32 ? 8 : P >= 8 ? 4 : P >= 2 ? 2 : 1;
     if (g.rows == 1) PW = P;                    // a point list (or a one-row band): the nodes side by side
     g.pw_log2 = PW == 64 ? 6 : PW == 32 ? 5 : PW == 16 ? 4 : PW == 8 ? 3 : PW == 4 ? 2 : PW == 2 ? 1 : 0;
