@@ -559,6 +559,38 @@ int mrtx_horizon_windows(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int
                          const float* host_horizon, const MrtxIllumEpoch* epochs_a, const MrtxIllumEpoch* epochs_b, int32_t m,
                          double min_a, double min_b, void* dev_out, float* host_out, MrtxStats* out);
 
+/* ---- Site power budgets (additive to ABI 7) --------------------------------------------------------
+ * Does an asset survive at a site, and on how much battery?  Energy is counted in integers: one count is 2^-cpw_log2 W times
+ * the epoch spacing. */
+#define MRTX_PANEL_TRACK   0   /* two-axis tracking: c = 1                                                              */
+#define MRTX_PANEL_FIXED   1   /* a fixed panel with unit normal normal_enu: c = max(0, n . l)                          */
+#define MRTX_PANEL_AZIMUTH 2   /* a vertical panel turned toward the Sun's azimuth: c = min(1, cos of the Sun's elevation) */
+typedef struct MrtxPowerModel {
+    int32_t panel;          /* MRTX_PANEL_*                                                                              */
+    double normal_enu[3];   /* FIXED: the panel's normal in local (east, north, up) of each point, any length > 0        */
+    int32_t cpw_log2;       /* counts per watt = 2^cpw_log2, in [-20, 20]                                                */
+    int64_t capacity;       /* the battery, counts: 0 <= initial <= capacity <= 2^52                                     */
+    int64_t initial;        /* its charge before epoch 0, counts                                                         */
+} MrtxPowerModel;
+/* Horizons, epochs and points as for mrtx_horizon_sun (exactly one of dev_horizon and host_horizon; m <= 2^24).  gen_w[k] is
+ * the power in watts the array delivers facing the whole unobstructed Sun at epoch k, load_w[k] the power drawn during it: m
+ * doubles each, finite, >= 0 and at most 2^28 counts after scaling.  Per (point, epoch), in float32: f = mrtx_horizon_sun
+ * FULL's fraction bit for bit, c the panel's factor from the Sun's direction in the point's frame,
+ *   G_k = (int32)rintf((((float)gen_w[k] * f) * c) * 2^cpw_log2),  L_k = (int32)rintf((float)load_w[k] * 2^cpw_log2),
+ * e_k = G_k - L_k; from there on int64.  mode 0 (FULL): n x m int32 G_k, point-major, at most 2^31 outputs per call.  mode 1
+ * (SUMMARY): n x 8 int64, point-major (dev_out 16-byte aligned); with S_j = e_0 + ... + e_j (S_-1 = 0), s_-1 = initial,
+ * t_k = s_{k-1} + e_k and s_k = min(capacity, max(0, t_k)):
+ *   [0] sum of G_k                          [1] S_{m-1}
+ *   [2] D = max(0, max_j (max_{-1 <= i < j} S_i - S_j)): the least capacity which, starting full, never empties
+ *   [3] first and [4] last epoch of that drawdown ([4] the smallest j that attains D, [3] = i + 1 for the latest i < j with
+ *       S_i maximal; both -1 if D == 0)
+ *   [5] min_k s_k     [6] epochs with t_k < 0 (load not met)     [7] sum of max(0, -t_k) (energy not delivered)
+ * Output into exactly one of dev_out and host_out; no n x m buffer is allocated in SUMMARY.  Needs a DEM, but neither a light
+ * nor a Moon frame; leaves the light, Moon frame and render state as they were.  out: launches, kernel_ms. */
+int mrtx_power_budget(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t n_az, const void* dev_horizon,
+                      const float* host_horizon, const MrtxIllumEpoch* epochs, const double* gen_w, const double* load_w,
+                      int32_t m, const MrtxPowerModel* model, int32_t mode, void* dev_out, void* host_out, MrtxStats* out);
+
 /* Math conformance probe (ABI 7): the kernels' domain-restricted reciprocal (v_rcp_f32 + Newton steps) and square root (v_sqrt_f32 + a
  * +-1 ulp residual fix) against the compiler's IEEE expansions of 1.0f / x and sqrtf(x), ON THE DEVICE, for the n float bit patterns
  * from lo_bits on: which = 0 one Newton step, 1 two steps (what the kernels use), 2 the square root.  mismatches = how many differ;

@@ -97,6 +97,13 @@ class MrtxVolatile(C.Structure):
     _fields_ = [("b", C.c_double * 4)]
 
 
+class MrtxPowerModel(C.Structure):
+    """The panel and the battery of a site power budget (mrtx_power_budget)."""
+    _fields_ = [("panel", C.c_int32), ("normal_enu", C.c_double * 3), ("cpw_log2", C.c_int32), ("capacity", C.c_int64),
+                ("initial", C.c_int64)]
+
+
+PANEL_TRACK, PANEL_FIXED, PANEL_AZIMUTH = 0, 1, 2           # MRTX_PANEL_*: MoonRT.PANELS names them
 F_COUNT_STATS = 1
 F_FORCE_WIDE = 2
 F_NO_SKIP = 4
@@ -169,6 +176,8 @@ SIGNATURES = {
                                       C.POINTER(MrtxStats)]),
     "mrtx_horizon_windows": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, C.c_double, C.c_double,
                                        _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_power_budget": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, C.c_int32, C.POINTER(MrtxPowerModel),
+                                    C.c_int32, _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_sight_grid": (C.c_int, [_VP, C.POINTER(MrtxSightGrid), _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_sight_points": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _VP,
                                     _VP, C.POINTER(MrtxStats)]),

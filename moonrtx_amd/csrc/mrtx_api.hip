@@ -62,6 +62,7 @@ hipError_t mrtx_launch_horizon(const FrameC& f, HorizonC h, bool stats, hipStrea
 hipError_t mrtx_launch_horizon_sun(const FrameC& f, HorizonSunC q, hipStream_t st);
 hipError_t mrtx_launch_horizon_raised(const FrameC& f, HorizonRaisedC q, bool stats, hipStream_t st);
 hipError_t mrtx_launch_horizon_windows(const FrameC& f, HorizonWindowsC q, hipStream_t st);
+hipError_t mrtx_launch_power_budget(const FrameC& f, PowerC q, hipStream_t st);
 hipError_t mrtx_launch_sight(const FrameC& f, SightC q, bool stats, hipStream_t st);
 hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, bool ext, hipStream_t st);
 hipError_t mrtx_launch_view_hits(const FrameC& f, const ViewC& q, bool stats, hipStream_t st);
@@ -1652,6 +1653,76 @@ int mrtx_horizon_windows(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n
     if ((rc = stage_start(c, &cold, false)) != MRTX_OK) return rc;
     HIPCHK(c, mrtx_launch_horizon_windows(f, q, c->stream));
     return stage_finish(c, dev_out, host_out, out_bytes, out, kNoRays);
+}
+
+// ---- Site power budgets ----------------------------------------------------------------------------
+int mrtx_power_budget(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon, const float* host_horizon,
+                      const MrtxIllumEpoch* epochs, const double* gen_w, const double* load_w, int32_t m,
+                      const MrtxPowerModel* model, int32_t mode, void* dev_out, void* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!latlon || !epochs) return fail(c, MRTX_E_INVALID, "null point list or epoch table");
+    if (!gen_w || !load_w || !model) return fail(c, MRTX_E_INVALID, "null generation table, load table or power model");
+    if (n < 1 || m < 1) return fail(c, MRTX_E_INVALID, "n and m must be >= 1 (got %d, %d)", n, m);
+    // 2^24 epochs of at most 2^28 counts: every sum stays within 2^52
+    if (m > (1 << 24)) return fail(c, MRTX_E_INVALID, "at most 2^24 epochs per call (got %d)", m);
+    if (!horizon_az_ok(n_az)) return fail(c, MRTX_E_INVALID, "n_az must be 4, 8, ..., 4096 (got %d)", n_az);
+    if (mode != 0 && mode != 1) return fail(c, MRTX_E_INVALID, "mode must be 0 (FULL) or 1 (SUMMARY) (got %d)", mode);
+    int rc = horizon_args(c, dev_horizon, host_horizon, n, n_az, dev_out, (const float*)host_out);
+    if (rc != MRTX_OK) return rc;
+    if (mode == 1 && dev_out && ((uintptr_t)dev_out & 15)) return fail(c, MRTX_E_INVALID, "dev_out must be 16-byte aligned");
+    if (mode == 0 && (int64_t)n * (int64_t)m > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "FULL holds at most 2^31 outputs per call: split the points into more calls");
+    if (model->panel < 0 || model->panel > 2)
+        return fail(c, MRTX_E_INVALID, "panel must be 0 (TRACK), 1 (FIXED) or 2 (AZIMUTH) (got %d)", model->panel);
+    float nrm[3] = {0.0f, 0.0f, 1.0f};
+    if (model->panel == 1) {
+        const double* e = model->normal_enu;
+        const double len = std::sqrt((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]);
+        if (!check_vec(e) || !std::isfinite(len) || !(len > 0.0)) return fail(c, MRTX_E_INVALID, "normal_enu must be finite and not zero");
+        for (int i = 0; i < 3; i++) nrm[i] = (float)(e[i] / len);
+    }
+    if (model->cpw_log2 < -20 || model->cpw_log2 > 20)
+        return fail(c, MRTX_E_INVALID, "cpw_log2 must lie in [-20, 20] (got %d)", model->cpw_log2);
+    if (model->capacity < 0 || model->capacity > ((int64_t)1 << 52))
+        return fail(c, MRTX_E_INVALID, "capacity must lie in [0, 2^52] counts");
+    if (model->initial < 0 || model->initial > model->capacity) return fail(c, MRTX_E_INVALID, "initial must lie in [0, capacity]");
+    const float scale = std::ldexp(1.0f, model->cpw_log2);
+    std::vector<float> gen((size_t)m);
+    std::vector<int32_t> load((size_t)m);
+    for (int32_t k = 0; k < m; k++) {
+        const float g = (float)gen_w[k] * scale, l = (float)load_w[k] * scale;      // a power of two: exact
+        if (!std::isfinite(gen_w[k]) || !(gen_w[k] >= 0.0) || !(g <= 268435456.0f))
+            return fail(c, MRTX_E_INVALID, "gen_w[%d] must be finite, >= 0 and at most 2^28 counts", k);
+        if (!std::isfinite(load_w[k]) || !(load_w[k] >= 0.0) || !(l <= 268435456.0f))
+            return fail(c, MRTX_E_INVALID, "load_w[%d] must be finite, >= 0 and at most 2^28 counts", k);
+        gen[(size_t)k] = (float)gen_w[k];
+        load[(size_t)k] = (int32_t)std::nearbyint(l);       // round to nearest even, the kernel's rintf
+    }
+    if ((rc = horizon_entries(c, host_horizon, n, n_az)) != MRTX_OK) return rc;
+    std::vector<float> rtab, ctab, lights;
+    if ((rc = point_tables(c, latlon, n, rtab, ctab)) != MRTX_OK) return rc;
+    if ((rc = epoch_lights(c, epochs, m, lights)) != MRTX_OK) return rc;
+    FrameC f;
+    FrameCold cold;
+    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
+    const size_t nh = host_horizon ? (size_t)n * (size_t)n_az : 0;
+    const size_t out_bytes = mode == 0 ? (size_t)n * (size_t)m * sizeof(int32_t) : (size_t)n * 64;
+    float* d[6];
+    if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK ||
+        (rc = stage_tables(c, {rtab, ctab, lights, gen, {load.data(), load.size()}, {host_horizon, nh}}, d)) != MRTX_OK)
+        return rc;
+    PowerC q;
+    std::memset(&q, 0, sizeof q);
+    q.g.rtab = d[0]; q.g.ctab = d[1];
+    q.g.rows = n; q.g.cols = n; q.g.points = 1;
+    q.lights = d[2]; q.gen = d[3]; q.load = reinterpret_cast<const int32_t*>(d[4]);
+    q.horizon = host_horizon ? d[5] : (const float*)dev_horizon;
+    q.out = dev_out; q.capacity = model->capacity; q.initial = model->initial; q.scale = scale;
+    q.nE = nrm[0]; q.nN = nrm[1]; q.nU = nrm[2];
+    q.panel = model->panel; q.az_log2 = log2_of(n_az); q.m = m; q.mode = mode;
+    if ((rc = stage_start(c, &cold, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_power_budget(f, q, c->stream));
+    return stage_finish(c, dev_out, (float*)host_out, out_bytes, out, kNoRays);
 }
 
 // ---- Terrain line of sight -------------------------------------------------------------------------

@@ -232,6 +232,25 @@ struct HorizonWindowsC {
     int32_t m;              // epochs
 };
 
+// Site power budgets (mrtx_power_budget, DESIGN.md sections 3.17 and 4.19): HorizonSunC's point list, horizons and epoch lights,
+// the generation table as float32 watts and the load table already quantised to int32 counts.  One wave per point.
+struct PowerC {
+    IllumC g;               // the point list (g.rows points), as in HorizonC
+    const float* horizon;   // n_points x n_az float32 elevations (degrees)
+    const float* lights;    // 8 floats per epoch, as IllumSeriesC's
+    const float* gen;       // m float32: (float)gen_w[k]
+    const int32_t* load;    // m int32: L_k = (int32)rintf((float)load_w[k] * scale), formed on the host
+    void* out;              // mode 0: n_points x m int32 G_k; mode 1: n_points x 8 int64 (four 16-byte stores per point)
+    long long capacity;     // counts, 0 .. 2^52
+    long long initial;      // counts, 0 .. capacity
+    float scale;            // 2^cpw_log2, exact
+    float nE, nN, nU;       // FIXED: the panel's unit normal in the point's (east, north, up), float64 rounded once
+    int32_t panel;          // 0 TRACK, 1 FIXED, 2 AZIMUTH
+    int32_t az_log2;        // log2(n_az)
+    int32_t m;              // epochs
+    int32_t mode;           // 0 FULL, 1 SUMMARY
+};
+
 // Regolith surface temperatures (mrtx_thermal): per point the absorbed flux of every epoch from its
 // vertex, its horizon row and the epoch's light constants, and a 1D heat-conduction column stepped through the epochs.  One
 // lane per point; the column lives in registers, so the node count is capped at compile time.  The layer tables are shared by

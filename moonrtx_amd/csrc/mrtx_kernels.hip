@@ -2079,6 +2079,129 @@ __global__ void __launch_bounds__(64) horizon_windows_kernel(const FrameC f, con
     }
 }
 
+// Site power budgets (DESIGN.md sections 3.17 and 4.19): horizon_windows_kernel's walk -- one wave per point, the epochs 64 at
+// a time, the vertex and frame once, the horizon row in L1 -- with disc_fraction turned into integer counts of generated energy
+// G_k (the panel's cosine factor from the same xu, xn, xe) and, with the host's counts of the load L_k, e_k = G_k - L_k.  FULL
+// stores G_k.  SUMMARY reduces e in int64, so no result depends on the order of a reduction: per chunk an inclusive add scan
+// (the running balance S), an exclusive scan of its peak (value and index, the later index on equal values), the wave's
+// largest drawdown peak - S (its lowest lane from a ballot, kept only when strictly greater than the one held), and an
+// inclusive scan of the clamp functions x -> min(hi, max(lo, x + a)) (closed under composition), which each lane applies to
+// the carried state of charge.  Everything carried is wave-uniform and read from the chunk's last valid lane.  A lane past the
+// last epoch holds e = 0 and no peak, no drawdown and no count: its clamp (0, 0, capacity) is the identity on a state of charge.
+// Plain shuffles; no atomics, no LDS; lane 0 stores the point's four 16-byte pairs.
+__device__ __forceinline__ long long ll_min(long long a, long long b) { return a < b ? a : b; }
+__device__ __forceinline__ long long ll_max(long long a, long long b) { return a > b ? a : b; }
+template <bool WIDE>
+__global__ void __launch_bounds__(64) power_budget_kernel(const FrameC f, const PowerC q) {
+    constexpr long long kLowest = -0x7fffffffffffffffll - 1;
+    const int lane = threadIdx.x;
+    const int pt = (int)blockIdx.x;
+    const int n_az = 1 << q.az_log2;
+    Vertex v;
+    (void)illum_vertex<false, WIDE>(f, q.g, pt, pt, v, nullptr);
+    const PointFrame p = point_frame(f, q.g, pt, pt, v);
+    const float* const hz = q.horizon + ((int64_t)pt << q.az_log2);
+    const float4* const lights = reinterpret_cast<const float4*>(q.lights);
+    const long long cap = q.capacity;
+    long long sum_g = 0, unmet = 0, min_s = 0x7fffffffffffffffll;   // per lane, reduced at the end
+    uint32_t n_unmet = 0;                                           // wave-uniform
+    long long S_c = 0, pk_c = 0, s_c = q.initial, D = 0;            // the carries: balance, its peak, state of charge; the drawdown
+    int pki_c = -1, d_first = -1, d_last = -1;
+    for (int k0 = 0; k0 < q.m; k0 += 64) {
+        const int k = k0 + lane;
+        const bool in = k < q.m;
+        int G = 0, L = 0;
+        if (in) {
+            float la, lb, lc;
+            const float fr = disc_fraction(lights[2 * (int64_t)k], p, hz, n_az, la, lb, lc);
+            float c = 1.0f;
+            if (q.panel != 0) {                                     // wave-uniform; xu, xn, xe as disc_fraction forms them
+                const float xu = fmaf(p.uc, lc, fmaf(p.ub, lb, p.ua * la));
+                const float xn = fmaf(p.Nc, lc, fmaf(p.Nb, lb, p.Na * la));
+                const float xe = fmaf(-p.ct.x, lb, p.ct.y * la);
+                c = q.panel == 1 ? fmaxf(0.0f, fmaf(q.nU, xu, fmaf(q.nN, xn, q.nE * xe)))
+                                 : fminf(1.0f, sqrtf(fmaf(xe, xe, xn * xn)));
+            }
+            const float g = (q.gen[k] * fr) * c;
+            G = (int)rintf(g * q.scale);
+            if (q.mode == 0) reinterpret_cast<int32_t*>(q.out)[(int64_t)pt * q.m + k] = G;
+            else L = q.load[k];
+        }
+        if (q.mode == 0) continue;
+        const long long e = (long long)G - (long long)L;
+        sum_g += (long long)G;
+        // the balance after each epoch
+        long long S = e;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            const long long t = __shfl_up(S, s, 64);
+            if (lane >= s) S += t;
+        }
+        S += S_c;
+        // its peak up to and including each epoch (ps, pi), then up to the epoch before (xs, xi) with the carried peak
+        long long ps = in ? S : kLowest;
+        int pi = k;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            const long long ts = __shfl_up(ps, s, 64);
+            const int ti = __shfl_up(pi, s, 64);
+            if (lane >= s && ts > ps) { ps = ts; pi = ti; }         // the earlier one only when strictly greater
+        }
+        long long xs = __shfl_up(ps, 1, 64);
+        int xi = __shfl_up(pi, 1, 64);
+        if (lane == 0 || pk_c > xs) { xs = pk_c; xi = pki_c; }
+        const long long d = in ? xs - S : -1;
+        long long mx = d;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) mx = ll_max(mx, __shfl_xor(mx, s, 64));
+        if (mx > D) {                                               // wave-uniform; the lowest lane at mx: the earliest end
+            const int jl = (int)__builtin_ctzll(__ballot(d == mx));
+            D = mx;
+            d_last = k0 + jl;
+            d_first = __shfl(xi, jl, 64) + 1;
+        }
+        // the clamps of epochs k0 .. k composed: (fa, flo, fhi)
+        long long fa = e, flo = 0, fhi = cap;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            const long long ta = __shfl_up(fa, s, 64), tlo = __shfl_up(flo, s, 64), thi = __shfl_up(fhi, s, 64);
+            if (lane >= s) {                                        // this lane's function after the earlier lanes'
+                const long long nlo = ll_min(fhi, ll_max(flo, tlo + fa)), nhi = ll_min(fhi, ll_max(flo, thi + fa));
+                fa += ta; flo = nlo; fhi = nhi;
+            }
+        }
+        const long long sk = ll_min(fhi, ll_max(flo, s_c + fa));
+        long long sp = __shfl_up(sk, 1, 64);
+        if (lane == 0) sp = s_c;
+        const long long t = sp + e;
+        const bool miss = in && t < 0;
+        if (in) min_s = ll_min(min_s, sk);
+        if (miss) unmet -= t;
+        n_unmet += (uint32_t)__popcll(__ballot(miss));
+        const int last = min(64, q.m - k0) - 1;
+        S_c = __shfl(S, last, 64);
+        s_c = __shfl(sk, last, 64);
+        const long long ls = __shfl(ps, last, 64);
+        const int li = __shfl(pi, last, 64);
+        if (!(pk_c > ls)) { pk_c = ls; pki_c = li; }
+    }
+    if (q.mode != 0) {
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            sum_g += __shfl_xor(sum_g, s, 64);
+            unmet += __shfl_xor(unmet, s, 64);
+            min_s = ll_min(min_s, __shfl_xor(min_s, s, 64));
+        }
+        if (lane == 0) {
+            longlong2* const o = reinterpret_cast<longlong2*>(q.out) + 4 * (int64_t)pt;
+            o[0] = make_longlong2(sum_g, S_c);
+            o[1] = make_longlong2(D, (long long)d_first);
+            o[2] = make_longlong2((long long)d_last, min_s);
+            o[3] = make_longlong2((long long)n_unmet, unmet);
+        }
+    }
+}
+
 // Regolith surface temperatures (DESIGN.md sections 3.10 and 4.11).  One lane = one point: its vertex and local frame are
 // formed once, then per epoch the absorbed flux (the disc fraction of horizon_sun_kernel, illum_mu's mu, the albedo law) and
 // n_sub explicit steps of its heat-conduction column.  The column's temperatures are float64 registers (a deep node moves by
@@ -3625,6 +3748,18 @@ hipError_t mrtx_launch_horizon_windows(const FrameC& f, HorizonWindowsC q, hipSt
     const dim3 grid((unsigned)q.g.rows), block(64);
     if (f.dem_wide) hipLaunchKernelGGL((mrtx::horizon_windows_kernel<true>), grid, block, 0, st, f, q);
     else hipLaunchKernelGGL((mrtx::horizon_windows_kernel<false>), grid, block, 0, st, f, q);
+    return hipGetLastError();
+}
+
+// Site power budgets (power_budget_kernel): one wave per point.
+hipError_t mrtx_launch_power_budget(const FrameC& f, PowerC q, hipStream_t st) {
+    if (q.g.rows < 1 || q.az_log2 < 2 || q.az_log2 > 12 || q.m < 1 || q.m > (1 << 24) || (q.mode != 0 && q.mode != 1) ||
+        q.panel < 0 || q.panel > 2 || q.initial < 0 || q.initial > q.capacity || q.capacity > (1ll << 52) || !q.g.points ||
+        !q.horizon || !q.lights || !q.gen || !q.load || !q.out)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)q.g.rows), block(64);
+    if (f.dem_wide) hipLaunchKernelGGL((mrtx::power_budget_kernel<true>), grid, block, 0, st, f, q);
+    else hipLaunchKernelGGL((mrtx::power_budget_kernel<false>), grid, block, 0, st, f, q);
     return hipGetLastError();
 }
 

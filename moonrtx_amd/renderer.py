@@ -10,7 +10,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import MrtxConfig, MrtxParams, MrtxStats, vec3
+from ._lib import MrtxConfig, MrtxParams, MrtxPowerModel, MrtxStats, vec3
 
 
 class MoonRTError(RuntimeError):
@@ -423,6 +423,67 @@ class MoonRT:
             self._check(self._lib.mrtx_horizon_windows(self._ctx, pts[a:].ctypes.data, b - a, n_az, dh, hh, ea.ctypes.data,
                                                        eb.ctypes.data, m, float(min_a), float(min_b), None,
                                                        res[a:].ctypes.data, C.byref(st)), "mrtx_horizon_windows")
+            self._add_stats(stats, st)
+        return res
+
+    POWER_COLUMNS = ("generated", "net", "storage_need", "drawdown_first", "drawdown_last", "min_charge", "epochs_unmet",
+                     "energy_unmet")
+    PANELS = {"track": _lib.PANEL_TRACK, "fixed": _lib.PANEL_FIXED, "azimuth": _lib.PANEL_AZIMUTH}
+
+    @staticmethod
+    def power_scale(gen_w, load_w):
+        """The largest cpw_log2 in [-20, 20] that keeps both tables, as float32 watts times 2^cpw_log2, at or below 2^28 counts
+        (DESIGN.md section 3.17); ValueError if even 2^-20 counts per watt does not."""
+        top = max(float(np.max(np.asarray(gen_w, np.float64).astype(np.float32), initial=0.0)),
+                  float(np.max(np.asarray(load_w, np.float64).astype(np.float32), initial=0.0)))
+        if not top > 0.0:
+            return 20
+        if not math.isfinite(top):
+            raise ValueError("gen_w and load_w must be finite")
+        mant, exp = math.frexp(top)             # top = mant * 2^exp, mant in [0.5, 1)
+        e = (29 if mant == 0.5 else 28) - exp
+        if e < -20:
+            raise ValueError("gen_w or load_w exceeds 2^28 counts at 2^-20 counts per watt")
+        return min(e, 20)
+
+    def power_budget(self, lat_deg, lon_deg, horizon, epochs, gen_w, load_w, panel="track", normal_enu=None, cpw_log2=None,
+                     capacity=0, initial=None, mode="summary", n_az=None, stats=None, chunk_bytes=256 << 20):
+        """The energy balance of a solar-powered asset at N points against the horizons of `horizon`, in integer counts of
+        2^-cpw_log2 W x the epoch spacing.  gen_w[k]: the watts the array delivers facing the whole
+        Sun at epoch k; load_w[k]: the watts drawn (one value or one per epoch).  panel: "track" (two-axis), "fixed" (normal
+        normal_enu in each point's east, north, up) or "azimuth" (a vertical panel turned toward the Sun).  capacity and
+        initial are counts (initial=None: full); cpw_log2=None picks power_scale's.  mode "summary": (N, 8) int64 columns
+        POWER_COLUMNS -- the generated and the net energy, the least capacity that starting full never empties, the first and
+        last epoch of that drawdown (-1: none), the lowest state of charge, the epochs whose load was not met and the energy
+        not delivered; mode "full": (N, m) int32 generated counts G_k.  `horizon` as for horizon_sun; SUMMARY forms no (N, m)
+        table anywhere."""
+        la, lo = self._points(lat_deg, lon_deg)
+        ep = self._epochs(epochs)
+        m = ep.shape[0]
+        gen = np.ascontiguousarray(np.broadcast_to(np.asarray(gen_w, np.float64), (m,)))
+        load = np.ascontiguousarray(np.broadcast_to(np.asarray(load_w, np.float64), (m,)))
+        if mode not in ("summary", "full"):
+            raise ValueError(f"mode must be 'summary' or 'full' (got {mode!r})")
+        if panel not in self.PANELS:
+            raise ValueError(f"panel must be one of {sorted(self.PANELS)} (got {panel!r})")
+        if (panel == "fixed") != (normal_enu is not None):
+            raise ValueError("normal_enu goes with panel='fixed', and only with it")
+        md = MrtxPowerModel()
+        md.panel = self.PANELS[panel]
+        md.normal_enu[:] = [float(x) for x in (normal_enu if normal_enu is not None else (0.0, 0.0, 1.0))]
+        md.cpw_log2 = self.power_scale(gen, load) if cpw_log2 is None else int(cpw_log2)
+        md.capacity = int(capacity)
+        md.initial = int(capacity) if initial is None else int(initial)
+        n_az, hz_at = self._horizon_arg(horizon, la.size, n_az)
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        full = mode == "full"
+        res = np.empty((la.size, m), np.int32) if full else np.empty((la.size, 8), np.int64)
+        for a, b in self._chunks(la.size, max(m, 1) if full else max(int(n_az), 0) + 16, chunk_bytes):
+            st = MrtxStats()
+            dh, hh = hz_at(a)
+            self._check(self._lib.mrtx_power_budget(self._ctx, pts[a:].ctypes.data, b - a, n_az, dh, hh, ep.ctypes.data,
+                                                    gen.ctypes.data, load.ctypes.data, m, C.byref(md), 0 if full else 1, None,
+                                                    res[a:].ctypes.data, C.byref(st)), "mrtx_power_budget")
             self._add_stats(stats, st)
         return res
 

@@ -188,6 +188,80 @@ def site_windows(rt, lat, lon, start, days, step_min=60, height_m=0.0, min_sun=0
     return SiteWindows(times, out[:, 0], run(1), out[:, 2], run(3), out[:, 4], run(5), out[:, 6].astype(np.int64), run(7), stats)
 
 
+class PowerBudget(NamedTuple):
+    times: list                   # the dates used
+    generated_wh: np.ndarray      # (N,) energy the array generated over the dates, Wh
+    net_wh: np.ndarray            # (N,) generated minus drawn, Wh
+    storage_wh: np.ndarray        # (N,) the least battery which, starting full, never empties: the worst cumulative deficit, Wh
+    deficit_start: np.ndarray     # (N,) int: index into `times` of that deficit's first date (-1: the balance never falls)
+    deficit_end: np.ndarray       # (N,) int: index of its last date (-1: none)
+    min_charge_wh: np.ndarray     # (N,) lowest state of charge of the capacity_wh battery, Wh
+    unmet_h: np.ndarray           # (N,) hours during which that battery could not carry the load
+    unmet_wh: np.ndarray          # (N,) energy the load asked for and did not get, Wh
+    cpw_log2: int                 # counts per watt = 2^cpw_log2 (section 3.17)
+    stats: dict                   # summed counters and kernel times of the horizon and the budget calls
+
+
+def counts_to_wh(counts, cpw_log2, step_min):
+    """Counts of 2^-cpw_log2 W x one epoch as Wh, float64: exact up to the one rounding of the
+    product with the epoch's hours."""
+    return np.asarray(counts, np.float64) * 2.0 ** -int(cpw_log2) * (float(step_min) / 60.0)
+
+
+def wh_to_counts(wh, cpw_log2, step_min):
+    """The whole number of counts nearest to `wh` (a battery's capacity, say)."""
+    return int(round(float(wh) * 2.0 ** int(cpw_log2) / (float(step_min) / 60.0)))
+
+
+def power_budget(rt, lat, lon, start, days, step_min=60, height_m=0.0, *, area_m2, efficiency, load_w, panel="track",
+                 normal_enu=None, capacity_wh=0.0, initial_wh=None, n_az=256, n_bis=14, observer=None, chunk=65536,
+                 radius_m=1737400.0, cpw_log2=None):
+    """Does a solar-powered asset survive at the points (lat, lon in degrees), and on how much battery, from `start`
+    (timezone-aware) over `days` at `step_min` minutes?  Each point's horizon is computed once from
+    a panel height_m above it (MoonRT.horizon), the Sun's epochs and flux once (ephemeris.sun_epochs, sun_flux); the array
+    delivers flux x area_m2 x efficiency W facing the whole Sun, scaled per date by the visible share of the disc and the
+    panel's cosine ("track", "fixed" with normal_enu, "azimuth").  load_w is the power drawn: one value, or one per date (an
+    (awake, hibernating) rule would depend on each point's own Sun and is not offered).  The balance is reduced on the
+    device (MoonRT.power_budget): points are streamed `chunk` at a time, their horizons stay in a device buffer and no
+    (points x dates) table is formed.  capacity_wh is the battery whose state of charge is followed (initial_wh=None:
+    full).  Returns PowerBudget."""
+    from .renderer import DeviceBuffer
+    la = np.atleast_1d(np.asarray(lat, np.float64)).ravel()
+    lo = np.atleast_1d(np.asarray(lon, np.float64)).ravel()
+    if la.shape != lo.shape:
+        raise ValueError("lat and lon must have the same number of points")
+    m = int(round(days * 1440.0 / step_min))
+    if m < 1:
+        raise ValueError("days / step_min gives no date")
+    times = [start + timedelta(minutes=k * step_min) for k in range(m)]
+    load = np.asarray(load_w, np.float64)
+    if load.ndim > 1 or (load.ndim == 1 and load.size != m):
+        raise ValueError("load_w must be one value or one per date")
+    load = np.ascontiguousarray(np.broadcast_to(load, (m,)))
+    ep = ephemeris.sun_epochs(times, observer)
+    gen = ephemeris.sun_flux(times) * (float(area_m2) * float(efficiency))
+    cpw = rt.power_scale(gen, load) if cpw_log2 is None else int(cpw_log2)
+    cap = wh_to_counts(capacity_wh, cpw, step_min)
+    ini = cap if initial_wh is None else wh_to_counts(initial_wh, cpw, step_min)
+    rt.horizon_azimuths(n_az)       # checks n_az
+    raised = _heights(0.0 if height_m is None else height_m, radius_m, la.size)
+    chunk = max(1, min(int(chunk), la.size, (1 << 31) // int(n_az)))
+    out = np.empty((la.size, 8), np.int64)
+    stats = {}
+    buf = DeviceBuffer(chunk * int(n_az) * 4, rt.config()["device"])
+    try:
+        for a in range(0, la.size, chunk):
+            b = min(a + chunk, la.size)
+            rt.horizon(la[a:b], lo[a:b], n_az=n_az, n_bis=n_bis, stats=stats, out=buf, **raised(a, b))
+            out[a:b] = rt.power_budget(la[a:b], lo[a:b], buf, ep, gen, load, panel=panel, normal_enu=normal_enu, cpw_log2=cpw,
+                                       capacity=cap, initial=ini, n_az=n_az, stats=stats)
+    finally:
+        buf.free()
+    wh = lambda j: counts_to_wh(out[:, j], cpw, step_min)     # noqa: E731
+    return PowerBudget(times, wh(0), wh(1), wh(2), out[:, 3].copy(), out[:, 4].copy(), wh(5),
+                       out[:, 6].astype(np.float64) * (step_min / 60.0), wh(7), cpw, stats)
+
+
 class SurfaceTemperatures(NamedTuple):
     t_max: np.ndarray             # (N,) highest surface temperature over the recorded dates, K
     t_min: np.ndarray             # (N,) lowest, K
