@@ -591,6 +591,37 @@ int mrtx_power_budget(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_
                       const float* host_horizon, const MrtxIllumEpoch* epochs, const double* gen_w, const double* load_w,
                       int32_t m, const MrtxPowerModel* model, int32_t mode, void* dev_out, void* host_out, MrtxStats* out);
 
+/* ---- The Earth's occultation of the Sun (additive to ABI 7) ----------------------------------------
+ * Per (point, epoch) the share g in [0, 1] of the source's disc that the body's disc leaves uncovered, seen from the lifted
+ * vertex of mrtx_horizon_points: the geometric discs of epochs_source (the Sun moved out to its true distance:
+ * moonrtx_amd.ephemeris.far_sun_epochs) and epochs_body (the Earth: earth_epochs), m rows each for the same dates, by the
+ * planar two-disc rule of section 3.18 in float32.  No atmosphere.  The host marks in float64 the epochs in which no point of
+ * the Moon's bounding sphere can see the discs overlap; those take g = 1, the value the rule would give, without being formed.
+ * m <= 2^24.  mode 0 (FULL): n x m float32, point-major, at most 2^31 outputs per call.  mode 1 (SUMMARY): n x 8 float32,
+ * point-major (dev_out 16-byte aligned), no n x m buffer:
+ *   [0] mean g                                   [1] min g
+ *   [2] share of epochs with g < 1               [3] share with g == 0          (both (float)(count / (double)m))
+ *   [4] longest run of consecutive epochs with g < 1
+ *   [5] index of the first epoch of that run (the earliest such run; -1 if [4] is 0)
+ *   [6] longest run with g == 0                  [7] number of maximal runs of g < 1: the eclipses the point saw
+ * Output into exactly one of dev_out and host_out.  Refused with MRTX_E_INVALID before any launch: a null table, m < 1, a
+ * non-finite entry, a negative source radius, a body radius <= 0, a body whose centre is nearer to the Moon's centre than the
+ * bounding sphere plus its own radius, a body that is not nearer than the source from every point of the bounding sphere, a
+ * bad mode, both or neither output, a misaligned dev_out in SUMMARY.  Needs a DEM, but neither a light nor a Moon frame;
+ * leaves the light, Moon frame and render state as they were.  out: launches, kernel_ms. */
+int mrtx_occultation(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, const MrtxIllumEpoch* epochs_source,
+                     const MrtxIllumEpoch* epochs_body, int32_t m, int32_t mode, void* dev_out, float* host_out, MrtxStats* out);
+/* mrtx_thermal_column under that occultation.  occ_source and occ_body: both NULL (then mrtx_thermal_column bit for bit in
+ * every mode: outputs, counters, refusals, range flag) or both given, m rows each, checked as mrtx_occultation checks them.
+ * With the tables the disc fraction f of every epoch k, spin-up included, becomes f * g_k with g_k mrtx_occultation's value at
+ * the point for epoch k: in Q_abs, in FLUX and in EXITANCE's M_vis.  The product is exact where the terrain hides nothing of
+ * the disc and an approximation elsewhere (section 3.18). */
+int mrtx_thermal_occulted(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t n_az, const void* dev_horizon,
+                          const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux_Wm2, int32_t m,
+                          const MrtxThermalModel* model, int32_t mode, const void* dev_extra, const float* host_extra,
+                          int64_t extra_len, const MrtxVolatile* species, const MrtxIllumEpoch* occ_source,
+                          const MrtxIllumEpoch* occ_body, void* dev_out, void* host_out, MrtxStats* out);
+
 /* Math conformance probe (ABI 7): the kernels' domain-restricted reciprocal (v_rcp_f32 + Newton steps) and square root (v_sqrt_f32 + a
  * +-1 ulp residual fix) against the compiler's IEEE expansions of 1.0f / x and sqrtf(x), ON THE DEVICE, for the n float bit patterns
  * from lo_bits on: which = 0 one Newton step, 1 two steps (what the kernels use), 2 the square root.  mismatches = how many differ;

@@ -198,6 +198,9 @@ SIGNATURES = {
                                        C.c_int64, _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_thermal_column": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                       C.c_int64, C.POINTER(MrtxVolatile), _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_occultation": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_thermal_occulted": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
+                                        C.c_int64, C.POINTER(MrtxVolatile), _VP, _VP, _VP, _VP, C.POINTER(MrtxStats)]),
 }
 
 _lib = None

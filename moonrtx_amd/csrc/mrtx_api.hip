@@ -62,6 +62,7 @@ hipError_t mrtx_launch_horizon(const FrameC& f, HorizonC h, bool stats, hipStrea
 hipError_t mrtx_launch_horizon_sun(const FrameC& f, HorizonSunC q, hipStream_t st);
 hipError_t mrtx_launch_horizon_raised(const FrameC& f, HorizonRaisedC q, bool stats, hipStream_t st);
 hipError_t mrtx_launch_horizon_windows(const FrameC& f, HorizonWindowsC q, hipStream_t st);
+hipError_t mrtx_launch_occultation(const FrameC& f, OccultC q, hipStream_t st);
 hipError_t mrtx_launch_power_budget(const FrameC& f, PowerC q, hipStream_t st);
 hipError_t mrtx_launch_sight(const FrameC& f, SightC q, bool stats, hipStream_t st);
 hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, bool ext, hipStream_t st);
@@ -1655,6 +1656,77 @@ int mrtx_horizon_windows(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n
     return stage_finish(c, dev_out, host_out, out_bytes, out, kNoRays);
 }
 
+// ---- The Earth's occultation of the Sun ------------------------------------------------------------
+// The two epoch tables of mrtx_occultation and mrtx_thermal_occulted: epoch_lights' checks and constants for both, the
+// geometry the two-disc rule stands on, and per epoch the float64 mark "some point inside the bounding sphere may see the
+// discs overlap".  With Rb the bounding sphere (the Moon's radius and the vertex lift, plus a thousandth), d the centre
+// distances and r the radii: the centre's separation, less both bodies' largest parallax asin(Rb / d), against the sum of the
+// largest angular radii asin(r / (d - Rb)) widened by 1 % and 1e-4 rad -- a hundred times what float32 directions can move.
+static int occult_tables(mrtx_ctx* c, const MrtxIllumEpoch* src, const MrtxIllumEpoch* body, int32_t m, std::vector<float>& ls,
+                         std::vector<float>& lb, std::vector<float>& marks) {
+    int rc;
+    if ((rc = epoch_lights(c, src, m, ls)) != MRTX_OK) return rc;
+    if ((rc = epoch_lights(c, body, m, lb)) != MRTX_OK) return rc;
+    const double Rb = 1.001 * c->radius + std::fabs((double)c->prm.scene_epsilon);
+    marks.assign((size_t)m, 0.0f);
+    int32_t* const mk = reinterpret_cast<int32_t*>(marks.data());
+    for (int32_t k = 0; k < m; k++) {
+        double a[3], b[3];
+        for (int i = 0; i < 3; i++) { a[i] = src[k].light_pos[i] - src[k].center[i]; b[i] = body[k].light_pos[i] - body[k].center[i]; }
+        const double ds = std::sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+        const double db = std::sqrt((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]);
+        const double rs = src[k].light_radius, rb = body[k].light_radius;
+        if (!(rb > 0.0)) return fail(c, MRTX_E_INVALID, "epoch %d: the body's radius must be > 0", k);
+        if (!(db > Rb + rb))
+            return fail(c, MRTX_E_INVALID, "epoch %d: the body reaches into the Moon's bounding sphere (centre %g away, radius %g)",
+                        k, db, rb);
+        if (!(db + Rb < ds - Rb))
+            return fail(c, MRTX_E_INVALID, "epoch %d: the body (%g away) is not nearer than the source (%g) from every point", k, db,
+                        ds);
+        double x[3];
+        cross(a, b, x);
+        const double sep = std::atan2(std::sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]), (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]);
+        const double reach = std::asin(std::min(1.0, rs / (ds - Rb))) + std::asin(std::min(1.0, rb / (db - Rb)));
+        mk[k] = sep - std::asin(Rb / ds) - std::asin(Rb / db) <= 1.01 * reach + 1e-4 ? 1 : 0;
+    }
+    return MRTX_OK;
+}
+
+int mrtx_occultation(mrtx_ctx* c, const double* latlon, int32_t n, const MrtxIllumEpoch* epochs_source,
+                     const MrtxIllumEpoch* epochs_body, int32_t m, int32_t mode, void* dev_out, float* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!latlon || !epochs_source || !epochs_body) return fail(c, MRTX_E_INVALID, "null point list or epoch table");
+    if (n < 1 || m < 1) return fail(c, MRTX_E_INVALID, "n and m must be >= 1 (got %d, %d)", n, m);
+    // the runs, the start index and the run count are float counts, exact up to 2^24
+    if (m > (1 << 24)) return fail(c, MRTX_E_INVALID, "at most 2^24 epochs per call (got %d)", m);
+    if (mode != 0 && mode != 1) return fail(c, MRTX_E_INVALID, "mode must be 0 (FULL) or 1 (SUMMARY) (got %d)", mode);
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    if (mode == 1 && dev_out && ((uintptr_t)dev_out & 15)) return fail(c, MRTX_E_INVALID, "dev_out must be 16-byte aligned");
+    if (mode == 0 && (int64_t)n * (int64_t)m > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "FULL holds at most 2^31 outputs per call: split the points into more calls");
+    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
+    std::vector<float> rtab, ctab, ls, lb, marks;
+    int rc;
+    if ((rc = point_tables(c, latlon, n, rtab, ctab)) != MRTX_OK) return rc;
+    if ((rc = occult_tables(c, epochs_source, epochs_body, m, ls, lb, marks)) != MRTX_OK) return rc;
+    FrameC f;
+    FrameCold cold;
+    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
+    const size_t out_bytes = mode == 0 ? (size_t)n * (size_t)m * sizeof(float) : (size_t)n * 32;
+    float* d[5];
+    if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK || (rc = stage_tables(c, {rtab, ctab, ls, lb, marks}, d)) != MRTX_OK)
+        return rc;
+    OccultC q;
+    std::memset(&q, 0, sizeof q);
+    q.g.rtab = d[0]; q.g.ctab = d[1];
+    q.g.rows = n; q.g.cols = n; q.g.points = 1;
+    q.src = d[2]; q.body = d[3]; q.mark = reinterpret_cast<const int32_t*>(d[4]);
+    q.out = (float*)dev_out; q.m = m; q.mode = mode;
+    if ((rc = stage_start(c, &cold, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_occultation(f, q, c->stream));
+    return stage_finish(c, dev_out, host_out, out_bytes, out, kNoRays);
+}
+
 // ---- Site power budgets ----------------------------------------------------------------------------
 int mrtx_power_budget(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon, const float* host_horizon,
                       const MrtxIllumEpoch* epochs, const double* gen_w, const double* load_w, int32_t m,
@@ -2247,9 +2319,12 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
                        const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux, int32_t m,
                        const MrtxThermalModel* model, int32_t mode, void* dev_out, void* host_out, MrtxStats* out,
                        ThermalEntry entry, const void* dev_extra, const float* host_extra, int64_t extra_len,
-                       const MrtxVolatile* species) {
+                       const MrtxVolatile* species, const MrtxIllumEpoch* occ_source = nullptr,
+                       const MrtxIllumEpoch* occ_body = nullptr) {
     const bool ext = entry != kThermal;
     if (!c) return MRTX_E_INVALID;
+    if ((occ_source == nullptr) != (occ_body == nullptr))
+        return fail(c, MRTX_E_INVALID, "give both occultation tables or neither");
     if (!latlon || !epochs || !flux || !model) return fail(c, MRTX_E_INVALID, "null point list, epoch table, flux or model");
     if (n < 1 || m < 1) return fail(c, MRTX_E_INVALID, "n and m must be >= 1 (got %d, %d)", n, m);
     if (m > (1 << 24)) return fail(c, MRTX_E_INVALID, "at most 2^24 epochs per call (got %d)", m);
@@ -2313,6 +2388,8 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
     std::vector<float> rtab, ctab, lights;
     if ((rc = point_tables(c, latlon, n, rtab, ctab)) != MRTX_OK) return rc;
     if ((rc = epoch_lights(c, epochs, m, lights)) != MRTX_OK) return rc;
+    std::vector<float> occ_s, occ_b, occ_m;     // section 3.18: empty segments without the tables
+    if (occ_source && (rc = occult_tables(c, occ_source, occ_body, m, occ_s, occ_b, occ_m)) != MRTX_OK) return rc;
     FrameC f;
     FrameCold cold;
     if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
@@ -2321,12 +2398,13 @@ static int thermal_run(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_a
     const size_t nh = host_horizon ? (size_t)n * (size_t)n_az : 0;
     const size_t nx = host_extra ? (size_t)n * (size_t)m : 0;
     const size_t out_bytes = (size_t)n * (size_t)width * (mode == 5 ? sizeof(double) : sizeof(float));
-    float* d[6];
+    float* d[9];
     if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK ||
-        (rc = stage_tables(c, {rtab, ctab, lights, fl, {host_horizon, nh}, {host_extra, nx}}, d)) != MRTX_OK)
+        (rc = stage_tables(c, {rtab, ctab, lights, fl, {host_horizon, nh}, {host_extra, nx}, occ_s, occ_b, occ_m}, d)) != MRTX_OK)
         return rc;
     ThermalC q;
     std::memset(&q, 0, sizeof q);
+    if (occ_source) { q.occ_src = d[6]; q.occ_body = d[7]; q.occ_mark = reinterpret_cast<const int32_t*>(d[8]); }
     q.g.rtab = d[0]; q.g.ctab = d[1];
     q.g.rows = n; q.g.cols = n; q.g.points = 1;
     q.horizon = host_horizon ? d[4] : (const float*)dev_horizon;
@@ -2385,6 +2463,16 @@ int mrtx_thermal_column(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_
                         int64_t extra_len, const MrtxVolatile* species, void* dev_out, void* host_out, MrtxStats* out) {
     return thermal_run(c, latlon, n, n_az, dev_horizon, host_horizon, epochs, flux, m, model, mode, dev_out, host_out, out,
                        kThermalColumn, dev_extra, host_extra, extra_len, species);
+}
+
+// ---- The thermal column under the Earth's occultation of the Sun ----------------------------------
+int mrtx_thermal_occulted(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon,
+                          const float* host_horizon, const MrtxIllumEpoch* epochs, const double* flux, int32_t m,
+                          const MrtxThermalModel* model, int32_t mode, const void* dev_extra, const float* host_extra,
+                          int64_t extra_len, const MrtxVolatile* species, const MrtxIllumEpoch* occ_source,
+                          const MrtxIllumEpoch* occ_body, void* dev_out, void* host_out, MrtxStats* out) {
+    return thermal_run(c, latlon, n, n_az, dev_horizon, host_horizon, epochs, flux, m, model, mode, dev_out, host_out, out,
+                       kThermalColumn, dev_extra, host_extra, extra_len, species, occ_source, occ_body);
 }
 
 // ---- Terrain-scattered sunlight and infrared -------------------------------------------------------

@@ -288,6 +288,23 @@ struct ThermalC {
     const float* xflux;             // null, or n x m float32 extra absorbed flux, point-major
     // thermal_kernel<WIDE, true, 2> only (mrtx_thermal_column's VOLATILE, section 3.16)
     double vb[4];                   // ln E(T) = vb[0] - vb[1] / T + vb[2] ln T + vb[3] T
+    // thermal_kernel<.., OCC = true> only (mrtx_thermal_occulted, section 3.18); appended, so the members above keep their offsets
+    const float* occ_src;           // m epochs of the far source, 8 floats each as `lights`
+    const float* occ_body;          // m epochs of the occulting body
+    const int32_t* occ_mark;        // per epoch: nonzero where some point of the bounding sphere may have g < 1
+};
+
+// The occultation of a source by a body (mrtx_occultation): per (point, epoch) the share g of the
+// source's disc that the body's disc leaves uncovered, seen from the point's lifted vertex.  One wave per point walks the
+// epochs 64 at a time; an epoch whose mark is 0 takes g = 1 without forming anything.
+struct OccultC {
+    IllumC g;               // the point list (g.rows points), as in HorizonC
+    const float* src;       // 8 floats per epoch, as IllumSeriesC's lights: the source (the Sun at its true distance)
+    const float* body;      // the same for the occulting body (the Earth)
+    const int32_t* mark;    // m int32, the host's float64 prefilter: 0 = no point of the bounding sphere can have g < 1
+    float* out;             // mode 0: n_points x m float32 g; mode 1: n_points x 8 float32 (two float4 per point)
+    int32_t m;              // epochs
+    int32_t mode;           // 0 FULL, 1 SUMMARY
 };
 
 // What terrain a point sees (mrtx_view_hits).

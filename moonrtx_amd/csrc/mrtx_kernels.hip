@@ -1949,6 +1949,35 @@ __device__ __forceinline__ float disc_fraction(const float4 l0, const PointFrame
     return fr;
 }
 
+// The share g of a source's disc that a body's disc leaves uncovered, from the epoch's (Lb.xyz, rL2)
+// of the source ls and of the body lb and the point's frame p (its lifted origin).  Both unit directions and both angular
+// radii (radians) as disc_fraction forms them; the separation from atan2f of |a x b| and a . b (acosf of the dot product keeps
+// no digit at a third of a degree); then the planar two-disc rule.  In the lens the half-angles acos(x) and acos(y) are taken as
+// atan2f(K, x's numerator) and atan2f(K, y's numerator), K = 2 sep alpha_s sin = the square root of the four-factor product:
+// the same angles, but formed from the factored gap, so that they go to 0 at a contact as fast as the gap does (acosf of the
+// quotient keeps half the digits there, and the area is a difference of terms (alpha_b / alpha_s)^2 = 13 solar discs large).
+__device__ __forceinline__ float occult_fraction(const float4 ls, const float4 lb, const PointFrame& p) {
+    const float sa = ls.x - p.oa, sb = ls.y - p.ob, sc = ls.z - p.oc;
+    const float inv_s = rcp_cr(sqrt_sh(fmaf(sc, sc, fmaf(sb, sb, sa * sa))));
+    const float ax = sa * inv_s, ay = sb * inv_s, az = sc * inv_s;
+    const float ta = lb.x - p.oa, tb = lb.y - p.ob, tc = lb.z - p.oc;
+    const float inv_b = rcp_cr(sqrt_sh(fmaf(tc, tc, fmaf(tb, tb, ta * ta))));
+    const float bx = ta * inv_b, by = tb * inv_b, bz = tc * inv_b;
+    const float as = asinf(fminf(1.0f, sqrtf(ls.w) * inv_s));
+    const float ab = asinf(fminf(1.0f, sqrtf(lb.w) * inv_b));
+    const float cx = fmaf(ay, bz, -(az * by)), cy = fmaf(az, bx, -(ax * bz)), cz = fmaf(ax, by, -(ay * bx));
+    const float sep = atan2f(sqrtf(fmaf(cz, cz, fmaf(cy, cy, cx * cx))), fmaf(az, bz, fmaf(ay, by, ax * bx)));
+    if (!(as > 0.0f)) return sep > ab ? 1.0f : 0.0f;               // a point source: a step
+    if (sep >= as + ab) return 1.0f;                                // apart
+    if (ab >= as) { if (sep <= ab - as) return 0.0f; }              // total
+    else if (sep <= as - ab) { const float r = ab / as; return 1.0f - r * r; }     // annular
+    const float K = sqrtf(fmaxf(0.0f, ((as + ab - sep) * (sep + as - ab)) * ((sep - as + ab) * (sep + as + ab))));
+    const float s2 = sep * sep, as2 = as * as, ab2 = ab * ab;
+    const float d2 = as2 - ab2;
+    const float A = fmaf(as2, atan2f(K, s2 + d2), ab2 * atan2f(K, s2 - d2)) - 0.5f * K;
+    return fminf(1.0f, fmaxf(0.0f, 1.0f - A / (kPi * as2)));
+}
+
 // The Sun against a horizon (DESIGN.md sections 3.9 and 4.10): per (point, epoch) the share of the light's disc above the
 // point's horizon, interpolated at the light's azimuth.  One wave = one point; it walks the epochs 64 at a time (lane = epoch),
 // so the point's vertex is formed once and its horizon row stays in L1.  FULL writes every fraction; SUMMARY reduces them in
@@ -2202,6 +2231,70 @@ __global__ void __launch_bounds__(64) power_budget_kernel(const FrameC f, const 
     }
 }
 
+// The Earth's occultation of the Sun (DESIGN.md sections 3.18 and 4.20): horizon_windows_kernel's walk -- one wave per point,
+// the epochs 64 at a time with lane = epoch, the vertex and frame once -- with occult_fraction in place of disc_fraction and no
+// horizon.  A lane whose epoch the host did not mark takes g = 1 without forming anything: the value it would have computed
+// (the host's float64 test keeps a margin float32 cannot bridge).  FULL stores g.  SUMMARY: the float64 sum per lane in epoch
+// order and the minimum, reduced at the end; the counts of g < 1 and g == 0 from the ballots; their runs by run_ending_here /
+// wave_max, the earliest longest g < 1 run kept with its first epoch; and the number of maximal g < 1 runs, a set epoch whose
+// predecessor is unset, lane 0's predecessor being the carried last bit of the chunk before.  Everything carried is
+// wave-uniform.  No atomics, no LDS; lane 0 stores the point's two float4.
+template <bool WIDE>
+__global__ void __launch_bounds__(64) occultation_kernel(const FrameC f, const OccultC q) {
+    const int lane = threadIdx.x;
+    const int pt = (int)blockIdx.x;
+    Vertex v;
+    (void)illum_vertex<false, WIDE>(f, q.g, pt, pt, v, nullptr);
+    const PointFrame p = point_frame(f, q.g, pt, pt, v);
+    const float4* const src = reinterpret_cast<const float4*>(q.src);
+    const float4* const body = reinterpret_cast<const float4*>(q.body);
+    double sum = 0.0;                                       // per lane, reduced at the end
+    float g_min = 1.0f;
+    uint32_t n_part = 0, n_tot = 0, n_runs = 0;             // wave-uniform counts
+    int cur_p = 0, cur_t = 0, best_p = 0, best_t = 0, first_p = -1;
+    unsigned long long prev = 0;                            // the g < 1 bit of the previous chunk's last epoch
+    for (int k0 = 0; k0 < q.m; k0 += 64) {
+        const int k = k0 + lane;
+        const bool in = k < q.m;
+        float g = 1.0f;
+        if (in) {
+            if (q.mark[k] != 0) g = occult_fraction(src[2 * (int64_t)k], body[2 * (int64_t)k], p);
+            if (q.mode == 0) q.out[(int64_t)pt * q.m + k] = g;
+        }
+        if (q.mode == 0) continue;
+        sum += in ? (double)g : 0.0;
+        g_min = fminf(g_min, g);
+        const unsigned long long mp = __ballot(in && g < 1.0f), mt = __ballot(in && g == 0.0f);
+        n_part += (uint32_t)__popcll(mp); n_tot += (uint32_t)__popcll(mt);
+        const int last = min(64, q.m - k0) - 1;
+        const int rp = run_ending_here(mp, lane, in, cur_p);
+        const int rt = run_ending_here(mt, lane, in, cur_t);
+        cur_p = __shfl(rp, last, 64); cur_t = __shfl(rt, last, 64);
+        best_t = max(best_t, wave_max(rt));
+        const int mx = wave_max(rp);
+        if (mx > best_p) {                                  // wave-uniform; the lowest lane that ends a run of mx: the earliest
+            const unsigned long long at = __ballot(rp == mx);
+            best_p = mx;
+            first_p = k0 + (int)__builtin_ctzll(at) - mx + 1;
+        }
+        n_runs += (uint32_t)__popcll(mp & ~((mp << 1) | prev));
+        prev = (mp >> last) & 1ull;
+    }
+    if (q.mode != 0) {
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            sum += __shfl_xor(sum, s, 64);
+            g_min = fminf(g_min, __shfl_xor(g_min, s, 64));
+        }
+        if (lane == 0) {
+            const double md = (double)q.m;
+            float4* const o = reinterpret_cast<float4*>(q.out) + 2 * (int64_t)pt;
+            o[0] = make_float4((float)(sum * (1.0 / md)), g_min, (float)((double)n_part / md), (float)((double)n_tot / md));
+            o[1] = make_float4((float)best_p, (float)first_p, (float)best_t, (float)n_runs);
+        }
+    }
+}
+
 // Regolith surface temperatures (DESIGN.md sections 3.10 and 4.11).  One lane = one point: its vertex and local frame are
 // formed once, then per epoch the absorbed flux (the disc fraction of horizon_sun_kernel, illum_mu's mu, the albedo law) and
 // n_sub explicit steps of its heat-conduction column.  The column's temperatures are float64 registers (a deep node moves by
@@ -2221,9 +2314,17 @@ __global__ void __launch_bounds__(64) power_budget_kernel(const FrameC f, const 
 // After each epoch's steps the column is checked once (not per step, which would cost a share of the step itself): a node
 // that is not finite or lies outside [20, 450] K, the range the step bound and the heat capacity were checked on, counts
 // that (point, epoch) in q.caps[1]; the host then refuses the call's results (sections 3.10, 3.11).
-template <bool WIDE, bool EXT, int COL = 0>
+// COLX = COL + 4 (section 3.18, mrtx_thermal_occulted; EXT's column and its modes, COL = COLX & 3): the disc fraction of
+// every epoch, spin-up included, times occult_fraction's g for the far source and the body of q.occ_src / q.occ_body at the
+// point's own vertex.  The epoch is wave-uniform, so its mark is a scalar branch: an unmarked epoch costs one scalar load.
+// The flag rides in the third template argument so that the instantiations without it (COLX = 0, 1, 2) keep their names and
+// their machine code (tools/asm_same.py).
+template <bool WIDE, bool EXT, int COLX = 0>
 __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const ThermalC q) {
+    constexpr int COL = COLX & 3;
+    constexpr bool OCC = (COLX & 4) != 0;
     static_assert(COL == 0 || EXT, "the subsurface modes run EXT's column");
+    static_assert(!OCC || EXT, "the occulted column runs EXT's column");
     constexpr int NN = MRTX_THERMAL_NODES;
     constexpr float kDeg = 57.2957795130823209f;
     const int lane = threadIdx.x;
@@ -2240,7 +2341,12 @@ __global__ void __launch_bounds__(64) thermal_kernel(const FrameC f, const Therm
     // Q_abs of epoch k: (1 - A(theta)) S_k f max(mu, 0), exactly 0 when f == 0 or mu <= 0; EXT: mv = A(theta) S_k f max(mu, 0)
     auto sunlit = [&](int k, float& mv) -> float {
         float la, lb, lc;
-        const float fr = disc_fraction(lights[2 * (int64_t)k], p, hz, n_az, la, lb, lc);
+        float fr = disc_fraction(lights[2 * (int64_t)k], p, hz, n_az, la, lb, lc);
+        if constexpr (OCC) {
+            if (q.occ_mark[k] != 0)                                      // wave-uniform
+                fr = fr * occult_fraction(reinterpret_cast<const float4*>(q.occ_src)[2 * (int64_t)k],
+                                          reinterpret_cast<const float4*>(q.occ_body)[2 * (int64_t)k], p);
+        }
         const float mu = fmaf(v.nc, lc, fmaf(v.nb, lb, v.na * la));      // illum_mu's expression
         if (!(fr > 0.0f) || !(mu > 0.0f)) { mv = 0.0f; return 0.0f; }
         const float th = acosf(fminf(mu, 1.0f)) * kDeg;
@@ -3782,6 +3888,7 @@ hipError_t mrtx_launch_sight(const FrameC& f, SightC q, bool stats, hipStream_t 
 // Regolith surface temperatures (thermal_kernel): one lane per point, 64 per wave.  ext: the same column with an extra
 // absorbed flux and the EXITANCE mode 3 (mrtx_thermal_scatter, section 3.11), and the subsurface modes 4 (COLUMN) and
 // 5 (VOLATILE) of mrtx_thermal_column (section 3.16), which have instantiations of their own.
+static hipError_t mrtx_launch_thermal_occulted(const FrameC& f, const ThermalC& q, dim3 grid, hipStream_t st);
 hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, bool ext, hipStream_t st) {
     if (q.g.rows < 1 || q.az_log2 < 2 || q.az_log2 > 12 || q.m < 1 || q.mode < 0 || q.mode > (ext ? 5 : 2) || q.n_nodes < 3 ||
         q.n_nodes > MRTX_THERMAL_NODES || q.n_sub < 1 || q.block < 1 || q.n_spin < 0 || q.n_reset < 0 || q.ref < 0 ||
@@ -3791,6 +3898,10 @@ hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, bool ext, hip
     if (q.mode == 4 && (int64_t)q.g.rows * (q.m - q.n_spin) * q.n_nodes > (int64_t)1 << 31) return hipErrorInvalidValue;
     if (q.mode == 5 && ((uintptr_t)q.out & 7)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((q.g.rows + 63) / 64)), block(64);
+    if (q.occ_mark || q.occ_src || q.occ_body) {            // mrtx_thermal_occulted with tables: kernels of their own
+        if (!ext || !q.occ_mark || !q.occ_src || !q.occ_body) return hipErrorInvalidValue;
+        return mrtx_launch_thermal_occulted(f, q, grid, st);
+    }
     if (q.mode >= 4)
         pick2(f.dem_wide != 0, q.mode == 5, [&](auto w, auto v) {
             hipLaunchKernelGGL((mrtx::thermal_kernel<w(), true, v() ? 2 : 1>), grid, block, 0, st, f, q);
@@ -4016,6 +4127,32 @@ hipError_t mrtx_launch_color_pairs(const uint32_t* src, void* dst, int h, int w,
 }
 hipError_t mrtx_launch_pad_dem(const float* src, float* dst, int h, int w, hipStream_t st) {
     hipLaunchKernelGGL(mrtx::pad_dem_kernel, dim3(grid_for((int64_t)(h + 4) * (w + 4))), dim3(256), 0, st, src, dst, h, w);
+    return hipGetLastError();
+}
+
+// The kernels of DESIGN.md section 3.18 are instantiated here, after every other: the compiler numbers a listing's labels by
+// function in this order, so the earlier kernels' listings stay as they were (tools/asm_same.py).
+// The Earth's occultation of the Sun (occultation_kernel): one wave per point.
+hipError_t mrtx_launch_occultation(const FrameC& f, OccultC q, hipStream_t st) {
+    if (q.g.rows < 1 || q.m < 1 || q.m > (1 << 24) || (q.mode != 0 && q.mode != 1) || !q.g.points || !q.src || !q.body || !q.mark ||
+        !q.out)
+        return hipErrorInvalidValue;
+    if (q.mode == 0 && (int64_t)q.g.rows * q.m > (int64_t)1 << 31) return hipErrorInvalidValue;
+    if (q.mode == 1 && ((uintptr_t)q.out & 15)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)q.g.rows), block(64);
+    if (f.dem_wide) hipLaunchKernelGGL((mrtx::occultation_kernel<true>), grid, block, 0, st, f, q);
+    else hipLaunchKernelGGL((mrtx::occultation_kernel<false>), grid, block, 0, st, f, q);
+    return hipGetLastError();
+}
+
+// The thermal column under occultation (thermal_kernel<.., COL + 4>; called by mrtx_launch_thermal, which made the checks).
+static hipError_t mrtx_launch_thermal_occulted(const FrameC& f, const ThermalC& q, dim3 grid, hipStream_t st) {
+    const dim3 block(64);
+    pick2(f.dem_wide != 0, q.mode >= 4, [&](auto w, auto c) {
+        if (!c()) hipLaunchKernelGGL((mrtx::thermal_kernel<w(), true, 4>), grid, block, 0, st, f, q);
+        else if (q.mode == 4) hipLaunchKernelGGL((mrtx::thermal_kernel<w(), true, 5>), grid, block, 0, st, f, q);
+        else hipLaunchKernelGGL((mrtx::thermal_kernel<w(), true, 6>), grid, block, 0, st, f, q);
+    });
     return hipGetLastError();
 }
 }

@@ -479,22 +479,28 @@ def calculate_moon_ephemeris(dt_local, parallactic_mode, observer=None):
         rotation_matrix=view_rotation(l_top, b_top, P - q))
 
 
+def _geocentric_sun_moon_km(t):
+    """(sun, moon): the geocentric vectors, km, equator of date, of the series calculate_moon_ephemeris uses."""
+    if t.tzinfo is None:
+        raise ValueError("times must be timezone-aware")
+    dt_utc = t.astimezone(timezone.utc)
+    jde = julian_day(dt_utc) + tt_minus_utc(dt_utc) / 86400.0
+    T = (jde - 2451545.0) / 36525.0
+    dpsi, _, eps, _ = nutation(T)
+    lam_m, beta_m, dist_m = moon_position(T)
+    lam_s, _, r_s, _ = sun_position(T)
+    ra_m, dec_m = ecl_to_equ(lam_m + dpsi, beta_m, eps)
+    ra_s, dec_s = ecl_to_equ(lam_s + dpsi, 0.0, eps)
+    return _vec(ra_s, dec_s, r_s * AU_KM), _vec(ra_m, dec_m, dist_m)
+
+
 def sun_flux(times, solar_constant=1361.0):
     """Solar flux at the Moon, W m^-2, per timezone-aware datetime: solar_constant x (1 AU / r)^2 with r the Sun-Moon centre
     distance, the geocentric Sun minus the geocentric Moon of the series calculate_moon_ephemeris uses."""
     out = np.empty(len(times), np.float64)
     for i, t in enumerate(times):
-        if t.tzinfo is None:
-            raise ValueError("times must be timezone-aware")
-        dt_utc = t.astimezone(timezone.utc)
-        jde = julian_day(dt_utc) + tt_minus_utc(dt_utc) / 86400.0
-        T = (jde - 2451545.0) / 36525.0
-        dpsi, _, eps, _ = nutation(T)
-        lam_m, beta_m, dist_m = moon_position(T)
-        lam_s, _, r_s, _ = sun_position(T)
-        ra_m, dec_m = ecl_to_equ(lam_m + dpsi, beta_m, eps)
-        ra_s, dec_s = ecl_to_equ(lam_s + dpsi, 0.0, eps)
-        r = np.linalg.norm(_vec(ra_s, dec_s, r_s * AU_KM) - _vec(ra_m, dec_m, dist_m)) / AU_KM
+        sun, moon = _geocentric_sun_moon_km(t)
+        r = np.linalg.norm(sun - moon) / AU_KM
         out[i] = solar_constant / (r * r)
     return out
 
@@ -569,3 +575,89 @@ def earth_epochs(times, observer=None):
     light_radius = the Earth's equatorial radius in scene units, light_radiance = 0.  MoonRT.horizon_sun then returns the
     visible share of the Earth's disc from each point, the parallax of the surface point included."""
     return sun_earth_epochs(times, observer)[1]
+
+
+# ---- the Earth's occultation of the Sun (DESIGN.md section 3.18) --------------------------------------------------------------
+def far_sun_epochs(sun_epochs, times):
+    """The rows of sun_epochs(times, ...) with the light moved out, along the ray from the Moon's centre (`center`), to the
+    Sun's true distance in scene units -- the Sun-Moon centre distance sun_flux uses -- and light_radius scaled by the same
+    factor: from the Moon's centre the direction and the angular radius are unchanged, and the parallax across the Moon is
+    the real one (the scene's light stands 40 times too near for an occultation by the Earth: DESIGN.md section 3.18).  The
+    Moon frame and the radiance are copied.  For MoonRT.occultation and thermal_column(occultation=...) only; every other
+    consumer keeps sun_epochs."""
+    from .scene import MOON_RADIUS, MOON_RADIUS_KM
+    ep = np.array(sun_epochs, np.float64).reshape(-1, 14)
+    if len(times) != ep.shape[0]:
+        raise ValueError("times must hold one date per row")
+    for i, t in enumerate(times):
+        sun, moon = _geocentric_sun_moon_km(t)
+        d_true = float(np.linalg.norm(sun - moon)) * (MOON_RADIUS / MOON_RADIUS_KM)
+        ray = ep[i, 0:3] - ep[i, 5:8]
+        k = d_true / float(np.linalg.norm(ray))
+        ep[i, 0:3] = ep[i, 5:8] + k * ray
+        ep[i, 3] *= k
+    return ep
+
+
+def two_disc_fraction(sep, alpha_s, alpha_b):
+    """The share g of a source disc of angular radius alpha_s that a body disc of radius alpha_b, sep away, leaves uncovered:
+    the planar two-disc rule of DESIGN.md section 3.18 in float64 (arrays or scalars, radians or any one unit)."""
+    sep, a_s, a_b = np.broadcast_arrays(*(np.asarray(v, np.float64) for v in (sep, alpha_s, alpha_b)))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        x = np.clip((sep * sep + a_s * a_s - a_b * a_b) / (2.0 * sep * a_s), -1.0, 1.0)
+        y = np.clip((sep * sep + a_b * a_b - a_s * a_s) / (2.0 * sep * a_b), -1.0, 1.0)
+        k2 = (-sep + a_s + a_b) * (sep + a_s - a_b) * (sep - a_s + a_b) * (sep + a_s + a_b)
+        area = a_s * a_s * np.arccos(x) + a_b * a_b * np.arccos(y) - 0.5 * np.sqrt(np.maximum(0.0, k2))
+        g = np.clip(1.0 - area / (np.pi * a_s * a_s), 0.0, 1.0)
+        g = np.where((a_b < a_s) & (sep <= a_s - a_b), 1.0 - (a_b / a_s) ** 2, g)
+    g = np.where((a_b >= a_s) & (sep <= a_b - a_s), 0.0, g)
+    g = np.where(sep >= a_s + a_b, 1.0, g)
+    return np.where(a_s > 0.0, g, (sep > a_b).astype(np.float64))
+
+
+def _centre_geometry(t):
+    """(sep, alpha_s, alpha_b, parallax) in radians from the Moon's centre at a date: the Sun-Earth separation, the two
+    angular radii, and the most a point of the Moon's surface can shift the Earth plus the Sun against each other."""
+    from .scene import MOON_RADIUS_KM, SUN_RADIUS_KM
+    sun, moon = _geocentric_sun_moon_km(t)
+    to_sun, to_earth = sun - moon, -moon
+    d_s, d_e = float(np.linalg.norm(to_sun)), float(np.linalg.norm(to_earth))
+    sep = math.atan2(float(np.linalg.norm(np.cross(to_sun, to_earth))), float(np.dot(to_sun, to_earth)))
+    return (sep, math.asin(SUN_RADIUS_KM / d_s), math.asin(EARTH_RADIUS_KM / d_e),
+            math.asin(MOON_RADIUS_KM / d_e) + math.asin(MOON_RADIUS_KM / d_s))
+
+
+ECLIPSE_SLACK_RAD = math.radians(0.05)      # eclipse_candidates' allowance beyond the parallax: ten times the tables' own
+
+
+def eclipse_candidates(times, observer=None):
+    """The index ranges [(first, end), ...] of `times` in which some point of the Moon may see the Earth's disc touch the
+    Sun's: the separation of the two from the Moon's centre is below alpha_s + alpha_b plus the parallax across the Moon and
+    0.05 deg.  A cheap host prefilter (two series evaluations per date, no tables): drivers sample these ranges finely
+    without sampling a year finely.  The geometry from the Moon's centre does not depend on `observer`, which is accepted so
+    that the call reads like sun_epochs'."""
+    on = []
+    for t in times:
+        sep, a_s, a_b, par = _centre_geometry(t)
+        on.append(sep < a_s + a_b + par + ECLIPSE_SLACK_RAD)
+    out, start = [], None
+    for i, v in enumerate(on + [False]):
+        if v and start is None:
+            start = i
+        elif not v and start is not None:
+            out.append((start, i))
+            start = None
+    return out
+
+
+def eclipse_factor(times, observer=None):
+    """(m,) float64: g of DESIGN.md section 3.18 at the Moon's CENTRE per date, by two_disc_fraction -- the Moon-wide factor
+    that sunlight.power_budget(..., eclipses=True) and tools/power_map.py --eclipses multiply into gen_w.  One factor for the
+    whole Moon costs accuracy: the contacts of an eclipse differ by up to about half an hour across the disc, so near a
+    contact a site's own g differs from this one by up to the whole step 0 .. 1; MoonRT.occultation gives the per-point
+    value.  `observer` as for eclipse_candidates."""
+    g = np.ones(len(times), np.float64)
+    for i, t in enumerate(times):
+        sep, a_s, a_b, _ = _centre_geometry(t)
+        g[i] = float(two_disc_fraction(sep, a_s, a_b))
+    return g

@@ -509,6 +509,32 @@ class MoonRT:
             self._add_stats(stats, st)
         return res
 
+    OCCULTATION_COLUMNS = ("mean", "min", "share_partial", "share_total", "longest_partial", "first_partial", "longest_total",
+                           "eclipses")
+
+    def occultation(self, lat_deg, lon_deg, source_epochs, body_epochs, summary=False, stats=None, chunk_bytes=256 << 20):
+        """The Earth's occultation of the Sun: per (point, epoch) the share g of the source's disc
+        that the body's disc leaves uncovered, seen from the point's vertex.  source_epochs: ephemeris.far_sun_epochs (the Sun
+        at its true distance); body_epochs: ephemeris.earth_epochs, for the same m dates.  summary=False: (N, m) float32 g;
+        summary=True: the (N, 8) float32 columns OCCULTATION_COLUMNS -- the mean and the least g, the shares of epochs with
+        g < 1 and with g == 0, the longest run of epochs with g < 1 and its first epoch (the earliest such run; -1 if none),
+        the longest run with g == 0, and the number of separate runs of g < 1 (the eclipses the point saw) -- with no (N, m)
+        table anywhere.  The geometric discs only: no atmosphere.  FULL calls hold at most chunk_bytes of output."""
+        la, lo = self._points(lat_deg, lon_deg)
+        es, eb = self._epochs(source_epochs), self._epochs(body_epochs)
+        if es.shape != eb.shape:
+            raise ValueError("source_epochs and body_epochs must hold the same number of epochs")
+        m = es.shape[0]
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        res = np.empty((la.size, 8 if summary else m), np.float32)
+        for a, b in self._chunks(la.size, None if summary else max(m, 1), chunk_bytes):
+            st = MrtxStats()
+            self._check(self._lib.mrtx_occultation(self._ctx, pts[a:].ctypes.data, b - a, es.ctypes.data, eb.ctypes.data, m,
+                                                   1 if summary else 0, None, res[a:].ctypes.data, C.byref(st)),
+                        "mrtx_occultation")
+            self._add_stats(stats, st)
+        return res
+
     @staticmethod
     def thermal_grid(spacing_s=3600.0, spinup_lunations=None, resets=None, F=None):
         """The MrtxThermalModel of the default regolith for epochs `spacing_s` apart: the layer
@@ -656,13 +682,15 @@ class MoonRT:
         return np.concatenate([[0.0], np.cumsum(np.array(model.dz[:n - 1], np.float64))])
 
     def thermal_column(self, lat_deg, lon_deg, horizon, epochs, flux, model=None, mode="column", extra_flux=None, species=None,
-                       stats=None, n_az=None, out=None):
+                       stats=None, n_az=None, out=None, occultation=None):
         """surface_temperature_scatter with the subsurface modes of DESIGN.md section 3.16, in one call.  Its modes ("full",
         "summary", "flux", "exitance") give its bits; "column": (N, m - n_spin, n_nodes) float32, every node's temperature
         after each recorded epoch (node 0 is "full"); "volatile": (N, n_nodes, 2) float64 (E_mean, T_max) per node, the mean
         over the recorded epochs of the free sublimation rate of `species` (a volatiles.Species, an MrtxVolatile or its four
         coefficients; kg m^-2 s^-1) and the node's highest temperature.  thermal_depths(model) gives the nodes' depths.
-        out = a DeviceBuffer: the output is written there and `out` returned."""
+        out = a DeviceBuffer: the output is written there and `out` returned.  occultation = (source_epochs, body_epochs) as
+        for MoonRT.occultation, m rows each: every epoch's disc fraction, spin-up included, is multiplied by that call's g at
+        the point (section 3.18); None is the call without it."""
         modes = {"full": 0, "summary": 1, "flux": 2, "exitance": 3, "column": 4, "volatile": 5}
         if mode not in modes:
             raise ValueError(f"mode must be one of {sorted(modes)} (got {mode!r})")
@@ -697,6 +725,18 @@ class MoonRT:
             raise ValueError("the device buffer is smaller than the output")
         res = np.empty(shape, dtype) if out is None else None
         st = MrtxStats()
+        if occultation is not None:
+            os_, ob_ = (self._epochs(e) for e in occultation)
+            if os_.shape != ep.shape or ob_.shape != ep.shape:
+                raise ValueError("the occultation tables must hold one row per epoch")
+            self._check(self._lib.mrtx_thermal_occulted(self._ctx, pts.ctypes.data, la.size, n_az, dh, hh, ep.ctypes.data,
+                                                        fl.ctypes.data, m, C.byref(model), modes[mode], dx, hx, x_len,
+                                                        None if sp is None else C.byref(sp), os_.ctypes.data, ob_.ctypes.data,
+                                                        None if out is None else out.ptr,
+                                                        None if res is None else res.ctypes.data, C.byref(st)),
+                        "mrtx_thermal_occulted")
+            self._add_stats(stats, st, {"newton_cap_hits": "reserved"})
+            return out if out is not None else res
         self._check(self._lib.mrtx_thermal_column(self._ctx, pts.ctypes.data, la.size, n_az, dh, hh, ep.ctypes.data,
                                                   fl.ctypes.data, m, C.byref(model), modes[mode], dx, hx, x_len,
                                                   None if sp is None else C.byref(sp), None if out is None else out.ptr,

@@ -4,6 +4,7 @@ section 3.7): a coarse series over the sampled dates, then one refining series o
 The reference times these events on the smooth sphere only (astro.py: find_terminator_windows, find_clair_obscur_events,
 whose catalogue tunes each window by hand for the relief); here the terrain decides, and each event also reports the
 sphere's Sun altitude at its time -- the number that catalogue tunes."""
+import math
 from datetime import timedelta
 from typing import NamedTuple
 
@@ -215,7 +216,7 @@ def wh_to_counts(wh, cpw_log2, step_min):
 
 def power_budget(rt, lat, lon, start, days, step_min=60, height_m=0.0, *, area_m2, efficiency, load_w, panel="track",
                  normal_enu=None, capacity_wh=0.0, initial_wh=None, n_az=256, n_bis=14, observer=None, chunk=65536,
-                 radius_m=1737400.0, cpw_log2=None):
+                 radius_m=1737400.0, cpw_log2=None, eclipses=False):
     """Does a solar-powered asset survive at the points (lat, lon in degrees), and on how much battery, from `start`
     (timezone-aware) over `days` at `step_min` minutes?  Each point's horizon is computed once from
     a panel height_m above it (MoonRT.horizon), the Sun's epochs and flux once (ephemeris.sun_epochs, sun_flux); the array
@@ -224,7 +225,9 @@ def power_budget(rt, lat, lon, start, days, step_min=60, height_m=0.0, *, area_m
     (awake, hibernating) rule would depend on each point's own Sun and is not offered).  The balance is reduced on the
     device (MoonRT.power_budget): points are streamed `chunk` at a time, their horizons stay in a device buffer and no
     (points x dates) table is formed.  capacity_wh is the battery whose state of charge is followed (initial_wh=None:
-    full).  Returns PowerBudget."""
+    full).  eclipses=True multiplies the array's output by ephemeris.eclipse_factor, the Earth's cover of the Sun seen from
+    the Moon's centre (section 3.18): one factor for the whole Moon, so near a contact a site's own cover differs from it;
+    a per-point term in the budget kernel does not exist.  Returns PowerBudget."""
     from .renderer import DeviceBuffer
     la = np.atleast_1d(np.asarray(lat, np.float64)).ravel()
     lo = np.atleast_1d(np.asarray(lon, np.float64)).ravel()
@@ -240,6 +243,8 @@ def power_budget(rt, lat, lon, start, days, step_min=60, height_m=0.0, *, area_m
     load = np.ascontiguousarray(np.broadcast_to(load, (m,)))
     ep = ephemeris.sun_epochs(times, observer)
     gen = ephemeris.sun_flux(times) * (float(area_m2) * float(efficiency))
+    if eclipses:
+        gen = gen * ephemeris.eclipse_factor(times, observer)
     cpw = rt.power_scale(gen, load) if cpw_log2 is None else int(cpw_log2)
     cap = wh_to_counts(capacity_wh, cpw, step_min)
     ini = cap if initial_wh is None else wh_to_counts(initial_wh, cpw, step_min)
@@ -272,7 +277,8 @@ class SurfaceTemperatures(NamedTuple):
 
 
 def surface_temperatures(rt, lat, lon, start, days, step_min=60, spinup_lunations=None, n_az=256, n_bis=14, observer=None,
-                         chunk=65536, thermal=None, scatter=0, budget_bytes=8 << 30, q_sec_mean=False, alloc=None):
+                         chunk=65536, thermal=None, scatter=0, budget_bytes=8 << 30, q_sec_mean=False, alloc=None,
+                         eclipses=False):
     """Regolith surface temperatures of the points (lat, lon in degrees) from `start` (timezone-aware) over `days` at
     `step_min` minutes.  The column is spun up over `spinup_lunations` lunations of dates before
     `start` (default thermal.SPINUP_LUNATIONS), stepped but not recorded.  Each point's horizon is computed once
@@ -282,18 +288,32 @@ def surface_temperatures(rt, lat, lon, start, days, step_min=60, spinup_lunation
     scatter = K > 0 adds the sunlight and infrared the surrounding terrain sends (section 3.11): K view rays per point, the
     hits' own columns in EXITANCE mode, the gather and the points' columns with that extra flux.  Device tables stay under
     about `budget_bytes` per group of points; `q_sec_mean` also returns each point's mean extra flux over the recorded dates
-    (stats["q_sec_mean"]; it downloads the flux).  `alloc(nbytes)` replaces the device allocation (tests)."""
+    (stats["q_sec_mean"]; it downloads the flux).  `alloc(nbytes)` replaces the device allocation (tests).
+
+    eclipses=True lets the Earth cover the Sun (section 3.18): every column call, the scatter path's hit columns included,
+    runs MoonRT.thermal_column with the occultation tables (ephemeris.far_sun_epochs, earth_epochs) of its dates.  A
+    `thermal` replacement keeps today's signature, which has no place for them: the two together raise ValueError."""
     out, times, stats, _ = _columns(rt, lat, lon, start, days, step_min, spinup_lunations, n_az, n_bis, observer, chunk, thermal,
-                                    scatter, budget_bytes, q_sec_mean, alloc, None)
+                                    scatter, budget_bytes, q_sec_mean, alloc, None, eclipses)
     return SurfaceTemperatures(out[:, 0], out[:, 1], out[:, 2], out[:, 3], times, stats)
 
 
+def _occultation_tables(times, observer):
+    """(sun_epochs, (far_sun_epochs, earth_epochs)) of the dates, from one pass over them."""
+    ep, earth = ephemeris.sun_earth_epochs(times, observer)
+    return ep, (ephemeris.far_sun_epochs(ep, times), earth)
+
+
 def _columns(rt, lat, lon, start, days, step_min, spinup_lunations, n_az, n_bis, observer, chunk, thermal, scatter, budget_bytes,
-             q_sec_mean, alloc, species):
+             q_sec_mean, alloc, species, eclipses=False):
     """The flow surface_temperatures and ice_stability share: the dates, the model, and per chunk of points the horizons and
     the columns.  species = None: the points' columns run in SUMMARY, (N, 4) float32; a species: in VOLATILE
-    (MoonRT.thermal_column, section 3.16), (N, n_nodes, 2) float64.  Returns (out, the recorded dates, stats, model)."""
+    (MoonRT.thermal_column, section 3.16), (N, n_nodes, 2) float64.  eclipses: every column call goes through
+    MoonRT.thermal_column with the occultation tables of its dates (section 3.18).  Returns (out, the recorded dates, stats,
+    model)."""
     from . import thermal as th
+    if eclipses and thermal is not None:
+        raise ValueError("thermal= keeps its signature, which has no occultation tables: it cannot be combined with eclipses=True")
     la = np.atleast_1d(np.asarray(lat, np.float64)).ravel()
     lo = np.atleast_1d(np.asarray(lon, np.float64)).ravel()
     if la.shape != lo.shape:
@@ -306,16 +326,20 @@ def _columns(rt, lat, lon, start, days, step_min, spinup_lunations, n_az, n_bis,
     n_spin = int(model.n_spin)
     step = timedelta(minutes=float(step_min))
     all_times = [start + (k - n_spin) * step for k in range(n_spin + m_rec)]
-    ep = ephemeris.sun_epochs(all_times, observer)
-    fl = ephemeris.sun_flux(all_times)
     rt.horizon_azimuths(n_az)       # checks n_az
     chunk = max(1, min(int(chunk), la.size, (1 << 31) // int(n_az)))
     out = _columns_out(la.size, model, species)
     stats = {}
     if scatter:
         times, stats = _scatter_temperatures(rt, la, lo, start, step, m_rec, model, n_az, n_bis, observer, chunk, int(scatter),
-                                             budget_bytes, q_sec_mean, alloc, species, out)
+                                             budget_bytes, q_sec_mean, alloc, species, out, eclipses)
         return out, times, stats, model
+    occ = None
+    if eclipses:
+        ep, occ = _occultation_tables(all_times, observer)
+    else:
+        ep = ephemeris.sun_epochs(all_times, observer)
+    fl = ephemeris.sun_flux(all_times)
     if thermal is not None:
         if species is not None:
             raise ValueError("thermal= replaces the SUMMARY call only")
@@ -330,7 +354,11 @@ def _columns(rt, lat, lon, start, days, step_min, spinup_lunations, n_az, n_bis,
             for a in range(0, la.size, chunk):
                 b = min(a + chunk, la.size)
                 rt.horizon(la[a:b], lo[a:b], n_az=n_az, n_bis=n_bis, stats=stats, out=buf)
-                if species is None:
+                if occ is not None:
+                    out[a:b] = rt.thermal_column(la[a:b], lo[a:b], buf, ep, fl, model=model,
+                                                 mode="summary" if species is None else "volatile", species=species,
+                                                 stats=stats, n_az=n_az, occultation=occ)
+                elif species is None:
                     out[a:b] = rt.surface_temperature(la[a:b], lo[a:b], buf, ep, fl, model=model, mode="summary", stats=stats,
                                                       n_az=n_az)
                 else:
@@ -378,7 +406,7 @@ def scatter_groups(hit_counts, m_hits, m_targets, n_az, budget_bytes):
 
 
 def _scatter_temperatures(rt, la, lo, start, step, m_rec, model, n_az, n_bis, observer, chunk, k, budget_bytes, q_sec_mean,
-                          alloc, species, out):
+                          alloc, species, out, eclipses=False):
     """_columns with scatter = K (section 3.11).  Per chunk of points: their view hits; per group of points that fits the
     budget: their horizons, the hits' horizons, the hits' columns in EXITANCE mode over [own spin-up | the points' spin-up |
     recorded], the gather, and the points' columns with the extra flux (SUMMARY, or with a species VOLATILE) into `out`.
@@ -390,7 +418,12 @@ def _scatter_temperatures(rt, la, lo, start, step, m_rec, model, n_az, n_bis, ob
     m_t = n_spin + m_rec
     # the hits' epochs: their own spin-up, then the points' epochs (spin-up and recorded), which the hits record
     times = [start + (i - 2 * n_spin) * step for i in range(2 * n_spin + m_rec)]
-    ep_h = ephemeris.sun_epochs(times, observer)
+    occ_h = occ_t = None
+    if eclipses:                    # section 3.18: the hits' columns and the points' columns both under the Earth's cover
+        ep_h, occ_h = _occultation_tables(times, observer)
+        occ_t = (occ_h[0][n_spin:], occ_h[1][n_spin:])
+    else:
+        ep_h = ephemeris.sun_epochs(times, observer)
     fl_h = ephemeris.sun_flux(times)
     ep_t, fl_t = ep_h[n_spin:], fl_h[n_spin:]
     a_h = th.albedo_hemispherical()
@@ -435,9 +468,14 @@ def _scatter_temperatures(rt, la, lo, start, step, m_rec, model, n_az, n_bis, ob
                                                              out=hz_h))
                     ex = alloc(n_h * m_t * 8)
                     bufs.append(ex)
-                    timed("hit_columns", lambda: rt.surface_temperature_scatter(
-                        h_lat[h0:h1], h_lon[h0:h1], hz_h, ep_h, fl_h, model=model, mode="exitance", stats=stats, n_az=n_az,
-                        out=ex))
+                    if occ_h is not None:
+                        timed("hit_columns", lambda: rt.thermal_column(
+                            h_lat[h0:h1], h_lon[h0:h1], hz_h, ep_h, fl_h, model=model, mode="exitance", stats=stats, n_az=n_az,
+                            out=ex, occultation=occ_h))
+                    else:
+                        timed("hit_columns", lambda: rt.surface_temperature_scatter(
+                            h_lat[h0:h1], h_lon[h0:h1], hz_h, ep_h, fl_h, model=model, mode="exitance", stats=stats, n_az=n_az,
+                            out=ex))
                     q = alloc((p1 - p0) * m_t * 4)
                     bufs.append(q)
                     idx = np.where(index[ga:gb] >= 0, index[ga:gb] - h0, -1).astype(np.int32)
@@ -446,7 +484,11 @@ def _scatter_temperatures(rt, la, lo, start, step, m_rec, model, n_az, n_bis, ob
                     if q_sec_mean:
                         qs = q.download(np.float32, (p1 - p0, m_t))
                         stats["q_sec_mean"][p0:p1] = qs[:, n_spin:].astype(np.float64).mean(axis=1)
-                if species is None:
+                if occ_t is not None:
+                    out[p0:p1] = timed("columns", lambda: rt.thermal_column(
+                        la[p0:p1], lo[p0:p1], hz_t, ep_t, fl_t, model=model, mode="summary" if species is None else "volatile",
+                        extra_flux=q, species=species, stats=stats, n_az=n_az, occultation=occ_t))
+                elif species is None:
                     out[p0:p1] = timed("columns", lambda: rt.surface_temperature_scatter(
                         la[p0:p1], lo[p0:p1], hz_t, ep_t, fl_t, model=model, mode="summary", extra_flux=q, stats=stats,
                         n_az=n_az))
@@ -471,7 +513,8 @@ class IceStability(NamedTuple):
 
 
 def ice_stability(rt, lat, lon, start, days, step_min=60, spinup_lunations=None, n_az=256, n_bis=14, observer=None,
-                  chunk=65536, species=None, scatter=0, rate_max=None, barrier_m=None, budget_bytes=8 << 30, alloc=None):
+                  chunk=65536, species=None, scatter=0, rate_max=None, barrier_m=None, budget_bytes=8 << 30, alloc=None,
+                  eclipses=False):
     """How deep must ice of `species` (default volatiles.H2O) be buried at the points (lat, lon in degrees) to survive
     ?  The run is surface_temperatures' -- the same dates, spin-up, horizons, chunks and, with
     scatter = K, scatter groups -- with the points' final columns in VOLATILE mode: per node the mean over the recorded dates
@@ -479,13 +522,63 @@ def ice_stability(rt, lat, lon, start, days, step_min=60, spinup_lunations=None,
     shallowest at which the retreat rate E_mean / rho_solid is at most rate_max (default 1 mm per 10^9 years), with
     barrier_m the diffusion length of an overlying dry lag (None: the exposed-ice criterion).  One species per call.  The
     regolith's properties are the dry ones throughout: ice changes neither its conductivity nor its heat capacity, and the
-    rate is the time mean of the free rate, without pumping or recondensation.  Returns IceStability."""
+    rate is the time mean of the free rate, without pumping or recondensation.  eclipses as for surface_temperatures.
+    Returns IceStability."""
     from . import volatiles
     species = volatiles.H2O if species is None else species
     rate_max = volatiles.RATE_MAX if rate_max is None else float(rate_max)
     out, times, stats, model = _columns(rt, lat, lon, start, days, step_min, spinup_lunations, n_az, n_bis, observer, chunk,
-                                        None, scatter, budget_bytes, False, alloc, species)
+                                        None, scatter, budget_bytes, False, alloc, species, eclipses)
     z = rt.thermal_depths(model)
     e_mean = out[:, :, 0]
     depth = volatiles.stability_depth(e_mean, z, species, rate_max=rate_max, barrier_m=barrier_m)
     return IceStability(depth, e_mean[:, 0] / species.rho_solid, e_mean, out[:, :, 1], z, times, stats)
+
+
+class LunarEclipse(NamedTuple):
+    times: list                   # the finely sampled dates of this eclipse
+    penumbral_start: np.ndarray   # (N,) object: the first date at which the point has g < 1 (None: the point saw nothing)
+    penumbral_end: np.ndarray     # (N,) object: the last such date
+    total_start: np.ndarray       # (N,) object: the first date with g == 0 (None: no totality at the point)
+    total_end: np.ndarray         # (N,) object: the last such date
+    g_min: np.ndarray             # (N,) float32: the least uncovered share of the Sun's disc
+    totality_min: np.ndarray      # (N,) minutes with g == 0
+    stats: dict                   # summed counters and kernel time of the occultation call
+
+
+def lunar_eclipses(rt, lat, lon, start, days, step_min=1, observer=None, coarse_min=10):
+    """The lunar eclipses the points (lat, lon in degrees) see from `start` (timezone-aware) over `days` (DESIGN.md section
+    3.18): the span is scanned every coarse_min minutes by ephemeris.eclipse_candidates on the host; each range it finds,
+    widened by one coarse step on either side, is sampled every step_min minutes and handed to MoonRT.occultation (FULL,
+    points x the few hundred dates of one eclipse; nothing is sampled finely outside the candidates).  Returns a list of
+    LunarEclipse, one per candidate range in which some point has g < 1, in date order.  g is the geometric discs' -- no
+    atmosphere -- and counts whether or not the terrain or the point's own horizon lets it see the Sun."""
+    la = np.atleast_1d(np.asarray(lat, np.float64)).ravel()
+    lo = np.atleast_1d(np.asarray(lon, np.float64)).ravel()
+    if la.shape != lo.shape:
+        raise ValueError("lat and lon must have the same number of points")
+    n_coarse = int(math.ceil(days * 1440.0 / coarse_min))
+    if n_coarse < 1:
+        raise ValueError("days / coarse_min gives no date")
+    coarse = [start + timedelta(minutes=k * coarse_min) for k in range(n_coarse)]
+    out = []
+    for a, b in ephemeris.eclipse_candidates(coarse, observer):
+        t0 = max(coarse[a] - timedelta(minutes=coarse_min), start)
+        t1 = min(coarse[b - 1] + timedelta(minutes=coarse_min), start + timedelta(days=days))
+        m = int((t1 - t0).total_seconds() // (60.0 * step_min)) + 1
+        times = [t0 + timedelta(minutes=k * step_min) for k in range(m)]
+        sun, earth = ephemeris.sun_earth_epochs(times, observer)
+        stats = {}
+        g = rt.occultation(la, lo, ephemeris.far_sun_epochs(sun, times), earth, stats=stats)
+        part, tot = g < 1.0, g == 0.0
+        if not part.any():
+            continue
+
+        def ends(mask):
+            first = np.array([times[int(np.argmax(r))] if r.any() else None for r in mask], object)
+            last = np.array([times[m - 1 - int(np.argmax(r[::-1]))] if r.any() else None for r in mask], object)
+            return first, last
+        p0, p1 = ends(part)
+        u0, u1 = ends(tot)
+        out.append(LunarEclipse(times, p0, p1, u0, u1, g.min(axis=1), tot.sum(axis=1) * float(step_min), stats))
+    return out

@@ -9,7 +9,8 @@ The window's nodes are MoonRT.grid_nodes; power.npy holds an (8, h, w) float64 a
 energy (Wh), the least battery which, starting full, never empties (Wh), the indices of the first and last date of that worst
 deficit (-1: none), and for the --capacity-wh battery the lowest state of charge (Wh), the hours during which it could not
 carry the load and the energy not delivered (Wh).  --point prints time, f, G, e, s per date as CSV (G, e and s in Wh) and the
-summary line on stderr.  Synthetic LOLA-like DEM unless --elevation-file is given."""
+summary line on stderr.  --eclipses multiplies the array's output by ephemeris.eclipse_factor, the Earth's cover of the Sun
+seen from the Moon's centre (section 3.18): one factor for the whole Moon.  Synthetic LOLA-like DEM unless --elevation-file is given."""
 import argparse, os, sys
 from datetime import datetime
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -39,6 +40,7 @@ ap.add_argument("--n-bis", type=int, default=14)
 ap.add_argument("--downscale", type=int, default=2)
 ap.add_argument("--dem-size", type=int, nargs=2, default=None, help="synthetic DEM (h, w); default 46080/downscale x 92160/downscale")
 ap.add_argument("--elevation-file", default=None)
+ap.add_argument("--eclipses", action="store_true", help="the Earth's cover of the Sun, one factor for the whole Moon")
 ap.add_argument("--out", default="power.npy")
 a = ap.parse_args()
 if (a.window is None) == (a.point is None):
@@ -68,12 +70,14 @@ n_az = 1 << max(2, int(np.ceil(np.log2(a.n_az))))
 obs = ephemeris.Observer(a.lat, a.lon, 0.0)
 start = datetime.fromisoformat(a.time)
 kw = dict(area_m2=a.area, efficiency=a.eff, load_w=a.load, panel=a.panel, normal_enu=a.normal, capacity_wh=a.capacity_wh,
-          n_az=n_az, n_bis=a.n_bis, observer=obs)
+          n_az=n_az, n_bis=a.n_bis, observer=obs, eclipses=a.eclipses)
 if a.point is not None:
     la, lo = [a.point[0]], [a.point[1]]
     r = sunlight.power_budget(rt, la, lo, start, a.days, a.step_min, a.height, **kw)
     ep = ephemeris.sun_epochs(r.times, obs)
     gen = ephemeris.sun_flux(r.times) * (a.area * a.eff)
+    if a.eclipses:
+        gen = gen * ephemeris.eclipse_factor(r.times, obs)
     hz = rt.horizon(la, lo, n_az=n_az, n_bis=a.n_bis, height_m=a.height)
     f = rt.horizon_sun(la, lo, hz, ep)[0]
     G = rt.power_budget(la, lo, hz, ep, gen, a.load, panel=a.panel, normal_enu=a.normal, cpw_log2=r.cpw_log2, mode="full")[0]

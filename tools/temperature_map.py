@@ -8,6 +8,9 @@ the thermal stage (DESIGN.md sections 3.8 and 3.10), headless.
 --scatter K adds the sunlight and infrared the surrounding terrain sends, from K view rays per point (section 3.11); with
 --point it also prints the point's terrain view factor and its mean scattered flux.  --point ... --depths prints every
 node's temperature per date (the COLUMN mode of section 3.16) instead of the surface's alone.
+--eclipses lets the Earth cover the Sun (section 3.18); with --point over the hours of a lunar eclipse this prints the
+eclipse cooling curve:
+  python tools/temperature_map.py --point 0 0 --time 2025-03-14T03:00:00+00:00 --days 0.4 --step-min 5 --eclipses
 The window's nodes are MoonRT.grid_nodes; temps.npy holds a (4, h, w) float32 array: the maximum, minimum and mean surface
 temperature over the dates and the mean temperature of the column's bottom node, K.  The column is spun up over
 --spinup-lunations lunations before the first date.  Synthetic LOLA-like DEM unless --elevation-file is given."""
@@ -36,6 +39,7 @@ ap.add_argument("--dem-size", type=int, nargs=2, default=None, help="synthetic D
 ap.add_argument("--elevation-file", default=None)
 ap.add_argument("--scatter", type=int, default=0, help="K view rays per point for the terrain-scattered flux (0: none)")
 ap.add_argument("--depths", action="store_true", help="with --point: the whole column per date, one CSV column per node")
+ap.add_argument("--eclipses", action="store_true", help="the Earth's occultation of the Sun in every column (section 3.18)")
 ap.add_argument("--out", default="temps.npy")
 a = ap.parse_args()
 if a.depths and a.point is None:
@@ -70,6 +74,12 @@ if a.point is not None:
     times = [start + timedelta(minutes=(k - model.n_spin) * a.step_min) for k in range(model.n_spin + m_rec)]
     st = {}
     hz = rt.horizon([a.point[0]], [a.point[1]], n_az=n_az, n_bis=a.n_bis, stats=st)
+    occ = None
+    if a.eclipses:
+        if a.scatter:
+            ap.error("--point with --scatter keeps the series without eclipses; use --window, or drop --scatter")
+        sun, earth = ephemeris.sun_earth_epochs(times, obs)
+        occ = (ephemeris.far_sun_epochs(sun, times), earth)
     if a.scatter:
         # the stages of sunlight.surface_temperatures(scatter=K) for one point, with the series kept
         hits, share = rt.view_hits([a.point[0]], [a.point[1]], k=a.scatter, stats=st)
@@ -87,9 +97,9 @@ if a.point is not None:
                  mode="column" if a.depths else "full", extra_flux=q, stats=st)[0]
         print(f"# terrain view factor {float(share[0]):.4f} ({h_lat.size} of {a.scatter} rays), mean scattered flux "
               f"{float(q[0, n_spin:].astype(np.float64).mean()):.3f} W m^-2 over the recorded dates", file=sys.stderr)
-    elif a.depths:
+    elif a.depths or occ is not None:
         ts = rt.thermal_column([a.point[0]], [a.point[1]], hz, ephemeris.sun_epochs(times, obs), ephemeris.sun_flux(times),
-                               model, mode="column", stats=st)[0]
+                               model, mode="column" if a.depths else "full", stats=st, occultation=occ)[0]
     else:
         ts = rt.surface_temperature([a.point[0]], [a.point[1]], hz, ephemeris.sun_epochs(times, obs),
                                     ephemeris.sun_flux(times), model, mode="full", stats=st)[0]
@@ -108,7 +118,7 @@ else:
     la, lo = MoonRT.grid_nodes(lat=(N, S), lon=(W, E), shape=tuple(a.size))
     LA, LO = np.meshgrid(la, lo, indexing="ij")
     r = sunlight.surface_temperatures(rt, LA.ravel(), LO.ravel(), start, a.days, a.step_min, a.spinup_lunations, n_az,
-                                      a.n_bis, obs, scatter=a.scatter)
+                                      a.n_bis, obs, scatter=a.scatter, eclipses=a.eclipses)
     out = np.stack([r.t_max, r.t_min, r.t_mean, r.t_bottom_mean]).reshape(4, *a.size)
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     np.save(a.out, out.astype(np.float32))
