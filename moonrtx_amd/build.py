@@ -5,7 +5,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libmoonrt.so")
-SOURCES = ["mrtx_kernels.hip", "mrtx_traverse.hip", "mrtx_relief.hip", "mrtx_api.hip", "mrtx_device.h", os.path.join("..", "..", "include", "moonrt.h")]
+SOURCES = ["mrtx_kernels.hip", "mrtx_terrain.hip", "mrtx_march.h", "mrtx_traverse.hip", "mrtx_relief.hip", "mrtx_api.hip", "mrtx_device.h", os.path.join("..", "..", "include", "moonrt.h")]
 
 
 def stale():
@@ -34,7 +34,7 @@ def build_native(force=False):
     """Compile the HIP extension in-tree; returns the library path."""
     def go():
         if force or stale():
-            subprocess.check_call(["make", "-C", CSRC, "-s", "all"])
+            subprocess.check_call(["make", "-C", CSRC, "-s", "-j4", "all"])   # independent objects; four jobs whatever the machine
     _locked(go)
     return LIB
 

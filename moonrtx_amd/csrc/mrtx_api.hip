@@ -666,7 +666,7 @@ void mrtx_destroy(mrtx_ctx* c) {
 
 const char* mrtx_last_error(mrtx_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
-// The context keeps its own PADDED copy of the DEM (see dem_march() in mrtx_kernels.hip).
+// The context keeps its own PADDED copy of the DEM (see dem_march() in mrtx_march.h).
 static int ingest_dem(mrtx_ctx* c, const float* dev_src, int32_t h, int32_t w) {
     if (c->dem) { HIPCHK(c, hipFree(c->dem)); }
     c->dem = nullptr; c->dem_h = c->dem_w = 0;
@@ -1356,7 +1356,7 @@ static int stage_start(mrtx_ctx* c, const FrameCold* cold, bool zero) {
     return MRTX_OK;
 }
 
-// the counter slot of a launch's rays (mrtx_kernels.hip's ST_SHADOW, ST_BOUNCE), or none when it did not count
+// the counter slot of a launch's rays (mrtx_march.h's ST_SHADOW, ST_BOUNCE), or none when it did not count
 enum StageRays { kNoRays = -1, kShadowRays = 2, kBounceRays = 8 };
 
 // right after the launch: the end event, wait, time, read back, counters (rays: reported as shadow_rays or bounce_rays)

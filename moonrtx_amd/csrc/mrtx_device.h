@@ -17,7 +17,7 @@ struct GridC {          // equirectangular grid: row 0 = +90 deg, column 0 = -18
     float row_scale, row_off, col_scale, col_off, wf;
 };
 
-// DEM layout in HBM (see dem_march() in mrtx_kernels.hip): row pairs, element (r, c) = float2 (D[r][c], D[r+1][c]),
+// DEM layout in HBM (see dem_march() in mrtx_march.h): row pairs, element (r, c) = float2 (D[r][c], D[r+1][c]),
 // so the 2x2 footprint of a bilinear evaluation is ONE 16-byte load (plain padded float32, two 8-byte loads: retired,
 // DESIGN.md section 4.18).
 #define MRTX_DEM_ELEM_BYTES 8
@@ -48,7 +48,7 @@ static inline int mrtx_tile_shift(int world) {
 #define MRTX_PATH_MIP2 0
 #endif
 // The medium mip also cuts the skip interval of a segment from one end, with tests that stop at the first inconclusive step
-// (first_kept_step / last_kept_step in mrtx_kernels.hip; round 4): bit 2 (4) camera rays, from the front: render 15.4 -> 13.9 ms at cfg3;
+// (first_kept_step / last_kept_step in mrtx_march.h; round 4): bit 2 (4) camera rays, from the front: render 15.4 -> 13.9 ms at cfg3;
 // bit 1 (2) shadow rays in render_kernel, from the end: -> 13.8; bit 3 (8) path_kernel's marches, from the end: path stage 5.0 -> 4.65;
 // bit 0 (1) the trial segment, from the end: +0.17 ms, off.  The host builds the medium mip when either switch is set.
 #ifndef MRTX_M2_DELTA
@@ -91,7 +91,7 @@ struct FrameCold {
     float* hits;            // W*H float4: x,y,z,d of sample 0 of the last block
     unsigned long long* stats;  // 10 counters, see MrtxStats (render_kernel's; [15] = path_kernel's watchdog)
     unsigned long long* stats_paths;   // the same counters as path_kernel adds them (MrtxStats::camera_* = the render kernel's share)
-    // horizon mip (horizon_kend in mrtx_kernels.hip): hm_h x hm_w cells of 2^hm_shift texels, or null
+    // horizon mip (horizon_kend in mrtx_march.h): hm_h x hm_w cells of 2^hm_shift texels, or null
     const float* hmip;
     int32_t hm_h, hm_w, hm_shift;
     float hm_cell;                  // cell size in texels

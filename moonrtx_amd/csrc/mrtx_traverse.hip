@@ -13,7 +13,7 @@
 // loads and the stores of d that another workgroup may read in the same launch are relaxed agent-scope 64-bit atomics (no torn
 // double); a stale read only costs another launch.  Only kernel boundaries order anything.
 //
-// Own translation unit: the existing kernels of mrtx_kernels.hip are compiled exactly as before.  Build flags as there
+// Own translation unit: the kernels of mrtx_kernels.hip and mrtx_terrain.hip are compiled exactly as before.  Build flags as there
 // (-ffp-contract=off, correctly rounded /): the edge weight is the spec's float32 expression operation by operation.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

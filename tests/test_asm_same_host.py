@@ -42,3 +42,36 @@ def test_functions_are_cut_at_type_and_size():
     fs = asm_same.functions(_listing(F, "1234abcd"))
     assert sorted(fs) == ["_Z1av", "_Z1bv", "_Z1cv"]
     assert "v_fma_f32" in fs["_Z1cv"] and "amdhsa_kernel" not in fs["_Z1cv"]
+
+
+def _numbered(first, edit=lambda name, body: body):
+    """The three functions with a loop each, as the `first`-th and following functions of a translation unit: the compiler
+    puts a function's index into its local labels and into the comments that mention them."""
+    funcs = []
+    for k, (name, body) in enumerate(F):
+        f = first + k
+        funcs.append((name, edit(name, [f"s_cbranch_scc1 .LBB{f}_2", f".LBB{f}_1:", body[0],
+                                        f"s_cbranch_vccnz .LBB{f}_1 ; in Loop: Header=BB{f}_1 Depth=1", f".LBB{f}_2:",
+                                        f".Ltmp{3 * f}:", f"s_getpc_b64 s[0:1] ; .Ltmp{3 * f}", f".LBB{f}_3:", body[1],
+                                        f".Lfunc_end{f}:"])))
+    return funcs
+
+
+def _b_changed(name, body):
+    return [l.replace("v_add_f32_e32", "v_sub_f32_e32") for l in body]
+
+
+def _b_retargeted(name, body):
+    return [l.replace("s_cbranch_scc1 .LBB7_2", "s_cbranch_scc1 .LBB7_3") for l in body]
+
+
+@pytest.mark.parametrize("b_funcs, status, lines", [
+    (_numbered(6), 0, ["3 / 3 functions: 0 differ, 0 added, 0 removed"]),
+    (_numbered(6, _b_changed), 1, ["differs _Z1bv", "3 / 3 functions: 1 differ, 0 added, 0 removed"]),
+    (_numbered(6, _b_retargeted), 1, ["differs _Z1bv", "3 / 3 functions: 1 differ, 0 added, 0 removed"]),
+], ids=["renumbered", "renumbered_instruction_changed", "renumbered_branch_retargeted"])
+def test_asm_same_ignores_the_function_index_of_local_labels(b_funcs, status, lines):
+    assert any(".LBB7_2" in l for l in dict(_numbered(6))["_Z1bv"])      # the function the edits aim at is number 7 there
+    out = io.StringIO()
+    assert asm_same.compare(_listing(_numbered(0), "1234abcd"), _listing(b_funcs, "9876fedc"), out) == status
+    assert out.getvalue().splitlines() == lines

@@ -55,7 +55,7 @@ def test_math_primitives_bit_exact(native_lib):
 
 def test_domain_restricted_reciprocal_and_sqrt_are_ieee_exact(native_lib):
     """The kernels take 1/x as v_rcp_f32 + one Newton step and sqrt as v_sqrt_f32 + a residual fix where the argument's range is
-    known (mrtx_kernels.hip: rcp_cr, sqrt_cr); the oracle uses the C compiler's IEEE division and sqrtf.  Equality is checked
+    known (mrtx_march.h: rcp_cr, sqrt_cr); the oracle uses the C compiler's IEEE division and sqrtf.  Equality is checked
     EXHAUSTIVELY on the device against the compiler's IEEE expansions: every normal float of either sign whose reciprocal is normal
     (exponents -126 .. 125), and every float from 2^-104 up plus zero for the square root."""
     import ctypes as C

@@ -3,14 +3,34 @@
 
 A listing is cut into functions at its `.type <sym>,@function` ... `.size <sym>` lines (the kernel descriptors and
 everything else outside them are not compared); the `__hip_cuid_<hash>` object is ignored, since the hash changes with
-any edit of the source text.  Text is compared as it stands.  Prints the functions that were added, removed or differ,
-then one count line; the exit status is 1 on any difference.
+any edit of the source text.  What is compared is the code: everything from `;` to the end of a line is a comment, and the
+compiler's local labels (.LBB<f>_<n>, .LJTI<f>_<n>, .LCPI<f>_<n>, .Lfunc_begin<f>, .Lfunc_end<f>) carry the index <f> of the
+function within its translation unit, which moves when a function is compiled next to other ones: the index is dropped, the
+block number <n> stays.  .Ltmp<n> counts through the whole unit and is renumbered by first appearance within the function.
+Everything else is compared as it stands.  A tree of several translation units is compared by concatenating its listings
+(cat mrtx_kernels.s mrtx_terrain.s).  Prints the functions that were added, removed or differ, then one count line; the exit
+status is 1 on any difference.
 """
 import re
 import sys
 
 TYPE = re.compile(r"\s*\.type\s+([^,\s]+),@function")
 SIZE = re.compile(r"\s*\.size\s+([^,\s]+),")
+INDEXED = re.compile(r"\.L(BB|JTI|CPI)\d+_(\d+)\b")
+FUNC = re.compile(r"\.Lfunc_(begin|end)\d+\b")
+TMP = re.compile(r"\.Ltmp\d+\b")
+
+
+def code(body):
+    """The lines of a function body without comments and without the compiler's numbering of its local labels."""
+    tmp, out = {}, []
+    for line in body:
+        line = line.split(";", 1)[0].rstrip()
+        if not line or "__hip_cuid_" in line:
+            continue
+        line = FUNC.sub(r".Lfunc_\1", INDEXED.sub(r".L\1_\2", line))
+        out.append(TMP.sub(lambda m: ".Ltmp_%d" % tmp.setdefault(m.group(0), len(tmp)), line))
+    return "\n".join(out)
 
 
 def functions(text):
@@ -22,7 +42,7 @@ def functions(text):
         elif name is not None:
             m = SIZE.match(line)
             if m and m.group(1) == name:
-                out[name] = "\n".join(l for l in body if "__hip_cuid_" not in l)
+                out[name] = code(body)
                 name = None
             else:
                 body.append(line)
