@@ -489,6 +489,42 @@ int mrtx_traverse(mrtx_ctx* ctx, const MrtxTraverse* t, const int32_t* src_ij, c
  * checked as mrtx_traverse checks it; needs a DEM.  out: launches, kernel_ms. */
 int mrtx_traverse_heights(mrtx_ctx* ctx, const MrtxTraverse* t, void* dev_out, float* host_out, MrtxStats* out);
 
+/* ---- Timed traverses: drive masks and earliest arrival (additive to ABI 7) -----------------------
+ * mrtx_horizon_windows' joint predicate kept as bits.  Per point W64 = (m + 63) / 64 uint64 words, point-major: bit k & 63 of
+ * word k >> 6 is `both` at epoch k, ok_a = f_a >= (float)min_a and ok_b = f_b >= (float)min_b with f mrtx_horizon_sun FULL's
+ * value bit for bit (equality counts as met); with epochs_b NULL the bit is ok_a alone and min_b is ignored.  The bits past
+ * epoch m - 1 are 0.  Arguments, limits, state and counters are mrtx_horizon_windows': m <= 2^24, min in (0, 1], exactly one
+ * of each pointer pair, dev_out 8-byte aligned; needs a DEM, neither a light nor a Moon frame; leaves the render state alone. */
+int mrtx_horizon_mask(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, int32_t n_az, const void* dev_horizon,
+                      const float* host_horizon, const MrtxIllumEpoch* epochs_a, const MrtxIllumEpoch* epochs_b, int32_t m,
+                      double min_a, double min_b, void* dev_out, uint64_t* host_out, MrtxStats* out);
+/* Time in integer ticks.  An edge u -> v of mrtx_traverse's float32 weight w lasts q ticks: x = (double)w * ticks_per_cost (one
+ * float64 product), q = 1 if x <= 1, else ceil(x); it is not driven if w is infinite or x > 2^31.  Tick t lies in epoch
+ * t / ticks_per_epoch; node v is available in epoch e iff bit e of its row of the availability table is set (the layout of
+ * mrtx_horizon_mask) and e < n_epochs.  Without a table every epoch is available and there is no end.  A drive that starts at
+ * tick t occupies ticks t .. t + q - 1 and arrives at t + q; it is allowed iff all of its epochs are available at both u and
+ * v.  Waiting at a node is free.  g_uv(a) = (the least t >= a at which the drive is allowed) + q, and the arrival field is the
+ * least fixed point of A[v] = min(src[v], min over u of g_uv(A[u])); UINT64_MAX where unreachable. */
+typedef struct MrtxTraverseTimed {
+    double  ticks_per_cost;   /* ticks per unit of edge weight w (finite, > 0): e.g. 1 s ticks at 0.2 m/s -> 5 */
+    int32_t ticks_per_epoch;  /* >= 1 */
+    int32_t n_epochs;         /* epochs in the availability table, 1 .. 2^24 (ignored without a table) */
+    int32_t reserved;         /* 0 */
+} MrtxTraverseTimed;
+/* The arrival field and its predecessors.  Window, sources, penalties, outputs, refusals and their order as mrtx_traverse's;
+ * src_tick = the sources' start ticks (null: all 0; duplicates: the smallest wins; a source need not be available at its
+ * start tick), each below n_epochs * ticks_per_epoch with a table and below 2^62 without.  At most one of dev_avail /
+ * host_avail (rows x cols x W64 uint64, node-major, W64 = (n_epochs + 63) / 64; both null: no table), exactly one of
+ * dev_arrival / host_arrival (rows x cols uint64) and of dev_pred / host_pred.  dev_avail and dev_arrival are 8-byte aligned;
+ * no two device tables overlap.  pred: 8 = a source whose arrival is its start tick; else the first direction k whose
+ * neighbour u is in the window with A[u] < A[v], a driven edge and g_uv(A[u]) == A[v]; 255 = unreachable, 254 = none found.
+ * Also refused: a null tt, reserved != 0, ticks_per_cost not finite and > 0, ticks_per_epoch < 1, n_epochs out of range while
+ * a table is given.  out and tile_visits as mrtx_traverse's. */
+int mrtx_traverse_timed(mrtx_ctx* ctx, const MrtxTraverse* t, const MrtxTraverseTimed* tt, const int32_t* src_ij,
+                        const uint64_t* src_tick, int32_t n_src, const void* dev_penalty, const float* host_penalty,
+                        const void* dev_avail, const uint64_t* host_avail, void* dev_arrival, uint64_t* host_arrival,
+                        void* dev_pred, uint8_t* host_pred, uint64_t* tile_visits, MrtxStats* out);
+
 /* ---- Terrain relief: slope, roughness and landing hazard (additive to ABI 7) -----------------------
  * A window of the DEM's texel lattice as MrtxTraverse's, never wrapped: node (i, j) is texel (row0 + i stride,
  * (col0 + j stride) mod W); the last row lies inside the DEM and the columns are distinct.  A node's footprint is the

@@ -60,6 +60,11 @@ class MrtxTraverse(C.Structure):
                 ("descent_cost", C.c_double), ("reserved", C.c_int32)]
 
 
+class MrtxTraverseTimed(C.Structure):
+    """The tick scales of a timed traverse (mrtx_traverse_timed)."""
+    _fields_ = [("ticks_per_cost", C.c_double), ("ticks_per_epoch", C.c_int32), ("n_epochs", C.c_int32), ("reserved", C.c_int32)]
+
+
 class MrtxRelief(C.Structure):
     """A window of the DEM's texel lattice and the footprint of a relief map (mrtx_relief)."""
     _fields_ = [("row0", C.c_int32), ("col0", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("stride", C.c_int32),
@@ -185,6 +190,10 @@ SIGNATURES = {
     "mrtx_traverse": (C.c_int, [_VP, C.POINTER(MrtxTraverse), _VP, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
                                 C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
     "mrtx_traverse_heights": (C.c_int, [_VP, C.POINTER(MrtxTraverse), _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_horizon_mask": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, C.c_double, C.c_double,
+                                    _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_traverse_timed": (C.c_int, [_VP, C.POINTER(MrtxTraverse), C.POINTER(MrtxTraverseTimed), _VP, _VP, C.c_int32, _VP, _VP,
+                                      _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
     "mrtx_relief_scales": (C.c_int, [C.POINTER(MrtxRelief), C.c_int32, C.c_int32, _VP]),
     "mrtx_relief": (C.c_int, [_VP, C.POINTER(MrtxRelief), _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_relief_share": (C.c_int, [_VP, C.POINTER(MrtxReliefShare), _VP, _VP, _VP, _VP, C.POINTER(MrtxStats)]),

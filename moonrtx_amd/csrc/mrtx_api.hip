@@ -72,6 +72,10 @@ hipError_t mrtx_launch_traverse_init(const TraverseC& q, hipStream_t st);
 hipError_t mrtx_launch_traverse_relax(const TraverseC& q, hipStream_t st);
 hipError_t mrtx_launch_traverse_pred(const TraverseC& q, hipStream_t st);
 hipError_t mrtx_launch_traverse_heights(const TraverseC& q, float* out, hipStream_t st);
+hipError_t mrtx_launch_timed_init(const TraverseTimedC& q, hipStream_t st);
+hipError_t mrtx_launch_timed_relax(const TraverseTimedC& q, hipStream_t st);
+hipError_t mrtx_launch_timed_pred(const TraverseTimedC& q, hipStream_t st);
+hipError_t mrtx_launch_horizon_mask(const FrameC& f, HorizonMaskC q, hipStream_t st);
 hipError_t mrtx_launch_relief(const ReliefC& q, int tile, hipStream_t st);
 hipError_t mrtx_launch_relief_share(const ShareC& q, hipStream_t st);
 size_t mrtx_relief_tile_lds(int th, int tw, int ri, int rj);
@@ -1656,6 +1660,49 @@ int mrtx_horizon_windows(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n
     return stage_finish(c, dev_out, host_out, out_bytes, out, kNoRays);
 }
 
+// ---- Drive masks: mrtx_horizon_windows' predicate kept as bits -------------------------------------
+int mrtx_horizon_mask(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az, const void* dev_horizon,
+                      const float* host_horizon, const MrtxIllumEpoch* epochs_a, const MrtxIllumEpoch* epochs_b, int32_t m,
+                      double min_a, double min_b, void* dev_out, uint64_t* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!latlon || !epochs_a) return fail(c, MRTX_E_INVALID, "null point list or epoch table");
+    if (n < 1 || m < 1) return fail(c, MRTX_E_INVALID, "n and m must be >= 1 (got %d, %d)", n, m);
+    if (m > (1 << 24)) return fail(c, MRTX_E_INVALID, "at most 2^24 epochs per call (got %d)", m);
+    if (!horizon_az_ok(n_az)) return fail(c, MRTX_E_INVALID, "n_az must be 4, 8, ..., 4096 (got %d)", n_az);
+    if (!epochs_b) min_b = 1.0;        // ignored without a second table
+    if (!(min_a > 0.0 && min_a <= 1.0) || !(min_b > 0.0 && min_b <= 1.0))
+        return fail(c, MRTX_E_INVALID, "min_a and min_b must lie in (0, 1]");
+    if (!((float)min_a > 0.0f) || !((float)min_b > 0.0f))
+        return fail(c, MRTX_E_INVALID, "min_a and min_b must be positive as float32");
+    int rc = horizon_args(c, dev_horizon, host_horizon, n, n_az, dev_out, reinterpret_cast<const float*>(host_out));
+    if (rc != MRTX_OK) return rc;
+    if (dev_out && ((uintptr_t)dev_out & 7)) return fail(c, MRTX_E_INVALID, "dev_out must be 8-byte aligned");
+    if ((rc = horizon_entries(c, host_horizon, n, n_az)) != MRTX_OK) return rc;
+    std::vector<float> rtab, ctab, lights_a, lights_b;
+    if ((rc = point_tables(c, latlon, n, rtab, ctab)) != MRTX_OK) return rc;
+    if ((rc = epoch_lights(c, epochs_a, m, lights_a)) != MRTX_OK) return rc;
+    if (epochs_b && (rc = epoch_lights(c, epochs_b, m, lights_b)) != MRTX_OK) return rc;
+    FrameC f;
+    FrameCold cold;
+    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
+    const size_t nh = host_horizon ? (size_t)n * (size_t)n_az : 0;
+    const size_t out_bytes = (size_t)n * (size_t)((m + 63) / 64) * 8;
+    float* d[5];
+    if ((rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK ||
+        (rc = stage_tables(c, {rtab, ctab, lights_a, lights_b, {host_horizon, nh}}, d)) != MRTX_OK)
+        return rc;
+    HorizonMaskC q;
+    std::memset(&q, 0, sizeof q);
+    q.g.rtab = d[0]; q.g.ctab = d[1];
+    q.g.rows = n; q.g.cols = n; q.g.points = 1;
+    q.lights_a = d[2]; q.lights_b = epochs_b ? d[3] : nullptr;
+    q.horizon = host_horizon ? d[4] : (const float*)dev_horizon;
+    q.out = (unsigned long long*)dev_out; q.min_a = (float)min_a; q.min_b = (float)min_b; q.az_log2 = log2_of(n_az); q.m = m;
+    if ((rc = stage_start(c, &cold, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_horizon_mask(f, q, c->stream));
+    return stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays);
+}
+
 // ---- The Earth's occultation of the Sun ------------------------------------------------------------
 // The two epoch tables of mrtx_occultation and mrtx_thermal_occulted: epoch_lights' checks and constants for both, the
 // geometry the two-disc rule stands on, and per epoch the float64 mark "some point inside the bounding sphere may see the
@@ -2068,6 +2115,148 @@ int mrtx_traverse(mrtx_ctx* c, const MrtxTraverse* t, const int32_t* src_ij, con
     float ms = 0.0f;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
     if (host_cost) HIPCHK(c, hipMemcpy(host_cost, d_cost, N * 8, hipMemcpyDeviceToHost));
+    if (host_pred) HIPCHK(c, hipMemcpy(host_pred, d_pred, N, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost));
+    if (tile_visits) *tile_visits = cnt[0];
+    if (out) {
+        std::memset(out, 0, sizeof *out);
+        out->kernel_ms = ms;
+        out->launches = launches;
+    }
+    return MRTX_OK;
+}
+
+// ---- Timed traverses: earliest arrival under per-node drive windows --------------------------------
+int mrtx_traverse_timed(mrtx_ctx* c, const MrtxTraverse* t, const MrtxTraverseTimed* tt, const int32_t* src_ij,
+                        const uint64_t* src_tick, int32_t n_src, const void* dev_penalty, const float* host_penalty,
+                        const void* dev_avail, const uint64_t* host_avail, void* dev_arrival, uint64_t* host_arrival,
+                        void* dev_pred, uint8_t* host_pred, uint64_t* tile_visits, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!t) return fail(c, MRTX_E_INVALID, "null window");
+    if (!tt) return fail(c, MRTX_E_INVALID, "null tick scales");
+    int rc = traverse_params(c, t);
+    if (rc != MRTX_OK) return rc;
+    if (tt->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    if (!std::isfinite(tt->ticks_per_cost) || !(tt->ticks_per_cost > 0.0))
+        return fail(c, MRTX_E_INVALID, "ticks_per_cost must be finite and > 0");
+    if (tt->ticks_per_epoch < 1) return fail(c, MRTX_E_INVALID, "ticks_per_epoch must be >= 1 (got %d)", tt->ticks_per_epoch);
+    const bool table = dev_avail || host_avail;
+    if (table && (tt->n_epochs < 1 || tt->n_epochs > (1 << 24)))
+        return fail(c, MRTX_E_INVALID, "n_epochs must lie in [1, 2^24] (got %d)", tt->n_epochs);
+    if (dev_penalty && host_penalty) return fail(c, MRTX_E_INVALID, "give at most one of dev_penalty and host_penalty");
+    if (dev_avail && host_avail) return fail(c, MRTX_E_INVALID, "give at most one of dev_avail and host_avail");
+    if ((dev_arrival == nullptr) == (host_arrival == nullptr))
+        return fail(c, MRTX_E_INVALID, "give exactly one of dev_arrival and host_arrival");
+    if ((dev_pred == nullptr) == (host_pred == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_pred and host_pred");
+    if (dev_arrival && (reinterpret_cast<uintptr_t>(dev_arrival) & 7))
+        return fail(c, MRTX_E_INVALID, "dev_arrival must be 8-byte aligned (uint64, read and written atomically)");
+    if ((rc = traverse_dev_buffers(c, t, dev_penalty, dev_arrival, dev_pred)) != MRTX_OK) return rc;
+    const size_t N = (size_t)t->rows * (size_t)t->cols;
+    const size_t W64 = table ? ((size_t)tt->n_epochs + 63) / 64 : 0;
+    if (dev_avail && (reinterpret_cast<uintptr_t>(dev_avail) & 7)) return fail(c, MRTX_E_INVALID, "dev_avail must be 8-byte aligned");
+    if (traverse_overlap(dev_avail, 8 * N * W64, dev_arrival, 8 * N) || traverse_overlap(dev_avail, 8 * N * W64, dev_pred, N) ||
+        traverse_overlap(dev_avail, 8 * N * W64, dev_penalty, 4 * N))
+        return fail(c, MRTX_E_INVALID, "dev_avail must not overlap dev_penalty, dev_arrival or dev_pred");
+    if (n_src < 1 || !src_ij) return fail(c, MRTX_E_INVALID, "need n_src >= 1 sources (got %d)", n_src);
+    // a start tick lies inside the table; without one it leaves room for 2^31 edges of 2^31 ticks below UINT64_MAX
+    const uint64_t tick_end = table ? (uint64_t)tt->n_epochs * (uint64_t)tt->ticks_per_epoch : (uint64_t)1 << 62;
+    std::vector<std::pair<int64_t, uint64_t>> src((size_t)n_src);
+    for (int32_t k = 0; k < n_src; k++) {
+        const int32_t i = src_ij[2 * (size_t)k], j = src_ij[2 * (size_t)k + 1];
+        const uint64_t s = src_tick ? src_tick[k] : 0;
+        if (i < 0 || i >= t->rows || j < 0 || j >= t->cols)
+            return fail(c, MRTX_E_INVALID, "source %d: node (%d, %d) lies outside the %d x %d window", k, i, j, t->rows, t->cols);
+        if (s >= tick_end)
+            return fail(c, MRTX_E_INVALID, "source %d: start tick %llu must be below %llu", k, (unsigned long long)s,
+                        (unsigned long long)tick_end);
+        src[(size_t)k] = {(int64_t)i * t->cols + j, s};
+    }
+    std::sort(src.begin(), src.end());
+    std::vector<int64_t> sn;
+    std::vector<uint64_t> sc;
+    for (const auto& e : src)
+        if (sn.empty() || sn.back() != e.first) { sn.push_back(e.first); sc.push_back(e.second); }
+    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
+    std::vector<float> len((size_t)t->rows * 3);
+    if ((rc = traverse_window(c, t, c->dem_h, c->dem_w, len.data())) != MRTX_OK) return rc;
+    if (host_penalty)
+        for (size_t n = 0; n < N; n++)
+            if (!traverse_penalty_ok(host_penalty[n]))
+                return fail(c, MRTX_E_INVALID, "penalty %zu must be finite in [1e-3, 1e6] or +inf (got %g)", n, (double)host_penalty[n]);
+    int TS = 32;        // MOONRT_TRAVERSE_TILE, as in mrtx_traverse
+    if (const char* e = std::getenv("MOONRT_TRAVERSE_TILE")) {
+        TS = std::atoi(e);
+        if (TS != 8 && TS != 16 && TS != 32) return fail(c, MRTX_E_INVALID, "MOONRT_TRAVERSE_TILE must be 8, 16 or 32 (got %s)", e);
+    }
+    // ---- device work from here
+    FrameC f;
+    FrameCold cold;
+    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
+    const int tiles_x = (t->cols + TS - 1) / TS, tiles_y = (t->rows + TS - 1) / TS;
+    const size_t tiles = (size_t)tiles_x * (size_t)tiles_y;
+    const size_t arr_b = host_arrival ? N * 8 : 0, pred_b = host_pred ? (N + 15) & ~(size_t)15 : 0;
+    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, arr_b + pred_b + 2 * tiles * 4)) != MRTX_OK) return rc;
+    char* tb = reinterpret_cast<char*>(c->trav_buf);
+    unsigned long long* d_arr = host_arrival ? reinterpret_cast<unsigned long long*>(tb) : static_cast<unsigned long long*>(dev_arrival);
+    uint8_t* d_pred = host_pred ? reinterpret_cast<uint8_t*>(tb + arr_b) : static_cast<uint8_t*>(dev_pred);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(tb + arr_b + pred_b);
+    const size_t np = host_penalty ? N : 0, na = host_avail ? 2 * N * W64 : 0;
+    float* d[5];
+    if ((rc = stage_tables(c, {len, {sn.data(), 2 * sn.size()}, {sc.data(), 2 * sc.size()}, {host_penalty, np}, {host_avail, na}},
+                           d)) != MRTX_OK)
+        return rc;
+    TraverseTimedC q;
+    std::memset(&q, 0, sizeof q);
+    TraverseC& g = q.t;
+    g.dem = f.dem; g.dem_pitch = f.dem_pitch; g.dem_w = c->dem_w;
+    g.row0 = t->row0; g.col0 = t->col0; g.rows = t->rows; g.cols = t->cols; g.stride = t->stride; g.wrap = t->wrap;
+    g.len = d[0];
+    g.src_node = reinterpret_cast<const int64_t*>(d[1]);
+    g.n_src = (int32_t)sn.size();
+    g.pen = host_penalty ? d[3] : static_cast<const float*>(dev_penalty);
+    g.pred = d_pred;
+    g.rm = (float)t->radius_m; g.gmax = (float)t->max_grade; g.a_up = (float)t->climb_cost; g.a_dn = (float)t->descent_cost;
+    g.tile = TS; g.tiles_x = tiles_x; g.tiles_y = tiles_y;
+    g.visits = c->illum_stats;                                       // [0] tile visits, [1] bad device penalties
+    g.changed = reinterpret_cast<uint32_t*>(c->illum_stats + 2);     // kTraverseBatch per-launch change counters
+    q.arr = d_arr;
+    q.src_tick = reinterpret_cast<const unsigned long long*>(d[2]);
+    q.avail = host_avail ? reinterpret_cast<const unsigned long long*>(d[4]) : static_cast<const unsigned long long*>(dev_avail);
+    q.tpc = tt->ticks_per_cost; q.tpe = tt->ticks_per_epoch;
+    q.n_epochs = table ? tt->n_epochs : 0; q.w64 = (int32_t)W64;
+    uint32_t* fa = flags;
+    uint32_t* fb = flags + tiles;
+    HIPCHK(c, hipMemsetAsync(flags, 0, 2 * tiles * 4, c->stream));
+    if ((rc = stage_start(c, nullptr, true)) != MRTX_OK) return rc;
+    g.flag_in = fa;
+    HIPCHK(c, mrtx_launch_timed_init(q, c->stream));
+    unsigned long long cnt[2] = {0, 0};
+    if (dev_penalty) {
+        HIPCHK(c, hipMemcpyAsync(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (cnt[1])
+            return fail(c, MRTX_E_INVALID, "%llu entries of the device penalty table are not finite in [1e-3, 1e6] or +inf", cnt[1]);
+    }
+    uint32_t launches = 0;
+    for (;;) {      // no launch cap: every store strictly lowers a uint64 arrival, and the fixed point is finite (section 4.22)
+        HIPCHK(c, hipMemsetAsync(g.changed, 0, kTraverseBatch * sizeof(uint32_t), c->stream));
+        for (int s = 0; s < kTraverseBatch; s++) {
+            g.flag_in = fa; g.flag_out = fb; g.slot = s;
+            HIPCHK(c, mrtx_launch_timed_relax(q, c->stream));
+            std::swap(fa, fb);
+            launches++;
+        }
+        uint32_t last = 0;
+        HIPCHK(c, hipMemcpyAsync(&last, g.changed + (kTraverseBatch - 1), sizeof last, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (last == 0) break;       // a whole launch lowered nothing: every later one is empty too
+    }
+    HIPCHK(c, mrtx_launch_timed_pred(q, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (host_arrival) HIPCHK(c, hipMemcpy(host_arrival, d_arr, N * 8, hipMemcpyDeviceToHost));
     if (host_pred) HIPCHK(c, hipMemcpy(host_pred, d_pred, N, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost));
     if (tile_visits) *tile_visits = cnt[0];

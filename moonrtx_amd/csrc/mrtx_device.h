@@ -363,6 +363,33 @@ struct TraverseC {
     int32_t n_src;
 };
 
+// Timed traverses (mrtx_traverse_timed, DESIGN.md sections 3.19 and 4.22; kernels in mrtx_traverse.hip): TraverseC's window,
+// lattice, penalties, tiles, flags and counters (its d and src_cost are not used), with arrival ticks in place of costs and an
+// optional availability table of w64 = (n_epochs + 63) / 64 words per node, bit e & 63 of word e >> 6 = epoch e.
+struct TraverseTimedC {
+    TraverseC t;
+    unsigned long long* arr;            // rows x cols uint64 arrival ticks, UINT64_MAX = unreachable
+    const unsigned long long* avail;    // rows x cols x w64 words, node-major, or null (always drivable, no end)
+    const unsigned long long* src_tick; // the sources' start ticks (duplicates reduced on the host)
+    double tpc;                         // ticks per unit of edge weight
+    int32_t tpe;                        // ticks per epoch, >= 1
+    int32_t n_epochs;                   // epochs in the table, 1 .. 2^24
+    int32_t w64;                        // words per node
+};
+
+// Drive masks (mrtx_horizon_mask, DESIGN.md sections 3.19 and 4.22): HorizonWindowsC's inputs, the joint predicate kept as bits.
+// A struct of its own, so that horizon_windows_kernel's arguments stay as they were.
+struct HorizonMaskC {
+    IllumC g;               // the point list (g.rows points), as in HorizonC
+    const float* horizon;   // n_points x n_az float32 elevations (degrees)
+    const float* lights_a;  // 8 floats per epoch, as IllumSeriesC's
+    const float* lights_b;  // the same, or null: the bit is ok_a alone
+    unsigned long long* out;    // n_points x (m + 63) / 64 words, point-major
+    float min_a, min_b;     // ok = f >= min
+    int32_t az_log2;        // log2(n_az)
+    int32_t m;              // epochs
+};
+
 // Terrain relief (mrtx_relief, DESIGN.md sections 3.14 and 4.15; kernels in mrtx_relief.hip).  A window of the DEM's texel
 // lattice as in TraverseC, never wrapped; the footprint of a node is the (2 ri + 1) x (2 rj + 1) lattice nodes around it, read
 // straight from the DEM (rows outside [0, dem_h) make the node NaN, columns wrap modulo dem_w).

@@ -5,6 +5,7 @@
 //   horizon_kernel, horizon_raised_kernel   terrain horizon profiles, from the ground or from a mast (3.8, 3.15)
 //   horizon_sun_kernel                      the Sun's visible fraction per epoch against a horizon, and its statistics (3.8)
 //   horizon_windows_kernel                  joint Sun / Earth windows (3.15)
+//   horizon_mask_kernel                     the joint predicate as bits: drive masks (3.19)
 //   power_budget_kernel                     energy-storage need and state of charge (3.17)
 //   occultation_kernel                      the Earth's occultation of the Sun (3.18)
 //   thermal_kernel                          regolith temperatures and subsurface columns (3.9, 3.11, 3.16, 3.18)
@@ -439,6 +440,35 @@ __global__ void __launch_bounds__(64) horizon_windows_kernel(const FrameC f, con
         float4* const o = reinterpret_cast<float4*>(q.out) + 2 * (int64_t)pt;
         o[0] = make_float4((float)((double)n_a / md), (float)no_a.best, (float)((double)n_b / md), (float)no_b.best);
         o[1] = make_float4((float)((double)n_ab / md), (float)ab.best, (float)ab.first, (float)no_ab.best);
+    }
+}
+
+// Drive masks (DESIGN.md sections 3.19 and 4.22): horizon_windows_kernel's walk -- one wave per point, the epochs 64 at a time,
+// the vertex and frame once, the horizon row in L1 -- with the joint predicate kept, not reduced: the chunk's ballot of
+// ok_a && ok_b is the chunk's word (bit = lane = epoch & 63; the lanes past the last epoch vote 0), stored by lane 0.  Without a
+// second table the bit is ok_a.  Nothing is carried from chunk to chunk; no atomics, no LDS.
+template <bool WIDE>
+__global__ void __launch_bounds__(64) horizon_mask_kernel(const FrameC f, const HorizonMaskC q) {
+    const int lane = threadIdx.x;
+    const int pt = (int)blockIdx.x;
+    const int n_az = 1 << q.az_log2;
+    Vertex v;
+    (void)illum_vertex<false, WIDE>(f, q.g, pt, pt, v, nullptr);
+    const PointFrame p = point_frame(f, q.g, pt, pt, v);
+    const float* const hz = q.horizon + ((int64_t)pt << q.az_log2);
+    const float4* const la4 = reinterpret_cast<const float4*>(q.lights_a);
+    const float4* const lb4 = reinterpret_cast<const float4*>(q.lights_b);
+    unsigned long long* const row = q.out + (int64_t)pt * ((q.m + 63) >> 6);
+    for (int k0 = 0; k0 < q.m; k0 += 64) {
+        const int k = k0 + lane;
+        bool ok = false;
+        if (k < q.m) {
+            float la, lb, lc;
+            ok = disc_fraction(la4[2 * (int64_t)k], p, hz, n_az, la, lb, lc) >= q.min_a;
+            if (lb4) ok = (disc_fraction(lb4[2 * (int64_t)k], p, hz, n_az, la, lb, lc) >= q.min_b) && ok;
+        }
+        const unsigned long long word = __ballot(ok);
+        if (lane == 0) row[k0 >> 6] = word;
     }
 }
 
@@ -1138,6 +1168,17 @@ hipError_t mrtx_launch_horizon_windows(const FrameC& f, HorizonWindowsC q, hipSt
     const dim3 grid((unsigned)q.g.rows), block(64);
     if (f.dem_wide) hipLaunchKernelGGL((mrtx::horizon_windows_kernel<true>), grid, block, 0, st, f, q);
     else hipLaunchKernelGGL((mrtx::horizon_windows_kernel<false>), grid, block, 0, st, f, q);
+    return hipGetLastError();
+}
+
+// Drive masks (horizon_mask_kernel): one wave per point.
+hipError_t mrtx_launch_horizon_mask(const FrameC& f, HorizonMaskC q, hipStream_t st) {
+    if (q.g.rows < 1 || q.az_log2 < 2 || q.az_log2 > 12 || q.m < 1 || q.m > (1 << 24) || !q.g.points || !q.horizon ||
+        !q.lights_a || !q.out)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)q.g.rows), block(64);
+    if (f.dem_wide) hipLaunchKernelGGL((mrtx::horizon_mask_kernel<true>), grid, block, 0, st, f, q);
+    else hipLaunchKernelGGL((mrtx::horizon_mask_kernel<false>), grid, block, 0, st, f, q);
     return hipGetLastError();
 }
 

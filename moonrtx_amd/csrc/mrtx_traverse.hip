@@ -9,6 +9,8 @@
 //                          whose shared edge or corner changed flagged for the next launch
 //   traverse_pred_kernel   one lane per node: the predecessor code
 //   traverse_heights_kernel  one lane per node: its D (mrtx_traverse_heights, for routes)
+// and beside them the timed traverse (mrtx_traverse_timed, sections 3.19 and 4.22), the same scheme over uint64 arrival ticks:
+//   timed_init_kernel, timed_seed_kernel, timed_relax_kernel, timed_pred_kernel, timed_source_pred_kernel
 // Memory rule: correctness never depends on seeing, within a launch, what another workgroup of that launch wrote.  The halo
 // loads and the stores of d that another workgroup may read in the same launch are relaxed agent-scope 64-bit atomics (no torn
 // double); a stale read only costs another launch.  Only kernel boundaries order anything.
@@ -273,6 +275,306 @@ __global__ void __launch_bounds__(256) traverse_heights_kernel(const TraverseC q
         out[n] = node_D(q, n / q.cols, n % q.cols);
 }
 
+// ---- Timed traverses (mrtx_traverse_timed, DESIGN.md sections 3.19 and 4.22) ------------------------------------------------
+// Arrival ticks in place of costs: A[v] = min(src[v], min_u g_uv(A[u])) with g_uv(a) = start(u, v, a) + q, q the edge's
+// duration in ticks and start the first tick >= a from which the q ticks of the drive lie in epochs available at both ends.
+// Waiting is free, so g_uv is non-decreasing and g_uv(a) >= a + q: the tile scheme and the memory rule above carry over, every
+// store strictly lowers a uint64, and the fixed point does not depend on the order of the relaxations.
+constexpr unsigned long long kNever = ~0ull;     // unreachable
+constexpr uint32_t kNoDrive = 0u;                 // the duration sentinel: a driven edge lasts >= 1 tick
+
+// q of an edge of weight w: x = (double)w * ticks_per_cost (one product, never contracted); 1 if x <= 1, else ceil(x); not
+// driven if w is infinite or x > 2^31
+__device__ __forceinline__ uint32_t edge_ticks(float w, double tpc) {
+    if (w == __builtin_huge_valf()) return kNoDrive;
+    const double x = (double)w * tpc;
+    if (!(x <= 2147483648.0)) return kNoDrive;
+    return x <= 1.0 ? 1u : (uint32_t)ceil(x);
+}
+
+// word wd of the epochs available at both nodes; the bits from epoch n_epochs on are 0 (the table ends)
+__device__ __forceinline__ unsigned long long both_word(const TraverseTimedC& q, const unsigned long long* ru,
+                                                        const unsigned long long* rv, int wd) {
+    unsigned long long w = ru[wd] & rv[wd];
+    if (wd == q.w64 - 1 && (q.n_epochs & 63)) w &= (1ull << (q.n_epochs & 63)) - 1ull;
+    return w;
+}
+
+// t / d: ticks below 2^32 (every table of up to 2^32 ticks) divide in 32 bits
+__device__ __forceinline__ unsigned long long div_ticks(unsigned long long t, uint32_t d) {
+    return (t >> 32) ? t / d : (unsigned long long)((uint32_t)t / d);
+}
+
+// g_uv(a) for nodes nu, nv and a duration dq >= 1, or kNever.  The drive starts in the first available epoch e0 at or after
+// a's; it fits if the run of available epochs from e0 reaches the epoch of its last tick.  If not, no later tick of that run
+// fits either (the last tick only moves on), so the search goes on behind the first unavailable epoch.  The scan for an
+// available epoch stops at word w64, the scan for an unavailable one at the word of the drive's last tick.
+__device__ __forceinline__ unsigned long long timed_arrive(const TraverseTimedC& q, uint32_t nu, uint32_t nv,
+                                                            unsigned long long a, uint32_t dq) {
+    const unsigned long long* const ru = q.avail + (uint64_t)nu * (uint64_t)q.w64;
+    const unsigned long long* const rv = q.avail + (uint64_t)nv * (uint64_t)q.w64;
+    const uint32_t tpe = (uint32_t)q.tpe;
+    unsigned long long t = a;
+    for (;;) {
+        const unsigned long long ea = div_ticks(t, tpe);
+        if (ea >= (unsigned long long)q.n_epochs) return kNever;
+        int e0 = (int)ea;
+        // the first available epoch at or after e0 (ctz on the word)
+        int wd = e0 >> 6;
+        unsigned long long w = both_word(q, ru, rv, wd) & (~0ull << (e0 & 63));
+        while (!w) {
+            if (++wd >= q.w64) return kNever;
+            w = both_word(q, ru, rv, wd);
+        }
+        const int e1 = (wd << 6) + (int)__builtin_ctzll(w);
+        if (e1 > e0) { t = (unsigned long long)e1 * tpe; e0 = e1; }
+        // the drive's last tick must lie inside the table: if it does not, no later start does either
+        const unsigned long long el = div_ticks(t + dq - 1ull, tpe);
+        if (el >= (unsigned long long)q.n_epochs) return kNever;
+        const int last = (int)el;
+        // the first unavailable epoch in e0 .. last (ctz on the complement), if any
+        w = ~both_word(q, ru, rv, wd) & (~0ull << (e0 & 63));
+        int z = -1;
+        for (;;) {
+            if (w) {
+                const int c = (wd << 6) + (int)__builtin_ctzll(w);
+                if (c <= last) z = c;
+                break;
+            }
+            if (++wd > (last >> 6)) break;
+            w = ~both_word(q, ru, rv, wd);
+        }
+        if (z < 0) return t + dq;
+        t = ((unsigned long long)z + 1ull) * tpe;
+    }
+}
+
+__device__ __forceinline__ unsigned long long load_a(const unsigned long long* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void __launch_bounds__(256) timed_init_kernel(const TraverseTimedC q) {
+    const TraverseC& c = q.t;
+    const int64_t n_nodes = (int64_t)c.rows * c.cols;
+    unsigned long long bad = 0;
+    for (int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < n_nodes; n += (int64_t)gridDim.x * blockDim.x) {
+        q.arr[n] = kNever;
+        if (c.pen && !penalty_ok(c.pen[n])) bad++;
+    }
+    if (bad) atomicAdd(&c.visits[1], bad);
+}
+
+// one lane per source: its start tick, and the 3 x 3 tiles around its own
+__global__ void __launch_bounds__(64) timed_seed_kernel(const TraverseTimedC q) {
+    const TraverseC& c = q.t;
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= c.n_src) return;
+    const int64_t n = c.src_node[s];
+    q.arr[n] = q.src_tick[s];
+    const int ty = (int)(n / c.cols) / c.tile, tx = (int)(n % c.cols) / c.tile;
+    for (int a = -1; a <= 1; a++)
+        for (int b = -1; b <= 1; b++) {
+            int y = ty + a, x = tx + b;
+            if (y < 0 || y >= c.tiles_y) continue;
+            if (x < 0 || x >= c.tiles_x) {
+                if (!c.wrap) continue;
+                x = x < 0 ? x + c.tiles_x : x - c.tiles_x;
+            }
+            __hip_atomic_store(&c.flag_in[(int64_t)y * c.tiles_x + x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+}
+
+// one incoming edge of v: the arrival over it if that lowers `best`.  The test au + dq < best needs LDS only; the
+// availability words are read (from global memory) only behind it.
+__device__ __forceinline__ unsigned long long timed_try(const TraverseTimedC& q, unsigned long long best, unsigned long long au,
+                                                         uint32_t dq, uint32_t nu, uint32_t nv) {
+    if (dq == kNoDrive || au == kNever || au + dq >= best) return best;
+    const unsigned long long g = q.avail ? timed_arrive(q, nu, nv, au, dq) : au + dq;
+    return g < best ? g : best;
+}
+
+template <int TS>
+__global__ void __launch_bounds__(64) timed_relax_kernel(const TraverseTimedC q) {
+    constexpr int HP = TS + 2;      // pitch of the staged D, P and node indices: the tile and its halo
+    constexpr int DP = TS + 3;      // pitch of the staged arrivals (odd in 8-byte words: fewer bank conflicts down a column)
+    constexpr int WP = TS + 1;      // pitch of the durations (odd: a column's lanes hit distinct banks)
+    __shared__ unsigned long long sa[HP * DP];
+    __shared__ float sD[HP * HP], sP[HP * HP];
+    __shared__ uint32_t sn[HP * HP];
+    __shared__ uint32_t sq[8 * TS * WP];
+    __shared__ uint32_t s_mask;
+
+    const TraverseC& c = q.t;
+    const int64_t t = blockIdx.x;
+    if (c.flag_in[t] == 0u) return;          // not active in this launch (wave-uniform)
+    const int lane = threadIdx.x;
+    if (lane == 0) {
+        c.flag_in[t] = 0u;                   // only this workgroup touches flag_in[t] in this launch
+        s_mask = 0u;
+        atomicAdd(&c.visits[0], 1ull);
+    }
+    const int ty = (int)(t / c.tiles_x), tx = (int)(t % c.tiles_x);
+    const int64_t i0 = (int64_t)ty * TS, j0 = (int64_t)tx * TS;
+    const int th = (int)min((int64_t)TS, c.rows - i0), tw = (int)min((int64_t)TS, c.cols - j0);
+
+    // stage A, D, P and the node index of the tile and its halo
+    for (int p = lane; p < (th + 2) * (tw + 2); p += 64) {
+        const int a = p / (tw + 2) - 1, b = p % (tw + 2) - 1;
+        const int64_t gi = i0 + a;
+        int64_t gj = j0 + b;
+        unsigned long long av = kNever;
+        float Dv = 0.0f, Pv = 1.0f;
+        uint32_t nn = 0u;
+        if (in_window(c, gi, gj)) {
+            const int64_t n = gi * c.cols + gj;
+            av = load_a(&q.arr[n]);
+            Dv = node_D(c, gi, gj);
+            if (c.pen) Pv = c.pen[n];
+            nn = (uint32_t)n;
+        }
+        sa[(a + 1) * DP + (b + 1)] = av;
+        sD[(a + 1) * HP + (b + 1)] = Dv;
+        sP[(a + 1) * HP + (b + 1)] = Pv;
+        sn[(a + 1) * HP + (b + 1)] = nn;
+    }
+    __syncthreads();
+    // the tile's incoming durations: sq[k][a][b] = q(u -> v), u = v + step k, kNoDrive where u is no node or not driven
+    for (int p = lane; p < th * tw; p += 64) {
+        const int a = p / tw, b = p % tw;
+        const int vi = (a + 1) * HP + (b + 1);
+        for (int k = 0; k < 8; k++) {
+            const int64_t gi = i0 + a + kDi[k];
+            int64_t gj = j0 + b + kDj[k];
+            uint32_t dq = kNoDrive;
+            if (in_window(c, gi, gj)) {
+                const int ui = (a + 1 + kDi[k]) * HP + (b + 1 + kDj[k]);
+                dq = edge_ticks(edge_w(c, sD[ui], sD[vi], sP[ui], sP[vi], edge_len(c, i0 + a, kDi[k], kDj[k])), q.tpc);
+            }
+            sq[k * TS * WP + a * WP + b] = dq;
+        }
+    }
+    __syncthreads();
+
+    // sweeps as in traverse_relax_kernel: lanes 0-31 down then right, lanes 32-63 up then left; a lowered arrival is an LDS
+    // atomic min on the uint64, so the two halves never lose each other's update where they meet
+    const int half = lane >> 5, x = lane & 31;
+    for (;;) {
+        int ch = 0;
+        for (int s = 0; s < th; s++) {
+            if (x < tw) {
+                const int a = half ? th - 1 - s : s, da = half ? 1 : -1;
+                const int kc = half ? 4 : 0, kl = half ? 5 : 7, kr = half ? 3 : 1;
+                unsigned long long* v = &sa[(a + 1) * DP + (x + 1)];
+                const unsigned long long* u = &sa[(a + 1 + da) * DP + (x + 1)];
+                const uint32_t* nu = &sn[(a + 1 + da) * HP + (x + 1)];
+                const uint32_t nv = sn[(a + 1) * HP + (x + 1)];
+                const int wi = a * WP + x;
+                const unsigned long long av = *v;
+                unsigned long long g = timed_try(q, av, u[0], sq[kc * TS * WP + wi], nu[0], nv);
+                g = timed_try(q, g, u[-1], sq[kl * TS * WP + wi], nu[-1], nv);
+                g = timed_try(q, g, u[1], sq[kr * TS * WP + wi], nu[1], nv);
+                if (g < av) {
+                    atomicMin(v, g);
+                    ch = 1;
+                }
+            }
+            __syncthreads();
+        }
+        for (int s = 0; s < tw; s++) {
+            if (x < th) {
+                const int b = half ? tw - 1 - s : s, db = half ? 1 : -1;
+                const int kc = half ? 2 : 6, ku = half ? 1 : 7, kd = half ? 3 : 5;
+                unsigned long long* v = &sa[(x + 1) * DP + (b + 1)];
+                const unsigned long long* u = v + db;
+                const uint32_t* nu = &sn[(x + 1) * HP + (b + 1 + db)];
+                const uint32_t nv = sn[(x + 1) * HP + (b + 1)];
+                const int wi = x * WP + b;
+                const unsigned long long av = *v;
+                unsigned long long g = timed_try(q, av, u[0], sq[kc * TS * WP + wi], nu[0], nv);
+                g = timed_try(q, g, u[-DP], sq[ku * TS * WP + wi], nu[-HP], nv);
+                g = timed_try(q, g, u[DP], sq[kd * TS * WP + wi], nu[HP], nv);
+                if (g < av) {
+                    atomicMin(v, g);
+                    ch = 1;
+                }
+            }
+            __syncthreads();
+        }
+        if (!__syncthreads_or(ch)) break;
+    }
+
+    // write back what was lowered; note which neighbour tiles see a changed node in their halo (bit k = direction k)
+    uint32_t mask = 0u;
+    bool lowered = false;
+    for (int p = lane; p < th * tw; p += 64) {
+        const int a = p / tw, b = p % tw;
+        const int64_t n = (i0 + a) * c.cols + (j0 + b);
+        const unsigned long long nv = sa[(a + 1) * DP + (b + 1)];
+        if (nv < q.arr[n]) {                 // only this workgroup writes its own nodes
+            __hip_atomic_store(&q.arr[n], nv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            lowered = true;
+            const bool n_ = a == 0, s_ = a == th - 1, w_ = b == 0, e_ = b == tw - 1;
+            mask |= (n_ ? 1u : 0u) | (n_ && e_ ? 2u : 0u) | (e_ ? 4u : 0u) | (s_ && e_ ? 8u : 0u) | (s_ ? 16u : 0u) |
+                    (s_ && w_ ? 32u : 0u) | (w_ ? 64u : 0u) | (n_ && w_ ? 128u : 0u);
+        }
+    }
+    if (mask) atomicOr(&s_mask, mask);
+    const int any = __syncthreads_or(lowered ? 1 : 0);
+    if (lane == 0 && any) {
+        atomicAdd(&c.changed[c.slot], 1u);
+        const uint32_t m = s_mask;
+        for (int k = 0; k < 8; k++) {
+            if (!(m & (1u << k))) continue;
+            const int y = ty + kDi[k];
+            int xx = tx + kDj[k];
+            if (y < 0 || y >= c.tiles_y) continue;
+            if (xx < 0 || xx >= c.tiles_x) {
+                if (!c.wrap) continue;
+                xx = xx < 0 ? xx + c.tiles_x : xx - c.tiles_x;
+            }
+            __hip_atomic_store(&c.flag_out[(int64_t)y * c.tiles_x + xx], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// one lane per node: 255 unreachable; else the first direction k whose neighbour u has A[u] < A[v], a driven edge and
+// g_uv(A[u]) == A[v]; 254 if none (the sources get code 8 from timed_source_pred_kernel afterwards)
+__global__ void __launch_bounds__(256) timed_pred_kernel(const TraverseTimedC q) {
+    const TraverseC& c = q.t;
+    const int64_t n_nodes = (int64_t)c.rows * c.cols;
+    for (int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < n_nodes; n += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = n / c.cols, j = n % c.cols;
+        const unsigned long long av = q.arr[n];
+        uint8_t code = 255;
+        if (av != kNever) {
+            code = 254;
+            const float Dv = node_D(c, i, j), Pv = c.pen ? c.pen[n] : 1.0f;
+            for (int k = 0; k < 8; k++) {
+                const int64_t ui = i + kDi[k];
+                int64_t uj = j + kDj[k];
+                if (!in_window(c, ui, uj)) continue;
+                const int64_t u = ui * c.cols + uj;
+                const unsigned long long au = q.arr[u];
+                if (!(au < av)) continue;
+                const uint32_t dq = edge_ticks(edge_w(c, node_D(c, ui, uj), Dv, c.pen ? c.pen[u] : 1.0f, Pv,
+                                                      edge_len(c, i, kDi[k], kDj[k])), q.tpc);
+                if (dq == kNoDrive || au + dq > av) continue;
+                const unsigned long long g = q.avail ? timed_arrive(q, (uint32_t)u, (uint32_t)n, au, dq) : au + dq;
+                if (g == av) { code = (uint8_t)k; break; }
+            }
+        }
+        c.pred[n] = code;
+    }
+}
+
+__global__ void __launch_bounds__(64) timed_source_pred_kernel(const TraverseTimedC q) {
+    const TraverseC& c = q.t;
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= c.n_src) return;
+    const int64_t n = c.src_node[s];
+    if (q.arr[n] == q.src_tick[s]) c.pred[n] = 8;
+}
+
 }  // namespace mrtx_tr
 
 static unsigned traverse_grid(int64_t n, int per_block) {
@@ -316,5 +618,43 @@ hipError_t mrtx_launch_traverse_heights(const TraverseC& q, float* out, hipStrea
     if (q.rows < 1 || q.cols < 1 || !q.dem || !out) return hipErrorInvalidValue;
     const int64_t n = (int64_t)q.rows * q.cols;
     hipLaunchKernelGGL(mrtx_tr::traverse_heights_kernel, dim3(traverse_grid(n, 256)), dim3(256), 0, st, q, out);
+    return hipGetLastError();
+}
+
+// ---- Timed traverses: the same three steps over TraverseTimedC
+static bool timed_ok(const TraverseTimedC& q) {
+    return q.arr && q.src_tick && q.tpe >= 1 && q.tpc > 0.0 &&
+           (!q.avail || (q.n_epochs >= 1 && q.n_epochs <= (1 << 24) && q.w64 == (q.n_epochs + 63) / 64));
+}
+
+hipError_t mrtx_launch_timed_init(const TraverseTimedC& q, hipStream_t st) {
+    const TraverseC& c = q.t;
+    if (c.rows < 1 || c.cols < 1 || c.n_src < 1 || !c.visits || !c.flag_in || !c.src_node || !timed_ok(q)) return hipErrorInvalidValue;
+    const int64_t n = (int64_t)c.rows * c.cols;
+    hipLaunchKernelGGL(mrtx_tr::timed_init_kernel, dim3(traverse_grid(n, 256)), dim3(256), 0, st, q);
+    hipLaunchKernelGGL(mrtx_tr::timed_seed_kernel, dim3((unsigned)((c.n_src + 63) / 64)), dim3(64), 0, st, q);
+    return hipGetLastError();
+}
+
+hipError_t mrtx_launch_timed_relax(const TraverseTimedC& q, hipStream_t st) {
+    const TraverseC& c = q.t;
+    const int64_t tiles = (int64_t)c.tiles_x * c.tiles_y;
+    if (tiles < 1 || tiles > 0xFFFFFFFFll || !c.flag_in || !c.flag_out || !c.changed || !c.len || !timed_ok(q)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)tiles), block(64);
+    switch (c.tile) {
+        case 8: hipLaunchKernelGGL(mrtx_tr::timed_relax_kernel<8>, grid, block, 0, st, q); break;
+        case 16: hipLaunchKernelGGL(mrtx_tr::timed_relax_kernel<16>, grid, block, 0, st, q); break;
+        case 32: hipLaunchKernelGGL(mrtx_tr::timed_relax_kernel<32>, grid, block, 0, st, q); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t mrtx_launch_timed_pred(const TraverseTimedC& q, hipStream_t st) {
+    const TraverseC& c = q.t;
+    if (c.rows < 1 || c.cols < 1 || !c.pred || !c.len || !c.src_node || !timed_ok(q)) return hipErrorInvalidValue;
+    const int64_t n = (int64_t)c.rows * c.cols;
+    hipLaunchKernelGGL(mrtx_tr::timed_pred_kernel, dim3(traverse_grid(n, 256)), dim3(256), 0, st, q);
+    hipLaunchKernelGGL(mrtx_tr::timed_source_pred_kernel, dim3((unsigned)((c.n_src + 63) / 64)), dim3(64), 0, st, q);
     return hipGetLastError();
 }

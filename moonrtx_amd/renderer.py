@@ -426,6 +426,38 @@ class MoonRT:
             self._add_stats(stats, st)
         return res
 
+    def horizon_mask(self, lat_deg, lon_deg, horizon, epochs_a, epochs_b=None, min_a=0.5, min_b=1.0, n_az=None, out=None,
+                     stats=None, chunk_bytes=256 << 20, out_offset=0):
+        """horizon_windows' joint predicate kept as bits (mrtx_horizon_mask): an (N, W64) uint64
+        array, W64 = (m + 63) // 64, in which bit k & 63 of word k >> 6 of row p says that at epoch k point p has
+        f_a >= min_a and f_b >= min_b (f = horizon_sun's fractions; equality counts as met).  epochs_b = None: ok_a alone.
+        The bits past epoch m - 1 are 0.  out = a DeviceBuffer: the words are written there from byte out_offset (a multiple
+        of 8) on, point-major, and `out` is returned.  `horizon` as for horizon_sun; calls hold at most chunk_bytes of
+        horizons and output.  moonrtx_amd.traverse.unpack_mask turns rows into booleans."""
+        la, lo = self._points(lat_deg, lon_deg)
+        ea = self._epochs(epochs_a)
+        eb = None if epochs_b is None else self._epochs(epochs_b)
+        if eb is not None and ea.shape != eb.shape:
+            raise ValueError("epochs_a and epochs_b must hold the same number of epochs")
+        m = ea.shape[0]
+        w64 = (m + 63) // 64
+        n_az, hz_at = self._horizon_arg(horizon, la.size, n_az)
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        out_offset = int(out_offset)
+        if out is not None and (out_offset < 0 or out_offset % 8 or out.nbytes < out_offset + la.size * w64 * 8):
+            raise ValueError("the device buffer is smaller than N x W64 uint64 from out_offset (a multiple of 8) on")
+        res = np.empty((la.size, w64), np.uint64) if out is None else None
+        for a, b in self._chunks(la.size, max(int(n_az), 0) + 2 * max(w64, 1), chunk_bytes):
+            st = MrtxStats()
+            dh, hh = hz_at(a)
+            dev = None if out is None else out.ptr + out_offset + a * w64 * 8
+            hp = None if out is not None else res[a:].ctypes.data
+            self._check(self._lib.mrtx_horizon_mask(self._ctx, pts[a:].ctypes.data, b - a, n_az, dh, hh, ea.ctypes.data,
+                                                    None if eb is None else eb.ctypes.data, m, float(min_a), float(min_b),
+                                                    dev, hp, C.byref(st)), "mrtx_horizon_mask")
+            self._add_stats(stats, st)
+        return out if out is not None else res
+
     POWER_COLUMNS = ("generated", "net", "storage_need", "drawdown_first", "drawdown_last", "min_charge", "epochs_unmet",
                      "energy_unmet")
     PANELS = {"track": _lib.PANEL_TRACK, "fixed": _lib.PANEL_FIXED, "azimuth": _lib.PANEL_AZIMUTH}
@@ -900,6 +932,91 @@ class MoonRT:
         lat, lon, _ = self.traverse_nodes(w)
         D = self.traverse_heights(w) if heights else None
         return tv.TraverseField(cost, pred, w, lengths, radius_m, lat, lon, D=D)
+
+    def traverse_timed(self, window, sources=None, nodes=None, start_tick=None, avail=None, n_epochs=None, ticks_per_epoch=3600,
+                       ticks_per_cost=5.0, penalty=None, max_slope_deg=20.0, climb_cost=8.0, descent_cost=0.0,
+                       radius_m=1737400.0, stats=None):
+        """The earliest-arrival field over a traverse window (mrtx_traverse_timed): time in integer
+        ticks, an edge of `traverse`'s weight w lasting ceil(w * ticks_per_cost) ticks (at least 1), epoch e covering the
+        ticks [e, e + 1) * ticks_per_epoch, and an edge driven only while every epoch it touches is available at both of
+        its ends; waiting at a node is free.  window, sources / nodes, penalty and the effort model as for `traverse`;
+        start_tick = the sources' start ticks (default 0).  avail: None (always drivable), an (rows, cols, W64) or
+        (rows * cols, W64) uint64 array in horizon_mask's layout, or a DeviceBuffer holding one (moonrtx_amd.traverse.
+        drive_mask); n_epochs = the epochs it covers (default W64 * 64 for an array, required for a buffer).  Returns a
+        moonrtx_amd.traverse.TimedField; `stats`, if a dict, receives kernel_ms, launches and tile_visits."""
+        from . import traverse as tv
+        w = tv.window_dict(window)
+        H, W = self._dem_hw()
+        if (sources is None) == (nodes is None):
+            raise ValueError("give exactly one of sources ((lat, lon) degrees) and nodes ((i, j) indices)")
+        if nodes is not None:
+            ij = np.asarray(nodes)
+            if not np.issubdtype(ij.dtype, np.integer):
+                raise ValueError("nodes must be integer (i, j) indices")
+            ij = np.ascontiguousarray(ij.reshape(-1, 2) if ij.ndim == 1 else ij, np.int32)
+        else:
+            ll = np.asarray(sources, np.float64)
+            ll = ll.reshape(1, -1) if ll.ndim == 1 else ll
+            if ll.ndim != 2 or ll.shape[1] != 2:
+                raise ValueError("sources must be (N, 2) (lat, lon) degrees")
+            ij = self.snap_to_nodes(w, ll[:, 0], ll[:, 1])
+        if ij.ndim != 2 or ij.shape[1] != 2:
+            raise ValueError("nodes must be (N, 2) (i, j) indices")
+        tick0 = None if start_tick is None else np.ascontiguousarray(np.broadcast_to(np.asarray(start_tick, np.uint64),
+                                                                                      (ij.shape[0],)))
+        max_grade = tv.max_slope_grade(max_slope_deg)
+        t = self._traverse_window(w, radius_m, max_grade, climb_cost, descent_cost)
+        lengths = np.empty((max(w["rows"], 1), 3), np.float32)
+        rc = self._lib.mrtx_traverse_lengths(C.byref(t), H, W, lengths.ctypes.data)
+        if rc != 0:
+            raise MoonRTError(f"mrtx_traverse_lengths failed ({rc}): bad window or lengths")
+        N = w["rows"] * w["cols"]
+        dev_pen = host_pen = pen = None
+        if isinstance(penalty, DeviceBuffer):
+            if penalty.nbytes < 4 * N:
+                raise ValueError("the penalty buffer is smaller than rows x cols float32")
+            dev_pen = penalty.ptr
+        elif penalty is not None:
+            pen = np.ascontiguousarray(penalty, np.float32)
+            if pen.shape != (w["rows"], w["cols"]):
+                raise ValueError(f"penalty must be a (rows, cols) = {(w['rows'], w['cols'])} map")
+            host_pen = pen.ctypes.data
+        dev_av = host_av = av = None
+        if isinstance(avail, DeviceBuffer):
+            if n_epochs is None:
+                raise ValueError("n_epochs is required with a device buffer")
+            if avail.nbytes < 8 * N * tv.mask_words(n_epochs):
+                raise ValueError("the availability buffer is smaller than rows x cols x W64 uint64")
+            dev_av = avail.ptr
+        elif avail is not None:
+            av = np.ascontiguousarray(avail, np.uint64)
+            if av.ndim not in (2, 3) or av.size % max(N, 1) or av.shape[:-1] not in ((N,), (w["rows"], w["cols"])):
+                raise ValueError("avail must be a (rows, cols, W64) or (rows * cols, W64) uint64 array")
+            n_epochs = av.shape[-1] * 64 if n_epochs is None else int(n_epochs)
+            if av.shape[-1] != tv.mask_words(n_epochs):
+                raise ValueError(f"{n_epochs} epochs take {tv.mask_words(n_epochs)} words per node (got {av.shape[-1]})")
+            av = av.reshape(w["rows"], w["cols"], -1)
+            host_av = av.ctypes.data
+        tt = _lib.MrtxTraverseTimed(float(ticks_per_cost), int(ticks_per_epoch), 0 if avail is None else int(n_epochs), 0)
+        arrival = np.empty((w["rows"], w["cols"]), np.uint64)
+        pred = np.empty((w["rows"], w["cols"]), np.uint8)
+        visits = C.c_uint64()
+        st = MrtxStats()
+        self._check(self._lib.mrtx_traverse_timed(self._ctx, C.byref(t), C.byref(tt), ij.ctypes.data,
+                                                  None if tick0 is None else tick0.ctypes.data, ij.shape[0], dev_pen, host_pen,
+                                                  dev_av, host_av, None, arrival.ctypes.data, None, pred.ctypes.data,
+                                                  C.byref(visits), C.byref(st)), "mrtx_traverse_timed")
+        if isinstance(stats, dict):
+            stats["kernel_ms"] = stats.get("kernel_ms", 0) + st.kernel_ms
+            stats["launches"] = stats.get("launches", 0) + st.launches
+            stats["tile_visits"] = stats.get("tile_visits", 0) + int(visits.value)
+        lat, lon, _ = self.traverse_nodes(w)
+        if dev_pen is not None:
+            pen = penalty.download(np.float32, (w["rows"], w["cols"]))
+        return tv.TimedField(arrival, pred, w, lengths, radius_m, lat, lon, D=self.traverse_heights(w),
+                             ticks_per_cost=ticks_per_cost, ticks_per_epoch=ticks_per_epoch,
+                             n_epochs=None if avail is None else n_epochs, max_grade=max_grade, climb_cost=climb_cost,
+                             descent_cost=descent_cost, penalty=pen, avail=av)
 
     @staticmethod
     def _traverse_window(w, radius_m=1737400.0, max_grade=1.0, climb_cost=0.0, descent_cost=0.0):
