@@ -230,8 +230,16 @@ int mrtx_unpack_all(mrtx_ctx* ctx, const void* const* dev_srcs, int32_t n);
  * float2 (D[r][c], D[r+1][c]), two-texel border (rows clamp, columns wrap) -- not the array that was uploaded.
  * MRTX_BUF_COLOR likewise: (h+1) x (w+4) elements of two RGBA8 texels (T[r][c], T[r+1][c]).  mrtx_bind_dem_device and
  * mrtx_bind_color_device read the caller's device array once; the caller may free it afterwards. */
-enum { MRTX_BUF_ACCUM = 0, MRTX_BUF_HITS = 1, MRTX_BUF_DEM = 2, MRTX_BUF_COLOR = 3 };
+/* MRTX_BUF_MIP, MRTX_BUF_MIP2 and MRTX_BUF_HMIP are the structures the marches skip with, built from the DEM by the first
+ * marching call for the march step in force (null and 0 bytes before that, and again after a new DEM): the max-mip in row
+ * pairs, (mip_h+2) x (mip_w+2) elements of float2 (m[i][j], m[i+1][j]); the medium max-mip, (m2_h+2) x (m2_w+2) floats;
+ * the horizon mip, hm_h x hm_w floats.  Read-only; the layouts are defined in DESIGN.md section 4.23. */
+enum { MRTX_BUF_ACCUM = 0, MRTX_BUF_HITS = 1, MRTX_BUF_DEM = 2, MRTX_BUF_COLOR = 3, MRTX_BUF_MIP = 4, MRTX_BUF_MIP2 = 5,
+       MRTX_BUF_HMIP = 6 };
 int mrtx_device_ptr(mrtx_ctx* ctx, int32_t which, void** out, uint64_t* bytes);
+/* out = { mip_shift, mip_h, mip_w, m2_shift, m2_h, m2_w, hm_shift, hm_h, hm_w }: cells of 2^shift texels, sizes without the
+ * borders.  All zero while nothing is built. */
+int mrtx_mip_info(mrtx_ctx* ctx, int32_t out[9]);
 
 /* ---- ingest kernels (data_loader.py:166-247, the step before set_displacement) ----------------
  * Device-side restatement of load_elevation_data: int16 LDEM units -> block mean (two-stage f32,

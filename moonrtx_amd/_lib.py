@@ -116,6 +116,7 @@ F_NO_CULL = 8
 F_NO_SORT = 16
 F_INWAVE_PATHS = 32
 BUF_ACCUM, BUF_HITS, BUF_DEM, BUF_COLOR = 0, 1, 2, 3
+BUF_MIP, BUF_MIP2, BUF_HMIP = 4, 5, 6           # the march's skip structures
 
 _D3 = C.POINTER(C.c_double)
 _VP = C.c_void_p
@@ -158,6 +159,7 @@ SIGNATURES = {
     "mrtx_unpack_shard": (C.c_int, [_VP, C.c_int32, _VP, _VP]),
     "mrtx_unpack_all": (C.c_int, [_VP, C.POINTER(_VP), C.c_int32]),
     "mrtx_device_ptr": (C.c_int, [_VP, C.c_int32, C.POINTER(_VP), C.POINTER(C.c_uint64)]),
+    "mrtx_mip_info": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
     "mrtx_dem_from_ldem": (C.c_int, [C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32, _VP,
                                      C.POINTER(C.c_float), C.c_char_p, C.c_int32]),
     "mrtx_synth_ldem": (C.c_int, [C.c_int32, _VP, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p, C.c_int32]),

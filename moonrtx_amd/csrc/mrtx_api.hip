@@ -2999,8 +2999,22 @@ int mrtx_device_ptr(mrtx_ctx* c, int32_t which, void** out, uint64_t* bytes) {
         case MRTX_BUF_HITS: *out = c->hits; if (bytes) *bytes = fb; break;
         case MRTX_BUF_DEM: *out = c->dem; if (bytes) *bytes = c->dem ? (uint64_t)(c->dem_h + 4) * (c->dem_w + 4) * MRTX_DEM_ELEM_BYTES : 0; break;
         case MRTX_BUF_COLOR: *out = c->color; if (bytes) *bytes = c->color ? ((uint64_t)(c->color_h + 1) * (c->color_w + 4) + 1) * 8 : 0; break;
+        // the march's skip structures (ensure_mip): null until the first marching call has built them for the step in force
+        case MRTX_BUF_MIP: *out = c->mip; if (bytes) *bytes = c->mip ? (uint64_t)(c->mip_h + 2) * (c->mip_w + 2) * 8 : 0; break;   // without the slack element
+        case MRTX_BUF_MIP2: *out = c->mip2; if (bytes) *bytes = c->mip2 ? (uint64_t)(c->m2_h + 2) * (c->m2_w + 2) * 4 : 0; break;
+        case MRTX_BUF_HMIP: *out = c->hmip; if (bytes) *bytes = c->hmip ? (uint64_t)c->hm_h * c->hm_w * 4 : 0; break;
         default: return fail(c, MRTX_E_INVALID, "unknown buffer id %d", which);
     }
+    return MRTX_OK;
+}
+
+int mrtx_mip_info(mrtx_ctx* c, int32_t out[9]) {
+    if (!c || !out) return MRTX_E_INVALID;
+    for (int i = 0; i < 9; i++) out[i] = 0;
+    if (!c->mip) return MRTX_OK;      // nothing built (yet, or since the last DEM upload)
+    out[0] = c->mip_shift; out[1] = c->mip_h; out[2] = c->mip_w;
+    if (c->mip2) { out[3] = c->m2_shift; out[4] = c->m2_h; out[5] = c->m2_w; }
+    if (c->hmip) { out[6] = c->hm_shift; out[7] = c->hm_h; out[8] = c->hm_w; }
     return MRTX_OK;
 }
 

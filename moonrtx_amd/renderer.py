@@ -116,15 +116,18 @@ class MoonRT:
     def upload_color(self, rgba):
         if rgba is None:
             self._check(self._lib.mrtx_upload_color(self._ctx, None, 0, 0), "mrtx_upload_color")
+            self._color_shape = None
             return
         a = np.ascontiguousarray(rgba, np.uint8)
         if a.ndim != 3 or a.shape[2] != 4:
             raise ValueError("colour texture must be (h, w, 4) uint8")
         self._check(self._lib.mrtx_upload_color(self._ctx, a.ctypes.data, a.shape[0], a.shape[1]), "mrtx_upload_color")
         self._keepalive.pop("color", None)
+        self._color_shape = (int(a.shape[0]), int(a.shape[1]))
 
     def bind_color(self, buf, h, w):
         self._check(self._lib.mrtx_bind_color_device(self._ctx, buf.ptr if buf else None, h, w), "mrtx_bind_color_device")
+        self._color_shape = (int(h), int(w)) if buf else None
 
     def upload_background(self, rgba):
         if rgba is None:
@@ -1176,6 +1179,45 @@ class MoonRT:
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self._lib.mrtx_device_ptr(self._ctx, which, C.byref(p), C.byref(n)), "mrtx_device_ptr")
         return p.value, n.value
+
+    MIP_INFO = ("mip_shift", "mip_h", "mip_w", "m2_shift", "m2_h", "m2_w", "hm_shift", "hm_h", "hm_w")
+
+    def mip_info(self):
+        """The shifts and sizes of the march's skip structures (mrtx_mip_info) as a dict of MIP_INFO; all zero while nothing is
+        built (before the first marching call, and again after a new DEM)."""
+        out = (C.c_int32 * 9)()
+        self._check(self._lib.mrtx_mip_info(self._ctx, out), "mrtx_mip_info")
+        return dict(zip(self.MIP_INFO, (int(v) for v in out)))
+
+    def read_structure(self, which):
+        """A device structure the marches read, downloaded in its documented shape, or None while it
+        does not exist: BUF_DEM (h+4, w+4, 2) float32, BUF_COLOR (h+1, w+4, 2) uint32, BUF_MIP (mip_h+2, mip_w+2, 2) float32,
+        BUF_MIP2 (m2_h+2, m2_w+2) float32, BUF_HMIP (hm_h, hm_w) float32."""
+        ptr, nbytes = self.device_ptr(which)
+        if not ptr:
+            return None
+        i = self.mip_info()
+        if which == _lib.BUF_DEM:
+            h, w = self._dem_hw()
+            dtype, shape = np.float32, (h + 4, w + 4, 2)
+        elif which == _lib.BUF_COLOR:
+            h, w = self._color_shape
+            dtype, shape = np.uint32, (h + 1, w + 4, 2)
+        elif which == _lib.BUF_MIP:
+            dtype, shape = np.float32, (i["mip_h"] + 2, i["mip_w"] + 2, 2)
+        elif which == _lib.BUF_MIP2:
+            dtype, shape = np.float32, (i["m2_h"] + 2, i["m2_w"] + 2)
+        elif which == _lib.BUF_HMIP:
+            dtype, shape = np.float32, (i["hm_h"], i["hm_w"])
+        else:
+            raise ValueError(f"buffer {which} has no documented layout to read")
+        out = np.empty(shape, dtype)
+        if out.nbytes > nbytes:
+            raise MoonRTError(f"buffer {which} holds {nbytes} bytes, its layout needs {out.nbytes}")
+        rc = self._lib.mrtx_dev_download(self.config()["device"], out.ctypes.data, ptr, out.nbytes)
+        if rc != 0:
+            raise MoonRTError(f"device download failed (code {rc})")
+        return out
 
 
 # ---- context-free device helpers ------------------------------------------------------------------
