@@ -68,13 +68,6 @@ hipError_t mrtx_launch_sight(const FrameC& f, SightC q, bool stats, hipStream_t 
 hipError_t mrtx_launch_thermal(const FrameC& f, const ThermalC& q, bool ext, hipStream_t st);
 hipError_t mrtx_launch_view_hits(const FrameC& f, const ViewC& q, bool stats, hipStream_t st);
 hipError_t mrtx_launch_scatter_flux(const ScatterC& q, hipStream_t st);
-hipError_t mrtx_launch_traverse_init(const TraverseC& q, hipStream_t st);
-hipError_t mrtx_launch_traverse_relax(const TraverseC& q, hipStream_t st);
-hipError_t mrtx_launch_traverse_pred(const TraverseC& q, hipStream_t st);
-hipError_t mrtx_launch_traverse_heights(const TraverseC& q, float* out, hipStream_t st);
-hipError_t mrtx_launch_timed_init(const TraverseTimedC& q, hipStream_t st);
-hipError_t mrtx_launch_timed_relax(const TraverseTimedC& q, hipStream_t st);
-hipError_t mrtx_launch_timed_pred(const TraverseTimedC& q, hipStream_t st);
 hipError_t mrtx_launch_horizon_mask(const FrameC& f, HorizonMaskC q, hipStream_t st);
 hipError_t mrtx_launch_relief(const ReliefC& q, int tile, hipStream_t st);
 hipError_t mrtx_launch_relief_share(const ShareC& q, hipStream_t st);
@@ -2009,8 +2002,161 @@ static int traverse_dev_buffers(mrtx_ctx* c, const MrtxTraverse* t, const void* 
 
 static bool traverse_penalty_ok(float p) { return (p >= 1e-3f && p <= 1e6f) || p == INFINITY; }
 
+// a host penalty table is refused at its first bad entry (a device table's bad entries are counted by the init kernel)
+static int traverse_host_penalty(mrtx_ctx* c, const float* host_penalty, size_t N) {
+    if (host_penalty)
+        for (size_t n = 0; n < N; n++)
+            if (!traverse_penalty_ok(host_penalty[n]))
+                return fail(c, MRTX_E_INVALID, "penalty %zu must be finite in [1e-3, 1e6] or +inf (got %g)", n, (double)host_penalty[n]);
+    return MRTX_OK;
+}
+
+// MOONRT_TRAVERSE_TILE: the tile edge, 8, 16 or 32 (the same field in every case)
+static int traverse_tile_edge(mrtx_ctx* c, int& TS) {
+    TS = 32;
+    if (const char* e = std::getenv("MOONRT_TRAVERSE_TILE")) {
+        TS = std::atoi(e);
+        if (TS != 8 && TS != 16 && TS != 32) return fail(c, MRTX_E_INVALID, "MOONRT_TRAVERSE_TILE must be 8, 16 or 32 (got %s)", e);
+    }
+    return MRTX_OK;
+}
+
+// The sources of a field with starts of type S: each inside the window and with a start that start_rule(k, s) accepts (it
+// fails with the field's own text), then sorted by node and duplicates reduced to their smallest start
+extern "C++" template <class S, class Rule>
+static int traverse_sources(mrtx_ctx* c, const MrtxTraverse* t, const int32_t* src_ij, const S* src_start, int32_t n_src,
+                            Rule start_rule, std::vector<int64_t>& sn, std::vector<S>& sc) {
+    if (n_src < 1 || !src_ij) return fail(c, MRTX_E_INVALID, "need n_src >= 1 sources (got %d)", n_src);
+    std::vector<std::pair<int64_t, S>> src((size_t)n_src);
+    for (int32_t k = 0; k < n_src; k++) {
+        const int32_t i = src_ij[2 * (size_t)k], j = src_ij[2 * (size_t)k + 1];
+        const S s = src_start ? src_start[k] : S(0);
+        if (i < 0 || i >= t->rows || j < 0 || j >= t->cols)
+            return fail(c, MRTX_E_INVALID, "source %d: node (%d, %d) lies outside the %d x %d window", k, i, j, t->rows, t->cols);
+        const int rc = start_rule(k, s);
+        if (rc != MRTX_OK) return rc;
+        src[(size_t)k] = {(int64_t)i * t->cols + j, s + S(0)};      // -0 made +0: the kernels order costs by their bits
+    }
+    std::sort(src.begin(), src.end());
+    for (const auto& e : src)
+        if (sn.empty() || sn.back() != e.first) { sn.push_back(e.first); sc.push_back(e.second); }
+    return MRTX_OK;
+}
+
+// the DEM and the window of a traverse block: all that mrtx_traverse_heights needs of it
+static void traverse_fill_window(const mrtx_ctx* c, const FrameC& f, const MrtxTraverse* t, TraverseC& g) {
+    g.dem = f.dem; g.dem_pitch = f.dem_pitch; g.dem_w = c->dem_w;
+    g.row0 = t->row0; g.col0 = t->col0; g.rows = t->rows; g.cols = t->cols; g.stride = t->stride; g.wrap = t->wrap;
+}
+
+// A field's block Q (TraverseC, or one that holds it) and its three launch steps
+static TraverseC& traverse_block(TraverseC& q) { return q; }
+static TraverseC& traverse_block(TraverseTimedC& q) { return q.t; }
+extern "C++" template <class Q>
+struct TraverseSteps {
+    hipError_t (*init)(const Q&, hipStream_t);
+    hipError_t (*relax)(const Q&, hipStream_t);
+    hipError_t (*pred)(const Q&, hipStream_t);
+};
+
 // the relaxation launches one batch at a time; the change counter of the batch's last launch is read after each batch
 static const int kTraverseBatch = 8;
+
+// What mrtx_traverse and mrtx_traverse_timed share, from the sources on; their own argument checks come before it.  q: the
+// field's zeroed block; S: the type of a start and of a value (8 bytes); extra: one more host table (or none) for stage_tables;
+// set_field(values, starts, extra's device copy) fills what is the field's own in q.  trav_buf holds the values and the
+// codes the caller wants on the host, then the two tile-flag arrays.
+extern "C++" template <class Q, class S, class Rule, class Field>
+static int traverse_run(mrtx_ctx* c, const MrtxTraverse* t, Q& q, const TraverseSteps<Q>& steps, const int32_t* src_ij,
+                        const S* src_start, int32_t n_src, Rule start_rule, const void* dev_penalty, const float* host_penalty,
+                        HostSeg extra, void* dev_val, S* host_val, void* dev_pred, uint8_t* host_pred, Field set_field,
+                        uint64_t* tile_visits, MrtxStats* out) {
+    static_assert(sizeof(S) == 8, "values and starts are 64-bit");
+    std::vector<int64_t> sn;
+    std::vector<S> sc;
+    int rc = traverse_sources(c, t, src_ij, src_start, n_src, start_rule, sn, sc);
+    if (rc != MRTX_OK) return rc;
+    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
+    std::vector<float> len((size_t)t->rows * 3);
+    if ((rc = traverse_window(c, t, c->dem_h, c->dem_w, len.data())) != MRTX_OK) return rc;
+    const size_t N = (size_t)t->rows * (size_t)t->cols;
+    if ((rc = traverse_host_penalty(c, host_penalty, N)) != MRTX_OK) return rc;
+    int TS;
+    if ((rc = traverse_tile_edge(c, TS)) != MRTX_OK) return rc;
+    // ---- device work from here
+    FrameC f;
+    FrameCold cold;
+    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
+    const int tiles_x = (t->cols + TS - 1) / TS, tiles_y = (t->rows + TS - 1) / TS;
+    const size_t tiles = (size_t)tiles_x * (size_t)tiles_y;
+    const size_t val_b = host_val ? N * 8 : 0, pred_b = host_pred ? (N + 15) & ~(size_t)15 : 0;
+    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, val_b + pred_b + 2 * tiles * 4)) != MRTX_OK) return rc;
+    char* tb = reinterpret_cast<char*>(c->trav_buf);
+    void* d_val = host_val ? tb : dev_val;
+    uint8_t* d_pred = host_pred ? reinterpret_cast<uint8_t*>(tb + val_b) : static_cast<uint8_t*>(dev_pred);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(tb + val_b + pred_b);
+    const size_t np = host_penalty ? N : 0;
+    float* d[5];
+    if ((rc = stage_tables(c, {len, {sn.data(), 2 * sn.size()}, {sc.data(), 2 * sc.size()}, {host_penalty, np}, extra}, d)) != MRTX_OK)
+        return rc;
+    TraverseC& g = traverse_block(q);
+    traverse_fill_window(c, f, t, g);
+    g.len = d[0];
+    g.src_node = reinterpret_cast<const int64_t*>(d[1]);
+    g.n_src = (int32_t)sn.size();
+    g.pen = host_penalty ? d[3] : static_cast<const float*>(dev_penalty);
+    g.pred = d_pred;
+    g.rm = (float)t->radius_m; g.gmax = (float)t->max_grade; g.a_up = (float)t->climb_cost; g.a_dn = (float)t->descent_cost;
+    g.tile = TS; g.tiles_x = tiles_x; g.tiles_y = tiles_y;
+    g.visits = c->illum_stats;                                       // [0] tile visits, [1] bad device penalties
+    g.changed = reinterpret_cast<uint32_t*>(c->illum_stats + 2);     // kTraverseBatch per-launch change counters
+    set_field(d_val, d[2], d[4]);
+    uint32_t* fa = flags;
+    uint32_t* fb = flags + tiles;
+    HIPCHK(c, hipMemsetAsync(flags, 0, 2 * tiles * 4, c->stream));
+    if ((rc = stage_start(c, nullptr, true)) != MRTX_OK) return rc;
+    g.flag_in = fa;
+    HIPCHK(c, steps.init(q, c->stream));
+    unsigned long long cnt[2] = {0, 0};
+    if (dev_penalty) {
+        HIPCHK(c, hipMemcpyAsync(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (cnt[1])
+            return fail(c, MRTX_E_INVALID, "%llu entries of the device penalty table are not finite in [1e-3, 1e6] or +inf", cnt[1]);
+    }
+    // no launch cap: every store strictly lowers a value, and the fixed point is reached after finitely many of them
+    // (DESIGN.md section 4.14 for the costs, 4.22 for the arrival ticks)
+    uint32_t launches = 0;
+    for (;;) {
+        HIPCHK(c, hipMemsetAsync(g.changed, 0, kTraverseBatch * sizeof(uint32_t), c->stream));
+        for (int s = 0; s < kTraverseBatch; s++) {
+            g.flag_in = fa; g.flag_out = fb; g.slot = s;
+            HIPCHK(c, steps.relax(q, c->stream));
+            std::swap(fa, fb);
+            launches++;
+        }
+        uint32_t last = 0;
+        HIPCHK(c, hipMemcpyAsync(&last, g.changed + (kTraverseBatch - 1), sizeof last, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (last == 0) break;       // a whole launch lowered nothing: every later one is empty too
+    }
+    HIPCHK(c, steps.pred(q, c->stream));
+    // finish: time, the 64-bit and uint8 read-backs, the counters
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (host_val) HIPCHK(c, hipMemcpy(host_val, d_val, N * 8, hipMemcpyDeviceToHost));
+    if (host_pred) HIPCHK(c, hipMemcpy(host_pred, d_pred, N, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost));
+    if (tile_visits) *tile_visits = cnt[0];
+    if (out) {
+        std::memset(out, 0, sizeof *out);
+        out->kernel_ms = ms;
+        out->launches = launches;
+    }
+    return MRTX_OK;
+}
 
 int mrtx_traverse(mrtx_ctx* c, const MrtxTraverse* t, const int32_t* src_ij, const double* src_cost, int32_t n_src,
                   const void* dev_penalty, const float* host_penalty, void* dev_cost, double* host_cost, void* dev_pred,
@@ -2023,107 +2169,20 @@ int mrtx_traverse(mrtx_ctx* c, const MrtxTraverse* t, const int32_t* src_ij, con
     if ((dev_cost == nullptr) == (host_cost == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_cost and host_cost");
     if ((dev_pred == nullptr) == (host_pred == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_pred and host_pred");
     if ((rc = traverse_dev_buffers(c, t, dev_penalty, dev_cost, dev_pred)) != MRTX_OK) return rc;
-    if (n_src < 1 || !src_ij) return fail(c, MRTX_E_INVALID, "need n_src >= 1 sources (got %d)", n_src);
-    // the sources, duplicates reduced to their smallest start cost (-0 made +0: the kernels order costs by their bits)
-    std::vector<std::pair<int64_t, double>> src((size_t)n_src);
-    for (int32_t k = 0; k < n_src; k++) {
-        const int32_t i = src_ij[2 * (size_t)k], j = src_ij[2 * (size_t)k + 1];
-        const double s = src_cost ? src_cost[k] : 0.0;
-        if (i < 0 || i >= t->rows || j < 0 || j >= t->cols)
-            return fail(c, MRTX_E_INVALID, "source %d: node (%d, %d) lies outside the %d x %d window", k, i, j, t->rows, t->cols);
-        if (!std::isfinite(s) || !(s >= 0.0)) return fail(c, MRTX_E_INVALID, "source %d: start cost must be finite and >= 0", k);
-        src[(size_t)k] = {(int64_t)i * t->cols + j, s + 0.0};
-    }
-    std::sort(src.begin(), src.end());
-    std::vector<int64_t> sn;
-    std::vector<double> sc;
-    for (const auto& e : src)
-        if (sn.empty() || sn.back() != e.first) { sn.push_back(e.first); sc.push_back(e.second); }
-    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
-    std::vector<float> len((size_t)t->rows * 3);
-    if ((rc = traverse_window(c, t, c->dem_h, c->dem_w, len.data())) != MRTX_OK) return rc;
-    const size_t N = (size_t)t->rows * (size_t)t->cols;
-    if (host_penalty)
-        for (size_t n = 0; n < N; n++)
-            if (!traverse_penalty_ok(host_penalty[n]))
-                return fail(c, MRTX_E_INVALID, "penalty %zu must be finite in [1e-3, 1e6] or +inf (got %g)", n, (double)host_penalty[n]);
-    int TS = 32;        // MOONRT_TRAVERSE_TILE: the tile edge, 8, 16 or 32 (the same field in every case)
-    if (const char* e = std::getenv("MOONRT_TRAVERSE_TILE")) {
-        TS = std::atoi(e);
-        if (TS != 8 && TS != 16 && TS != 32) return fail(c, MRTX_E_INVALID, "MOONRT_TRAVERSE_TILE must be 8, 16 or 32 (got %s)", e);
-    }
-    // ---- device work from here
-    FrameC f;
-    FrameCold cold;
-    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
-    const int tiles_x = (t->cols + TS - 1) / TS, tiles_y = (t->rows + TS - 1) / TS;
-    const size_t tiles = (size_t)tiles_x * (size_t)tiles_y;
-    const size_t cost_b = host_cost ? N * 8 : 0, pred_b = host_pred ? (N + 15) & ~(size_t)15 : 0;
-    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, cost_b + pred_b + 2 * tiles * 4)) != MRTX_OK) return rc;
-    char* tb = reinterpret_cast<char*>(c->trav_buf);
-    double* d_cost = host_cost ? reinterpret_cast<double*>(tb) : static_cast<double*>(dev_cost);
-    uint8_t* d_pred = host_pred ? reinterpret_cast<uint8_t*>(tb + cost_b) : static_cast<uint8_t*>(dev_pred);
-    uint32_t* flags = reinterpret_cast<uint32_t*>(tb + cost_b + pred_b);
-    const size_t np = host_penalty ? N : 0;
-    float* d[4];
-    if ((rc = stage_tables(c, {len, {sn.data(), 2 * sn.size()}, {sc.data(), 2 * sc.size()}, {host_penalty, np}}, d)) != MRTX_OK)
-        return rc;
     TraverseC q;
     std::memset(&q, 0, sizeof q);
-    q.dem = f.dem; q.dem_pitch = f.dem_pitch; q.dem_w = c->dem_w;
-    q.row0 = t->row0; q.col0 = t->col0; q.rows = t->rows; q.cols = t->cols; q.stride = t->stride; q.wrap = t->wrap;
-    q.len = d[0];
-    q.src_node = reinterpret_cast<const int64_t*>(d[1]); q.src_cost = reinterpret_cast<const double*>(d[2]);
-    q.n_src = (int32_t)sn.size();
-    q.pen = host_penalty ? d[3] : static_cast<const float*>(dev_penalty);
-    q.d = d_cost; q.pred = d_pred;
-    q.rm = (float)t->radius_m; q.gmax = (float)t->max_grade; q.a_up = (float)t->climb_cost; q.a_dn = (float)t->descent_cost;
-    q.tile = TS; q.tiles_x = tiles_x; q.tiles_y = tiles_y;
-    q.visits = c->illum_stats;                                       // [0] tile visits, [1] bad device penalties
-    q.changed = reinterpret_cast<uint32_t*>(c->illum_stats + 2);     // kTraverseBatch per-launch change counters
-    uint32_t* fa = flags;
-    uint32_t* fb = flags + tiles;
-    HIPCHK(c, hipMemsetAsync(flags, 0, 2 * tiles * 4, c->stream));
-    if ((rc = stage_start(c, nullptr, true)) != MRTX_OK) return rc;
-    q.flag_in = fa;
-    HIPCHK(c, mrtx_launch_traverse_init(q, c->stream));
-    unsigned long long cnt[2] = {0, 0};
-    if (dev_penalty) {
-        HIPCHK(c, hipMemcpyAsync(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (cnt[1])
-            return fail(c, MRTX_E_INVALID, "%llu entries of the device penalty table are not finite in [1e-3, 1e6] or +inf", cnt[1]);
-    }
-    uint32_t launches = 0;
-    for (;;) {      // no launch cap: the relaxation only lowers costs, and reaches its fixed point
-        HIPCHK(c, hipMemsetAsync(q.changed, 0, kTraverseBatch * sizeof(uint32_t), c->stream));
-        for (int s = 0; s < kTraverseBatch; s++) {
-            q.flag_in = fa; q.flag_out = fb; q.slot = s;
-            HIPCHK(c, mrtx_launch_traverse_relax(q, c->stream));
-            std::swap(fa, fb);
-            launches++;
-        }
-        uint32_t last = 0;
-        HIPCHK(c, hipMemcpyAsync(&last, q.changed + (kTraverseBatch - 1), sizeof last, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (last == 0) break;       // a whole launch lowered nothing: every later one is empty too
-    }
-    HIPCHK(c, mrtx_launch_traverse_pred(q, c->stream));
-    // finish: time, the float64 and uint8 read-backs, the counters
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    if (host_cost) HIPCHK(c, hipMemcpy(host_cost, d_cost, N * 8, hipMemcpyDeviceToHost));
-    if (host_pred) HIPCHK(c, hipMemcpy(host_pred, d_pred, N, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost));
-    if (tile_visits) *tile_visits = cnt[0];
-    if (out) {
-        std::memset(out, 0, sizeof *out);
-        out->kernel_ms = ms;
-        out->launches = launches;
-    }
-    return MRTX_OK;
+    const TraverseSteps<TraverseC> steps = {mrtx_launch_traverse_init, mrtx_launch_traverse_relax, mrtx_launch_traverse_pred};
+    return traverse_run(
+        c, t, q, steps, src_ij, src_cost, n_src,
+        [&](int32_t k, double s) {
+            return std::isfinite(s) && s >= 0.0 ? MRTX_OK : fail(c, MRTX_E_INVALID, "source %d: start cost must be finite and >= 0", k);
+        },
+        dev_penalty, host_penalty, HostSeg(nullptr, 0), dev_cost, host_cost, dev_pred, host_pred,
+        [&](void* val, const float* start, const float*) {
+            q.d = static_cast<double*>(val);
+            q.src_cost = reinterpret_cast<const double*>(start);
+        },
+        tile_visits, out);
 }
 
 // ---- Timed traverses: earliest arrival under per-node drive windows --------------------------------
@@ -2157,115 +2216,27 @@ int mrtx_traverse_timed(mrtx_ctx* c, const MrtxTraverse* t, const MrtxTraverseTi
     if (traverse_overlap(dev_avail, 8 * N * W64, dev_arrival, 8 * N) || traverse_overlap(dev_avail, 8 * N * W64, dev_pred, N) ||
         traverse_overlap(dev_avail, 8 * N * W64, dev_penalty, 4 * N))
         return fail(c, MRTX_E_INVALID, "dev_avail must not overlap dev_penalty, dev_arrival or dev_pred");
-    if (n_src < 1 || !src_ij) return fail(c, MRTX_E_INVALID, "need n_src >= 1 sources (got %d)", n_src);
     // a start tick lies inside the table; without one it leaves room for 2^31 edges of 2^31 ticks below UINT64_MAX
     const uint64_t tick_end = table ? (uint64_t)tt->n_epochs * (uint64_t)tt->ticks_per_epoch : (uint64_t)1 << 62;
-    std::vector<std::pair<int64_t, uint64_t>> src((size_t)n_src);
-    for (int32_t k = 0; k < n_src; k++) {
-        const int32_t i = src_ij[2 * (size_t)k], j = src_ij[2 * (size_t)k + 1];
-        const uint64_t s = src_tick ? src_tick[k] : 0;
-        if (i < 0 || i >= t->rows || j < 0 || j >= t->cols)
-            return fail(c, MRTX_E_INVALID, "source %d: node (%d, %d) lies outside the %d x %d window", k, i, j, t->rows, t->cols);
-        if (s >= tick_end)
-            return fail(c, MRTX_E_INVALID, "source %d: start tick %llu must be below %llu", k, (unsigned long long)s,
-                        (unsigned long long)tick_end);
-        src[(size_t)k] = {(int64_t)i * t->cols + j, s};
-    }
-    std::sort(src.begin(), src.end());
-    std::vector<int64_t> sn;
-    std::vector<uint64_t> sc;
-    for (const auto& e : src)
-        if (sn.empty() || sn.back() != e.first) { sn.push_back(e.first); sc.push_back(e.second); }
-    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
-    std::vector<float> len((size_t)t->rows * 3);
-    if ((rc = traverse_window(c, t, c->dem_h, c->dem_w, len.data())) != MRTX_OK) return rc;
-    if (host_penalty)
-        for (size_t n = 0; n < N; n++)
-            if (!traverse_penalty_ok(host_penalty[n]))
-                return fail(c, MRTX_E_INVALID, "penalty %zu must be finite in [1e-3, 1e6] or +inf (got %g)", n, (double)host_penalty[n]);
-    int TS = 32;        // MOONRT_TRAVERSE_TILE, as in mrtx_traverse
-    if (const char* e = std::getenv("MOONRT_TRAVERSE_TILE")) {
-        TS = std::atoi(e);
-        if (TS != 8 && TS != 16 && TS != 32) return fail(c, MRTX_E_INVALID, "MOONRT_TRAVERSE_TILE must be 8, 16 or 32 (got %s)", e);
-    }
-    // ---- device work from here
-    FrameC f;
-    FrameCold cold;
-    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
-    const int tiles_x = (t->cols + TS - 1) / TS, tiles_y = (t->rows + TS - 1) / TS;
-    const size_t tiles = (size_t)tiles_x * (size_t)tiles_y;
-    const size_t arr_b = host_arrival ? N * 8 : 0, pred_b = host_pred ? (N + 15) & ~(size_t)15 : 0;
-    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, arr_b + pred_b + 2 * tiles * 4)) != MRTX_OK) return rc;
-    char* tb = reinterpret_cast<char*>(c->trav_buf);
-    unsigned long long* d_arr = host_arrival ? reinterpret_cast<unsigned long long*>(tb) : static_cast<unsigned long long*>(dev_arrival);
-    uint8_t* d_pred = host_pred ? reinterpret_cast<uint8_t*>(tb + arr_b) : static_cast<uint8_t*>(dev_pred);
-    uint32_t* flags = reinterpret_cast<uint32_t*>(tb + arr_b + pred_b);
-    const size_t np = host_penalty ? N : 0, na = host_avail ? 2 * N * W64 : 0;
-    float* d[5];
-    if ((rc = stage_tables(c, {len, {sn.data(), 2 * sn.size()}, {sc.data(), 2 * sc.size()}, {host_penalty, np}, {host_avail, na}},
-                           d)) != MRTX_OK)
-        return rc;
     TraverseTimedC q;
     std::memset(&q, 0, sizeof q);
-    TraverseC& g = q.t;
-    g.dem = f.dem; g.dem_pitch = f.dem_pitch; g.dem_w = c->dem_w;
-    g.row0 = t->row0; g.col0 = t->col0; g.rows = t->rows; g.cols = t->cols; g.stride = t->stride; g.wrap = t->wrap;
-    g.len = d[0];
-    g.src_node = reinterpret_cast<const int64_t*>(d[1]);
-    g.n_src = (int32_t)sn.size();
-    g.pen = host_penalty ? d[3] : static_cast<const float*>(dev_penalty);
-    g.pred = d_pred;
-    g.rm = (float)t->radius_m; g.gmax = (float)t->max_grade; g.a_up = (float)t->climb_cost; g.a_dn = (float)t->descent_cost;
-    g.tile = TS; g.tiles_x = tiles_x; g.tiles_y = tiles_y;
-    g.visits = c->illum_stats;                                       // [0] tile visits, [1] bad device penalties
-    g.changed = reinterpret_cast<uint32_t*>(c->illum_stats + 2);     // kTraverseBatch per-launch change counters
-    q.arr = d_arr;
-    q.src_tick = reinterpret_cast<const unsigned long long*>(d[2]);
-    q.avail = host_avail ? reinterpret_cast<const unsigned long long*>(d[4]) : static_cast<const unsigned long long*>(dev_avail);
-    q.tpc = tt->ticks_per_cost; q.tpe = tt->ticks_per_epoch;
-    q.n_epochs = table ? tt->n_epochs : 0; q.w64 = (int32_t)W64;
-    uint32_t* fa = flags;
-    uint32_t* fb = flags + tiles;
-    HIPCHK(c, hipMemsetAsync(flags, 0, 2 * tiles * 4, c->stream));
-    if ((rc = stage_start(c, nullptr, true)) != MRTX_OK) return rc;
-    g.flag_in = fa;
-    HIPCHK(c, mrtx_launch_timed_init(q, c->stream));
-    unsigned long long cnt[2] = {0, 0};
-    if (dev_penalty) {
-        HIPCHK(c, hipMemcpyAsync(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (cnt[1])
-            return fail(c, MRTX_E_INVALID, "%llu entries of the device penalty table are not finite in [1e-3, 1e6] or +inf", cnt[1]);
-    }
-    uint32_t launches = 0;
-    for (;;) {      // no launch cap: every store strictly lowers a uint64 arrival, and the fixed point is finite (section 4.22)
-        HIPCHK(c, hipMemsetAsync(g.changed, 0, kTraverseBatch * sizeof(uint32_t), c->stream));
-        for (int s = 0; s < kTraverseBatch; s++) {
-            g.flag_in = fa; g.flag_out = fb; g.slot = s;
-            HIPCHK(c, mrtx_launch_timed_relax(q, c->stream));
-            std::swap(fa, fb);
-            launches++;
-        }
-        uint32_t last = 0;
-        HIPCHK(c, hipMemcpyAsync(&last, g.changed + (kTraverseBatch - 1), sizeof last, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (last == 0) break;       // a whole launch lowered nothing: every later one is empty too
-    }
-    HIPCHK(c, mrtx_launch_timed_pred(q, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    if (host_arrival) HIPCHK(c, hipMemcpy(host_arrival, d_arr, N * 8, hipMemcpyDeviceToHost));
-    if (host_pred) HIPCHK(c, hipMemcpy(host_pred, d_pred, N, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(cnt, c->illum_stats, sizeof cnt, hipMemcpyDeviceToHost));
-    if (tile_visits) *tile_visits = cnt[0];
-    if (out) {
-        std::memset(out, 0, sizeof *out);
-        out->kernel_ms = ms;
-        out->launches = launches;
-    }
-    return MRTX_OK;
+    const TraverseSteps<TraverseTimedC> steps = {mrtx_launch_timed_init, mrtx_launch_timed_relax, mrtx_launch_timed_pred};
+    return traverse_run(
+        c, t, q, steps, src_ij, src_tick, n_src,
+        [&](int32_t k, uint64_t s) {
+            return s < tick_end ? MRTX_OK
+                                : fail(c, MRTX_E_INVALID, "source %d: start tick %llu must be below %llu", k, (unsigned long long)s,
+                                       (unsigned long long)tick_end);
+        },
+        dev_penalty, host_penalty, HostSeg(host_avail, host_avail ? 2 * N * W64 : 0), dev_arrival, host_arrival, dev_pred, host_pred,
+        [&](void* val, const float* start, const float* avail) {
+            q.arr = static_cast<unsigned long long*>(val);
+            q.src_tick = reinterpret_cast<const unsigned long long*>(start);
+            q.avail = host_avail ? reinterpret_cast<const unsigned long long*>(avail) : static_cast<const unsigned long long*>(dev_avail);
+            q.tpc = tt->ticks_per_cost; q.tpe = tt->ticks_per_epoch;
+            q.n_epochs = table ? tt->n_epochs : 0; q.w64 = (int32_t)W64;
+        },
+        tile_visits, out);
 }
 
 // The window's node heights D (rows x cols float32), gathered on the device: what a route's heights are read from
@@ -2285,8 +2256,7 @@ int mrtx_traverse_heights(mrtx_ctx* c, const MrtxTraverse* t, void* dev_out, flo
     if ((rc = stage_out(c, dev_out, bytes)) != MRTX_OK) return rc;
     TraverseC q;
     std::memset(&q, 0, sizeof q);
-    q.dem = f.dem; q.dem_pitch = f.dem_pitch; q.dem_w = c->dem_w;
-    q.row0 = t->row0; q.col0 = t->col0; q.rows = t->rows; q.cols = t->cols; q.stride = t->stride; q.wrap = t->wrap;
+    traverse_fill_window(c, f, t, q);
     if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
     HIPCHK(c, mrtx_launch_traverse_heights(q, static_cast<float*>(dev_out), c->stream));
     return stage_finish(c, dev_out, host_out, bytes, out, kNoRays);

@@ -377,6 +377,16 @@ struct TraverseTimedC {
     int32_t w64;                        // words per node
 };
 
+// The traverse stage's launchers (mrtx_traverse.hip), one per step and field: init + seed, one relaxation launch over every
+// tile, pred + source_pred; hipErrorInvalidValue for a block the kernels must not be started with.
+hipError_t mrtx_launch_traverse_init(const TraverseC& q, hipStream_t st);
+hipError_t mrtx_launch_traverse_relax(const TraverseC& q, hipStream_t st);
+hipError_t mrtx_launch_traverse_pred(const TraverseC& q, hipStream_t st);
+hipError_t mrtx_launch_traverse_heights(const TraverseC& q, float* out, hipStream_t st);
+hipError_t mrtx_launch_timed_init(const TraverseTimedC& q, hipStream_t st);
+hipError_t mrtx_launch_timed_relax(const TraverseTimedC& q, hipStream_t st);
+hipError_t mrtx_launch_timed_pred(const TraverseTimedC& q, hipStream_t st);
+
 // Drive masks (mrtx_horizon_mask, DESIGN.md sections 3.19 and 4.22): HorizonWindowsC's inputs, the joint predicate kept as bits.
 // A struct of its own, so that horizon_windows_kernel's arguments stay as they were.
 struct HorizonMaskC {

@@ -874,21 +874,9 @@ class MoonRT:
             raise ValueError(f"point ({la[k]}, {lo[k]}) lies outside the window")
         return np.ascontiguousarray(np.stack([i, j], -1).astype(np.int32))
 
-    def traverse(self, window, sources=None, penalty=None, max_slope_deg=20.0, climb_cost=8.0, descent_cost=0.0,
-                 radius_m=1737400.0, start_cost=None, stats=None, nodes=None, heights=True):
-        """The least-cost field over a window (row0, col0, rows, cols[, stride[, wrap]]) of the DEM's texel lattice
-        (mrtx_traverse, DESIGN.md section 3.13) from its sources: `sources` = an (N, 2) array of (lat, lon) degrees, each
-        snapped to its nearest node (snap_to_nodes), or `nodes` = an (N, 2) array of explicit (i, j) nodes -- exactly one of
-        the two; start_cost = N start costs (default 0).  penalty: None, a (rows, cols) float32 map or a DeviceBuffer
-        holding one (see moonrtx_amd.traverse for builders).  The effort of a step is its length plus climb_cost per metre
-        climbed and descent_cost per metre descended (the defaults: Naismith's rule, 8 m of walking per metre of ascent);
-        steps steeper than max_slope_deg are not driven.  radius_m = the metres of D = 1.  Returns a
-        moonrtx_amd.traverse.TraverseField; with `heights` it holds the window's node heights (mrtx_traverse_heights), so that
-        routes read their heights from the field and not from the context, which may be closed or hold another DEM by then.
-        `stats`, if a dict, receives kernel_ms, launches and tile_visits of the traverse."""
-        from . import traverse as tv
-        w = tv.window_dict(window)
-        H, W = self._dem_hw()
+    # what traverse and traverse_timed share: the sources as nodes, the edge lengths, the penalty argument, the stats
+    def _traverse_sources(self, w, sources, nodes):
+        """(N, 2) int32 (i, j) from exactly one of `sources` ((lat, lon) degrees, snapped) and `nodes`."""
         if (sources is None) == (nodes is None):
             raise ValueError("give exactly one of sources ((lat, lon) degrees) and nodes ((i, j) indices)")
         if nodes is not None:
@@ -904,14 +892,19 @@ class MoonRT:
             ij = self.snap_to_nodes(w, ll[:, 0], ll[:, 1])
         if ij.ndim != 2 or ij.shape[1] != 2:
             raise ValueError("nodes must be (N, 2) (i, j) indices")
-        cost0 = None if start_cost is None else np.ascontiguousarray(np.broadcast_to(np.asarray(start_cost, np.float64),
-                                                                                      (ij.shape[0],)))
-        t = self._traverse_window(w, radius_m, tv.max_slope_grade(max_slope_deg), climb_cost, descent_cost)
-        lengths = np.empty((max(w["rows"], 1), 3), np.float32)
+        return ij
+
+    def _traverse_lengths(self, t, H, W):
+        lengths = np.empty((max(t.rows, 1), 3), np.float32)
         rc = self._lib.mrtx_traverse_lengths(C.byref(t), H, W, lengths.ctypes.data)
         if rc != 0:
             raise MoonRTError(f"mrtx_traverse_lengths failed ({rc}): bad window or lengths")
-        dev_pen = host_pen = None
+        return lengths
+
+    @staticmethod
+    def _traverse_penalty(w, penalty):
+        """(dev_penalty, host_penalty, the host map or None) of a penalty argument; the map must outlive the call."""
+        dev_pen = host_pen = pen = None
         if isinstance(penalty, DeviceBuffer):
             if penalty.nbytes < 4 * w["rows"] * w["cols"]:
                 raise ValueError("the penalty buffer is smaller than rows x cols float32")
@@ -921,6 +914,36 @@ class MoonRT:
             if pen.shape != (w["rows"], w["cols"]):
                 raise ValueError(f"penalty must be a (rows, cols) = {(w['rows'], w['cols'])} map")
             host_pen = pen.ctypes.data
+        return dev_pen, host_pen, pen
+
+    @staticmethod
+    def _traverse_stats(stats, st, visits):
+        if isinstance(stats, dict):
+            stats["kernel_ms"] = stats.get("kernel_ms", 0) + st.kernel_ms
+            stats["launches"] = stats.get("launches", 0) + st.launches
+            stats["tile_visits"] = stats.get("tile_visits", 0) + int(visits.value)
+
+    def traverse(self, window, sources=None, penalty=None, max_slope_deg=20.0, climb_cost=8.0, descent_cost=0.0,
+                 radius_m=1737400.0, start_cost=None, stats=None, nodes=None, heights=True):
+        """The least-cost field over a window (row0, col0, rows, cols[, stride[, wrap]]) of the DEM's texel lattice
+        (mrtx_traverse, DESIGN.md section 3.13) from its sources: `sources` = an (N, 2) array of (lat, lon) degrees, each
+        snapped to its nearest node (snap_to_nodes), or `nodes` = an (N, 2) array of explicit (i, j) nodes -- exactly one of
+        the two; start_cost = N start costs (default 0).  penalty: None, a (rows, cols) float32 map or a DeviceBuffer
+        holding one (see moonrtx_amd.traverse for builders).  The effort of a step is its length plus climb_cost per metre
+        climbed and descent_cost per metre descended (the defaults: Naismith's rule, 8 m of walking per metre of ascent);
+        steps steeper than max_slope_deg are not driven.  radius_m = the metres of D = 1.  Returns a
+        moonrtx_amd.traverse.TraverseField; with `heights` it holds the window's node heights (mrtx_traverse_heights), so that
+        routes read their heights from the field and not from the context, which may be closed or hold another DEM by then.
+        `stats`, if a dict, receives kernel_ms, launches and tile_visits of the traverse."""
+        from . import traverse as tv
+        w = tv.window_dict(window)
+        H, W = self._dem_hw()
+        ij = self._traverse_sources(w, sources, nodes)
+        cost0 = None if start_cost is None else np.ascontiguousarray(np.broadcast_to(np.asarray(start_cost, np.float64),
+                                                                                      (ij.shape[0],)))
+        t = self._traverse_window(w, radius_m, tv.max_slope_grade(max_slope_deg), climb_cost, descent_cost)
+        lengths = self._traverse_lengths(t, H, W)
+        dev_pen, host_pen, pen = self._traverse_penalty(w, penalty)
         cost = np.empty((w["rows"], w["cols"]), np.float64)
         pred = np.empty((w["rows"], w["cols"]), np.uint8)
         visits = C.c_uint64()
@@ -928,10 +951,7 @@ class MoonRT:
         self._check(self._lib.mrtx_traverse(self._ctx, C.byref(t), ij.ctypes.data, None if cost0 is None else cost0.ctypes.data,
                                             ij.shape[0], dev_pen, host_pen, None, cost.ctypes.data, None, pred.ctypes.data,
                                             C.byref(visits), C.byref(st)), "mrtx_traverse")
-        if isinstance(stats, dict):
-            stats["kernel_ms"] = stats.get("kernel_ms", 0) + st.kernel_ms
-            stats["launches"] = stats.get("launches", 0) + st.launches
-            stats["tile_visits"] = stats.get("tile_visits", 0) + int(visits.value)
+        self._traverse_stats(stats, st, visits)
         lat, lon, _ = self.traverse_nodes(w)
         D = self.traverse_heights(w) if heights else None
         return tv.TraverseField(cost, pred, w, lengths, radius_m, lat, lon, D=D)
@@ -950,40 +970,14 @@ class MoonRT:
         from . import traverse as tv
         w = tv.window_dict(window)
         H, W = self._dem_hw()
-        if (sources is None) == (nodes is None):
-            raise ValueError("give exactly one of sources ((lat, lon) degrees) and nodes ((i, j) indices)")
-        if nodes is not None:
-            ij = np.asarray(nodes)
-            if not np.issubdtype(ij.dtype, np.integer):
-                raise ValueError("nodes must be integer (i, j) indices")
-            ij = np.ascontiguousarray(ij.reshape(-1, 2) if ij.ndim == 1 else ij, np.int32)
-        else:
-            ll = np.asarray(sources, np.float64)
-            ll = ll.reshape(1, -1) if ll.ndim == 1 else ll
-            if ll.ndim != 2 or ll.shape[1] != 2:
-                raise ValueError("sources must be (N, 2) (lat, lon) degrees")
-            ij = self.snap_to_nodes(w, ll[:, 0], ll[:, 1])
-        if ij.ndim != 2 or ij.shape[1] != 2:
-            raise ValueError("nodes must be (N, 2) (i, j) indices")
+        ij = self._traverse_sources(w, sources, nodes)
         tick0 = None if start_tick is None else np.ascontiguousarray(np.broadcast_to(np.asarray(start_tick, np.uint64),
                                                                                       (ij.shape[0],)))
         max_grade = tv.max_slope_grade(max_slope_deg)
         t = self._traverse_window(w, radius_m, max_grade, climb_cost, descent_cost)
-        lengths = np.empty((max(w["rows"], 1), 3), np.float32)
-        rc = self._lib.mrtx_traverse_lengths(C.byref(t), H, W, lengths.ctypes.data)
-        if rc != 0:
-            raise MoonRTError(f"mrtx_traverse_lengths failed ({rc}): bad window or lengths")
+        lengths = self._traverse_lengths(t, H, W)
         N = w["rows"] * w["cols"]
-        dev_pen = host_pen = pen = None
-        if isinstance(penalty, DeviceBuffer):
-            if penalty.nbytes < 4 * N:
-                raise ValueError("the penalty buffer is smaller than rows x cols float32")
-            dev_pen = penalty.ptr
-        elif penalty is not None:
-            pen = np.ascontiguousarray(penalty, np.float32)
-            if pen.shape != (w["rows"], w["cols"]):
-                raise ValueError(f"penalty must be a (rows, cols) = {(w['rows'], w['cols'])} map")
-            host_pen = pen.ctypes.data
+        dev_pen, host_pen, pen = self._traverse_penalty(w, penalty)
         dev_av = host_av = av = None
         if isinstance(avail, DeviceBuffer):
             if n_epochs is None:
@@ -1009,10 +1003,7 @@ class MoonRT:
                                                   None if tick0 is None else tick0.ctypes.data, ij.shape[0], dev_pen, host_pen,
                                                   dev_av, host_av, None, arrival.ctypes.data, None, pred.ctypes.data,
                                                   C.byref(visits), C.byref(st)), "mrtx_traverse_timed")
-        if isinstance(stats, dict):
-            stats["kernel_ms"] = stats.get("kernel_ms", 0) + st.kernel_ms
-            stats["launches"] = stats.get("launches", 0) + st.launches
-            stats["tile_visits"] = stats.get("tile_visits", 0) + int(visits.value)
+        self._traverse_stats(stats, st, visits)
         lat, lon, _ = self.traverse_nodes(w)
         if dev_pen is not None:
             pen = penalty.download(np.float32, (w["rows"], w["cols"]))

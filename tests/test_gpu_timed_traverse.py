@@ -1,7 +1,7 @@
 """Timed traverses on the MI355X (DESIGN.md sections 3.19 and 4.22): arrival fields and predecessor codes bit-equal to the integer
 model (tests/timed_traverse_model.py) on relief with partial tiles, a strided window with several sources and start ticks, a
 wrapped polar window and a spiral maze, under random, moving-night, closed-node, all-ones and short availability tables of odd
-lengths, with slow edges and a start on an epoch boundary; tile sizes, host and device tables and repeats; and one end-to-end
+lengths, with slow edges and a start on an epoch boundary; tile sizes, host and device tables and repeats; wrapped windows one and two tiles wide; and one end-to-end
 run from drive_mask to timed_route."""
 import ctypes as C
 import math
@@ -19,7 +19,7 @@ from moonrtx_amd import traverse as tv
 from moonrtx_amd.renderer import DeviceBuffer, MoonRT
 from test_gpu_horizon import OBS, scene
 from test_gpu_illumination import make
-from test_gpu_traverse import spiral_maze
+from test_gpu_traverse import SEAM_CASES, seam_case, spiral_maze
 
 pytestmark = pytest.mark.gpu
 
@@ -223,6 +223,33 @@ def test_tile_sizes_tables_and_repeats_agree(native_lib, monkeypatch):
         for b in (buf, ab, qb):
             b.free()
         rt.close()
+
+
+_SEAM_WANT = {}
+
+
+@pytest.mark.parametrize("ts,wname,across", SEAM_CASES)
+def test_narrow_wrapped_windows_match_the_model(native_lib, monkeypatch, ts, wname, across):
+    """test_gpu_traverse's seam windows, one and two tiles wide at every tile edge, under a random table and without one.  The
+    edges last 22 to 1916 ticks of epochs of 1500; the model alone reaches 0.875 to 0.9 of each window either way."""
+    dem, t, src, P = seam_case(wname)
+    assert (t.cols + int(ts) - 1) // int(ts) == across
+    ticks, n_ep, tpe, tpc = [0, 700], 130, 1500, 0.001
+    av = ttm.mask_random(t.rows, t.cols, n_ep, 0.8, seed=len(wname))
+    if wname not in _SEAM_WANT:
+        _SEAM_WANT[wname] = (ttm.field(dem, t, src, ticks, P, av, tpc, tpe), ttm.field(dem, t, src, ticks, P, None, tpc, tpe))
+    masked, plain = _SEAM_WANT[wname]
+    for want in (masked, plain):
+        assert (want[0] != NEVER).mean() > 0.3
+        assert np.isin(want[1][:, -1], (1, 2, 3)).any()     # predecessors east of the last column: across the seam
+    assert not np.array_equal(masked[0], plain[0])          # the table makes routes wait
+    monkeypatch.setenv("MOONRT_TRAVERSE_TILE", ts)
+    rt = ctx(dem)
+    got_masked = gpu_field(rt, t, src, ticks, P, tv.pack_mask(av), n_ep, tpe, tpc)
+    got_plain = gpu_field(rt, t, src, ticks, P, None, 0, tpe, tpc)
+    rt.close()
+    assert_field_equal(got_masked, masked, f"{wname}, tile {ts}: random table")
+    assert_field_equal(got_plain, plain, f"{wname}, tile {ts}: no table")
 
 
 def test_drive_mask_to_route(native_lib):

@@ -1,6 +1,6 @@
 """Least-cost traverses on the MI355X (DESIGN.md sections 3.13 and 4.14): cost and predecessor fields bit-equal to the float64
 model (tests/traverse_model.py) on relief, the bowl, strided and wrapped polar windows, several sources and a spiral maze of
-impassable walls; the minimum over sources; tile sizes, repeats, device pointers and a device penalty check; routes that keep
+impassable walls; the minimum over sources; tile sizes, repeats, device pointers and a device penalty check; wrapped windows one and two tiles wide; routes that keep
 the slope limit and a line of sight; the smooth sphere's symmetry; the render state left alone; the full-size DEM."""
 import ctypes as C
 import math
@@ -209,6 +209,48 @@ def test_tile_sizes_repeats_and_device_pointers_agree(native_lib, monkeypatch):
         with pytest.raises(MoonRTError):
             gpu_field(rt, bad_t, [(0, 0)])
     rt.close()
+
+
+# Wrapped windows of a 180 x 360 DEM (cols x stride = 360) so narrow that the tile grid is one tile wide -- a tile's east and
+# west neighbour is the tile itself -- or two tiles wide -- both are the same other tile -- at every tile edge.
+# name: (row0, rows, cols, stride); case: (tile edge, window, tiles across)
+SEAM_WINDOWS = {"w8": (10, 4, 8, 45), "w15": (5, 8, 15, 24), "w24": (3, 12, 24, 15), "w40": (4, 19, 40, 9)}
+SEAM_CASES = [("8", "w8", 1), ("8", "w15", 2), ("16", "w15", 1), ("16", "w24", 2), ("32", "w24", 1), ("32", "w40", 2)]
+_SEAM_DEM = []
+
+
+def seam_case(wname):
+    """(dem, t, sources, penalty) of a seam window: a wall of +inf penalties down the middle column and both sources just east
+    of the seam, so that the nodes between the wall and the seam are reached across the seam only.  max_grade = 0.004 from the
+    model alone: it reaches 0.875 to 0.9 of the four windows (0.53 to 0.81 at 0.002, under 0.1 of three of them at 0.001)."""
+    if not _SEAM_DEM:
+        _SEAM_DEM.append(synth_np.dem(180, 360, seed=3, craters=60))
+    row0, rows, cols, stride = SEAM_WINDOWS[wname]
+    t = tm.make_window(row0, 6, rows, cols, stride=stride, wrap=1, max_grade=0.004, descent_cost=1.0)
+    P = np.ones((rows, cols), np.float32)
+    P[:, cols // 2] = np.inf
+    return _SEAM_DEM[0], t, [(rows // 2, 1), (1, 2)], P
+
+
+_SEAM_WANT = {}
+
+
+@pytest.mark.parametrize("ts,wname,across", SEAM_CASES)
+def test_narrow_wrapped_windows_match_the_model(native_lib, monkeypatch, ts, wname, across):
+    dem, t, src, P = seam_case(wname)
+    assert (t.cols + int(ts) - 1) // int(ts) == across
+    if wname not in _SEAM_WANT:
+        _SEAM_WANT[wname] = tm.field(dem, t, src, [0.0, 5e5], P)
+    want = _SEAM_WANT[wname]
+    assert np.isfinite(want[0]).mean() > 0.3
+    assert np.isin(want[1][:, -1], (1, 2, 3)).any()         # predecessors east of the last column: across the seam
+    monkeypatch.setenv("MOONRT_TRAVERSE_TILE", ts)
+    rt = ctx(dem)
+    st = {}
+    got = gpu_field(rt, t, src, [0.0, 5e5], P, st)
+    rt.close()
+    print(f"{wname}, tile {ts}: {st['launches']} launches, {st['tile_visits']} tile visits, {st['kernel_ms']:.3f} ms")
+    assert_field_equal(got, want, f"{wname}, tile {ts}")
 
 
 def test_routes_keep_the_slope_limit_and_a_line_of_sight(native_lib):
