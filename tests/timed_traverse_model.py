@@ -1,7 +1,8 @@
 """The timed traverse on the CPU, TEST INFRASTRUCTURE: float32 edge weights from traverse_model, the
 durations q by the spec's rule, a word-free start() over a Python list of booleans, a heapq Dijkstra over Python ints and the
-predecessor rule.  Also a brute-force start(), a randomly ordered label-correcting loop and the synthetic masks of the GPU
-tests."""
+predecessor rule.  Also start_trace() (start() with a record of what it did), a brute-force start(), a randomly ordered
+label-correcting loop and the synthetic masks of the GPU tests."""
+import collections
 import heapq
 import math
 
@@ -44,6 +45,50 @@ def start(ok, a, q, tpe):
             z += 1
         if z > last:
             return t
+        t = (z + 1) * tpe
+
+
+Trace = collections.namedtuple("Trace", "t restarts boundaries skipped_zero_word past_table attempts")
+
+
+def start_trace(ok, a, q, tpe):
+    """start()'s result and what happened on the way, as a Trace:
+      t                  start(ok, a, q, tpe)
+      restarts           how often the search went on behind a blocking epoch
+      boundaries         the 64-epoch word boundaries between the first and the last epoch of the accepted drive (0 if none)
+      skipped_zero_word  a whole word of 64 unavailable epochs lay between an epoch the search looked from and the available
+                         epoch it found
+      past_table         t is None because the last tick of the drive falls past the table (no later start fits either)
+      attempts           (first epoch, last epoch, blocking epoch or None) of every drive that was tried
+    Word-free like start(): words appear only as e // 64 in the bookkeeping."""
+    if ok is None:
+        return Trace(a, 0, 0, False, False, [])
+    n = len(ok)
+    t = a
+    restarts, skipped, attempts = 0, False, []
+    while True:
+        e0 = t // tpe
+        e = e0
+        while e < n and not ok[e]:
+            e += 1
+        if e >= n:
+            return Trace(None, restarts, 0, skipped, False, attempts)
+        if e // 64 - e0 // 64 >= 2:
+            skipped = True
+        if e > e0:
+            t = e * tpe
+        last = (t + q - 1) // tpe
+        if last >= n:
+            attempts.append((e, last, None))
+            return Trace(None, restarts, 0, skipped, True, attempts)
+        z = e
+        while z <= last and ok[z]:
+            z += 1
+        if z > last:
+            attempts.append((e, last, None))
+            return Trace(t, restarts, last // 64 - e // 64, skipped, False, attempts)
+        attempts.append((e, last, z))
+        restarts += 1
         t = (z + 1) * tpe
 
 
