@@ -315,7 +315,10 @@ __device__ __forceinline__ bool sky_pixel_uniform(const FrameC& f, int x, int y,
 // in registers after all).
 // The shadow ray and the continuation ray leave the SAME point (vertex + scene_epsilon * normal): its exact texel coordinates and
 // horizon cell are evaluated once and sit out the shadow march in a fourth slot -- 4 KB per wave.
-#define MRTX_PARK_SLOTS 4
+// MRTX_TRIAL_WIDE: a fifth slot.  While the trial segment's steps are dealt out over the wave (trial_steps_wide, mrtx_march.h), slots
+// 2-4 hold the rays' state for the lanes that evaluate their steps and the spare word of slot 1 is the round's control word -- 5 KB per
+// wave, still 32 waves per CU.
+#define MRTX_PARK_SLOTS (MRTX_TRIAL_WIDE ? 5 : 4)
 __device__ __forceinline__ void park_put(v4f* park, int slot, float a, float b, float c, float d) {
     const v4f v = {a, b, c, d};
     park[slot * 64 + threadIdx.x] = v;
@@ -333,12 +336,46 @@ struct SampleOut {
     bool path;
 };
 
+// MRTX_TRIAL_WIDE, MODE 2: trace_sample() returns with the trial segment SET UP (`stage`).  The
+// wave then steps it in wave-uniform control flow -- lanes whose sample never got there included -- and trial_finish() does the rest.
+struct TrialState {
+    MarchState m;
+    Seg sg;
+    float rowB, colB, q2B;      // the segment's far anchor, for segment_tail()
+    float sk;                   // the step that landed at or below the surface (`hit`)
+    int stage;                  // 0: the sample has no trial segment; 1: begun, and over before its first step; 2: a segment is set up;
+                                // 3: ... an exact-fallback one (an int, not flags: a flag carried across the wave's join costs an SGPR pair)
+#ifdef MRTX_PROF
+    uint32_t tc[16];            // the trial's own section timers and counts
+#endif
+};
+// The end of the trial segment and what follows from it: the path is finished in this wave, or handed over with what the segment found
+// out -- the step that landed below the surface (MRTX_REC_HIT), or the march state at the segment's end (MRTX_REC_RESUME).
+template <bool STATS>
+__device__ __forceinline__ void trial_finish(const FrameC& f, SampleOut& o, MarchState& tm, bool tgo, bool thit, float tsk,
+                                             const v4f* park, uint32_t* cnt) {
+    const v4f p0 = park_get(park, 0), p1 = park_get(park, 1);
+    o.c0 = p0.x; o.c1 = p0.y; o.c2 = p0.z; o.t0 = p0.w;
+    o.t1 = p1.x; o.t2 = p1.y; o.ks = __float_as_uint(p1.z);
+    if (!tgo && !thit) {
+        escaped_path<STATS>(f, o.oa, o.ob, o.oc, o.da, o.db, o.dc, o.t0, o.t1, o.t2, o.c0, o.c1, o.c2, cnt);
+    } else {
+        o.path = true;
+        if (thit) {
+            o.aux = MRTX_REC_HIT | ((uint32_t)(int)rintf(tsk * f.inv_step) << 8);
+        } else {
+            o.aux = MRTX_REC_RESUME | ((uint32_t)tm.kend << 8);
+            o.row = tm.rowA; o.col = tm.colA;
+        }
+    }
+}
+
 // MODE: 0 = direct light only, 1 = the whole path inside this wave (BOUNCE), 2 = direct light + hand-over of the
 // vertex to path_kernel (DEFER), 3 = SKY: the host has proven that no sample of this tile can meet the Moon's bounding
 // sphere, the Sun disk or an overlay tube (cull_tiles), so a sample is its environment texel and nothing else
 template <bool STATS, bool WIDE, int MODE, bool OVERLAY>
 __device__ __forceinline__ void trace_sample(const FrameC& f, int lt, int x, int y, uint32_t gs, SampleOut& o,
-                                             uint32_t* cnt, bool lead = false, v4f* park = nullptr) {
+                                             uint32_t* cnt, bool lead = false, v4f* park = nullptr, TrialState* tw = nullptr) {
     constexpr bool BOUNCE = MODE == 1, DEFER = MODE == 2;
     // (writing the hit record from here, as soon as it is known, instead of carrying it to the end of the wave was measured for the
     // direct kernel: 13.33 ms against 13.21 -- its single late store stays.  render_kernel<MODE 2>, which parks in LDS, is held to 96
@@ -540,6 +577,27 @@ __device__ __forceinline__ void trace_sample(const FrameC& f, int lt, int x, int
                 // Moon and then read one texel of a 537 MB map.  Bit-exact; on the star-map frame render took 17.28 ms against 17.06:
                 // the 19 % extra look-ups, for rays that hit or march on, cost more than the hidden round.  Handing every ray over
                 // unmarched instead: render 11.2 + paths 11.1 = 22.3 ms against a 17.6 ms frame.)
+#if MRTX_TRIAL_WIDE
+                // the radiance so far, the throughput and the key sit out the trial segment in LDS
+                park_put(park, 0, o.c0, o.c1, o.c2, o.t0);
+                park_put(park, 1, o.t1, o.t2, __uint_as_float(o.ks), 0.0f);
+                park_fence();
+                // MRTX_TRIAL_WIDE: the segment is set up here; the wave steps through it in render_kernel, where every lane takes part
+                TrialState& t = *tw;
+#ifdef MRTX_PROF
+                uint32_t* const tcnt = t.tc;
+#else
+                uint32_t* const tcnt = cnt;
+#endif
+                t.m.rowA = o.row; t.m.colA = o.col;
+                bool tgo = march_begin_at<false, STATS, false, true>(f, o.oa, o.ob, o.oc, o.da, o.db, o.dc, t.m, tcnt, org_cell);
+                t.stage = 1;
+                if (tgo) {
+                    segment_head<false, STATS, 3, false>(f, t.m, 0.0f, t.sg, tgo, t.rowB, t.colB, t.q2B, tcnt);
+                    t.stage = t.sg.exact ? 3 : 2;
+                    if (STATS) tcnt[ST_HEIGHT] += count_in_steps<false>(f, o.oa, o.ob, o.oc, o.da, o.db, o.dc, 0.0f, 0, 1, t.sg.jlo - 1);
+                }
+#else
 #ifdef MRTX_PROF
                 uint32_t tcnt[16];
 #pragma unroll
@@ -564,28 +622,31 @@ __device__ __forceinline__ void trace_sample(const FrameC& f, int lt, int x, int
                 float tsk = 0.0f;
                 if (tgo) march_segment<WIDE, false, STATS, MRTX_TRIAL_BATCH, 3>(f, tm, 0.0f, tsg, tgo, thit, tsk, tcnt);
                 park_fence();
-                const v4f p0 = park_get(park, 0), p1 = park_get(park, 1);
-                o.c0 = p0.x; o.c1 = p0.y; o.c2 = p0.z; o.t0 = p0.w;
-                o.t1 = p1.x; o.t2 = p1.y; o.ks = __float_as_uint(p1.z);
-                t0r = o.t0; t1r = o.t1; t2r = o.t2;
-#ifdef MRTX_PROF_TRIAL   // measurement only: the trial's step iterations and the lanes evaluating in them (slots 13 / 14), its cycles (15)
-                cnt[13] += tcnt[11]; cnt[14] += tcnt[12]; cnt[15] += tcnt[6] + tcnt[7];
+#ifdef MRTX_PROF_TRIAL   // measurement only: the trial's step iterations and the lane-steps evaluated in them (slots 13 / 14), its cycles (15)
+                {
+                    // WAVE-level figures: the loop runs for as long as its longest lane.  A lane's own tcnt[11] only counts the
+                    // iterations it took part in, and the read-back takes one lane per wave, so the maximum and the sum over the
+                    // lanes are formed here (five ballots: a lane steps at most SEG_N = 16 times), kept by the first lane of the
+                    // region and added up over the wave at the kernel's end.
+                    const uint32_t mine = tcnt[11];
+                    uint32_t iters = 0u, steps = 0u;
+                    bool top = true;
+#pragma unroll
+                    for (int b = 4; b >= 0; b--) {
+                        const bool bit = ((mine >> b) & 1u) != 0u;
+                        steps += (uint32_t)__popcll(__ballot(bit)) << b;
+                        if (__ballot(top && bit) != 0ull) { iters |= 1u << b; top = top && bit; }
+                    }
+                    if ((int)(threadIdx.x & 63u) == __ffsll((long long)__ballot(true)) - 1) { cnt[13] += iters; cnt[14] += steps; }
+                    cnt[15] += tcnt[6] + tcnt[7];
+                }
 #endif
                 if (STATS) {
 #pragma unroll
                     for (int i = 0; i < ST_N; i++) cnt[i] += tcnt[i];
                 }
-                if (!tgo && !thit) {
-                    escaped_path<STATS>(f, o.oa, o.ob, o.oc, o.da, o.db, o.dc, t0r, t1r, t2r, o.c0, o.c1, o.c2, cnt);
-                } else {
-                    o.path = true;
-                    if (thit) {
-                        o.aux = MRTX_REC_HIT | ((uint32_t)(int)rintf(tsk * f.inv_step) << 8);
-                    } else {
-                        o.aux = MRTX_REC_RESUME | ((uint32_t)tm.kend << 8);
-                        o.row = tm.rowA; o.col = tm.colA;
-                    }
-                }
+                trial_finish<STATS>(f, o, tm, tgo, thit, tsk, park, cnt);
+#endif
             }
         }
         if (!BOUNCE) break;
@@ -658,14 +719,16 @@ __device__ __forceinline__ float tree_sum(float v) {
 // their paths in the wave): at 4 waves per SIMD they need no scratch and run as fast (4K, 1 spp: 1.302 ms against 1.312 with
 // 17 spilled registers at 5 waves; 2 spp 2.256 / 2.270); the larger S (an A/B path and the no-memory fall-back) keep 5.
 #define MRTX_BOUNCE_WAVES(STATS, SV) ((STATS) ? MRTX_BOUNCE_STATS_WAVES : ((SV) <= 2 ? 4 : MRTX_MIN_WAVES_BOUNCE))
-template <int S, bool STATS, bool WIDE, int MODE, bool OVERLAY>
 #ifndef MRTX_MIN_WAVES_DEFER
 #define MRTX_MIN_WAVES_DEFER 3   // no longer what sets the occupancy: with one block per launch and its cold state parked in LDS the kernel
                                  // needs 62 VGPRs under any bound up to 8 -- 8 waves per SIMD (rounds 2-3: 121-125 VGPRs, 4 waves; a bound of
                                  // 5 then meant 17 spilled registers and 22.2 ms against 18.9)
 #endif
-__global__ void __launch_bounds__(64, MODE == 1 ? MRTX_BOUNCE_WAVES(STATS, S) : MODE == 2 ? MRTX_MIN_WAVES_DEFER : MRTX_MIN_WAVES)
-render_kernel(const FrameC f, const PathQ pq) {
+#define MRTX_RENDER_BOUNDS(S, STATS, MODE) \
+    __launch_bounds__(64, (MODE) == 1 ? MRTX_BOUNCE_WAVES(STATS, S) : (MODE) == 2 ? MRTX_MIN_WAVES_DEFER : MRTX_MIN_WAVES)
+// the kernel's body (render_kernel below: the template and, MRTX_TRIAL_WIDE, the production instantiations of MODE 2 as specialisations)
+template <int S, bool STATS, bool WIDE, int MODE, bool OVERLAY>
+__device__ __forceinline__ void render_body(const FrameC& f, const PathQ& pq) {
     constexpr bool DEFER = MODE == 2;
     constexpr int P = 64 / S;
     constexpr int PW = P >= 64 ? 8 : P >= 32 ? 8 : P >= 16 ? 4 : P >= 8 ? 4 : P >= 4 ? 2 : P >= 2 ? 2 : 1;
@@ -777,7 +840,65 @@ render_kernel(const FrameC f, const PathQ pq) {
         for (uint32_t blk = 0; blk < n_blk; blk++) {
             o.c0 = o.c1 = o.c2 = o.hitflag = 0.f;
             PROF_BEGIN(0);
+#if MRTX_TRIAL_WIDE
+            TrialState ts;
+            ts.stage = 0;
+            ts.sk = 0.0f;
+            ts.sg.jlo = 1; ts.sg.jhi = 0;
+#ifdef MRTX_PROF
+#pragma unroll
+            for (int i = 0; i < 16; i++) ts.tc[i] = 0;
+            uint32_t* const tcnt = ts.tc;
+#else
+            uint32_t* const tcnt = cnt;
+#endif
+            if (inb) trace_sample<STATS, WIDE, MODE, OVERLAY>(f, lt, x, y, (f.first_block + blk) * (uint32_t)S + (uint32_t)s, o, cnt, s == 0, park, &ts);
+            if (DEFER) {
+                // the trial segments of the wave's samples are set up: their steps, with every lane of the wave at work
+                const bool live = ts.stage >= 2;
+                bool tgo = live, thit = false;
+                ts.sg.exact = ts.stage == 3;
+                if (__ballot(live) != 0ull) {
+#ifdef MRTX_PROF
+                    const unsigned long long pt7 = __builtin_readcyclecounter();
+#endif
+                    trial_steps_wide<WIDE, STATS>(f, ts.m, ts.sg, live, park + 2 * 64, reinterpret_cast<uint32_t*>(park + 64) + 3,
+                                                  tgo, thit, ts.sk, tcnt);
+#ifdef MRTX_PROF
+                    tcnt[7] += (uint32_t)(__builtin_readcyclecounter() - pt7);
+#endif
+                }
+                if (ts.stage != 0) {
+                    if (live) segment_tail<false, STATS>(f, ts.m, 0.0f, ts.sg, tgo, ts.rowB, ts.colB, ts.q2B, tcnt);
+                    park_fence();
+#ifdef MRTX_PROF
+                    if (STATS) {
+#pragma unroll
+                        for (int i = 0; i < ST_N; i++) cnt[i] += tcnt[i];
+                    }
+#endif
+                    trial_finish<STATS>(f, o, ts.m, tgo, thit, ts.sk, park, cnt);
+                }
+#ifdef MRTX_PROF_TRIAL   // measurement only: the trial's wave-level step iterations and the lane-steps evaluated in them (slots 13 / 14, see
+                         // trace_sample), its wide rounds and the items dealt in them (8 / 9), its cycles (15)
+                {
+                    const uint32_t mine = tcnt[11];
+                    uint32_t iters = 0u, steps = 0u;
+                    bool top = true;
+#pragma unroll
+                    for (int b = 4; b >= 0; b--) {
+                        const bool bit = ((mine >> b) & 1u) != 0u;
+                        steps += (uint32_t)__popcll(__ballot(bit)) << b;
+                        if (__ballot(top && bit) != 0ull) { iters |= 1u << b; top = top && bit; }
+                    }
+                    if (lane == 0) { cnt[13] += iters; cnt[14] += steps; }
+                    cnt[8] += tcnt[8]; cnt[9] += tcnt[9]; cnt[15] += tcnt[6] + tcnt[7];
+                }
+#endif
+            }
+#else
             if (inb) trace_sample<STATS, WIDE, MODE, OVERLAY>(f, lt, x, y, (f.first_block + blk) * (uint32_t)S + (uint32_t)s, o, cnt, s == 0, park);
+#endif
             PROF_END(0);
             if (blk == 0 && f.first_block != 0 && inb && s == 0) {
                 // the running sums of earlier launches are fetched HERE, not before the first block was traced (four registers
@@ -817,6 +938,15 @@ render_kernel(const FrameC f, const PathQ pq) {
     }
 
 #ifdef MRTX_PROF
+#ifdef MRTX_PROF_TRIAL   // the trial's wave-level counts sit in whichever lane was the first of its region
+    if (!STATS) {
+#pragma unroll
+        for (int i = 13; i <= 14; i++) {
+#pragma unroll
+            for (int m = 1; m < 64; m <<= 1) cnt[i] += __shfl_xor(cnt[i], m, 64);
+        }
+    }
+#endif
     if (!STATS && lane == 0 && (((uint32_t)(blockIdx.x >> 3) * 2654435761u) >> 26) == 0u) {   // 1/64 of the waves
         cnt[10] = 1;
 #pragma unroll
@@ -835,6 +965,25 @@ render_kernel(const FrameC f, const PathQ pq) {
         if (threadIdx.x < ST_N) atomicAdd(&CF(f)->stats[threadIdx.x], (unsigned long long)lds_cnt[threadIdx.x]);
     }
 }
+template <int S, bool STATS, bool WIDE, int MODE, bool OVERLAY>
+__global__ void MRTX_RENDER_BOUNDS(S, STATS, MODE) render_kernel(const FrameC f, const PathQ pq) {
+    render_body<S, STATS, WIDE, MODE, OVERLAY>(f, pq);
+}
+#if MRTX_TRIAL_WIDE
+// With the trial's steps moved to the wave's join the production kernel of the headline frame wants 104 scalar registers where it had
+// 96 -- the eighth wave per SIMD (8 x 100 fit).  Held to 96 it keeps ten of them in the lanes of a 63rd VGPR and stays at 8 waves:
+// 12.86 ms against 13.26 with seven waves.  The attribute takes no template value, hence specialisations;
+// every other instantiation keeps the registers it had.
+#ifndef MRTX_DEFER_SGPRS
+#define MRTX_DEFER_SGPRS 96
+#endif
+#define MRTX_DEFER_TIGHT(WD, OV)                                                                                                 \
+    template <> __global__ void __attribute__((amdgpu_num_sgpr(MRTX_DEFER_SGPRS))) MRTX_RENDER_BOUNDS(64, false, 2)              \
+    render_kernel<64, false, WD, 2, OV>(const FrameC f, const PathQ pq) { render_body<64, false, WD, 2, OV>(f, pq); }
+MRTX_DEFER_TIGHT(false, false)      // 32- and 64-bit DEM addressing; the overlay instantiations keep what they had
+MRTX_DEFER_TIGHT(true, false)
+#undef MRTX_DEFER_TIGHT
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // D6 behind a queue: what is left of a path after render_kernel<MODE 2> (set_uint("path_seg_range", 2, 4),
@@ -1819,7 +1968,9 @@ __global__ void mip_pair_kernel(const float* __restrict__ mip, float2* __restric
 #if MRTX_DEV_ONE_MODE == 9
 template __global__ void mrtx::path_kernel<false, true>(const FrameC, const PathQ);
 #else
+#if !(MRTX_TRIAL_WIDE && MRTX_DEV_ONE_MODE == 2)      // (that one is a specialisation then, and emitted as such)
 template __global__ void mrtx::render_kernel<64, false, true, MRTX_DEV_ONE_MODE, false>(const FrameC, const PathQ);
+#endif
 #endif
 #else
 // ------------------------------------------------------------------------------------------------

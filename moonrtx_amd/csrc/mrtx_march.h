@@ -669,15 +669,13 @@ __device__ __forceinline__ int first_kept_step(const FrameC& f, const MarchState
     }
     return first;
 }
-// ONE 16-step segment of a march (the lanes that call it are still marching): anchors + skip interval, the steps
-// that can be at/below the surface, the termination test at the segment end.  `hit` / `sk_hit` are set by the step
-// that lands at/below the surface, `go` says whether the ray continues with the next segment.
-template <bool WIDE, bool PRIMARY, bool STATS, int BATCH, int SCAN = PRIMARY ? 1 : 0, bool BOUNDED = false>
-__device__ __forceinline__ void march_segment(const FrameC& f, MarchState& m, float smax, Seg& sg, bool& go, bool& hit,
-                                              float& sk_hit, uint32_t* cnt) {
+// The part of march_segment() before the steps: the late horizon bound, anchors + skip interval, the cuts of the interval.  Returns false
+// when the march ended before this segment (`go` is false then); rowB / colB / q2B are the segment's far anchor, for segment_tail().
+template <bool PRIMARY, bool STATS, int SCAN, bool BOUNDED>
+__device__ __forceinline__ bool segment_head(const FrameC& f, MarchState& m, float smax, Seg& sg, bool& go, float& rowB, float& colB,
+                                             float& q2B, uint32_t* cnt) {
     const float oa = m.oa, ob = m.ob, oc = m.oc, da = m.da, db = m.db, dc = m.dc;
     const int ka = m.ka;
-    float rowB, colB, q2B;
     if (!PRIMARY && (MRTX_HORIZON_RETRY & 1) != 0 && ka > 0 && m.kend >= f.kmax) {
         // The horizon bound was out of reach at the ray's origin (its ground track to the sphere exit is longer than the horizon
         // cell's dilation: low rays, and any east-west ray at high latitude, where columns shrink).  The ray has climbed since:
@@ -686,7 +684,7 @@ __device__ __forceinline__ void march_segment(const FrameC& f, MarchState& m, fl
         if (ke < 1) {                        // above everything in reach already: the march ends before this segment
             if (STATS) cnt[ST_HEIGHT] += steps_after<BOUNDED>(f, m, ka + 1, smax);
             go = false;
-            return;
+            return false;
         }
         m.kend = min(f.kmax, ka + ke);       // ke == kmax: still unknown
     }
@@ -705,6 +703,18 @@ __device__ __forceinline__ void march_segment(const FrameC& f, MarchState& m, fl
     if (SCAN == 2 && (MRTX_SEG_MASK & 2) != 0 && CF(f)->mip2 != nullptr) sg.jhi = last_kept_step<STATS, MRTX_PMASK_Q>(f, m, sg, cnt);
     if (SCAN == 3 && (MRTX_SEG_MASK & 1) != 0 && CF(f)->mip2 != nullptr) sg.jhi = last_kept_step<STATS, MRTX_PMASK_Q>(f, m, sg, cnt);   // A/B: the trial segment
     PROF_END(6);
+    return true;
+}
+// ONE 16-step segment of a march (the lanes that call it are still marching): anchors + skip interval, the steps
+// that can be at/below the surface, the termination test at the segment end.  `hit` / `sk_hit` are set by the step
+// that lands at/below the surface, `go` says whether the ray continues with the next segment.
+template <bool WIDE, bool PRIMARY, bool STATS, int BATCH, int SCAN = PRIMARY ? 1 : 0, bool BOUNDED = false>
+__device__ __forceinline__ void march_segment(const FrameC& f, MarchState& m, float smax, Seg& sg, bool& go, bool& hit,
+                                              float& sk_hit, uint32_t* cnt) {
+    const float oa = m.oa, ob = m.ob, oc = m.oc, da = m.da, db = m.db, dc = m.dc;
+    const int ka = m.ka;
+    float rowB, colB, q2B;
+    if (!segment_head<PRIMARY, STATS, SCAN, BOUNDED>(f, m, smax, sg, go, rowB, colB, q2B, cnt)) return;
     PROF_BEGIN(7);
     if (STATS) cnt[ST_HEIGHT] += count_in_steps<PRIMARY, BOUNDED>(f, oa, ob, oc, da, db, dc, smax, ka, 1, sg.jlo - 1);
     if (__ballot(sg.exact) != 0ull)
@@ -724,6 +734,152 @@ __device__ __forceinline__ void march_segment(const FrameC& f, MarchState& m, fl
 #endif
 #endif
     segment_tail<PRIMARY, STATS, BOUNDED>(f, m, smax, sg, go, rowB, colB, q2B, cnt);
+}
+
+// ---- The trial segment's steps, dealt out over the wave (render_kernel<MODE 2>).
+// The trial segment is the first segment (ka = 0) of the 64 continuation rays of a wave.  Its rays are incoherent: a few grazing ones
+// keep all their steps while most have none or one, and the serial loop (step_loop_from, one step per iteration) runs for as long as
+// the longest lane.  A step's evaluation is a pure function of the ray, the segment's quadratic and the step number, and the loop
+// carries nothing from step to step but "stop at the first step that is outside or at/below the surface" -- so the pending steps of
+// all lanes are laid out as ONE work list (a ray's steps contiguous, rays in lane order), the list is evaluated 64 items at a time by
+// the 64 lanes, and two ballots per window give every ray its first terminating item.  Same arithmetic per step (the expressions of step_loop_from / below_seg with sa = 0), same
+// first terminating step, same counters: items past a ray's terminating step are speculative fetches inside the segment's range, like
+// the second step of MRTX_STEP_BATCH 2, and are not credited.  Not a skip: it stays on under MRTX_F_NO_SKIP.
+//
+// Called by ALL 64 lanes of the wave in wave-uniform control flow (`live`: this lane has a trial segment set up).  Exchange through
+// LDS: three 16-byte slots per lane for a ray's state (`st`: slot-major like the parking slots, which are free during the trial) and
+// one spare 32-bit word per lane (`ctl`, stride four words; see below).
+#ifndef MRTX_TRIAL_WIDE
+#define MRTX_TRIAL_WIDE 1       // 0 = the serial loop (A/B switch; the results are the same bits)
+#endif
+#ifndef MRTX_TRIAL_WIDE_K
+#define MRTX_TRIAL_WIDE_K 5     // serial iterations before the pending steps are counted: the first ones still have most lanes at work
+                                // (render_kernel at cfg3: 0 -> 13.61 ms, 1 -> 13.33, 2 -> 13.00, 3 -> 12.85-12.91, 4 -> 12.86-12.95, 5 -> 12.86, 6 -> 12.94;
+                                // the serial loop 13.05-13.15)
+#endif
+#ifndef MRTX_TRIAL_WIDE_MIN
+#define MRTX_TRIAL_WIDE_MIN 2   // go wide when the longest lane has this many more steps pending than full rounds would take
+#endif
+typedef float xch4 __attribute__((ext_vector_type(4)));
+// one wave per workgroup: its LDS instructions execute in order; what is needed is that the compiler keeps them in order too
+__device__ __forceinline__ void xch_order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+// one step of a ka = 0, non-primary segment: step_loop_from's `in` and below_seg's `bel`, expression by expression
+template <bool WIDE>
+__device__ __forceinline__ void trial_step(const FrameC& f, float ra, float r1, float r2, float ca, float c1, float c2, float oa,
+                                           float ob, float oc, float da, float db, float dc, int k, bool& in, bool& bel) {
+    const float sk = (float)k * f.step;
+    const float pa = fmaf(sk, da, oa), pb = fmaf(sk, db, ob), pc = fmaf(sk, dc, oc);
+    const float q = fmaf(pc, pc, fmaf(pb, pb, pa * pa));
+    in = (q <= f.R2f) & (k <= f.kmax);
+    const float u = (sk - 0.0f) * f.inv_step;          // sg.sa = (float)0 * step
+    const float rowf = fmaf(u, fmaf(u, r2, r1), ra);
+    const float colf = fmaf(u, fmaf(u, c2, c1), ca);
+    const float surf = f.Rf * dem_march<WIDE>(f, rowf, colf);
+    bel = q <= surf * surf;
+}
+template <bool WIDE, bool STATS>
+__device__ __forceinline__ void trial_steps_wide(const FrameC& f, const MarchState& m, const Seg& sg, bool live, xch4* st,
+                                                 uint32_t* ctl, bool& go, bool& hit, float& sk_out, uint32_t* cnt) {
+    if (__ballot(live && sg.exact) != 0ull) {      // a lane in an exact-fallback segment: the wave keeps the serial loop
+        if (live) step_loop<WIDE, false, STATS, true, 1>(f, m.oa, m.ob, m.oc, m.da, m.db, m.dc, 0.0f, sg, 0, go, hit, sk_out, cnt);
+        return;
+    }
+    const uint32_t lane = threadIdx.x & 63u;
+    const int jhi = live ? sg.jhi : 0;
+    int j = live ? sg.jlo : 1;
+    bool pend = j <= jhi;
+#pragma unroll
+    for (int it = 0; it < MRTX_TRIAL_WIDE_K; it++) {
+        if (pend) {
+            bool in, bel;
+            trial_step<WIDE>(f, sg.ra, sg.r1, sg.r2, sg.ca, sg.c1, sg.c2, m.oa, m.ob, m.oc, m.da, m.db, m.dc, j, in, bel);
+            if (STATS) { cnt[ST_HEIGHT] += in ? 1u : 0u; cnt[ST_FETCH]++; }
+#ifdef MRTX_PROF
+            cnt[11] += 1;
+#endif
+            hit = in & bel; go = in & !bel; sk_out = (float)j * f.step;
+            j++;
+            pend = go & (j <= jhi);
+        }
+    }
+    // every lane's place in the work list: an exclusive prefix sum of the pending counts (at most SEG_N = 16: five ballots), their
+    // total and their maximum
+    uint32_t n, start, W, nmax;
+    auto deal = [&]() {
+        n = pend ? (uint32_t)(jhi - j + 1) : 0u;
+        start = 0u; W = 0u; nmax = 0u;
+        bool top = true;
+#pragma unroll
+        for (int b = 4; b >= 0; b--) {
+            const bool bit = ((n >> b) & 1u) != 0u;
+            const uint64_t mk = __ballot(bit);
+            start += __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u)) << b;
+            W += (uint32_t)__popcll(mk) << b;
+            if (__ballot(top && bit) != 0ull) { nmax |= 1u << b; top = top && bit; }
+        }
+    };
+    deal();
+    if (W == 0u) return;
+    if (((int)nmax - MRTX_TRIAL_WIDE_MIN) * 64 <= (int)W) {      // too few stragglers for a round's bookkeeping to pay
+        step_loop_from<WIDE, false, STATS, false, 1>(f, m.oa, m.ob, m.oc, m.da, m.db, m.dc, 0.0f, sg, 0, j, pend, go, hit, sk_out, cnt);
+        return;
+    }
+    // The list is cut into windows of 64 items.  Published once: every ray's state and (start, first pending step) under the ray's NUMBER
+    // among the rays with steps pending, and a bitmap of the list positions where a ray's steps begin -- the number of bits at or below
+    // an item's position is the number of the ray it belongs to.
+    const uint64_t rays = __ballot(n > 0u);
+    const uint32_t c = __builtin_amdgcn_mbcnt_hi((uint32_t)(rays >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rays, 0u));
+    uint16_t* const c16 = reinterpret_cast<uint16_t*>(ctl);     // spare word i = ctl[4 i]; words 0-31: the bitmap, 32-63: 64 16-bit entries
+    if (lane < 32u) ctl[lane * 4u] = 0u;
+    xch_order();
+    if (n > 0u) {
+        const xch4 a = {sg.ra, sg.r1, sg.r2, sg.ca}, b = {sg.c1, sg.c2, m.oa, m.ob}, cc = {m.oc, m.da, m.db, m.dc};
+        st[c] = a; st[64u + c] = b; st[128u + c] = cc;
+        c16[(32u + (c >> 1)) * 8u + (c & 1u)] = (uint16_t)(start | ((uint32_t)j << 10));
+        __hip_atomic_fetch_or(&ctl[(start >> 5) * 4u], 1u << (start & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    xch_order();
+    const uint64_t lanes_le = (2ull << lane) - 1ull;
+    uint32_t before = 0u;                                       // rays that begin below this window
+    for (uint32_t base = 0u;; base += 64u) {
+        const uint32_t h0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)ctl[(base >> 5) * 4u]);
+        const uint32_t h1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)ctl[((base >> 5) + 1u) * 4u]);
+        const uint64_t heads = ((uint64_t)h1 << 32) | h0;
+        const uint32_t ci = (before + (uint32_t)__popcll(heads & lanes_le) - 1u) & 63u;      // window 0 begins with a ray: never negative
+        const uint32_t t = base + lane;
+        const uint32_t sj = c16[(32u + (ci >> 1)) * 8u + (ci & 1u)];
+        const int jj = min((int)((sj >> 10) + (t - (sj & 1023u))), SEG_N);           // items past the end of the list stay inside the segment
+#ifdef MRTX_PROF_TRIAL
+        if (lane == 0u) { cnt[8] += 1u; cnt[9] += min(W - base, 64u); }              // wave-level: windows and the items in them
+#endif
+        const xch4 a = st[ci], b = st[64u + ci], cc = st[128u + ci];
+        bool in, bel;
+        trial_step<WIDE>(f, a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, cc.x, cc.y, cc.z, cc.w, jj, in, bel);
+        const uint64_t term = __ballot((t < W) & !(in & !bel)), inside = __ballot(in);
+        if (pend && start < base + 64u) {
+            // this ray's items in the window are the list positions [p0, p1): its first terminating one, if any
+            const uint32_t p0 = start > base ? start - base : 0u, p1 = min(start + n - base, 64u);
+            const uint64_t mine = term & ~((1ull << p0) - 1ull) & (p1 >= 64u ? ~0ull : (1ull << p1) - 1ull);
+            if (mine != 0ull) {
+                const uint32_t p = (uint32_t)__ffsll((long long)mine) - 1u;
+                const int jt = j + (int)(base + p - start);
+                hit = ((inside >> p) & 1ull) != 0ull;       // terminated inside: at or below the surface
+                go = false;
+                sk_out = (float)jt * f.step;
+                if (STATS) { cnt[ST_FETCH] += (uint32_t)(jt - j + 1); cnt[ST_HEIGHT] += (uint32_t)(jt - j) + (hit ? 1u : 0u); }
+                pend = false;
+            } else if (start + n <= base + 64u) {           // through all its steps: inside and above the surface at each
+                if (STATS) { cnt[ST_FETCH] += n; cnt[ST_HEIGHT] += n; }
+                pend = false;
+            }
+        }
+        if (__ballot(pend) == 0ull) break;
+        before += (uint32_t)__popc(h0) + (uint32_t)__popc(h1);
+    }
 }
 
 // Coarse march s_k = k*step, k = 1, 2, ...; returns true and s_k at the first sample at/below the surface.

@@ -44,7 +44,10 @@ for i, n in enumerate(names):
 print(f"  wave-level step iterations {v[11]} ({v[11] / max(1, v[10]):.1f} per wave), mean lanes evaluating {v[12] / max(1, v[11]):.1f}")
 print(f"  primary segments {v[15]} of which empty for the whole wave {v[13]}; shadow segments {v[8] - v[15]}, empty {v[14]}")
 if os.environ.get("TRIAL"):   # a -DMRTX_PROF -DMRTX_PROF_TRIAL build, PATH_SEG=2,4
+    # wave-level: the serial loop runs for as long as its longest lane (slot 13), and slot 14 sums the steps of all 64 lanes
     print(f"  TRIAL: step iterations {v[13]} ({v[13] / max(1, v[10]):.2f} per wave), mean lanes evaluating {v[14] / max(1, v[13]):.1f}; set-up + steps {v[15] / v[0]:.3f} of the trace")
+    print(f"  TRIAL, -DMRTX_TRIAL_WIDE=1: windows of 64 items {v[8]} ({v[8] / max(1, v[10]):.2f} per wave), items per window {v[9] / max(1, v[8]):.1f}")
+    sys.exit(0)        # slots 8 / 9 are the trial's in this build, not the segments'
 if os.environ.get("FULLIV"):   # a -DMRTX_PROF -DMRTX_PROF_FULLIV build
     print(f"  FULLIV: lane-segments {v[9]}, of which without a skip interval from the max-mip {v[13]} ({v[13] / max(1, v[9]):.3f}), exact-fallback {v[14]} ({v[14] / max(1, v[9]):.4f}); "
           f"of the former: footprint over more than two cell ROWS {v[5] / max(1, v[9]):.4f}, over more than the tap's COLUMNS {v[6] / max(1, v[9]):.4f}, map edge {v[7] / max(1, v[9]):.4f} "
