@@ -576,6 +576,50 @@ typedef struct MrtxReliefShare {
 int mrtx_relief_share(mrtx_ctx* ctx, const MrtxReliefShare* s, const void* dev_relief, const float* host_relief, void* dev_out,
                       float* host_out, MrtxStats* out);
 
+/* ---- Connected regions of a per-node map (additive to ABI 7) ---------------------------------------
+ * A lattice of rows x cols nodes, node (i, j) at index i cols + j, at most 2^31 nodes; wrap = 1 (needs cols >= 3) joins column
+ * cols - 1 to column 0, as in MrtxTraverse and MrtxReliefShare.  The set is given by exactly one of a field, rows x cols x n_ch
+ * float32 (1 <= n_ch <= 16): node in the set iff x >= (float)lo && x <= (float)hi for x = its channel ch (a NaN is out; lo =
+ * -inf and hi = +inf are allowed; lo <= hi, neither NaN), and a mask, rows x cols uint8: nonzero is in (n_ch, ch, lo, hi are
+ * not read then).  connectivity: 4 (N, E, S, W) or 8; no edge crosses the first or the last row.  A region is a connected
+ * component of the set, its root its least node index; regions are numbered 0 .. K - 1 in ascending order of their roots. */
+typedef struct MrtxRegions {
+    int32_t rows, cols;
+    int32_t wrap;           /* 1: column cols - 1 joins column 0 */
+    int32_t connectivity;   /* 4 or 8 */
+    int32_t n_ch, ch;       /* the field's channels and the one compared */
+    double lo, hi;          /* the closed interval of the set, compared as float32 */
+    int32_t reserved;       /* 0 */
+} MrtxRegions;
+/* One region of the catalogue, 56 bytes, all integers, so that it does not depend on the order of summation.  dj is a node's
+ * column relative to its region's root: j - root_j, and with wrap ((j - root_j + cols / 2) mod cols) - cols / 2 (integer
+ * division, non-negative mod). */
+typedef struct MrtxRegion {
+    uint64_t weight;        /* the sum of row_weight[i] over the region's nodes (= count without weights) */
+    int64_t sum_i;          /* the sum of i */
+    int64_t sum_dj;         /* the sum of dj */
+    uint32_t count;         /* nodes */
+    int32_t root_i, root_j; /* the root: the least node index */
+    int32_t i_min, i_max;   /* row extent */
+    int32_t dj_min, dj_max; /* column extent relative to the root's column */
+    uint32_t reserved;      /* 0 */
+} MrtxRegion;
+/* The labels of the set's regions: rows x cols int32, the region's number or -1 outside the set, into exactly one of
+ * dev_labels (4-byte aligned) and host_labels; *n_regions = K.  The input is exactly one of dev_field (4-byte aligned),
+ * host_field, dev_mask and host_mask; a device input must not overlap dev_labels.  Needs no DEM, no light and no Moon frame,
+ * and leaves the render state alone.  The number of launches depends on (rows, cols, wrap, connectivity) alone.  A refused
+ * call leaves *n_regions as it was.  out: launches, kernel_ms. */
+int mrtx_regions_label(mrtx_ctx* ctx, const MrtxRegions* r, const void* dev_field, const float* host_field, const void* dev_mask,
+                       const uint8_t* host_mask, void* dev_labels, int32_t* host_labels, uint32_t* n_regions, MrtxStats* out);
+/* The catalogue of a label table (exactly one of dev_labels, 4-byte aligned, and host_labels; it may be the caller's own):
+ * n_regions records into exactly one of dev_out (8-byte aligned, not overlapping dev_labels) and host_out.  row_weight: rows
+ * uint32 in host memory, the area of one node of row i in a unit of the caller's, or NULL: every node weighs 1.  Every entry
+ * of the table is checked in the kernels: one >= n_regions or < -1 is never used as an index, and the call returns
+ * MRTX_E_INVALID after the launch (the records are then not valid).  n_regions = 0 is valid: the table is checked and nothing
+ * is written.  A number no node carries gives count = 0, root (-1, -1) and extents 0.  out: launches, kernel_ms. */
+int mrtx_regions_stats(mrtx_ctx* ctx, int32_t rows, int32_t cols, int32_t wrap, const void* dev_labels, const int32_t* host_labels,
+                       uint32_t n_regions, const uint32_t* row_weight, void* dev_out, MrtxRegion* host_out, MrtxStats* out);
+
 /* ---- Mast-height horizons and joint windows (additive to ABI 7) ----------------------------------
  * mrtx_horizon_points from a raised origin: point p marches from P = fmaf(hs, u, o), hs = (float)(height_m[p] / radius_m * R),
  * the raised end of mrtx_sight_points (so a mast top is one point for the horizon and for the line of sight).  height_m: n

@@ -77,6 +77,19 @@ class MrtxReliefShare(C.Structure):
                 ("reserved", C.c_int32), ("grade_max", C.c_double), ("rms_max", C.c_double)]
 
 
+class MrtxRegions(C.Structure):
+    """The lattice, the connectivity and the interval of a region labelling (mrtx_regions_label)."""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("wrap", C.c_int32), ("connectivity", C.c_int32),
+                ("n_ch", C.c_int32), ("ch", C.c_int32), ("lo", C.c_double), ("hi", C.c_double), ("reserved", C.c_int32)]
+
+
+class MrtxRegion(C.Structure):
+    """One record of a region catalogue (mrtx_regions_stats): 56 bytes, all integers."""
+    _fields_ = [("weight", C.c_uint64), ("sum_i", C.c_int64), ("sum_dj", C.c_int64), ("count", C.c_uint32),
+                ("root_i", C.c_int32), ("root_j", C.c_int32), ("i_min", C.c_int32), ("i_max", C.c_int32),
+                ("dj_min", C.c_int32), ("dj_max", C.c_int32), ("reserved", C.c_uint32)]
+
+
 class MrtxIllumEpoch(C.Structure):
     """One date of a Sun-illumination series (mrtx_illum_series): what mrtx_set_light and
     mrtx_set_moon_frame would set for it."""
@@ -199,6 +212,10 @@ SIGNATURES = {
     "mrtx_relief_scales": (C.c_int, [C.POINTER(MrtxRelief), C.c_int32, C.c_int32, _VP]),
     "mrtx_relief": (C.c_int, [_VP, C.POINTER(MrtxRelief), _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_relief_share": (C.c_int, [_VP, C.POINTER(MrtxReliefShare), _VP, _VP, _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_regions_label": (C.c_int, [_VP, C.POINTER(MrtxRegions), _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_uint32),
+                                     C.POINTER(MrtxStats)]),
+    "mrtx_regions_stats": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, _VP, _VP, _VP,
+                                     C.POINTER(MrtxStats)]),
     "mrtx_thermal": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                C.POINTER(MrtxStats)]),
     "mrtx_view_dir_samples": (C.c_int, [C.c_int32, _VP]),

@@ -21,6 +21,7 @@
 
 #include "../../include/moonrt.h"
 #include "mrtx_device.h"
+#include "mrtx_regions.h"
 
 hipError_t mrtx_launch_render(const FrameC& f, int S, bool stats, int mode, bool overlay, const PathQ* pq, hipStream_t st);
 uint64_t mrtx_path_chunks(const FrameC& f, int S, uint32_t* grid_a, int* njobs_log2);
@@ -2390,6 +2391,124 @@ int mrtx_relief_share(mrtx_ctx* c, const MrtxReliefShare* s, const void* dev_rel
     HIPCHK(c, mrtx_launch_relief_share(q, c->stream));
     if ((rc = stage_finish(c, dev_out, host_out, 4 * N, out, kNoRays)) != MRTX_OK) return rc;
     if (out) out->launches = 3;
+    return MRTX_OK;
+}
+
+// ---- Connected regions of a per-node map ----------------------------------------------------------
+static_assert(sizeof(MrtxRegion) == 56 && sizeof(RegionRec) == sizeof(MrtxRegion), "MrtxRegion is 56 bytes");
+
+// the checks of a lattice that both calls share
+static int regions_lattice(mrtx_ctx* c, int32_t rows, int32_t cols, int32_t wrap) {
+    if (rows < 1 || cols < 1) return fail(c, MRTX_E_INVALID, "empty lattice (%d x %d)", rows, cols);
+    if ((int64_t)rows * (int64_t)cols > (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "a lattice holds at most 2^31 nodes (got %d x %d)", rows, cols);
+    if (wrap != 0 && wrap != 1) return fail(c, MRTX_E_INVALID, "wrap must be 0 or 1 (got %d)", wrap);
+    if (wrap && cols < 3) return fail(c, MRTX_E_INVALID, "a wrapped lattice needs cols >= 3 (got %d)", cols);
+    return MRTX_OK;
+}
+
+int mrtx_regions_label(mrtx_ctx* c, const MrtxRegions* r, const void* dev_field, const float* host_field, const void* dev_mask,
+                       const uint8_t* host_mask, void* dev_labels, int32_t* host_labels, uint32_t* n_regions, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!r) return fail(c, MRTX_E_INVALID, "null regions block");
+    if (r->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    int rc = regions_lattice(c, r->rows, r->cols, r->wrap);
+    if (rc != MRTX_OK) return rc;
+    if (r->connectivity != 4 && r->connectivity != 8) return fail(c, MRTX_E_INVALID, "connectivity must be 4 or 8 (got %d)", r->connectivity);
+    const bool has_field = dev_field || host_field, has_mask = dev_mask || host_mask;
+    if (has_field == has_mask) return fail(c, MRTX_E_INVALID, "give exactly one of a field and a mask");
+    if (dev_field && host_field) return fail(c, MRTX_E_INVALID, "give exactly one of dev_field and host_field");
+    if (dev_mask && host_mask) return fail(c, MRTX_E_INVALID, "give exactly one of dev_mask and host_mask");
+    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
+    if (!n_regions) return fail(c, MRTX_E_INVALID, "null n_regions");
+    if (has_field) {
+        if (r->n_ch < 1 || r->n_ch > 16) return fail(c, MRTX_E_INVALID, "n_ch must lie in 1 .. 16 (got %d)", r->n_ch);
+        if (r->ch < 0 || r->ch >= r->n_ch) return fail(c, MRTX_E_INVALID, "ch must lie in 0 .. n_ch - 1 (got %d of %d)", r->ch, r->n_ch);
+        if (std::isnan(r->lo) || std::isnan(r->hi)) return fail(c, MRTX_E_INVALID, "lo and hi must not be NaN");
+        if (r->lo > r->hi) return fail(c, MRTX_E_INVALID, "lo must be <= hi (got %g > %g)", r->lo, r->hi);
+    }
+    if (dev_field && (reinterpret_cast<uintptr_t>(dev_field) & 3)) return fail(c, MRTX_E_INVALID, "dev_field must be 4-byte aligned (float32)");
+    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
+    const size_t N = (size_t)r->rows * (size_t)r->cols;
+    const size_t in_bytes = has_field ? 4 * N * (size_t)r->n_ch : N;
+    if (traverse_overlap(dev_field ? dev_field : dev_mask, in_bytes, dev_labels, 4 * N))
+        return fail(c, MRTX_E_INVALID, "the device input and dev_labels must not overlap");
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    RegionsC q;
+    std::memset(&q, 0, sizeof q);
+    q.n_chunks = (uint32_t)((N + MRTX_RG_CHUNK - 1) / MRTX_RG_CHUNK);
+    q.tiles_x = (r->cols + MRTX_RG_TW - 1) / MRTX_RG_TW;
+    // scratch: the forest, the chunks' counts, K
+    const size_t sums_at = 4 * N, total_at = sums_at + 4 * (size_t)q.n_chunks;
+    if ((rc = stage_out(c, dev_labels, 4 * N)) != MRTX_OK ||
+        (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, total_at + 16)) != MRTX_OK)
+        return rc;
+    if (host_field || host_mask) {      // the caller's memory stays put until stage_finish
+        if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, std::max(in_bytes, (size_t)16))) != MRTX_OK) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->illum_tab, host_field ? (const void*)host_field : (const void*)host_mask, in_bytes,
+                                 hipMemcpyHostToDevice, c->stream));
+    }
+    char* tb = reinterpret_cast<char*>(c->trav_buf);
+    if (has_field) q.field = host_field ? c->illum_tab : static_cast<const float*>(dev_field);
+    else q.mask = host_mask ? reinterpret_cast<const uint8_t*>(c->illum_tab) : static_cast<const uint8_t*>(dev_mask);
+    q.parent = reinterpret_cast<int32_t*>(tb);
+    q.sums = reinterpret_cast<uint32_t*>(tb + sums_at);
+    q.total = reinterpret_cast<uint32_t*>(tb + total_at);
+    q.labels = static_cast<int32_t*>(dev_labels);
+    q.rows = r->rows; q.cols = r->cols; q.wrap = r->wrap; q.conn8 = r->connectivity == 8; q.n_ch = r->n_ch; q.ch = r->ch;
+    q.lo = (float)r->lo; q.hi = (float)r->hi;
+    uint32_t launches = 0, K = 0;
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_regions_label(q, c->stream, &launches));
+    if ((rc = stage_finish(c, dev_labels, reinterpret_cast<float*>(host_labels), 4 * N, out, kNoRays)) != MRTX_OK) return rc;
+    HIPCHK(c, hipMemcpy(&K, q.total, sizeof K, hipMemcpyDeviceToHost));
+    *n_regions = K;
+    if (out) out->launches = launches;
+    return MRTX_OK;
+}
+
+int mrtx_regions_stats(mrtx_ctx* c, int32_t rows, int32_t cols, int32_t wrap, const void* dev_labels, const int32_t* host_labels,
+                       uint32_t n_regions, const uint32_t* row_weight, void* dev_out, MrtxRegion* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    int rc = regions_lattice(c, rows, cols, wrap);
+    if (rc != MRTX_OK) return rc;
+    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    const size_t N = (size_t)rows * (size_t)cols;
+    if ((size_t)n_regions > N) return fail(c, MRTX_E_INVALID, "n_regions = %u exceeds the lattice's %zu nodes", n_regions, N);
+    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
+    if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 7)) return fail(c, MRTX_E_INVALID, "dev_out must be 8-byte aligned (MrtxRegion)");
+    const size_t out_bytes = sizeof(MrtxRegion) * (size_t)n_regions;
+    if (traverse_overlap(dev_labels, 4 * N, dev_out, out_bytes)) return fail(c, MRTX_E_INVALID, "dev_labels and dev_out must not overlap");
+    // MOONRT_REGIONS_CATALOGUE=plain: one set of atomics per node, the yardstick of the in-wave run reduction; the same records
+    bool runs = true;
+    if (const char* e = std::getenv("MOONRT_REGIONS_CATALOGUE")) {
+        if (std::strcmp(e, "plain") == 0) runs = false;
+        else if (std::strcmp(e, "runs") != 0) return fail(c, MRTX_E_INVALID, "MOONRT_REGIONS_CATALOGUE must be runs or plain (got %s)", e);
+    }
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    float* d[2] = {nullptr, nullptr};
+    if ((rc = stage_out(c, dev_out, std::max(out_bytes, sizeof(MrtxRegion)))) != MRTX_OK ||
+        (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, 16)) != MRTX_OK ||
+        (rc = stage_tables(c, {{host_labels, host_labels ? N : 0}, {row_weight, row_weight ? (size_t)rows : 0}}, d)) != MRTX_OK)
+        return rc;
+    RegionStatsC q;
+    std::memset(&q, 0, sizeof q);
+    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_labels);
+    q.row_weight = row_weight ? reinterpret_cast<const uint32_t*>(d[1]) : nullptr;
+    q.out = static_cast<RegionRec*>(dev_out);
+    q.bad = reinterpret_cast<uint32_t*>(c->trav_buf);
+    q.rows = rows; q.cols = cols; q.wrap = wrap; q.n_regions = n_regions;
+    uint32_t launches = 0, bad = 0;
+    HIPCHK(c, hipMemsetAsync(q.bad, 0, 16, c->stream));
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_regions_stats(q, runs, c->stream, &launches));
+    if ((rc = stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays)) != MRTX_OK) return rc;
+    if (out) out->launches = launches;
+    HIPCHK(c, hipMemcpy(&bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad) return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", bad, (long long)n_regions - 1);
     return MRTX_OK;
 }
 

@@ -1,0 +1,101 @@
+"""Connected regions of a per-node terrain map: what MoonRT.regions returns, the per-row node areas
+that make a region's area an exact integer sum, and helpers over the catalogue.
+
+A region is a connected component (4- or 8-connected, the columns joined across the seam when the map is wrapped) of the nodes
+a predicate selects; its root is its least node index i cols + j, and regions are numbered in ascending order of their roots.
+The catalogue is all integers: it does not depend on the order in which the device summed it."""
+import math
+
+import numpy as np
+
+# mirrors MrtxRegion (include/moonrt.h), 56 bytes
+REGION_DTYPE = np.dtype([("weight", "<u8"), ("sum_i", "<i8"), ("sum_dj", "<i8"), ("count", "<u4"), ("root_i", "<i4"),
+                         ("root_j", "<i4"), ("i_min", "<i4"), ("i_max", "<i4"), ("dj_min", "<i4"), ("dj_max", "<i4"),
+                         ("reserved", "<u4")])
+assert REGION_DTYPE.itemsize == 56
+
+WEIGHT_MAX = 2 ** 32 - 1
+
+
+def row_weights(window, dem_hw, radius_m=1737400.0, unit_m2=1.0):
+    """(rows,) uint32: the area of one lattice cell of every row of a window (row0, col0, rows, cols[, stride[, wrap]]) of an
+    (H, W) DEM, in units of unit_m2 square metres, rounded to the nearest integer.  A cell is stride 2 pi / W wide in
+    longitude; in latitude it reaches half a row spacing (stride pi / H / 2) either side of the latitude of the row's texel
+    centres, pi / 2 - (row + 1 / 2) pi / H, clipped to the poles.  float64 spherical area radius_m^2 dlon (sin a - sin b).
+    ValueError for a weight that rounds to zero or does not fit 32 bits: choose another unit."""
+    from .traverse import window_dict
+    w = window_dict(window)
+    H, W = (int(v) for v in dem_hw)
+    if not (radius_m > 0.0 and unit_m2 > 0.0 and math.isfinite(radius_m) and math.isfinite(unit_m2)):
+        raise ValueError("radius_m and unit_m2 must be finite and > 0")
+    if w["rows"] < 1 or w["stride"] < 1 or H < 1 or W < 1:
+        raise ValueError("empty window or DEM")
+    if w["row0"] < 0 or w["row0"] + (w["rows"] - 1) * w["stride"] >= H:
+        raise ValueError(f"the window's rows leave the DEM's {H} rows")
+    row = w["row0"] + np.arange(w["rows"], dtype=np.float64) * w["stride"]
+    lat = 0.5 * math.pi - (row + 0.5) * (math.pi / H)
+    half = 0.5 * w["stride"] * math.pi / H
+    north = np.minimum(lat + half, 0.5 * math.pi)
+    south = np.maximum(lat - half, -0.5 * math.pi)
+    area = float(radius_m) ** 2 * (w["stride"] * 2.0 * math.pi / W) * (np.sin(north) - np.sin(south))
+    q = np.rint(area / float(unit_m2))
+    if not np.all(q >= 1.0):
+        k = int(np.argmin(q))
+        raise ValueError(f"row {k}: a node's area {area[k]:g} m^2 rounds to zero units of {unit_m2:g} m^2: use a smaller unit")
+    if not np.all(q <= WEIGHT_MAX):
+        k = int(np.argmax(q))
+        raise ValueError(f"row {k}: a node's area {area[k]:g} m^2 does not fit 32 bits in units of {unit_m2:g} m^2: use a larger unit")
+    return q.astype(np.uint32)
+
+
+class RegionMap:
+    """labels (rows, cols) int32, the region's number or -1; table (n,) REGION_DTYPE; n; wrap; unit_m2 = the square metres of
+    one unit of weight when the map was made with row weights of a known unit (else None: a weight is a node count or the
+    caller's own unit)."""
+
+    def __init__(self, labels, table, wrap=False, unit_m2=None):
+        self.labels = np.ascontiguousarray(labels, np.int32)
+        self.table = np.ascontiguousarray(table, REGION_DTYPE).reshape(-1)
+        if self.labels.ndim != 2:
+            raise ValueError("labels must be (rows, cols)")
+        self.n = int(self.table.shape[0])
+        self.wrap = bool(wrap)
+        self.unit_m2 = None if unit_m2 is None else float(unit_m2)
+
+    def area_m2(self, unit_m2=None):
+        """(n,) float64 areas: weight x unit_m2 (the map's own unit when none is given)."""
+        u = self.unit_m2 if unit_m2 is None else float(unit_m2)
+        if u is None:
+            raise ValueError("the map has no unit: give unit_m2")
+        return self.table["weight"].astype(np.float64) * u
+
+    def centroids(self, lat, lon):
+        """(n, 2) float64 (lat, lon) degrees of the regions' node-count centroids, from the node axes lat (rows,) and lon
+        (cols,) (MoonRT.traverse_nodes): row sum_i / count, column root_j + sum_dj / count, so a region that straddles the
+        seam of a wrapped map has its centroid on the seam and not half a circle away.  lon comes back in [-180, 180)."""
+        lat, lon = np.asarray(lat, np.float64), np.asarray(lon, np.float64)
+        rows, cols = self.labels.shape
+        if lat.shape != (rows,) or lon.shape != (cols,):
+            raise ValueError("lat must be (rows,) and lon (cols,)")
+        t = self.table
+        cnt = np.maximum(t["count"].astype(np.float64), 1.0)
+        dlat = lat[1] - lat[0] if rows > 1 else 0.0
+        dlon = ((lon[1] - lon[0] + 180.0) % 360.0 - 180.0) if cols > 1 else 0.0
+        la = lat[0] + (t["sum_i"] / cnt) * dlat
+        lo = lon[np.clip(t["root_j"], 0, cols - 1)] + (t["sum_dj"] / cnt) * dlon
+        return np.stack([la, (lo + 180.0) % 360.0 - 180.0], -1)
+
+    def largest(self, k=1):
+        """The numbers of the k regions of greatest weight, greatest first (equal weights: the lower number first)."""
+        order = np.lexsort((np.arange(self.n), -self.table["weight"].astype(np.float64)))
+        return order[:max(int(k), 0)]
+
+    def filter(self, min_count=0, min_area=0.0):
+        """A new RegionMap of the regions with count >= min_count and area >= min_area (square metres when the map has a
+        unit, else units of weight), renumbered in their old order; the nodes of the others get -1."""
+        t = self.table
+        area = t["weight"].astype(np.float64) * (self.unit_m2 if self.unit_m2 is not None else 1.0)
+        keep = (t["count"] >= min_count) & (area >= min_area)
+        new = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int32)
+        lut = np.concatenate([new, np.array([-1], np.int32)])       # label -1 reads the last entry
+        return RegionMap(lut[self.labels], t[keep], self.wrap, self.unit_m2)

@@ -1085,6 +1085,76 @@ class MoonRT:
         self._add_stats(stats, st)
         return out
 
+    # ---- Connected regions of a per-node map
+    def regions(self, field=None, mask=None, channel=0, lo=-math.inf, hi=math.inf, connectivity=4, wrap=False,
+                row_weights=None, stats=None, shape=None, unit_m2=None):
+        """The connected regions of a set of lattice nodes (mrtx_regions_label, mrtx_regions_stats).  Exactly one of `field`,
+        (rows, cols) or (rows, cols, n_ch) float32: the nodes with lo <= field[..., channel] <= hi, compared as float32 (NaN
+        is out), and `mask`, (rows, cols) uint8: the nonzero nodes.  Either may be a numpy array or a DeviceBuffer (then give
+        shape = (rows, cols[, n_ch]); labels and catalogue are made in device tables and downloaded).  connectivity 4 or 8;
+        wrap joins the last column to the first (cols >= 3).  row_weights: (rows,) uint32 node areas (regions.row_weights),
+        or None: every node weighs 1; unit_m2: their unit, remembered by the map.  Needs no DEM.  Returns a
+        moonrtx_amd.regions.RegionMap; `stats`, if a dict, receives the summed counters and label_ms / catalogue_ms."""
+        from . import regions as rg
+        if (field is None) == (mask is None):
+            raise ValueError("give exactly one of field and mask")
+        src = field if field is not None else mask
+        on_device = isinstance(src, DeviceBuffer)
+        if on_device:
+            if shape is None:
+                raise ValueError("a DeviceBuffer needs shape = (rows, cols[, n_ch])")
+            shp = tuple(int(v) for v in shape)
+        else:
+            src = np.ascontiguousarray(src, np.float32 if field is not None else np.uint8)
+            shp = src.shape
+        if field is not None and len(shp) == 2:
+            shp = shp + (1,)
+        if len(shp) != (3 if field is not None else 2):
+            raise ValueError("field must be (rows, cols) or (rows, cols, n_ch), mask (rows, cols)")
+        rows, cols = shp[0], shp[1]
+        n_ch = shp[2] if field is not None else 1
+        if on_device and src.nbytes < rows * cols * (4 * n_ch if field is not None else 1):
+            raise ValueError("the DeviceBuffer is smaller than its shape")
+        weights = None
+        if row_weights is not None:
+            weights = np.ascontiguousarray(row_weights)
+            if weights.shape != (rows,) or not np.issubdtype(weights.dtype, np.integer) or \
+                    (weights.size and (weights.min() < 0 or weights.max() > rg.WEIGHT_MAX)):
+                raise ValueError("row_weights must be (rows,) integers in 0 .. 2^32 - 1")
+            weights = weights.astype(np.uint32)
+        r = _lib.MrtxRegions(rows, cols, 1 if wrap else 0, int(connectivity), n_ch, int(channel), float(lo), float(hi), 0)
+        n = C.c_uint32(0)
+        st, st2 = MrtxStats(), MrtxStats()
+        wp = weights.ctypes.data if weights is not None else None
+        if on_device:
+            lab = DeviceBuffer(max(4 * rows * cols, 4), src.device)
+            args = (src.ptr, None, None, None) if field is not None else (None, None, src.ptr, None)
+            self._check(self._lib.mrtx_regions_label(self._ctx, C.byref(r), *args, lab.ptr, None, C.byref(n), C.byref(st)),
+                        "mrtx_regions_label")
+            rec = DeviceBuffer(max(56 * n.value, 56), src.device)
+            self._check(self._lib.mrtx_regions_stats(self._ctx, rows, cols, r.wrap, lab.ptr, None, n.value, wp, rec.ptr, None,
+                                                     C.byref(st2)), "mrtx_regions_stats")
+            labels = lab.download(np.int32, (rows, cols))
+            table = rec.download(rg.REGION_DTYPE, (n.value,))
+            lab.free()
+            rec.free()
+        else:
+            labels = np.empty((rows, cols), np.int32)
+            args = (None, src.ctypes.data, None, None) if field is not None else (None, None, None, src.ctypes.data)
+            self._check(self._lib.mrtx_regions_label(self._ctx, C.byref(r), *args, None, labels.ctypes.data, C.byref(n),
+                                                     C.byref(st)), "mrtx_regions_label")
+            table = np.zeros(max(n.value, 1), rg.REGION_DTYPE)
+            self._check(self._lib.mrtx_regions_stats(self._ctx, rows, cols, r.wrap, None, labels.ctypes.data, n.value, wp, None,
+                                                     table.ctypes.data, C.byref(st2)), "mrtx_regions_stats")
+            table = table[:n.value]
+        self._add_stats(stats, st)
+        self._add_stats(stats, st2)
+        if isinstance(stats, dict):
+            stats["label_ms"] = stats.get("label_ms", 0.0) + st.kernel_ms
+            stats["catalogue_ms"] = stats.get("catalogue_ms", 0.0) + st2.kernel_ms
+            stats["label_launches"] = stats.get("label_launches", 0) + st.launches
+        return rg.RegionMap(labels, table, wrap, unit_m2)
+
     @staticmethod
     def _add_stats(acc, st, extra=None):
         """Sum the counters of one call into the dict `acc` (if it is one); extra = {key: MrtxStats field} of the call's own."""
