@@ -29,7 +29,7 @@ def subsolar_latlon(scene):
 
 def illuminate(scene, dem, lat_deg, lon_deg, samples):
     """Per node: dict(lit, irr, mu, D) (float64, shape (N,)), V (N, n) per-sample visibility (cos > 0 and escaping),
-    flagged (N, n) and shadow_rays (the samples with cos > 0)."""
+    flagged (N, n), shadow_rays (the samples with cos > 0) and carried (N, n), what each sample carries when it arrives."""
     dem = dem if hasattr(dem, "shape") else np.asarray(dem)
     R = float(scene.radius)
     la = np.radians(np.asarray(lat_deg, float).ravel())
@@ -70,4 +70,5 @@ def illuminate(scene, dem, lat_deg, lon_deg, samples):
     fl = near["march"] | near["exit"] | near["cosine"]
     V = V.reshape(N, n)
     return dict(lit=V.mean(1), irr=np.where(V, carried.reshape(N, n), 0.0).mean(1), mu=mu, D=D, V=V,
-                flagged=fl.reshape(N, n), shadow_rays=int(up.size), cos_pos=(cosi > 0).reshape(N, n), cosi=cosi.reshape(N, n))
+                flagged=fl.reshape(N, n), shadow_rays=int(up.size), cos_pos=(cosi > 0).reshape(N, n), cosi=cosi.reshape(N, n),
+                carried=carried.reshape(N, n))
