@@ -620,6 +620,72 @@ int mrtx_regions_label(mrtx_ctx* ctx, const MrtxRegions* r, const void* dev_fiel
 int mrtx_regions_stats(mrtx_ctx* ctx, int32_t rows, int32_t cols, int32_t wrap, const void* dev_labels, const int32_t* host_labels,
                        uint32_t n_regions, const uint32_t* row_weight, void* dev_out, MrtxRegion* host_out, MrtxStats* out);
 
+/* ---- Zonal statistics and outlines of labelled regions (additive to ABI 7) -------------------------
+ * What is inside each region of a label table and what shape it has.  Lattice, wrap, label tables and their bound checks are
+ * mrtx_regions_stats': every entry is checked in the kernels, one >= n_regions or < -1 is never used as an index and gives
+ * MRTX_E_INVALID after the launch; n_regions = 0 checks the table and writes nothing; a number no node carries gets an empty
+ * record.  Both calls need no DEM, no light and no Moon frame and leave the render state alone; the number of launches depends
+ * on the lattice, n_regions and the options alone.  Every result is exact: integer sums modulo 2^64 (counts modulo 2^32) and
+ * float comparisons, nothing depends on the order of a reduction. */
+typedef struct MrtxZonalSpec {
+    int32_t rows, cols;
+    int32_t wrap;           /* 0 or 1, checked as in mrtx_regions_stats (the statistics themselves do not depend on it) */
+    int32_t n_ch;           /* the field's channels, 1 .. 16: every one gets a record per region */
+    double scale;           /* the fixed point: q = llrint((double)x * scale), finite and > 0 */
+    int32_t hist_ch;        /* the channel of the histogram, 0 .. n_ch - 1 (not read when n_bins = 0) */
+    int32_t n_bins;         /* 0: no histogram; else 1 .. 4096 */
+    double hist_lo;         /* the lower edge of bin 0, finite */
+    double hist_inv_w;      /* bins per unit of the field, n_bins / (hi - lo): finite and > 0 */
+    int32_t reserved;       /* 0 */
+} MrtxZonalSpec;
+/* One channel of one region, 56 bytes.  A NaN adds to n_nan only; every other value (the infinities too) is counted.  Its
+ * fixed-point value is q = llrint((double)x * scale), one float64 product rounded half to even; when |(double)x * scale| >=
+ * 2^31 the value adds to n_clipped and q is +-2^31 with the product's sign.  min, max and their places are taken in the total
+ * order of the float32 bit patterns (-0.0 precedes +0.0), the least node index among equals. */
+typedef struct MrtxZonal {
+    uint64_t wcount;        /* the sum of row_weight[i] over the counted nodes (= count without weights) */
+    int64_t wsum;           /* the sum of row_weight[i] * q, modulo 2^64 */
+    int64_t sum;            /* the sum of q */
+    uint32_t count;         /* counted nodes: the value is not NaN */
+    uint32_t n_nan;
+    uint32_t n_clipped;
+    float min, max;         /* +inf and -inf when count == 0 */
+    int32_t min_at, max_at; /* node index i cols + j of the extreme; -1 when count == 0 */
+    uint32_t reserved;      /* 0 */
+} MrtxZonal;
+/* n_regions x n_ch records, region-major, into exactly one of dev_out (8-byte aligned) and host_out, of the field rows x cols
+ * x n_ch float32 in exactly one of dev_field (4-byte aligned) and host_field, over the label table in exactly one of
+ * dev_labels and host_labels.  row_weight: rows uint32 in host memory or NULL (every node weighs 1).  With n_bins > 0 also
+ * n_regions x (n_bins + 2) uint64, at most 2^28 in all, into exactly one of dev_hist (8-byte aligned) and host_hist (both
+ * NULL when n_bins = 0): a counted value of channel hist_ch adds its node's weight to column 0 when t = ((double)x - hist_lo)
+ * * hist_inv_w < 0, to column n_bins + 1 when t >= n_bins, else to column 1 + floor(t) (one float64 subtraction, one float64
+ * product).  No two device tables may overlap.  MOONRT_REGIONS_ZONAL = runs (default) | plain chooses between the in-wave
+ * reduction of runs of one label and one set of atomics per node; both give the same bytes.  out: launches, kernel_ms. */
+int mrtx_regions_zonal(mrtx_ctx* ctx, const MrtxZonalSpec* z, const void* dev_labels, const int32_t* host_labels,
+                       uint32_t n_regions, const void* dev_field, const float* host_field, const uint32_t* row_weight,
+                       void* dev_out, MrtxZonal* host_out, void* dev_hist, uint64_t* host_hist, MrtxStats* out);
+/* One region's outline, 32 bytes.  A side of a node's cell is on the boundary when the node across it lies outside the lattice
+ * or carries another label (-1 included); with wrap the node east of the last column is column 0; a north or south side is
+ * never wrapped.  q1, q3, qd: the 2 x 2 windows of nodes (i - 1 .. i, j - 1 .. j), i = 0 .. rows, j = 0 .. cols (with wrap j =
+ * 0 .. cols - 1, column j - 1 taken mod cols; nodes outside the lattice belong to no region), in which exactly one, exactly
+ * three, and exactly the two nodes of one diagonal carry the region's label.  euler = (q1 - q3 + 2 qd) / 4 for connectivity 4
+ * and (q1 - q3 - 2 qd) / 4 for 8 (Gray 1971): components minus holes. */
+typedef struct MrtxRegionShape {
+    uint64_t perimeter;     /* the sum of the lengths of the boundary sides */
+    uint32_t sides_ns;      /* boundary sides that face north or south */
+    uint32_t sides_ew;      /* boundary sides that face east or west */
+    uint32_t q1, q3, qd;
+    int32_t euler;
+} MrtxRegionShape;
+/* n_regions records into exactly one of dev_out (8-byte aligned, not overlapping dev_labels) and host_out.  side_ew: rows
+ * uint32 in host memory, the length of the east and of the west side of a cell of row i; side_ns: rows + 1 uint32, entry i the
+ * length of the side between rows i - 1 and i (entry 0 the north side of row 0, entry rows the south side of the last row);
+ * both or neither, with neither every side counts 1.  connectivity: 4 or 8, the sense in which euler counts.  out: launches,
+ * kernel_ms. */
+int mrtx_regions_shape(mrtx_ctx* ctx, int32_t rows, int32_t cols, int32_t wrap, int32_t connectivity, const void* dev_labels,
+                       const int32_t* host_labels, uint32_t n_regions, const uint32_t* side_ew, const uint32_t* side_ns,
+                       void* dev_out, MrtxRegionShape* host_out, MrtxStats* out);
+
 /* ---- Mast-height horizons and joint windows (additive to ABI 7) ----------------------------------
  * mrtx_horizon_points from a raised origin: point p marches from P = fmaf(hs, u, o), hs = (float)(height_m[p] / radius_m * R),
  * the raised end of mrtx_sight_points (so a mast top is one point for the horizon and for the line of sight).  height_m: n

@@ -90,6 +90,26 @@ class MrtxRegion(C.Structure):
                 ("dj_min", C.c_int32), ("dj_max", C.c_int32), ("reserved", C.c_uint32)]
 
 
+class MrtxZonalSpec(C.Structure):
+    """The lattice, the fixed point and the histogram of zonal statistics (mrtx_regions_zonal)."""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("wrap", C.c_int32), ("n_ch", C.c_int32), ("scale", C.c_double),
+                ("hist_ch", C.c_int32), ("n_bins", C.c_int32), ("hist_lo", C.c_double), ("hist_inv_w", C.c_double),
+                ("reserved", C.c_int32)]
+
+
+class MrtxZonal(C.Structure):
+    """One channel of one region (mrtx_regions_zonal): 56 bytes, all exact."""
+    _fields_ = [("wcount", C.c_uint64), ("wsum", C.c_int64), ("sum", C.c_int64), ("count", C.c_uint32), ("n_nan", C.c_uint32),
+                ("n_clipped", C.c_uint32), ("min", C.c_float), ("max", C.c_float), ("min_at", C.c_int32), ("max_at", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
+class MrtxRegionShape(C.Structure):
+    """One region's outline (mrtx_regions_shape): 32 bytes, all integers."""
+    _fields_ = [("perimeter", C.c_uint64), ("sides_ns", C.c_uint32), ("sides_ew", C.c_uint32), ("q1", C.c_uint32),
+                ("q3", C.c_uint32), ("qd", C.c_uint32), ("euler", C.c_int32)]
+
+
 class MrtxIllumEpoch(C.Structure):
     """One date of a Sun-illumination series (mrtx_illum_series): what mrtx_set_light and
     mrtx_set_moon_frame would set for it."""
@@ -215,6 +235,10 @@ SIGNATURES = {
     "mrtx_regions_label": (C.c_int, [_VP, C.POINTER(MrtxRegions), _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_uint32),
                                      C.POINTER(MrtxStats)]),
     "mrtx_regions_stats": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, _VP, _VP, _VP,
+                                     C.POINTER(MrtxStats)]),
+    "mrtx_regions_zonal": (C.c_int, [_VP, C.POINTER(MrtxZonalSpec), _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                     C.POINTER(MrtxStats)]),
+    "mrtx_regions_shape": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP,
                                      C.POINTER(MrtxStats)]),
     "mrtx_thermal": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                C.POINTER(MrtxStats)]),

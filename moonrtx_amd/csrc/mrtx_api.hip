@@ -22,6 +22,7 @@
 #include "../../include/moonrt.h"
 #include "mrtx_device.h"
 #include "mrtx_regions.h"
+#include "mrtx_zonal.h"
 
 hipError_t mrtx_launch_render(const FrameC& f, int S, bool stats, int mode, bool overlay, const PathQ* pq, hipStream_t st);
 uint64_t mrtx_path_chunks(const FrameC& f, int S, uint32_t* grid_a, int* njobs_log2);
@@ -2505,6 +2506,139 @@ int mrtx_regions_stats(mrtx_ctx* c, int32_t rows, int32_t cols, int32_t wrap, co
     HIPCHK(c, hipMemsetAsync(q.bad, 0, 16, c->stream));
     if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
     HIPCHK(c, mrtx_launch_regions_stats(q, runs, c->stream, &launches));
+    if ((rc = stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays)) != MRTX_OK) return rc;
+    if (out) out->launches = launches;
+    HIPCHK(c, hipMemcpy(&bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad) return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", bad, (long long)n_regions - 1);
+    return MRTX_OK;
+}
+
+// ---- Zonal statistics and outlines of labelled regions -------------------------------------------
+static_assert(sizeof(MrtxZonal) == 56 && sizeof(ZonalRec) == sizeof(MrtxZonal), "MrtxZonal is 56 bytes");
+static_assert(sizeof(MrtxRegionShape) == 32 && sizeof(ShapeRec) == sizeof(MrtxRegionShape), "MrtxRegionShape is 32 bytes");
+
+// MOONRT_REGIONS_ZONAL=plain: one set of atomics per node, the yardstick of the in-wave run reduction; the same records
+static int zonal_variant(mrtx_ctx* c, bool* runs) {
+    *runs = true;
+    if (const char* e = std::getenv("MOONRT_REGIONS_ZONAL")) {
+        if (std::strcmp(e, "plain") == 0) *runs = false;
+        else if (std::strcmp(e, "runs") != 0) return fail(c, MRTX_E_INVALID, "MOONRT_REGIONS_ZONAL must be runs or plain (got %s)", e);
+    }
+    return MRTX_OK;
+}
+
+int mrtx_regions_zonal(mrtx_ctx* c, const MrtxZonalSpec* z, const void* dev_labels, const int32_t* host_labels, uint32_t n_regions,
+                       const void* dev_field, const float* host_field, const uint32_t* row_weight, void* dev_out,
+                       MrtxZonal* host_out, void* dev_hist, uint64_t* host_hist, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!z) return fail(c, MRTX_E_INVALID, "null zonal block");
+    if (z->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    int rc = regions_lattice(c, z->rows, z->cols, z->wrap);
+    if (rc != MRTX_OK) return rc;
+    if (z->n_ch < 1 || z->n_ch > 16) return fail(c, MRTX_E_INVALID, "n_ch must lie in 1 .. 16 (got %d)", z->n_ch);
+    if (!std::isfinite(z->scale) || !(z->scale > 0.0)) return fail(c, MRTX_E_INVALID, "scale must be finite and > 0 (got %g)", z->scale);
+    if (z->n_bins < 0 || z->n_bins > 4096) return fail(c, MRTX_E_INVALID, "n_bins must lie in 0 .. 4096 (got %d)", z->n_bins);
+    if (z->n_bins) {
+        if (z->hist_ch < 0 || z->hist_ch >= z->n_ch)
+            return fail(c, MRTX_E_INVALID, "hist_ch must lie in 0 .. n_ch - 1 (got %d of %d)", z->hist_ch, z->n_ch);
+        if (!std::isfinite(z->hist_lo) || !std::isfinite(z->hist_inv_w) || !(z->hist_inv_w > 0.0))
+            return fail(c, MRTX_E_INVALID, "hist_lo must be finite and hist_inv_w finite and > 0 (got %g, %g)", z->hist_lo, z->hist_inv_w);
+    }
+    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
+    if ((dev_field == nullptr) == (host_field == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_field and host_field");
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    if (z->n_bins == 0 && (dev_hist || host_hist)) return fail(c, MRTX_E_INVALID, "without bins dev_hist and host_hist must be NULL");
+    if (z->n_bins && (dev_hist == nullptr) == (host_hist == nullptr))
+        return fail(c, MRTX_E_INVALID, "give exactly one of dev_hist and host_hist");
+    const size_t N = (size_t)z->rows * (size_t)z->cols;
+    if ((size_t)n_regions > N) return fail(c, MRTX_E_INVALID, "n_regions = %u exceeds the lattice's %zu nodes", n_regions, N);
+    const size_t H = z->n_bins ? (size_t)n_regions * (size_t)(z->n_bins + 2) : 0;
+    if (H > ((size_t)1 << 28))
+        return fail(c, MRTX_E_INVALID, "a histogram holds at most 2^28 columns (got %u x %d)", n_regions, z->n_bins + 2);
+    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
+    if (dev_field && (reinterpret_cast<uintptr_t>(dev_field) & 3)) return fail(c, MRTX_E_INVALID, "dev_field must be 4-byte aligned (float32)");
+    if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 7)) return fail(c, MRTX_E_INVALID, "dev_out must be 8-byte aligned (MrtxZonal)");
+    if (dev_hist && (reinterpret_cast<uintptr_t>(dev_hist) & 7)) return fail(c, MRTX_E_INVALID, "dev_hist must be 8-byte aligned (uint64)");
+    const size_t R = (size_t)n_regions * (size_t)z->n_ch;
+    const size_t out_bytes = sizeof(MrtxZonal) * R, field_bytes = 4 * N * (size_t)z->n_ch, hist_bytes = 8 * H;
+    if (traverse_overlap(dev_labels, 4 * N, dev_out, out_bytes) || traverse_overlap(dev_field, field_bytes, dev_out, out_bytes) ||
+        traverse_overlap(dev_labels, 4 * N, dev_hist, hist_bytes) || traverse_overlap(dev_field, field_bytes, dev_hist, hist_bytes) ||
+        traverse_overlap(dev_out, out_bytes, dev_hist, hist_bytes))
+        return fail(c, MRTX_E_INVALID, "the device inputs, dev_out and dev_hist must not overlap");
+    bool runs;
+    if ((rc = zonal_variant(c, &runs)) != MRTX_OK) return rc;
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    // scratch: the count of bad entries, the packed extremes, and the histogram when it goes to the host
+    const size_t keys_at = 16, hist_at = keys_at + 16 * R;
+    float* d[3] = {nullptr, nullptr, nullptr};
+    if ((rc = stage_out(c, dev_out, std::max(out_bytes, sizeof(MrtxZonal)))) != MRTX_OK ||
+        (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, hist_at + (host_hist ? hist_bytes : 0) + 16)) != MRTX_OK ||
+        (rc = stage_tables(c, {{host_labels, host_labels ? N : 0}, {row_weight, row_weight ? (size_t)z->rows : 0},
+                               {host_field, host_field ? N * (size_t)z->n_ch : 0}}, d)) != MRTX_OK)
+        return rc;
+    char* tb = reinterpret_cast<char*>(c->trav_buf);
+    ZonalC q;
+    std::memset(&q, 0, sizeof q);
+    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_labels);
+    q.row_weight = row_weight ? reinterpret_cast<const uint32_t*>(d[1]) : nullptr;
+    q.field = host_field ? d[2] : static_cast<const float*>(dev_field);
+    q.out = static_cast<ZonalRec*>(dev_out);
+    q.bad = reinterpret_cast<uint32_t*>(tb);
+    q.keys = reinterpret_cast<unsigned long long*>(tb + keys_at);
+    q.hist = !z->n_bins ? nullptr : host_hist ? reinterpret_cast<unsigned long long*>(tb + hist_at) : static_cast<unsigned long long*>(dev_hist);
+    q.scale = z->scale; q.hist_lo = z->hist_lo; q.hist_inv_w = z->hist_inv_w;
+    q.rows = z->rows; q.cols = z->cols; q.n_ch = z->n_ch; q.hist_ch = z->hist_ch; q.n_bins = z->n_bins; q.n_regions = n_regions;
+    uint32_t launches = 0, bad = 0;
+    HIPCHK(c, hipMemsetAsync(q.bad, 0, 16, c->stream));
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_regions_zonal(q, runs, c->stream, &launches));
+    if ((rc = stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays)) != MRTX_OK) return rc;
+    if (out) out->launches = launches;
+    if (host_hist && hist_bytes) HIPCHK(c, hipMemcpy(host_hist, q.hist, hist_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad) return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", bad, (long long)n_regions - 1);
+    return MRTX_OK;
+}
+
+int mrtx_regions_shape(mrtx_ctx* c, int32_t rows, int32_t cols, int32_t wrap, int32_t connectivity, const void* dev_labels,
+                       const int32_t* host_labels, uint32_t n_regions, const uint32_t* side_ew, const uint32_t* side_ns, void* dev_out,
+                       MrtxRegionShape* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    int rc = regions_lattice(c, rows, cols, wrap);
+    if (rc != MRTX_OK) return rc;
+    if (connectivity != 4 && connectivity != 8) return fail(c, MRTX_E_INVALID, "connectivity must be 4 or 8 (got %d)", connectivity);
+    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    if ((side_ew == nullptr) != (side_ns == nullptr)) return fail(c, MRTX_E_INVALID, "give both of side_ew and side_ns or neither");
+    const size_t N = (size_t)rows * (size_t)cols;
+    if ((size_t)n_regions > N) return fail(c, MRTX_E_INVALID, "n_regions = %u exceeds the lattice's %zu nodes", n_regions, N);
+    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
+    if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 7)) return fail(c, MRTX_E_INVALID, "dev_out must be 8-byte aligned (MrtxRegionShape)");
+    const size_t out_bytes = sizeof(MrtxRegionShape) * (size_t)n_regions;
+    if (traverse_overlap(dev_labels, 4 * N, dev_out, out_bytes)) return fail(c, MRTX_E_INVALID, "dev_labels and dev_out must not overlap");
+    bool runs;
+    if ((rc = zonal_variant(c, &runs)) != MRTX_OK) return rc;
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    float* d[3] = {nullptr, nullptr, nullptr};
+    if ((rc = stage_out(c, dev_out, std::max(out_bytes, sizeof(MrtxRegionShape)))) != MRTX_OK ||
+        (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, 16)) != MRTX_OK ||
+        (rc = stage_tables(c, {{host_labels, host_labels ? N : 0}, {side_ew, side_ew ? (size_t)rows : 0},
+                               {side_ns, side_ns ? (size_t)rows + 1 : 0}}, d)) != MRTX_OK)
+        return rc;
+    ShapeC q;
+    std::memset(&q, 0, sizeof q);
+    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_labels);
+    q.side_ew = side_ew ? reinterpret_cast<const uint32_t*>(d[1]) : nullptr;
+    q.side_ns = side_ns ? reinterpret_cast<const uint32_t*>(d[2]) : nullptr;
+    q.out = static_cast<ShapeRec*>(dev_out);
+    q.bad = reinterpret_cast<uint32_t*>(c->trav_buf);
+    q.rows = rows; q.cols = cols; q.wrap = wrap; q.conn8 = connectivity == 8; q.n_regions = n_regions;
+    uint32_t launches = 0, bad = 0;
+    HIPCHK(c, hipMemsetAsync(q.bad, 0, 16, c->stream));
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_regions_shape(q, runs, c->stream, &launches));
     if ((rc = stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays)) != MRTX_OK) return rc;
     if (out) out->launches = launches;
     HIPCHK(c, hipMemcpy(&bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));

@@ -14,6 +14,16 @@ REGION_DTYPE = np.dtype([("weight", "<u8"), ("sum_i", "<i8"), ("sum_dj", "<i8"),
                          ("reserved", "<u4")])
 assert REGION_DTYPE.itemsize == 56
 
+# mirrors MrtxZonal, 56 bytes: one channel of one region
+ZONAL_DTYPE = np.dtype([("wcount", "<u8"), ("wsum", "<i8"), ("sum", "<i8"), ("count", "<u4"), ("n_nan", "<u4"),
+                        ("n_clipped", "<u4"), ("min", "<f4"), ("max", "<f4"), ("min_at", "<i4"), ("max_at", "<i4"),
+                        ("reserved", "<u4")])
+assert ZONAL_DTYPE.itemsize == 56
+# mirrors MrtxRegionShape, 32 bytes
+SHAPE_DTYPE = np.dtype([("perimeter", "<u8"), ("sides_ns", "<u4"), ("sides_ew", "<u4"), ("q1", "<u4"), ("q3", "<u4"),
+                        ("qd", "<u4"), ("euler", "<i4")])
+assert SHAPE_DTYPE.itemsize == 32
+
 WEIGHT_MAX = 2 ** 32 - 1
 
 
@@ -46,6 +56,96 @@ def row_weights(window, dem_hw, radius_m=1737400.0, unit_m2=1.0):
         k = int(np.argmax(q))
         raise ValueError(f"row {k}: a node's area {area[k]:g} m^2 does not fit 32 bits in units of {unit_m2:g} m^2: use a larger unit")
     return q.astype(np.uint32)
+
+
+def side_weights(window, dem_hw, radius_m=1737400.0, unit_m=1.0):
+    """(side_ew (rows,), side_ns (rows + 1,)) uint32: the lengths of the sides of a lattice cell of every row of a window, in
+    units of unit_m metres, rounded to the nearest integer, by row_weights' row convention: a cell reaches half a row spacing
+    either side of its row's latitude, clipped to the poles.  side_ew[i] is the meridian arc radius_m (north - south) of row
+    i's cells; side_ns[i] the arc of the parallel between rows i - 1 and i, radius_m cos(lat) dlon (entry 0: the north edge of
+    row 0; entry rows: the south edge of the last row).  ValueError for a length that rounds to zero (a side on a pole) or
+    does not fit 32 bits: choose another unit or window."""
+    from .traverse import window_dict
+    w = window_dict(window)
+    H, W = (int(v) for v in dem_hw)
+    if not (radius_m > 0.0 and unit_m > 0.0 and math.isfinite(radius_m) and math.isfinite(unit_m)):
+        raise ValueError("radius_m and unit_m must be finite and > 0")
+    if w["rows"] < 1 or w["stride"] < 1 or H < 1 or W < 1:
+        raise ValueError("empty window or DEM")
+    if w["row0"] < 0 or w["row0"] + (w["rows"] - 1) * w["stride"] >= H:
+        raise ValueError(f"the window's rows leave the DEM's {H} rows")
+    row = w["row0"] + np.arange(w["rows"], dtype=np.float64) * w["stride"]
+    lat = 0.5 * math.pi - (row + 0.5) * (math.pi / H)
+    half = 0.5 * w["stride"] * math.pi / H
+    north = np.minimum(lat + half, 0.5 * math.pi)
+    south = np.maximum(lat - half, -0.5 * math.pi)
+    dlon = w["stride"] * 2.0 * math.pi / W
+    ew = float(radius_m) * (north - south)
+    ns = float(radius_m) * dlon * np.cos(np.concatenate([north, south[-1:]]))
+    out = []
+    for name, length in (("side_ew", ew), ("side_ns", ns)):
+        q = np.rint(length / float(unit_m))
+        if not np.all(q >= 1.0):
+            k = int(np.argmin(q))
+            raise ValueError(f"{name}[{k}]: a side of {length[k]:g} m rounds to zero units of {unit_m:g} m: use a smaller unit")
+        if not np.all(q <= WEIGHT_MAX):
+            k = int(np.argmax(q))
+            raise ValueError(f"{name}[{k}]: a side of {length[k]:g} m does not fit 32 bits in units of {unit_m:g} m: use a larger unit")
+        out.append(q.astype(np.uint32))
+    return out[0], out[1]
+
+
+def fixed_point(x, scale):
+    """q of a float32 value as mrtx_regions_zonal forms it, a Python integer: rint(float64(x) * scale), and +-2^31 with the
+    product's sign when |float64(x) * scale| >= 2^31."""
+    p = float(np.float64(np.float32(x)) * np.float64(scale))
+    if abs(p) >= 2.0 ** 31:
+        return -2 ** 31 if p < 0.0 else 2 ** 31
+    return int(np.rint(p))
+
+
+def check_wsum(z, scale):
+    """OverflowError when a record's weighted sum may have wrapped: max(|q(min)|, |q(max)|) * wcount >= 2^63, in Python
+    integers from the record itself.  Every |q| of the record is at most that maximum, so a wsum that passes did not wrap."""
+    z = np.asarray(z)
+    flat = z.reshape(-1)
+    for k in np.flatnonzero(flat["count"] > 0):
+        r = flat[k]
+        bound = max(abs(fixed_point(r["min"], scale)), abs(fixed_point(r["max"], scale))) * int(r["wcount"])
+        if bound >= 2 ** 63:
+            raise OverflowError(f"record {int(k)}: |q| up to 2^{math.log2(max(bound // int(r['wcount']), 1)):.1f} times a weight "
+                                f"of {int(r['wcount'])} may exceed 63 bits, so wsum may have wrapped: lower scale")
+
+
+def zonal_mean(z, scale):
+    """float64 mean of every record: sum / count / scale (NaN where count == 0)."""
+    z = np.asarray(z)
+    cnt = z["count"].astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(cnt > 0, z["sum"].astype(np.float64) / cnt / float(scale), np.nan)
+
+
+def zonal_area_mean(z, scale):
+    """float64 weighted mean of every record: wsum / wcount / scale (NaN where wcount == 0)."""
+    z = np.asarray(z)
+    w = z["wcount"].astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(w > 0, z["wsum"].astype(np.float64) / w / float(scale), np.nan)
+
+
+def holes(shape, table=None, cols=None, wrap=False):
+    """(holes, may_wind): holes = 1 - euler of every region of a SHAPE_DTYPE table, right for a connected region that does not
+    wind round the seam; may_wind marks the regions of a wrapped map whose dj extent spans all cols columns (table: the
+    catalogue, REGION_DTYPE), which may wind and then read one hole more."""
+    shape = np.asarray(shape)
+    h = 1 - shape["euler"].astype(np.int64)
+    wind = np.zeros(h.shape, bool)
+    if wrap and table is not None:
+        if cols is None:
+            raise ValueError("give cols with a wrapped map's table")
+        t = np.asarray(table)
+        wind = (t["dj_max"].astype(np.int64) - t["dj_min"].astype(np.int64) + 1 >= int(cols)) & (t["count"] > 0)
+    return h, wind
 
 
 class RegionMap:
@@ -84,6 +184,20 @@ class RegionMap:
         la = lat[0] + (t["sum_i"] / cnt) * dlat
         lo = lon[np.clip(t["root_j"], 0, cols - 1)] + (t["sum_dj"] / cnt) * dlon
         return np.stack([la, (lo + 180.0) % 360.0 - 180.0], -1)
+
+    def zonal(self, rt, field, row_weights=None, scale=1.0, hist=None, stats=None):
+        """MoonRT.region_statistics of a (rows, cols[, n_ch]) float32 field over this map's regions."""
+        return rt.region_statistics(self.labels, self.n, field, row_weights=row_weights, scale=scale, hist=hist, wrap=self.wrap,
+                                    stats=stats)
+
+    def shapes(self, rt, connectivity=4, side_ew=None, side_ns=None, stats=None):
+        """MoonRT.region_shapes of this map's regions."""
+        return rt.region_shapes(self.labels, self.n, connectivity=connectivity, wrap=self.wrap, side_ew=side_ew, side_ns=side_ns,
+                                stats=stats)
+
+    def holes(self, shape):
+        """regions.holes of a shape table of this map: (holes, may_wind)."""
+        return holes(shape, self.table, self.labels.shape[1], self.wrap)
 
     def largest(self, k=1):
         """The numbers of the k regions of greatest weight, greatest first (equal weights: the lower number first)."""

@@ -1155,6 +1155,134 @@ class MoonRT:
             stats["label_launches"] = stats.get("label_launches", 0) + st.launches
         return rg.RegionMap(labels, table, wrap, unit_m2)
 
+    # ---- Zonal statistics and outlines of labelled regions
+    @staticmethod
+    def _label_arg(labels, shape):
+        """(device pointer, host pointer, rows, cols, keepalive) of a label table: (rows, cols) int32 or a DeviceBuffer."""
+        if isinstance(labels, DeviceBuffer):
+            if shape is None:
+                raise ValueError("a DeviceBuffer needs shape = (rows, cols)")
+            rows, cols = int(shape[0]), int(shape[1])
+            if labels.nbytes < 4 * rows * cols:
+                raise ValueError("the label DeviceBuffer is smaller than its shape")
+            return labels.ptr, None, rows, cols, labels
+        a = np.ascontiguousarray(labels, np.int32)
+        if a.ndim != 2:
+            raise ValueError("labels must be (rows, cols)")
+        return None, a.ctypes.data, int(a.shape[0]), int(a.shape[1]), a
+
+    @staticmethod
+    def _row_table(table, n, what):
+        if table is None:
+            return None
+        t = np.ascontiguousarray(table)
+        if t.shape != (n,) or not np.issubdtype(t.dtype, np.integer) or (t.size and (t.min() < 0 or t.max() > 2 ** 32 - 1)):
+            raise ValueError(f"{what} must be ({n},) integers in 0 .. 2^32 - 1")
+        return t.astype(np.uint32)
+
+    def region_statistics(self, labels, n_regions, field, row_weights=None, scale=1.0, hist=None, wrap=False, shape=None,
+                          stats=None):
+        """What is inside each region of a label table (mrtx_regions_zonal): count, NaN count, exact fixed-point sums (q =
+        llrint(x * scale)), area-weighted sums, and the extremes with their places, per region and channel.  labels: (rows,
+        cols) int32 or a DeviceBuffer (then give shape = (rows, cols)); field: (rows, cols) or (rows, cols, n_ch) float32 or a
+        DeviceBuffer (then shape = (rows, cols, n_ch)); both from one side: with a DeviceBuffer among them the records are
+        made in device tables and downloaded.  row_weights: (rows,) uint32 node areas or None.  hist = (channel, n_bins, lo,
+        hi): also the weight of every region per value band.  Returns a (n_regions, n_ch) array of regions.ZONAL_DTYPE, and
+        with hist the pair (records, (n_regions, n_bins + 2) uint64).  Raises MoonRTError when a weighted sum may have
+        wrapped (regions.check_wsum): lower scale then."""
+        from . import regions as rg
+        n_regions = int(n_regions)
+        dev_f = isinstance(field, DeviceBuffer)
+        dev_l = isinstance(labels, DeviceBuffer)
+        if dev_f != dev_l:
+            raise ValueError("labels and field must both be numpy arrays or both DeviceBuffers")
+        if dev_f:
+            if shape is None or len(shape) != 3:
+                raise ValueError("DeviceBuffers need shape = (rows, cols, n_ch)")
+            n_ch = int(shape[2])
+        else:
+            field = np.ascontiguousarray(field, np.float32)
+            if field.ndim == 2:
+                field = field[:, :, None]
+            if field.ndim != 3:
+                raise ValueError("field must be (rows, cols) or (rows, cols, n_ch)")
+            n_ch = int(field.shape[2])
+        lab_d, lab_h, rows, cols, _keep = self._label_arg(labels, shape)
+        if dev_f:
+            if field.nbytes < 4 * rows * cols * n_ch:
+                raise ValueError("the field DeviceBuffer is smaller than its shape")
+        elif field.shape[:2] != (rows, cols):
+            raise ValueError("field and labels differ in shape")
+        weights = self._row_table(row_weights, rows, "row_weights")
+        hist_ch, n_bins, lo, inv_w = 0, 0, 0.0, 1.0
+        if hist is not None:
+            hist_ch, n_bins, lo, hi = int(hist[0]), int(hist[1]), float(hist[2]), float(hist[3])
+            if n_bins < 1 or not hi > lo:
+                raise ValueError("hist = (channel, n_bins >= 1, lo, hi > lo)")
+            inv_w = n_bins / (hi - lo)
+        z = _lib.MrtxZonalSpec(rows, cols, 1 if wrap else 0, n_ch, float(scale), hist_ch, n_bins, lo, inv_w, 0)
+        wp = weights.ctypes.data if weights is not None else None
+        st = MrtxStats()
+        width = n_bins + 2
+        if dev_f:
+            rec = DeviceBuffer(max(56 * n_regions * n_ch, 56), field.device)
+            hb = DeviceBuffer(max(8 * n_regions * width, 8), field.device) if n_bins else None
+            try:
+                self._check(self._lib.mrtx_regions_zonal(self._ctx, C.byref(z), lab_d, None, n_regions, field.ptr, None, wp,
+                                                         rec.ptr, None, hb.ptr if hb else None, None, C.byref(st)),
+                            "mrtx_regions_zonal")
+                table = rec.download(rg.ZONAL_DTYPE, (n_regions, n_ch))
+                h = hb.download(np.uint64, (n_regions, width)) if hb else None
+            finally:
+                rec.free()
+                if hb:
+                    hb.free()
+        else:
+            table = np.zeros((max(n_regions, 1), n_ch), rg.ZONAL_DTYPE)
+            h = np.zeros((max(n_regions, 1), width), np.uint64) if n_bins else None
+            self._check(self._lib.mrtx_regions_zonal(self._ctx, C.byref(z), None, lab_h, n_regions, None, field.ctypes.data, wp,
+                                                     None, table.ctypes.data, None, h.ctypes.data if n_bins else None,
+                                                     C.byref(st)), "mrtx_regions_zonal")
+            table = table[:n_regions]
+            h = h[:n_regions] if n_bins else None
+        self._add_stats(stats, st)
+        try:
+            rg.check_wsum(table, float(scale))
+        except OverflowError as e:
+            raise MoonRTError(str(e)) from e
+        return (table, h) if n_bins else table
+
+    def region_shapes(self, labels, n_regions, connectivity=4, wrap=False, side_ew=None, side_ns=None, shape=None, stats=None):
+        """The outline of each region of a label table (mrtx_regions_shape): perimeter, boundary-side counts, the bit-quad
+        counts and the Euler number (components minus holes in the given connectivity).  labels: (rows, cols) int32 or a
+        DeviceBuffer (then give shape = (rows, cols)).  side_ew (rows,) and side_ns (rows + 1,) uint32 side lengths
+        (regions.side_weights), both or neither: with neither every side counts 1.  Returns (n_regions,) regions.SHAPE_DTYPE."""
+        from . import regions as rg
+        n_regions = int(n_regions)
+        lab_d, lab_h, rows, cols, _keep = self._label_arg(labels, shape)
+        if (side_ew is None) != (side_ns is None):
+            raise ValueError("give both of side_ew and side_ns or neither")
+        ew = self._row_table(side_ew, rows, "side_ew")
+        ns = self._row_table(side_ns, rows + 1, "side_ns")
+        ewp, nsp = (ew.ctypes.data, ns.ctypes.data) if ew is not None else (None, None)
+        st = MrtxStats()
+        if lab_d is not None:
+            rec = DeviceBuffer(max(32 * n_regions, 32), labels.device)
+            try:
+                self._check(self._lib.mrtx_regions_shape(self._ctx, rows, cols, 1 if wrap else 0, int(connectivity), lab_d, None,
+                                                         n_regions, ewp, nsp, rec.ptr, None, C.byref(st)), "mrtx_regions_shape")
+                table = rec.download(rg.SHAPE_DTYPE, (n_regions,))
+            finally:
+                rec.free()
+        else:
+            table = np.zeros(max(n_regions, 1), rg.SHAPE_DTYPE)
+            self._check(self._lib.mrtx_regions_shape(self._ctx, rows, cols, 1 if wrap else 0, int(connectivity), None, lab_h,
+                                                     n_regions, ewp, nsp, None, table.ctypes.data, C.byref(st)),
+                        "mrtx_regions_shape")
+            table = table[:n_regions]
+        self._add_stats(stats, st)
+        return table
+
     @staticmethod
     def _add_stats(acc, st, extra=None):
         """Sum the counters of one call into the dict `acc` (if it is one); extra = {key: MrtxStats field} of the call's own."""
