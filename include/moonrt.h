@@ -686,6 +686,52 @@ int mrtx_regions_shape(mrtx_ctx* ctx, int32_t rows, int32_t cols, int32_t wrap, 
                        const int32_t* host_labels, uint32_t n_regions, const uint32_t* side_ew, const uint32_t* side_ns,
                        void* dev_out, MrtxRegionShape* host_out, MrtxStats* out);
 
+/* ---- Proximity maps and the reach of labelled regions (additive to ABI 7) --------------------------
+ * Every node's nearest feature node and the exact squared distance to it, between node positions in three dimensions.  The
+ * lattice is that of mrtx_regions_stats (at most 2^31 nodes, node (i, j) at index v = i cols + j) but has no wrap flag and no
+ * metric of its own: the positions carry the geometry, so seam and pole need no special case.  Positions: three int32 (x, y, z)
+ * per node in a unit of the caller's, every coordinate in -2^29 .. 2^29.  d2(u, v) = (xu - xv)^2 + (yu - yv)^2 + (zu - zv)^2 in
+ * uint64, at most 3 x 2^60.  The features are the nodes with label >= 0 (MRTX_PROX_TO_SET) or with label < 0
+ * (MRTX_PROX_TO_OUTSIDE).  For every node v, nearest[v] is the feature u that minimises (d2(u, v), u) lexicographically (ties
+ * go to the least node index) and dist2[v] that d2; a feature node is treated like any other.  Without features nearest = -1
+ * and dist2 = UINT64_MAX everywhere.  Nothing depends on the order of evaluation.  Both calls need no DEM, no light and no Moon
+ * frame and leave the render state alone; the number of launches depends on the lattice and the variant alone. */
+#define MRTX_PROX_TO_SET 0
+#define MRTX_PROX_TO_OUTSIDE 1
+typedef struct MrtxProximity {
+    int32_t rows, cols;
+    int32_t mode;           /* MRTX_PROX_TO_SET or MRTX_PROX_TO_OUTSIDE */
+    int32_t reserved;       /* 0 */
+} MrtxProximity;
+/* Positions rows x cols x 3 int32 in exactly one of dev_pos and host_pos, labels rows x cols int32 in exactly one of dev_labels
+ * and host_labels; nearest rows x cols int32 into exactly one of dev_nearest and host_nearest, dist2 rows x cols uint64 into
+ * exactly one of dev_dist2 (8-byte aligned) and host_dist2; the other device tables are 4-byte aligned and no two device
+ * tables may overlap.  A coordinate outside -2^29 .. 2^29 gives MRTX_E_INVALID: in a host table before any device call, in a
+ * device table after the launch (the kernels clamp it, so nothing else goes wrong), as mrtx_traverse treats its penalties.
+ * pairs (or NULL): the number of (node, feature) distance evaluations, the same from run to run.  MOONRT_PROXIMITY = prune
+ * (default) | brute chooses between the scan that skips the feature tiles an integer bound proves too far and the scan of
+ * every feature; both give the same bytes.  out: launches, kernel_ms. */
+int mrtx_proximity(mrtx_ctx* ctx, const MrtxProximity* p, const void* dev_pos, const int32_t* host_pos, const void* dev_labels,
+                   const int32_t* host_labels, void* dev_nearest, int32_t* host_nearest, void* dev_dist2, uint64_t* host_dist2,
+                   uint64_t* pairs, MrtxStats* out);
+/* The reach of one region, 32 bytes: the extremes of a dist2 table over the region's nodes, the least node index among equals. */
+typedef struct MrtxRegionReach {
+    uint64_t d2_max, d2_min;    /* over the region's nodes; 0 and UINT64_MAX when count == 0 */
+    int32_t max_at, min_at;     /* least node index attaining each; -1 when count == 0 */
+    int32_t min_nearest;        /* nearest[min_at]; -1 when count == 0 */
+    uint32_t count;
+} MrtxRegionReach;
+/* n_regions records into exactly one of dev_out (8-byte aligned, overlapping no device input) and host_out, of any dist2 /
+ * nearest pair (each in exactly one of its device and host pointer; dev_dist2 8-byte aligned) over any label table, checked as
+ * in mrtx_regions_stats: an entry >= n_regions or < -1 is never used as an index and gives MRTX_E_INVALID after the launch;
+ * n_regions = 0 checks the table and writes nothing.  On MRTX_PROX_TO_OUTSIDE distances of the regions' own labels d2_max and
+ * max_at are the radius and the centre of the largest circle that fits in each region; on MRTX_PROX_TO_SET distances to another
+ * set d2_min, min_at and min_nearest say how close each region comes to it, where, and to which of its nodes.  out: launches,
+ * kernel_ms. */
+int mrtx_regions_reach(mrtx_ctx* ctx, int32_t rows, int32_t cols, const void* dev_labels, const int32_t* host_labels,
+                       uint32_t n_regions, const void* dev_dist2, const uint64_t* host_dist2, const void* dev_nearest,
+                       const int32_t* host_nearest, void* dev_out, MrtxRegionReach* host_out, MrtxStats* out);
+
 /* ---- Mast-height horizons and joint windows (additive to ABI 7) ----------------------------------
  * mrtx_horizon_points from a raised origin: point p marches from P = fmaf(hs, u, o), hs = (float)(height_m[p] / radius_m * R),
  * the raised end of mrtx_sight_points (so a mast top is one point for the horizon and for the line of sight).  height_m: n

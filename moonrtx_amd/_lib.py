@@ -110,6 +110,21 @@ class MrtxRegionShape(C.Structure):
                 ("q3", C.c_uint32), ("qd", C.c_uint32), ("euler", C.c_int32)]
 
 
+PROX_TO_SET = 0
+PROX_TO_OUTSIDE = 1
+
+
+class MrtxProximity(C.Structure):
+    """The lattice and the feature set of a proximity map (mrtx_proximity)."""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MrtxRegionReach(C.Structure):
+    """The extremes of a dist2 table over one region (mrtx_regions_reach): 32 bytes."""
+    _fields_ = [("d2_max", C.c_uint64), ("d2_min", C.c_uint64), ("max_at", C.c_int32), ("min_at", C.c_int32),
+                ("min_nearest", C.c_int32), ("count", C.c_uint32)]
+
+
 class MrtxIllumEpoch(C.Structure):
     """One date of a Sun-illumination series (mrtx_illum_series): what mrtx_set_light and
     mrtx_set_moon_frame would set for it."""
@@ -239,6 +254,10 @@ SIGNATURES = {
     "mrtx_regions_zonal": (C.c_int, [_VP, C.POINTER(MrtxZonalSpec), _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                      C.POINTER(MrtxStats)]),
     "mrtx_regions_shape": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP,
+                                     C.POINTER(MrtxStats)]),
+    "mrtx_proximity": (C.c_int, [_VP, C.POINTER(MrtxProximity), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_uint64),
+                                 C.POINTER(MrtxStats)]),
+    "mrtx_regions_reach": (C.c_int, [_VP, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP,
                                      C.POINTER(MrtxStats)]),
     "mrtx_thermal": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                C.POINTER(MrtxStats)]),

@@ -23,6 +23,7 @@
 #include "mrtx_device.h"
 #include "mrtx_regions.h"
 #include "mrtx_zonal.h"
+#include "mrtx_proximity.h"
 
 hipError_t mrtx_launch_render(const FrameC& f, int S, bool stats, int mode, bool overlay, const PathQ* pq, hipStream_t st);
 uint64_t mrtx_path_chunks(const FrameC& f, int S, uint32_t* grid_a, int* njobs_log2);
@@ -2639,6 +2640,127 @@ int mrtx_regions_shape(mrtx_ctx* c, int32_t rows, int32_t cols, int32_t wrap, in
     HIPCHK(c, hipMemsetAsync(q.bad, 0, 16, c->stream));
     if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
     HIPCHK(c, mrtx_launch_regions_shape(q, runs, c->stream, &launches));
+    if ((rc = stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays)) != MRTX_OK) return rc;
+    if (out) out->launches = launches;
+    HIPCHK(c, hipMemcpy(&bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad) return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", bad, (long long)n_regions - 1);
+    return MRTX_OK;
+}
+
+// ---- Proximity maps and the reach of labelled regions ---------------------------------------------
+static_assert(sizeof(MrtxRegionReach) == 32 && sizeof(ReachRec) == sizeof(MrtxRegionReach), "MrtxRegionReach is 32 bytes");
+static_assert(sizeof(MrtxProximity) == 16 && sizeof(ProxBox) == 32 && sizeof(ProxFeat) == 16, "the proximity blocks");
+
+int mrtx_proximity(mrtx_ctx* c, const MrtxProximity* p, const void* dev_pos, const int32_t* host_pos, const void* dev_labels,
+                   const int32_t* host_labels, void* dev_nearest, int32_t* host_nearest, void* dev_dist2, uint64_t* host_dist2,
+                   uint64_t* pairs, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!p) return fail(c, MRTX_E_INVALID, "null proximity block");
+    if (p->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    int rc = regions_lattice(c, p->rows, p->cols, 0);
+    if (rc != MRTX_OK) return rc;
+    if (p->mode != MRTX_PROX_TO_SET && p->mode != MRTX_PROX_TO_OUTSIDE)
+        return fail(c, MRTX_E_INVALID, "mode must be MRTX_PROX_TO_SET or MRTX_PROX_TO_OUTSIDE (got %d)", p->mode);
+    if ((dev_pos == nullptr) == (host_pos == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_pos and host_pos");
+    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
+    if ((dev_nearest == nullptr) == (host_nearest == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_nearest and host_nearest");
+    if ((dev_dist2 == nullptr) == (host_dist2 == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_dist2 and host_dist2");
+    if (dev_pos && (reinterpret_cast<uintptr_t>(dev_pos) & 3)) return fail(c, MRTX_E_INVALID, "dev_pos must be 4-byte aligned (int32)");
+    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
+    if (dev_nearest && (reinterpret_cast<uintptr_t>(dev_nearest) & 3)) return fail(c, MRTX_E_INVALID, "dev_nearest must be 4-byte aligned (int32)");
+    if (dev_dist2 && (reinterpret_cast<uintptr_t>(dev_dist2) & 7)) return fail(c, MRTX_E_INVALID, "dev_dist2 must be 8-byte aligned (uint64)");
+    const size_t N = (size_t)p->rows * (size_t)p->cols;
+    if (traverse_overlap(dev_pos, 12 * N, dev_labels, 4 * N) || traverse_overlap(dev_pos, 12 * N, dev_nearest, 4 * N) ||
+        traverse_overlap(dev_pos, 12 * N, dev_dist2, 8 * N) || traverse_overlap(dev_labels, 4 * N, dev_nearest, 4 * N) ||
+        traverse_overlap(dev_labels, 4 * N, dev_dist2, 8 * N) || traverse_overlap(dev_nearest, 4 * N, dev_dist2, 8 * N))
+        return fail(c, MRTX_E_INVALID, "dev_pos, dev_labels, dev_nearest and dev_dist2 must not overlap");
+    // MOONRT_PROXIMITY=brute: every tile's features against every node, the yardstick of the pruned scan; the same bytes
+    bool prune = true;
+    if (const char* e = std::getenv("MOONRT_PROXIMITY")) {
+        if (std::strcmp(e, "brute") == 0) prune = false;
+        else if (std::strcmp(e, "prune") != 0) return fail(c, MRTX_E_INVALID, "MOONRT_PROXIMITY must be prune or brute (got %s)", e);
+    }
+    // a host table is refused at its first bad coordinate (a device table's are counted by the tile kernel)
+    if (host_pos)
+        for (size_t n = 0; n < 3 * N; n++)
+            if (host_pos[n] < -MRTX_PX_CMAX || host_pos[n] > MRTX_PX_CMAX)
+                return fail(c, MRTX_E_INVALID, "coordinate %zu of node %zu must lie in -2^29 .. 2^29 (got %d)", n % 3, n / 3, host_pos[n]);
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    // scratch: the counters, the tiles' boxes and feature lists, and the outputs the caller wants on the host
+    const ProxLayout at = prox_layout(p->rows, p->cols, host_nearest != nullptr, host_dist2 != nullptr);
+    float* d[2] = {nullptr, nullptr};
+    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, at.end)) != MRTX_OK ||
+        (rc = stage_tables(c, {{host_pos, host_pos ? 3 * N : 0}, {host_labels, host_labels ? N : 0}}, d)) != MRTX_OK)
+        return rc;
+    char* tb = reinterpret_cast<char*>(c->trav_buf);
+    ProxC q;
+    std::memset(&q, 0, sizeof q);
+    q.pos = host_pos ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_pos);
+    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[1]) : static_cast<const int32_t*>(dev_labels);
+    q.nearest = host_nearest ? reinterpret_cast<int32_t*>(tb + at.near_at) : static_cast<int32_t*>(dev_nearest);
+    q.dist2 = host_dist2 ? reinterpret_cast<unsigned long long*>(tb + at.d2_at) : static_cast<unsigned long long*>(dev_dist2);
+    q.pairs = reinterpret_cast<unsigned long long*>(tb);
+    q.bad = reinterpret_cast<uint32_t*>(tb + 8);
+    q.box = reinterpret_cast<ProxBox*>(tb + at.box_at);
+    q.feat = reinterpret_cast<ProxFeat*>(tb + at.feat_at);
+    q.rows = p->rows; q.cols = p->cols; q.outside = p->mode == MRTX_PROX_TO_OUTSIDE; q.tiles_x = at.tiles_x; q.tiles_y = at.tiles_y;
+    uint32_t launches = 0;
+    unsigned long long head[2] = {0, 0};                    // pairs, bad
+    HIPCHK(c, hipMemsetAsync(tb, 0, 32, c->stream));
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_proximity(q, prune, c->stream, &launches));
+    if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
+    if (out) out->launches = launches;
+    HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
+    if ((uint32_t)head[1])
+        return fail(c, MRTX_E_INVALID, "%u coordinates of the device position table lie outside -2^29 .. 2^29", (uint32_t)head[1]);
+    if (host_nearest) HIPCHK(c, hipMemcpy(host_nearest, q.nearest, 4 * N, hipMemcpyDeviceToHost));
+    if (host_dist2) HIPCHK(c, hipMemcpy(host_dist2, q.dist2, 8 * N, hipMemcpyDeviceToHost));
+    if (pairs) *pairs = head[0];
+    return MRTX_OK;
+}
+
+int mrtx_regions_reach(mrtx_ctx* c, int32_t rows, int32_t cols, const void* dev_labels, const int32_t* host_labels, uint32_t n_regions,
+                       const void* dev_dist2, const uint64_t* host_dist2, const void* dev_nearest, const int32_t* host_nearest,
+                       void* dev_out, MrtxRegionReach* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    int rc = regions_lattice(c, rows, cols, 0);
+    if (rc != MRTX_OK) return rc;
+    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
+    if ((dev_dist2 == nullptr) == (host_dist2 == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_dist2 and host_dist2");
+    if ((dev_nearest == nullptr) == (host_nearest == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_nearest and host_nearest");
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    const size_t N = (size_t)rows * (size_t)cols;
+    if ((size_t)n_regions > N) return fail(c, MRTX_E_INVALID, "n_regions = %u exceeds the lattice's %zu nodes", n_regions, N);
+    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
+    if (dev_dist2 && (reinterpret_cast<uintptr_t>(dev_dist2) & 7)) return fail(c, MRTX_E_INVALID, "dev_dist2 must be 8-byte aligned (uint64)");
+    if (dev_nearest && (reinterpret_cast<uintptr_t>(dev_nearest) & 3)) return fail(c, MRTX_E_INVALID, "dev_nearest must be 4-byte aligned (int32)");
+    if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 7)) return fail(c, MRTX_E_INVALID, "dev_out must be 8-byte aligned (MrtxRegionReach)");
+    const size_t out_bytes = sizeof(MrtxRegionReach) * (size_t)n_regions;
+    if (traverse_overlap(dev_labels, 4 * N, dev_out, out_bytes) || traverse_overlap(dev_dist2, 8 * N, dev_out, out_bytes) ||
+        traverse_overlap(dev_nearest, 4 * N, dev_out, out_bytes))
+        return fail(c, MRTX_E_INVALID, "the device inputs and dev_out must not overlap");
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    float* d[3] = {nullptr, nullptr, nullptr};
+    if ((rc = stage_out(c, dev_out, std::max(out_bytes, sizeof(MrtxRegionReach)))) != MRTX_OK ||
+        (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, 16)) != MRTX_OK ||
+        (rc = stage_tables(c, {{host_labels, host_labels ? N : 0}, {host_dist2, host_dist2 ? 2 * N : 0},
+                               {host_nearest, host_nearest ? N : 0}}, d)) != MRTX_OK)
+        return rc;
+    ReachC q;
+    std::memset(&q, 0, sizeof q);
+    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_labels);
+    q.dist2 = host_dist2 ? reinterpret_cast<const unsigned long long*>(d[1]) : static_cast<const unsigned long long*>(dev_dist2);
+    q.nearest = host_nearest ? reinterpret_cast<const int32_t*>(d[2]) : static_cast<const int32_t*>(dev_nearest);
+    q.out = static_cast<ReachRec*>(dev_out);
+    q.bad = reinterpret_cast<uint32_t*>(c->trav_buf);
+    q.rows = rows; q.cols = cols; q.n_regions = n_regions;
+    uint32_t launches = 0, bad = 0;
+    HIPCHK(c, hipMemsetAsync(q.bad, 0, 16, c->stream));
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_regions_reach(q, c->stream, &launches));
     if ((rc = stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays)) != MRTX_OK) return rc;
     if (out) out->launches = launches;
     HIPCHK(c, hipMemcpy(&bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));

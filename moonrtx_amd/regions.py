@@ -23,8 +23,15 @@ assert ZONAL_DTYPE.itemsize == 56
 SHAPE_DTYPE = np.dtype([("perimeter", "<u8"), ("sides_ns", "<u4"), ("sides_ew", "<u4"), ("q1", "<u4"), ("q3", "<u4"),
                         ("qd", "<u4"), ("euler", "<i4")])
 assert SHAPE_DTYPE.itemsize == 32
+# mirrors MrtxRegionReach, 32 bytes
+REACH_DTYPE = np.dtype([("d2_max", "<u8"), ("d2_min", "<u8"), ("max_at", "<i4"), ("min_at", "<i4"), ("min_nearest", "<i4"),
+                        ("count", "<u4")])
+assert REACH_DTYPE.itemsize == 32
 
 WEIGHT_MAX = 2 ** 32 - 1
+# every coordinate of a node position lies in -COORD_MAX .. COORD_MAX (mrtx_proximity)
+COORD_MAX = 2 ** 29
+NO_FEATURE = np.uint64(2 ** 64 - 1)
 
 
 def row_weights(window, dem_hw, radius_m=1737400.0, unit_m2=1.0):
@@ -148,6 +155,89 @@ def holes(shape, table=None, cols=None, wrap=False):
     return h, wind
 
 
+def node_positions(window, dem_hw, radius_m=1737400.0, unit_m=0.01, heights_m=None):
+    """(rows, cols, 3) int32: the positions of the nodes of a window (row0, col0, rows, cols[, stride[, wrap]]) of an (H, W)
+    DEM in units of unit_m metres, for MoonRT.proximity: rint((radius_m + h) (cos lat cos lon, cos lat sin lon, sin lat) /
+    unit_m) in float64, h = heights_m (a scalar or (rows, cols) metres above the sphere) or 0.  lat and lon are the texel
+    centres of MoonRT.traverse_nodes and row_weights, in radians: lat = pi / 2 - (row + 1 / 2) pi / H of row = row0 + i
+    stride, lon = -pi + (col + 1 / 2) 2 pi / W of col = (col0 + j stride) mod W.  ValueError when a coordinate leaves
+    +-2^29: choose a larger unit."""
+    from .traverse import window_dict
+    w = window_dict(window)
+    H, W = (int(v) for v in dem_hw)
+    if not (radius_m > 0.0 and unit_m > 0.0 and math.isfinite(radius_m) and math.isfinite(unit_m)):
+        raise ValueError("radius_m and unit_m must be finite and > 0")
+    if w["rows"] < 1 or w["cols"] < 1 or w["stride"] < 1 or H < 1 or W < 1:
+        raise ValueError("empty window or DEM")
+    if w["row0"] < 0 or w["row0"] + (w["rows"] - 1) * w["stride"] >= H:
+        raise ValueError(f"the window's rows leave the DEM's {H} rows")
+    row = w["row0"] + np.arange(w["rows"], dtype=np.float64) * w["stride"]
+    col = ((w["col0"] + np.arange(w["cols"], dtype=np.int64) * w["stride"]) % W).astype(np.float64)
+    lat = (0.5 * math.pi - (row + 0.5) * (math.pi / H))[:, None]
+    lon = (-math.pi + (col + 0.5) * (2.0 * math.pi / W))[None, :]
+    r = np.full((w["rows"], w["cols"]), float(radius_m))
+    if heights_m is not None:
+        h = np.asarray(heights_m, np.float64)
+        if h.shape not in ((), (w["rows"], w["cols"])) or not np.all(np.isfinite(h)):
+            raise ValueError("heights_m must be a finite scalar or (rows, cols)")
+        r = r + h
+    p = np.stack([r * np.cos(lat) * np.cos(lon), r * np.cos(lat) * np.sin(lon), r * np.sin(lat) * np.ones_like(lon)], -1)
+    q = np.rint(p / float(unit_m))
+    if not np.all(np.abs(q) <= COORD_MAX):
+        raise ValueError(f"a coordinate of {np.abs(p).max():g} m leaves +-2^29 units of {unit_m:g} m: choose a larger unit")
+    return q.astype(np.int32)
+
+
+class ProximityMap:
+    """What MoonRT.proximity returns: nearest (rows, cols) int32, the node index of every node's
+    nearest feature (-1: there is none); dist2 (rows, cols) uint64, the exact squared distance to it in squared units of the
+    positions (2^64 - 1: none); unit_m, the metres of one unit of the positions, or None when they are not metres."""
+
+    def __init__(self, nearest, dist2, unit_m=None):
+        self.nearest = np.ascontiguousarray(nearest, np.int32)
+        self.dist2 = np.ascontiguousarray(dist2, np.uint64)
+        if self.nearest.ndim != 2 or self.dist2.shape != self.nearest.shape:
+            raise ValueError("nearest and dist2 must be (rows, cols) alike")
+        self.unit_m = None if unit_m is None else float(unit_m)
+
+    def _unit(self):
+        if self.unit_m is None:
+            raise ValueError("the map has no unit: give unit_m")
+        return self.unit_m
+
+    def chord_m(self):
+        """(rows, cols) float64: the straight-line distance sqrt(dist2) unit_m to the nearest feature, inf where there is none."""
+        u = self._unit()
+        return np.where(self.nearest < 0, np.inf, np.sqrt(self.dist2.astype(np.float64)) * u)
+
+    def arc_m(self, radius_m=1737400.0):
+        """(rows, cols) float64: the great-circle distance 2 R asin(chord / 2 R) on a sphere of radius_m of two points that
+        lie on it (a chord longer than the diameter reads as the half circle); inf where there is no feature."""
+        c = self.chord_m()
+        none = ~np.isfinite(c)
+        x = np.minimum(np.where(none, 0.0, c) / (2.0 * float(radius_m)), 1.0)
+        return np.where(none, np.inf, 2.0 * float(radius_m) * np.arcsin(x))
+
+    def nearest_label(self, labels):
+        """(rows, cols) int32: the label of every node's nearest feature, the Voronoi allocation of the nodes to the regions
+        of `labels`; -1 where nearest is -1."""
+        lab = np.ascontiguousarray(labels, np.int32)
+        if lab.shape != self.nearest.shape:
+            raise ValueError("labels and the map differ in shape")
+        return np.where(self.nearest < 0, -1, lab.reshape(-1)[np.maximum(self.nearest, 0)]).astype(np.int32)
+
+    def within(self, distance_m):
+        """(rows, cols) bool: the buffer chord_m() <= distance_m, compared in integers: dist2 <= floor((distance_m /
+        unit_m)^2), the quotient and the square in float64, the comparison exact.  A node without a feature is never
+        within, nor is any node for a negative or NaN distance."""
+        t = float(distance_m) / self._unit()
+        if not t >= 0.0:
+            return np.zeros(self.dist2.shape, bool)
+        sq = t * t
+        limit = 2 ** 64 - 2 if sq >= 2.0 ** 64 else min(int(math.floor(sq)), 2 ** 64 - 2)
+        return self.dist2 <= np.uint64(limit)
+
+
 class RegionMap:
     """labels (rows, cols) int32, the region's number or -1; table (n,) REGION_DTYPE; n; wrap; unit_m2 = the square metres of
     one unit of weight when the map was made with row weights of a known unit (else None: a weight is a node count or the
@@ -198,6 +288,26 @@ class RegionMap:
     def holes(self, shape):
         """regions.holes of a shape table of this map: (holes, may_wind)."""
         return holes(shape, self.table, self.labels.shape[1], self.wrap)
+
+    def proximity(self, rt, positions, to="set", unit_m=None, stats=None):
+        """MoonRT.proximity of this map's labels: every node's nearest node of any region (to="set") or nearest node outside
+        every region (to="outside"), over (rows, cols, 3) int32 positions (node_positions)."""
+        return rt.proximity(self.labels, positions, to=to, unit_m=unit_m, stats=stats)
+
+    def reach(self, rt, prox, stats=None):
+        """MoonRT.region_reach of a ProximityMap over this map's regions: (n,) REACH_DTYPE."""
+        return rt.region_reach(self.labels, self.n, prox, stats=stats)
+
+    def inscribed(self, rt, positions, unit_m=0.01, stats=None):
+        """(radius_m (n,) float64, centre_node (n,) int32): the largest circle that fits in each region, from the distances to
+        the nearest node outside every region: its centre is the region's node farthest from one (the least index among
+        equals) and its radius that chord, sqrt(d2_max) unit_m.  inf and the region's least node when no node of the window
+        lies outside a region.  Nodes beyond the window's edge are not "outside": a region that touches the edge (the i_min
+        / i_max and dj_min / dj_max extents of the catalogue tell which) may read a circle that leaves the window."""
+        prox = self.proximity(rt, positions, to="outside", unit_m=unit_m, stats=stats)
+        r = self.reach(rt, prox, stats=stats)
+        none = r["d2_max"] == NO_FEATURE
+        return np.where(none, np.inf, np.sqrt(r["d2_max"].astype(np.float64)) * float(unit_m)), r["max_at"].copy()
 
     def largest(self, k=1):
         """The numbers of the k regions of greatest weight, greatest first (equal weights: the lower number first)."""

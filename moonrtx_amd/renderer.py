@@ -1283,6 +1283,79 @@ class MoonRT:
         self._add_stats(stats, st)
         return table
 
+    # ---- Proximity maps and the reach of labelled regions
+    def proximity(self, labels, positions, to="set", shape=None, stats=None, unit_m=None):
+        """Every node's nearest feature node and the exact squared distance to it (mrtx_proximity), between node positions in
+        three dimensions: to="set" measures to the nodes with label >= 0, to="outside" to those with label < 0; ties go to
+        the least node index.  labels: (rows, cols) int32 or a DeviceBuffer; positions: (rows, cols, 3) int32
+        (regions.node_positions), every coordinate within +-2^29, or a DeviceBuffer; both from one side, and with
+        DeviceBuffers give shape = (rows, cols): the tables are then made on the device and downloaded.  unit_m: the metres
+        of one unit of the positions, for the map's distances in metres.  Returns regions.ProximityMap.  stats gains
+        launches, kernel_ms and pairs, the number of distance evaluations."""
+        from . import regions as rg
+        modes = {"set": _lib.PROX_TO_SET, "outside": _lib.PROX_TO_OUTSIDE}
+        if to not in modes:
+            raise ValueError('to must be "set" or "outside"')
+        dev = isinstance(positions, DeviceBuffer)
+        if dev != isinstance(labels, DeviceBuffer):
+            raise ValueError("labels and positions must both be numpy arrays or both DeviceBuffers")
+        lab_d, lab_h, rows, cols, _keep = self._label_arg(labels, shape)
+        n = rows * cols
+        p = _lib.MrtxProximity(rows, cols, modes[to], 0)
+        st = MrtxStats()
+        pairs = C.c_uint64(0)
+        if dev:
+            if positions.nbytes < 12 * n:
+                raise ValueError("the position DeviceBuffer is smaller than its shape")
+            near_b = DeviceBuffer(4 * n, positions.device)
+            d2_b = DeviceBuffer(8 * n, positions.device)
+            try:
+                self._check(self._lib.mrtx_proximity(self._ctx, C.byref(p), positions.ptr, None, lab_d, None, near_b.ptr, None,
+                                                     d2_b.ptr, None, C.byref(pairs), C.byref(st)), "mrtx_proximity")
+                nearest = near_b.download(np.int32, (rows, cols))
+                dist2 = d2_b.download(np.uint64, (rows, cols))
+            finally:
+                near_b.free()
+                d2_b.free()
+        else:
+            pos = np.ascontiguousarray(positions)
+            if pos.shape != (rows, cols, 3) or not np.issubdtype(pos.dtype, np.integer):
+                raise ValueError("positions must be (rows, cols, 3) integers")
+            if pos.size and (pos.min() < -rg.COORD_MAX or pos.max() > rg.COORD_MAX):
+                raise ValueError("a coordinate leaves +-2^29: choose a larger unit")
+            pos = pos.astype(np.int32)
+            nearest = np.empty((rows, cols), np.int32)
+            dist2 = np.empty((rows, cols), np.uint64)
+            self._check(self._lib.mrtx_proximity(self._ctx, C.byref(p), None, pos.ctypes.data, None, lab_h, None,
+                                                 nearest.ctypes.data, None, dist2.ctypes.data, C.byref(pairs), C.byref(st)),
+                        "mrtx_proximity")
+        self._add_stats(stats, st)
+        if isinstance(stats, dict):
+            stats["pairs"] = stats.get("pairs", 0) + int(pairs.value)
+        return rg.ProximityMap(nearest, dist2, unit_m)
+
+    def region_reach(self, labels, n_regions, prox, shape=None, stats=None):
+        """The extremes of a proximity map over each region of a label table (mrtx_regions_reach): the greatest and least
+        dist2 of the region's nodes, the least node index attaining each, and the nearest feature of the closest node.
+        labels: (rows, cols) int32 or a DeviceBuffer (then give shape = (rows, cols)); prox: a regions.ProximityMap or a pair
+        (dist2, nearest) of arrays.  On a to="outside" map of the regions' own labels d2_max and max_at are the radius and
+        the centre of the largest circle in each region; on a to="set" map of another set d2_min, min_at and min_nearest say
+        how close each region comes to it.  Returns (n_regions,) regions.REACH_DTYPE."""
+        from . import regions as rg
+        n_regions = int(n_regions)
+        lab_d, lab_h, rows, cols, _keep = self._label_arg(labels, shape)
+        d2, near = (prox.dist2, prox.nearest) if isinstance(prox, rg.ProximityMap) else prox
+        d2 = np.ascontiguousarray(d2, np.uint64)
+        near = np.ascontiguousarray(near, np.int32)
+        if d2.shape != (rows, cols) or near.shape != (rows, cols):
+            raise ValueError("the proximity map and labels differ in shape")
+        table = np.zeros(max(n_regions, 1), rg.REACH_DTYPE)
+        st = MrtxStats()
+        self._check(self._lib.mrtx_regions_reach(self._ctx, rows, cols, lab_d, lab_h, n_regions, None, d2.ctypes.data, None,
+                                                 near.ctypes.data, None, table.ctypes.data, C.byref(st)), "mrtx_regions_reach")
+        self._add_stats(stats, st)
+        return table[:n_regions]
+
     @staticmethod
     def _add_stats(acc, st, extra=None):
         """Sum the counters of one call into the dict `acc` (if it is one); extra = {key: MrtxStats field} of the call's own."""

@@ -25,16 +25,13 @@ import numpy as np
 from moonrtx_amd import regions as rg
 from moonrtx_amd.renderer import MoonRT
 from moonrtx_amd.traverse import window_dict
+import predicate_args
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--map", required=True, help=".npy, (rows, cols) or (rows, cols, channels)")
 ap.add_argument("--channel", type=int, default=0)
-g = ap.add_mutually_exclusive_group(required=True)
-g.add_argument("--below", type=float, metavar="X")
-g.add_argument("--above", type=float, metavar="X")
-g.add_argument("--between", type=float, nargs=2, metavar=("A", "B"))
-ap.add_argument("--window", type=int, nargs="+", required=True, metavar="N", help="ROW0 COL0 ROWS COLS [STRIDE [WRAP]] in DEM texels")
-ap.add_argument("--dem-size", type=int, nargs=2, default=(23040, 46080), metavar=("H", "W"), help="the DEM the window counts in")
+predicate_args.add_predicate(ap)
+predicate_args.add_window(ap)
 ap.add_argument("--connectivity", type=int, default=4, choices=(4, 8))
 ap.add_argument("--min-area-km2", type=float, default=0.0)
 ap.add_argument("--radius-m", type=float, default=1737400.0)
@@ -50,14 +47,10 @@ if not 4 <= len(a.window) <= 6:
     ap.error("--window takes ROW0 COL0 ROWS COLS [STRIDE [WRAP]]")
 w = window_dict(a.window)
 H, W = a.dem_size
-field = np.load(a.map)
-if field.ndim == 2:
-    field = field[:, :, None]
-if field.ndim != 3 or field.shape[:2] != (w["rows"], w["cols"]):
-    sys.exit(f"{a.map} is {field.shape}: the window has {w['rows']} x {w['cols']} nodes")
+field = predicate_args.load_map(a.map, w)
 if field.shape[2] > 16:           # the library compares one channel of at most 16
     field, a.channel = field[:, :, a.channel:a.channel + 1], 0
-lo, hi = (-math.inf, a.below) if a.below is not None else (a.above, math.inf) if a.above is not None else tuple(a.between)
+lo, hi = predicate_args.bounds(a)
 weights = rg.row_weights(w, (H, W), a.radius_m, a.unit_m2)
 rt = MoonRT(16, 16, device=0)
 st = {}
