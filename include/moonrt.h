@@ -732,6 +732,62 @@ int mrtx_regions_reach(mrtx_ctx* ctx, int32_t rows, int32_t cols, const void* de
                        uint32_t n_regions, const void* dev_dist2, const uint64_t* host_dist2, const void* dev_nearest,
                        const int32_t* host_nearest, void* dev_out, MrtxRegionReach* host_out, MrtxStats* out);
 
+/* ---- Region outlines: the ordered boundary rings of a label table (additive to ABI 7) --------------
+ * Lattice and labels are mrtx_regions_stats', with at most 2^28 nodes, so that every side id fits an int32.  The cell of node
+ * (i, j) has the corners NW (y, x) = (i, j), NE (i, j + 1), SE (i + 1, j + 1), SW (i + 1, j).  Side k of node v has the id
+ * 4 v + k and runs with the region on its right: 0 north NW -> NE, 1 east NE -> SE, 2 south SE -> SW, 3 west SW -> NW.  It is a
+ * boundary side by mrtx_regions_shape's rule.  Successor of boundary side k of node (i, j) with label l: with the travel
+ * direction T[k] = (0,1), (1,0), (0,-1), (-1,0), the outward direction D[k] = (-1,0), (0,1), (1,0), (0,-1), a = (i, j) + T[k]
+ * and b = a + D[k] (columns mod cols under wrap; a node outside the lattice carries no label): side k - 1 of b when a and b
+ * carry l (a left turn); side k of a when only a does (straight on); side k - 1 of b when only b does and connectivity is 8
+ * (through the saddle); else side k + 1 of the same node (a right turn).  The successor map is a permutation of the boundary
+ * sides and its cycles are the rings.  A ring's head is its least side id; rings are numbered by ascending head; a side's
+ * position is its distance from the head along the successor map.  MRTX_OUTLINE_ALL: every side contributes its start corner.
+ * MRTX_OUTLINE_CORNERS: only a side whose k differs from its predecessor's; a ring without a turn (a straight line all round a
+ * wrapped window) contributes its head's start corner alone.  The vertex table holds (y, x) int32 pairs, ring after ring, each
+ * ring from its head on.  x is unwrapped along the ring: the head's start corner has its natural column, every later vertex
+ * the previous one plus the signed column steps of the sides between, so a ring across the seam is continuous and x may leave
+ * 0 .. cols.
+ * Exact for any label table, connected or not: (1) the areas of a label's rings add up to its MrtxRegion.count, (2) their
+ * wareas to its MrtxRegion.weight, (3) their n_sides to sides_ns + sides_ew of its MrtxRegionShape, (4) its outer rings (wind
+ * == 0, area > 0) minus its holes (wind == 0, area < 0) are MrtxRegionShape.euler at the same connectivity; winding rings
+ * (wind != 0) count on neither side, so the number of hole rings is also right for a region that winds round the seam. */
+#define MRTX_OUTLINE_ALL 0
+#define MRTX_OUTLINE_CORNERS 1
+typedef struct MrtxOutline {
+    int32_t rows, cols, wrap;
+    int32_t connectivity;   /* 4 or 8 */
+    int32_t mode;           /* MRTX_OUTLINE_ALL or MRTX_OUTLINE_CORNERS */
+    int32_t reserved;       /* 0 */
+} MrtxOutline;
+typedef struct MrtxRing {
+    int64_t area;           /* the sum of i + 1 over the ring's south sides minus the sum of i over its north sides */
+    int64_t warea;          /* the same with cw[i + 1] and cw[i], cw the exclusive prefix sum of row_weight */
+    uint64_t first;         /* index of the ring's first vertex in the vertex table */
+    uint32_t n_sides;
+    uint32_t n_vertices;    /* in the chosen mode */
+    int32_t label;
+    int32_t head;           /* the least side id */
+    int32_t wind;           /* (north sides - south sides) / cols: 0 without wrap, else -1, 0 or +1 */
+    uint32_t reserved;      /* 0 */
+} MrtxRing;
+/* Labels in exactly one of dev_labels (4-byte aligned) and host_labels; row_weight: rows uint32 in host memory or NULL (every
+ * row weighs 1 and warea == area).  *n_rings and *n_vertices receive the true totals whenever the label table passes its
+ * checks.  With all four table pointers NULL and both caps 0 the call only counts.  Otherwise exactly one of dev_rings (8-byte
+ * aligned) and host_rings and exactly one of dev_vertices (4-byte aligned) and host_vertices is given, with room for ring_cap
+ * records and vertex_cap (y, x) pairs; no two device tables may overlap.  When both totals fit, the tables are written; when
+ * either does not, nothing is written to either, the call returns MRTX_E_INVALID naming both needed sizes, and the counts are
+ * still set.  A refused call leaves the two counts as they were.  The call needs no DEM, light or Moon frame and leaves the
+ * render state alone.  MOONRT_REGIONS_OUTLINE = contract (default) | jump chooses between pointer jumping over the chains of
+ * boundary sides inside tiles of 16 x 64 nodes and over every boundary side; both give the same bytes.  The number of launches
+ * depends on the lattice, the options, the variant and the number of boundary sides alone.  out: launches, kernel_ms (from the
+ * first launch to the last, the host's reads of the counts between them included); written also when the call fails for a
+ * bad label, not when it is refused. */
+int mrtx_regions_outline(mrtx_ctx* ctx, const MrtxOutline* o, const void* dev_labels, const int32_t* host_labels,
+                         uint32_t n_regions, const uint32_t* row_weight, void* dev_rings, MrtxRing* host_rings, uint64_t ring_cap,
+                         void* dev_vertices, int32_t* host_vertices, uint64_t vertex_cap, uint64_t* n_rings, uint64_t* n_vertices,
+                         MrtxStats* out);
+
 /* ---- Mast-height horizons and joint windows (additive to ABI 7) ----------------------------------
  * mrtx_horizon_points from a raised origin: point p marches from P = fmaf(hs, u, o), hs = (float)(height_m[p] / radius_m * R),
  * the raised end of mrtx_sight_points (so a mast top is one point for the horizon and for the line of sight).  height_m: n

@@ -125,6 +125,23 @@ class MrtxRegionReach(C.Structure):
                 ("min_nearest", C.c_int32), ("count", C.c_uint32)]
 
 
+OUTLINE_ALL = 0
+OUTLINE_CORNERS = 1
+
+
+class MrtxOutline(C.Structure):
+    """The lattice and the options of a region outline (mrtx_regions_outline)."""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("wrap", C.c_int32), ("connectivity", C.c_int32), ("mode", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class MrtxRing(C.Structure):
+    """One boundary ring of a label table (mrtx_regions_outline): 48 bytes, all integers."""
+    _fields_ = [("area", C.c_int64), ("warea", C.c_int64), ("first", C.c_uint64), ("n_sides", C.c_uint32),
+                ("n_vertices", C.c_uint32), ("label", C.c_int32), ("head", C.c_int32), ("wind", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
 class MrtxIllumEpoch(C.Structure):
     """One date of a Sun-illumination series (mrtx_illum_series): what mrtx_set_light and
     mrtx_set_moon_frame would set for it."""
@@ -259,6 +276,8 @@ SIGNATURES = {
                                  C.POINTER(MrtxStats)]),
     "mrtx_regions_reach": (C.c_int, [_VP, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP,
                                      C.POINTER(MrtxStats)]),
+    "mrtx_regions_outline": (C.c_int, [_VP, C.POINTER(MrtxOutline), _VP, _VP, C.c_uint32, _VP, _VP, _VP, C.c_uint64, _VP, _VP,
+                                       C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
     "mrtx_thermal": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                C.POINTER(MrtxStats)]),
     "mrtx_view_dir_samples": (C.c_int, [C.c_int32, _VP]),

@@ -24,6 +24,7 @@
 #include "mrtx_regions.h"
 #include "mrtx_zonal.h"
 #include "mrtx_proximity.h"
+#include "mrtx_outline.h"
 
 hipError_t mrtx_launch_render(const FrameC& f, int S, bool stats, int mode, bool overlay, const PathQ* pq, hipStream_t st);
 uint64_t mrtx_path_chunks(const FrameC& f, int S, uint32_t* grid_a, int* njobs_log2);
@@ -2765,6 +2766,141 @@ int mrtx_regions_reach(mrtx_ctx* c, int32_t rows, int32_t cols, const void* dev_
     if (out) out->launches = launches;
     HIPCHK(c, hipMemcpy(&bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));
     if (bad) return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", bad, (long long)n_regions - 1);
+    return MRTX_OK;
+}
+
+// ---- Region outlines: the ordered boundary rings of a label table --------------------------------
+static_assert(sizeof(MrtxRing) == 48 && sizeof(RingRec) == sizeof(MrtxRing), "MrtxRing is 48 bytes");
+static_assert(sizeof(OutlineJump) == 32, "two int4");
+
+int mrtx_regions_outline(mrtx_ctx* c, const MrtxOutline* o, const void* dev_labels, const int32_t* host_labels, uint32_t n_regions,
+                         const uint32_t* row_weight, void* dev_rings, MrtxRing* host_rings, uint64_t ring_cap, void* dev_vertices,
+                         int32_t* host_vertices, uint64_t vertex_cap, uint64_t* n_rings, uint64_t* n_vertices, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!o) return fail(c, MRTX_E_INVALID, "null outline block");
+    if (o->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    int rc = regions_lattice(c, o->rows, o->cols, o->wrap);
+    if (rc != MRTX_OK) return rc;
+    if ((int64_t)o->rows * (int64_t)o->cols > MRTX_OL_MAX_NODES)
+        return fail(c, MRTX_E_INVALID, "an outlined lattice holds at most 2^28 nodes (got %d x %d)", o->rows, o->cols);
+    if (o->connectivity != 4 && o->connectivity != 8) return fail(c, MRTX_E_INVALID, "connectivity must be 4 or 8 (got %d)", o->connectivity);
+    if (o->mode != MRTX_OUTLINE_ALL && o->mode != MRTX_OUTLINE_CORNERS)
+        return fail(c, MRTX_E_INVALID, "mode must be MRTX_OUTLINE_ALL or MRTX_OUTLINE_CORNERS (got %d)", o->mode);
+    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
+    if (!n_rings || !n_vertices) return fail(c, MRTX_E_INVALID, "null n_rings or n_vertices");
+    if (dev_rings && host_rings) return fail(c, MRTX_E_INVALID, "give at most one of dev_rings and host_rings");
+    if (dev_vertices && host_vertices) return fail(c, MRTX_E_INVALID, "give at most one of dev_vertices and host_vertices");
+    const bool has_rings = dev_rings || host_rings, has_vertices = dev_vertices || host_vertices;
+    if (has_rings != has_vertices) return fail(c, MRTX_E_INVALID, "give a ring table and a vertex table, or neither to count");
+    if (!has_rings && (ring_cap || vertex_cap))
+        return fail(c, MRTX_E_INVALID, "without tables ring_cap and vertex_cap must be 0 (got %llu, %llu)", (unsigned long long)ring_cap,
+                    (unsigned long long)vertex_cap);
+    const size_t N = (size_t)o->rows * (size_t)o->cols;
+    if ((size_t)n_regions > N) return fail(c, MRTX_E_INVALID, "n_regions = %u exceeds the lattice's %zu nodes", n_regions, N);
+    // a table never needs more than one ring per three sides and one vertex per side
+    const size_t ring_bytes = sizeof(MrtxRing) * (size_t)std::min<uint64_t>(ring_cap, 4 * N);
+    const size_t vertex_bytes = 8 * (size_t)std::min<uint64_t>(vertex_cap, 4 * N);
+    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
+    if (dev_rings && (reinterpret_cast<uintptr_t>(dev_rings) & 7)) return fail(c, MRTX_E_INVALID, "dev_rings must be 8-byte aligned (MrtxRing)");
+    if (dev_vertices && (reinterpret_cast<uintptr_t>(dev_vertices) & 3)) return fail(c, MRTX_E_INVALID, "dev_vertices must be 4-byte aligned (int32)");
+    if (traverse_overlap(dev_labels, 4 * N, dev_rings, ring_bytes) || traverse_overlap(dev_labels, 4 * N, dev_vertices, vertex_bytes) ||
+        traverse_overlap(dev_rings, ring_bytes, dev_vertices, vertex_bytes))
+        return fail(c, MRTX_E_INVALID, "dev_labels, dev_rings and dev_vertices must not overlap");
+    // MOONRT_REGIONS_OUTLINE=jump: pointer jumping over every boundary side, the yardstick of the contraction of the chains
+    // inside a tile; the same bytes
+    bool contract = MRTX_OL_DEFAULT_CONTRACT;
+    if (const char* e = std::getenv("MOONRT_REGIONS_OUTLINE")) {
+        if (std::strcmp(e, "jump") == 0) contract = false;
+        else if (std::strcmp(e, "contract") == 0) contract = true;
+        else return fail(c, MRTX_E_INVALID, "MOONRT_REGIONS_OUTLINE must be contract or jump (got %s)", e);
+    }
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    std::vector<uint64_t> cw;
+    if (row_weight) {
+        cw.assign((size_t)o->rows + 1, 0);
+        for (int32_t i = 0; i < o->rows; i++) cw[(size_t)i + 1] = cw[i] + row_weight[i];
+    }
+    const OutlineNodeLayout nl = outline_node_layout(o->rows, o->cols);
+    float* d[2] = {nullptr, nullptr};
+    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, nl.end)) != MRTX_OK ||
+        (rc = stage_tables(c, {{host_labels, host_labels ? N : 0}, {cw.data(), 2 * cw.size()}}, d)) != MRTX_OK)
+        return rc;
+    char* tb = reinterpret_cast<char*>(c->trav_buf);
+    OutlineC q;
+    std::memset(&q, 0, sizeof q);
+    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_labels);
+    q.cw = row_weight ? reinterpret_cast<const unsigned long long*>(d[1]) : nullptr;
+    q.bad = reinterpret_cast<uint32_t*>(tb);
+    q.totals = reinterpret_cast<unsigned long long*>(tb + 16);
+    q.bits = reinterpret_cast<uint8_t*>(tb + nl.bits_at);
+    q.base = reinterpret_cast<uint32_t*>(tb + nl.base_at);
+    q.node_sums = reinterpret_cast<uint2*>(tb + nl.sums_at);
+    q.rows = o->rows; q.cols = o->cols; q.wrap = o->wrap; q.conn8 = o->connectivity == 8; q.all = o->mode == MRTX_OUTLINE_ALL;
+    q.n_regions = n_regions; q.contract = contract;
+    uint32_t launches = 0;
+    unsigned long long head[6] = {0, 0, 0, 0, 0, 0};            // bad (and padding), then the four totals
+    HIPCHK(c, hipMemsetAsync(tb, 0, 64, c->stream));
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_outline_mark(q, c->stream, &launches));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                 // also: the pageable tables are no longer read
+    HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
+    if ((uint32_t)head[0]) {                                    // as the sibling calls: the stage ends, out says what ran
+        if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
+        if (out) out->launches = launches;
+        return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", (uint32_t)head[0],
+                    (long long)n_regions - 1);
+    }
+    q.B = (uint32_t)head[2];
+    q.rounds = outline_rounds(q.B);
+    uint64_t rings = 0, vertices = 0;
+    bool fits = true;
+    if (q.B) {
+        const OutlineSideLayout sl = outline_side_layout(q.B);
+        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, sl.end)) != MRTX_OK) return rc;
+        char* sb = reinterpret_cast<char*>(c->illum_out);
+        q.sid = reinterpret_cast<int32_t*>(sb + sl.sid_at);
+        q.next = reinterpret_cast<int32_t*>(sb + sl.next_at);
+        q.ringno = reinterpret_cast<uint32_t*>(sb + sl.ringno_at);
+        q.flag = reinterpret_cast<uint8_t*>(sb + sl.flag_at);
+        q.jflag = reinterpret_cast<uint8_t*>(sb + sl.jflag_at);
+        q.jidx = reinterpret_cast<uint32_t*>(sb + sl.jidx_at);
+        q.side_sums = reinterpret_cast<uint2*>(sb + sl.sums_at);
+        q.jump[0] = reinterpret_cast<OutlineJump*>(sb + sl.jump_at[0]);
+        q.jump[1] = reinterpret_cast<OutlineJump*>(sb + sl.jump_at[1]);
+        // where the per-side result ends up, and the buffer that is dead by then (mrtx_outline.h)
+        const int fin_at = (q.rounds & 1) ^ (contract ? 1 : 0);
+        q.fin = q.jump[fin_at];
+        HIPCHK(c, mrtx_launch_outline_trace(q, c->stream, &launches));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
+        if (head[0] >> 32) {
+            if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
+            return fail(c, MRTX_E_DEVICE, "the outline trace met %u broken successors or chains", (uint32_t)(head[0] >> 32));
+        }
+        rings = head[4]; vertices = head[5];
+        fits = rings <= ring_cap && vertices <= vertex_cap;
+        if (has_rings && fits) {
+            // a table bound for the host lies in the jump buffer that the trace left dead
+            char* dead = sb + sl.jump_at[fin_at ^ 1];
+            q.rings = host_rings ? reinterpret_cast<RingRec*>(dead) : static_cast<RingRec*>(dev_rings);
+            q.vertices = host_vertices ? reinterpret_cast<int32_t*>(dead + outline_host_vertices_at(rings)) : static_cast<int32_t*>(dev_vertices);
+            HIPCHK(c, mrtx_launch_outline_fill(q, rings, c->stream, &launches));
+        }
+    }
+    if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
+    if (out) out->launches = launches;
+    if (has_rings && fits && q.B) {                             // the fill's own check of what the trace handed it
+        HIPCHK(c, hipMemcpy(head, tb, 8, hipMemcpyDeviceToHost));
+        if (head[0] >> 32) return fail(c, MRTX_E_DEVICE, "the outline fill met %u sides without a ring", (uint32_t)(head[0] >> 32));
+    }
+    *n_rings = rings;
+    *n_vertices = vertices;
+    if (has_rings && !fits)
+        return fail(c, MRTX_E_INVALID, "the tables are too small: %llu rings and %llu vertices are needed (ring_cap = %llu, vertex_cap = %llu)",
+                    (unsigned long long)rings, (unsigned long long)vertices, (unsigned long long)ring_cap, (unsigned long long)vertex_cap);
+    if (host_rings && rings) HIPCHK(c, hipMemcpy(host_rings, q.rings, sizeof(MrtxRing) * (size_t)rings, hipMemcpyDeviceToHost));
+    if (host_vertices && vertices) HIPCHK(c, hipMemcpy(host_vertices, q.vertices, 8 * (size_t)vertices, hipMemcpyDeviceToHost));
     return MRTX_OK;
 }
 

@@ -27,6 +27,10 @@ assert SHAPE_DTYPE.itemsize == 32
 REACH_DTYPE = np.dtype([("d2_max", "<u8"), ("d2_min", "<u8"), ("max_at", "<i4"), ("min_at", "<i4"), ("min_nearest", "<i4"),
                         ("count", "<u4")])
 assert REACH_DTYPE.itemsize == 32
+# mirrors MrtxRing, 48 bytes
+RING_DTYPE = np.dtype([("area", "<i8"), ("warea", "<i8"), ("first", "<u8"), ("n_sides", "<u4"), ("n_vertices", "<u4"),
+                       ("label", "<i4"), ("head", "<i4"), ("wind", "<i4"), ("reserved", "<u4")])
+assert RING_DTYPE.itemsize == 48
 
 WEIGHT_MAX = 2 ** 32 - 1
 # every coordinate of a node position lies in -COORD_MAX .. COORD_MAX (mrtx_proximity)
@@ -188,6 +192,68 @@ def node_positions(window, dem_hw, radius_m=1737400.0, unit_m=0.01, heights_m=No
     return q.astype(np.int32)
 
 
+class Outlines:
+    """What MoonRT.region_outlines returns (DESIGN.md section 3.23): rings (n,) RING_DTYPE in ascending order of their heads;
+    vertices (m, 2) int32 (y, x) corner coordinates, ring after ring, each ring from its head on with the region on its right
+    (rows run down, columns right), x unwrapped along a ring that crosses the seam; rows, cols, wrap: the lattice.
+
+    holes() counts a label's hole rings (wind == 0 and area < 0).  Unlike regions.holes, which reads 1 - euler and is one too
+    many for a region that winds round the seam, this count is right for winding regions too: a winding ring counts neither
+    as an outer ring nor as a hole."""
+
+    def __init__(self, rings, vertices, rows, cols, wrap=False):
+        self.rings = np.ascontiguousarray(rings, RING_DTYPE).reshape(-1)
+        self.vertices = np.ascontiguousarray(vertices, np.int32).reshape(-1, 2)
+        self.rows, self.cols, self.wrap = int(rows), int(cols), bool(wrap)
+        if int(self.rings["n_vertices"].astype(np.int64).sum()) != self.vertices.shape[0]:
+            raise ValueError("the rings' n_vertices do not add up to the vertex table")
+
+    def __len__(self):
+        return int(self.rings.shape[0])
+
+    def ring(self, r):
+        """(n_vertices, 2) int32: the vertices of ring r, a view of the vertex table."""
+        rec = self.rings[int(r)]
+        return self.vertices[int(rec["first"]):int(rec["first"]) + int(rec["n_vertices"])]
+
+    def role(self, r):
+        """"outer" (wind == 0, area > 0), "hole" (wind == 0, area < 0) or "winding" (wind != 0: the ring goes round the window)."""
+        rec = self.rings[int(r)]
+        if rec["wind"] != 0:
+            return "winding"
+        return "outer" if rec["area"] > 0 else "hole"
+
+    def of(self, label):
+        """The numbers of a label's rings: outer rings first, then winding rings, then holes, each in ring order."""
+        idx = np.flatnonzero(self.rings["label"] == int(label))
+        order = {"outer": 0, "winding": 1, "hole": 2}
+        return np.array(sorted(idx, key=lambda r: (order[self.role(r)], r)), np.int64)
+
+    def holes(self, n_regions=None):
+        """(n_regions,) int64: per label the number of hole rings (n_regions: one more than the greatest label when not given)."""
+        lab = self.rings["label"].astype(np.int64)
+        n = int(n_regions) if n_regions is not None else (int(lab.max()) + 1 if lab.size else 0)
+        hole = (self.rings["wind"] == 0) & (self.rings["area"] < 0)
+        return np.bincount(lab[hole], minlength=n).astype(np.int64)
+
+    def corner_latlon(self, window, dem_hw):
+        """(m, 2) float64 (lat, lon) degrees of every vertex, for a window (row0, col0, rows, cols[, stride[, wrap]]) of an
+        (H, W) DEM.  Corners sit on the cell edges of row_weights / side_weights' convention, half a row or column spacing off
+        the texel-centre nodes: lat = 90 - (row0 + (y - 1 / 2) stride + 1 / 2) 180 / H clipped to the poles, lon = -180 +
+        (col0 + (x - 1 / 2) stride + 1 / 2) 360 / W.  lon is continuous along a ring: the unwrapped x of a ring across the seam
+        gives longitudes beyond +-180, which the caller may reduce."""
+        from .traverse import window_dict
+        w = window_dict(window)
+        H, W = (int(v) for v in dem_hw)
+        if w["stride"] < 1 or H < 1 or W < 1:
+            raise ValueError("empty window or DEM")
+        y = self.vertices[:, 0].astype(np.float64)
+        x = self.vertices[:, 1].astype(np.float64)
+        lat = 90.0 - (w["row0"] + (y - 0.5) * w["stride"] + 0.5) * (180.0 / H)
+        lon = -180.0 + (w["col0"] + (x - 0.5) * w["stride"] + 0.5) * (360.0 / W)
+        return np.stack([np.clip(lat, -90.0, 90.0), lon], -1)
+
+
 class ProximityMap:
     """What MoonRT.proximity returns: nearest (rows, cols) int32, the node index of every node's
     nearest feature (-1: there is none); dist2 (rows, cols) uint64, the exact squared distance to it in squared units of the
@@ -288,6 +354,11 @@ class RegionMap:
     def holes(self, shape):
         """regions.holes of a shape table of this map: (holes, may_wind)."""
         return holes(shape, self.table, self.labels.shape[1], self.wrap)
+
+    def outlines(self, rt, connectivity=4, corners=True, row_weights=None, stats=None):
+        """MoonRT.region_outlines of this map's regions: an Outlines."""
+        return rt.region_outlines(self.labels, self.n, connectivity=connectivity, wrap=self.wrap, corners=corners,
+                                  row_weights=row_weights, stats=stats)
 
     def proximity(self, rt, positions, to="set", unit_m=None, stats=None):
         """MoonRT.proximity of this map's labels: every node's nearest node of any region (to="set") or nearest node outside

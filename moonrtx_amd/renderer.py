@@ -1356,6 +1356,51 @@ class MoonRT:
         self._add_stats(stats, st)
         return table[:n_regions]
 
+    # ---- Region outlines
+    def region_outlines(self, labels, n_regions, connectivity=4, wrap=False, corners=True, row_weights=None, shape=None,
+                        stats=None):
+        """The ordered boundary rings of each region of a label table (mrtx_regions_outline): every ring from its least side
+        on, the region on its right, holes as rings of their own, x unwrapped along a ring that crosses the seam.  labels:
+        (rows, cols) int32 or a DeviceBuffer (then give shape = (rows, cols), and the tables are made on the device and
+        downloaded).  corners: only the vertices at which a ring turns (else one per boundary side).  row_weights: (rows,)
+        uint32 node areas for MrtxRing.warea, or None.  One call counts, a second fills tables of exactly that size.  Returns
+        regions.Outlines."""
+        from . import regions as rg
+        n_regions = int(n_regions)
+        lab_d, lab_h, rows, cols, _keep = self._label_arg(labels, shape)
+        weights = self._row_table(row_weights, rows, "row_weights")
+        wp = weights.ctypes.data if weights is not None else None
+        o = _lib.MrtxOutline(rows, cols, 1 if wrap else 0, int(connectivity), _lib.OUTLINE_CORNERS if corners else _lib.OUTLINE_ALL, 0)
+        nr, nv = C.c_uint64(0), C.c_uint64(0)
+        st, st2 = MrtxStats(), MrtxStats()
+        self._check(self._lib.mrtx_regions_outline(self._ctx, C.byref(o), lab_d, lab_h, n_regions, wp, None, None, 0, None, None, 0,
+                                                   C.byref(nr), C.byref(nv), C.byref(st)), "mrtx_regions_outline")
+        self._add_stats(stats, st)
+        n_r, n_v = int(nr.value), int(nv.value)
+        if lab_d is not None:
+            rb = DeviceBuffer(max(48 * n_r, 48), labels.device)
+            vb = DeviceBuffer(max(8 * n_v, 8), labels.device)
+            try:
+                self._check(self._lib.mrtx_regions_outline(self._ctx, C.byref(o), lab_d, None, n_regions, wp, rb.ptr, None, n_r, vb.ptr,
+                                                           None, n_v, C.byref(nr), C.byref(nv), C.byref(st2)), "mrtx_regions_outline")
+                rings = rb.download(rg.RING_DTYPE, (n_r,))
+                vertices = vb.download(np.int32, (n_v, 2))
+            finally:
+                rb.free()
+                vb.free()
+        else:
+            rings = np.zeros(max(n_r, 1), rg.RING_DTYPE)
+            vertices = np.zeros((max(n_v, 1), 2), np.int32)
+            self._check(self._lib.mrtx_regions_outline(self._ctx, C.byref(o), None, lab_h, n_regions, wp, None, rings.ctypes.data, n_r,
+                                                       None, vertices.ctypes.data, n_v, C.byref(nr), C.byref(nv), C.byref(st2)),
+                        "mrtx_regions_outline")
+            rings, vertices = rings[:n_r], vertices[:n_v]
+        self._add_stats(stats, st2)
+        if isinstance(stats, dict):
+            stats["count_ms"] = stats.get("count_ms", 0.0) + st.kernel_ms
+            stats["fill_ms"] = stats.get("fill_ms", 0.0) + st2.kernel_ms
+        return rg.Outlines(rings, vertices, rows, cols, wrap)
+
     @staticmethod
     def _add_stats(acc, st, extra=None):
         """Sum the counters of one call into the dict `acc` (if it is one); extra = {key: MrtxStats field} of the call's own."""

@@ -1,4 +1,4 @@
-"""The predicate options the map tools share (region_catalogue.py, proximity_map.py): --below X, --above X or --between A B
+"""The predicate options the map tools share (region_catalogue.py, proximity_map.py, region_outlines.py): --below X, --above X or --between A B
 select the nodes of one channel of a saved map, and --window places the map on the DEM."""
 import math
 import sys
