@@ -788,6 +788,58 @@ int mrtx_regions_outline(mrtx_ctx* ctx, const MrtxOutline* o, const void* dev_la
                          void* dev_vertices, int32_t* host_vertices, uint64_t vertex_cap, uint64_t* n_rings, uint64_t* n_vertices,
                          MrtxStats* out);
 
+/* ---- Terrain depressions: fill levels and the basin catalogue (additive to ABI 7) -----------------
+ * Lattice, wrap and connectivity are mrtx_regions_label's (at most 2^31 nodes, node (i, j) at index v = i cols + j, wrap joins
+ * column cols - 1 to column 0 and needs cols >= 3, no edge crosses the first or the last row).  Heights z[v]: int32 in a unit of
+ * the caller's, |z| <= 2^30.  Outlets: with edge_outlets = 1 every node of the first and of the last row and, without wrap, of
+ * the first and of the last column; and every node whose byte in the optional uint8 outlet table is nonzero.  fill[v] is the
+ * minimum, over all lattice paths from v to any outlet, of the maximum z on the path, both ends included; for an outlet fill =
+ * z; without any outlet (an all-zero table with edge_outlets = 0) fill = MRTX_FILL_NONE everywhere.  depth = fill - z >= 0, and a
+ * node is in a depression iff depth > 0.  Nothing depends on the order of evaluation.  Both calls need no DEM, no light and no
+ * Moon frame and leave the render state alone. */
+#define MRTX_FILL_NONE 2147483647
+typedef struct MrtxFill {
+    int32_t rows, cols, wrap;
+    int32_t connectivity;   /* 4 or 8 */
+    int32_t edge_outlets;   /* 0 or 1; 0 needs an outlet table */
+    int32_t reserved;       /* 0 */
+} MrtxFill;
+/* Heights rows x cols int32 in exactly one of dev_z and host_z; the outlet table rows x cols uint8 in at most one of
+ * dev_outlet and host_outlet (both NULL: none); the fill rows x cols int32 into exactly one of dev_fill and host_fill.  Device
+ * int32 tables are 4-byte aligned and no two device tables may overlap.  A height beyond +-2^30 gives MRTX_E_INVALID: in a host
+ * table at its first occurrence before any device call, in a device table after the launches (the kernels clamp it, so nothing
+ * else goes wrong), as mrtx_proximity treats its coordinates.  MOONRT_FILL = tiles (default) | sweep chooses between the
+ * relaxation in LDS tiles of 32 x 32 nodes, launched over the tiles whose surroundings changed, and one Jacobi step over the
+ * whole lattice per launch; both give the same bytes.  visits (or NULL): the tile visits, or the node updates of the sweep;
+ * with tiles it and the number of launches may differ from run to run.  There is no launch cap: every store lowers an int32.
+ * out: launches, kernel_ms (from the first launch to the last, the host's reads of the change counter included). */
+int mrtx_fill(mrtx_ctx* ctx, const MrtxFill* f, const void* dev_z, const int32_t* host_z, const void* dev_outlet,
+              const uint8_t* host_outlet, void* dev_fill, int32_t* host_fill, uint64_t* visits, MrtxStats* out);
+/* One region of a label table over a fill, 48 bytes.  The depth of a node is (int64)fill - z held in 0 .. INT32_MAX, so any fill
+ * table is accepted.  pour_at is chosen among the nodes u that carry another label (-1 included) and are adjacent, in the given
+ * connectivity and wrap, to a node of the region: the u that minimises (fill[u], u) lexicographically.  For a connected component
+ * of {depth > 0} at the fill's connectivity, level_min == level_max == pour_level. */
+typedef struct MrtxBasin {
+    uint64_t weight;        /* the sum of row_weight[i] over the region's nodes */
+    uint64_t volume;        /* the sum of row_weight[i] * depth, modulo 2^64 */
+    uint32_t count;         /* nodes */
+    int32_t level_min, level_max;   /* the extremes of fill over the region; INT32_MAX and INT32_MIN when count == 0 */
+    int32_t depth_max;      /* the largest depth; 0 when count == 0 */
+    int32_t deepest_at;     /* the least node index with the largest depth; -1 when count == 0 */
+    int32_t pour_at;        /* -1 when no node qualifies: count == 0, or the region covers the whole lattice */
+    int32_t pour_level;     /* fill[pour_at]; INT32_MAX when pour_at == -1 */
+    uint32_t reserved;      /* 0 */
+} MrtxBasin;
+/* n_regions records into exactly one of dev_out (8-byte aligned, overlapping no device input) and host_out, of the heights and
+ * the fill (each in exactly one of its device, 4-byte aligned, and host pointer) over any label table, checked as in
+ * mrtx_regions_stats: an entry >= n_regions or < -1 is never used as an index and gives MRTX_E_INVALID after the launch;
+ * n_regions = 0 checks the table and writes nothing.  Heights beyond +-2^30 are treated as in mrtx_fill.  row_weight: rows uint32
+ * in host memory or NULL (every node weighs 1).  out: launches, kernel_ms. */
+int mrtx_fill_basins(mrtx_ctx* ctx, int32_t rows, int32_t cols, int32_t wrap, int32_t connectivity, const void* dev_labels,
+                     const int32_t* host_labels, uint32_t n_regions, const void* dev_z, const int32_t* host_z,
+                     const void* dev_fill, const int32_t* host_fill, const uint32_t* row_weight, void* dev_out,
+                     MrtxBasin* host_out, MrtxStats* out);
+
 /* ---- Mast-height horizons and joint windows (additive to ABI 7) ----------------------------------
  * mrtx_horizon_points from a raised origin: point p marches from P = fmaf(hs, u, o), hs = (float)(height_m[p] / radius_m * R),
  * the raised end of mrtx_sight_points (so a mast top is one point for the horizon and for the line of sight).  height_m: n

@@ -142,6 +142,23 @@ class MrtxRing(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+FILL_NONE = 2 ** 31 - 1         # MRTX_FILL_NONE: the fill of a lattice without any outlet
+FILL_ZMAX = 2 ** 30             # |z| <= 2^30
+
+
+class MrtxFill(C.Structure):
+    """The lattice and the outlets of a depression fill (mrtx_fill)."""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("wrap", C.c_int32), ("connectivity", C.c_int32),
+                ("edge_outlets", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MrtxBasin(C.Structure):
+    """One region of a label table over a fill (mrtx_fill_basins): 48 bytes, all integers."""
+    _fields_ = [("weight", C.c_uint64), ("volume", C.c_uint64), ("count", C.c_uint32), ("level_min", C.c_int32),
+                ("level_max", C.c_int32), ("depth_max", C.c_int32), ("deepest_at", C.c_int32), ("pour_at", C.c_int32),
+                ("pour_level", C.c_int32), ("reserved", C.c_uint32)]
+
+
 class MrtxIllumEpoch(C.Structure):
     """One date of a Sun-illumination series (mrtx_illum_series): what mrtx_set_light and
     mrtx_set_moon_frame would set for it."""
@@ -278,6 +295,9 @@ SIGNATURES = {
                                      C.POINTER(MrtxStats)]),
     "mrtx_regions_outline": (C.c_int, [_VP, C.POINTER(MrtxOutline), _VP, _VP, C.c_uint32, _VP, _VP, _VP, C.c_uint64, _VP, _VP,
                                        C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
+    "mrtx_fill": (C.c_int, [_VP, C.POINTER(MrtxFill), _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
+    "mrtx_fill_basins": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP,
+                                   _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_thermal": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                C.POINTER(MrtxStats)]),
     "mrtx_view_dir_samples": (C.c_int, [C.c_int32, _VP]),

@@ -25,6 +25,7 @@
 #include "mrtx_zonal.h"
 #include "mrtx_proximity.h"
 #include "mrtx_outline.h"
+#include "mrtx_fill.h"
 
 hipError_t mrtx_launch_render(const FrameC& f, int S, bool stats, int mode, bool overlay, const PathQ* pq, hipStream_t st);
 uint64_t mrtx_path_chunks(const FrameC& f, int S, uint32_t* grid_a, int* njobs_log2);
@@ -2901,6 +2902,180 @@ int mrtx_regions_outline(mrtx_ctx* c, const MrtxOutline* o, const void* dev_labe
                     (unsigned long long)rings, (unsigned long long)vertices, (unsigned long long)ring_cap, (unsigned long long)vertex_cap);
     if (host_rings && rings) HIPCHK(c, hipMemcpy(host_rings, q.rings, sizeof(MrtxRing) * (size_t)rings, hipMemcpyDeviceToHost));
     if (host_vertices && vertices) HIPCHK(c, hipMemcpy(host_vertices, q.vertices, 8 * (size_t)vertices, hipMemcpyDeviceToHost));
+    return MRTX_OK;
+}
+
+// ---- Terrain depressions: fill levels and the basin catalogue -------------------------------------
+static_assert(sizeof(MrtxFill) == 24, "MrtxFill is 24 bytes");
+static_assert(sizeof(MrtxBasin) == 48 && sizeof(BasinRec) == sizeof(MrtxBasin), "MrtxBasin is 48 bytes");
+static_assert(MRTX_FILL_NONE == INT32_MAX, "the fill without an outlet");
+
+// a host height table is refused at its first height beyond the bound (a device table's are counted by the kernels)
+static int fill_host_heights(mrtx_ctx* c, const int32_t* host_z, size_t N) {
+    if (host_z)
+        for (size_t n = 0; n < N; n++)
+            if (host_z[n] < -MRTX_FILL_ZMAX || host_z[n] > MRTX_FILL_ZMAX)
+                return fail(c, MRTX_E_INVALID, "height %zu must lie in -2^30 .. 2^30 (got %d)", n, host_z[n]);
+    return MRTX_OK;
+}
+
+int mrtx_fill(mrtx_ctx* c, const MrtxFill* f, const void* dev_z, const int32_t* host_z, const void* dev_outlet,
+              const uint8_t* host_outlet, void* dev_fill, int32_t* host_fill, uint64_t* visits, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!f) return fail(c, MRTX_E_INVALID, "null fill block");
+    if (f->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    int rc = regions_lattice(c, f->rows, f->cols, f->wrap);
+    if (rc != MRTX_OK) return rc;
+    if (f->connectivity != 4 && f->connectivity != 8) return fail(c, MRTX_E_INVALID, "connectivity must be 4 or 8 (got %d)", f->connectivity);
+    if (f->edge_outlets != 0 && f->edge_outlets != 1) return fail(c, MRTX_E_INVALID, "edge_outlets must be 0 or 1 (got %d)", f->edge_outlets);
+    if (dev_outlet && host_outlet) return fail(c, MRTX_E_INVALID, "give at most one of dev_outlet and host_outlet");
+    if (!f->edge_outlets && !dev_outlet && !host_outlet)
+        return fail(c, MRTX_E_INVALID, "no outlet source: edge_outlets = 0 needs an outlet table");
+    if ((dev_z == nullptr) == (host_z == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_z and host_z");
+    if ((dev_fill == nullptr) == (host_fill == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_fill and host_fill");
+    if (dev_z && (reinterpret_cast<uintptr_t>(dev_z) & 3)) return fail(c, MRTX_E_INVALID, "dev_z must be 4-byte aligned (int32)");
+    if (dev_fill && (reinterpret_cast<uintptr_t>(dev_fill) & 3)) return fail(c, MRTX_E_INVALID, "dev_fill must be 4-byte aligned (int32)");
+    const size_t N = (size_t)f->rows * (size_t)f->cols;
+    if (traverse_overlap(dev_z, 4 * N, dev_fill, 4 * N) || traverse_overlap(dev_z, 4 * N, dev_outlet, N) ||
+        traverse_overlap(dev_outlet, N, dev_fill, 4 * N))
+        return fail(c, MRTX_E_INVALID, "dev_z, dev_outlet and dev_fill must not overlap");
+    // MOONRT_FILL=sweep: one Jacobi step over the whole lattice per launch, the yardstick of the tile scheme; the same bytes
+    bool tiles = true;
+    if (const char* e = std::getenv("MOONRT_FILL")) {
+        if (std::strcmp(e, "sweep") == 0) tiles = false;
+        else if (std::strcmp(e, "tiles") != 0) return fail(c, MRTX_E_INVALID, "MOONRT_FILL must be tiles or sweep (got %s)", e);
+    }
+    if ((rc = fill_host_heights(c, host_z, N)) != MRTX_OK) return rc;
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const int tiles_x = (f->cols + MRTX_FILL_TS - 1) / MRTX_FILL_TS, tiles_y = (f->rows + MRTX_FILL_TS - 1) / MRTX_FILL_TS;
+    const size_t n_tiles = (size_t)tiles_x * (size_t)tiles_y;
+    // scratch: 64 bytes of counters (visits, bad, the change counters), the fill when it goes to the host, then the second
+    // table of the sweep or the two flag arrays of the tiles
+    const size_t tab_b = (4 * N + 15) & ~(size_t)15;
+    const size_t fill_at = 64, work_at = fill_at + (host_fill ? tab_b : 0);
+    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, work_at + (tiles ? 8 * n_tiles : tab_b))) != MRTX_OK) return rc;
+    // the host tables: heights, then the outlet bytes (the caller's memory stays put until the end of the call)
+    const size_t hz_b = host_z ? tab_b : 0;
+    if (host_z || host_outlet) {
+        if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, hz_b + (host_outlet ? N : 0) + 16)) != MRTX_OK) return rc;
+        char* it = reinterpret_cast<char*>(c->illum_tab);
+        if (host_z) HIPCHK(c, hipMemcpyAsync(it, host_z, 4 * N, hipMemcpyHostToDevice, c->stream));
+        if (host_outlet) HIPCHK(c, hipMemcpyAsync(it + hz_b, host_outlet, N, hipMemcpyHostToDevice, c->stream));
+    }
+    char* tb = reinterpret_cast<char*>(c->trav_buf);
+    FillC q;
+    std::memset(&q, 0, sizeof q);
+    q.z = host_z ? reinterpret_cast<const int32_t*>(c->illum_tab) : static_cast<const int32_t*>(dev_z);
+    q.outlet = host_outlet ? reinterpret_cast<const uint8_t*>(c->illum_tab) + hz_b : static_cast<const uint8_t*>(dev_outlet);
+    int32_t* const d_fill = host_fill ? reinterpret_cast<int32_t*>(tb + fill_at) : static_cast<int32_t*>(dev_fill);
+    int32_t* const d_other = reinterpret_cast<int32_t*>(tb + work_at);      // sweep only
+    q.visits = reinterpret_cast<unsigned long long*>(tb);
+    q.bad = reinterpret_cast<uint32_t*>(tb + 8);
+    q.changed = reinterpret_cast<uint32_t*>(tb + 16);
+    q.rows = f->rows; q.cols = f->cols; q.wrap = f->wrap; q.conn8 = f->connectivity == 8; q.edge_outlets = f->edge_outlets;
+    q.tiles_x = tiles_x; q.tiles_y = tiles_y;
+    uint32_t* fa = reinterpret_cast<uint32_t*>(tb + work_at);
+    uint32_t* fb = fa + n_tiles;
+    HIPCHK(c, hipMemsetAsync(tb, 0, 64, c->stream));
+    if (tiles) HIPCHK(c, hipMemsetAsync(fa, 0, 8 * n_tiles, c->stream));
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
+    q.w = d_fill;
+    if (tiles) q.flag_in = fa;
+    HIPCHK(c, mrtx_launch_fill_init(q, tiles, c->stream));
+    // no launch cap: every store strictly lowers an int32, so the fixed point is reached after finitely many of them.  The
+    // sweep reads one table and writes the other; a batch is an even number of launches, so it ends in the caller's table.
+    static_assert(MRTX_FILL_BATCH % 2 == 0, "a batch of sweeps ends in the table it started from");
+    uint32_t launches = 1;
+    for (;;) {
+        HIPCHK(c, hipMemsetAsync(q.changed, 0, MRTX_FILL_BATCH * sizeof(uint32_t), c->stream));
+        for (int s = 0; s < MRTX_FILL_BATCH; s++) {
+            q.slot = s;
+            if (tiles) {
+                q.flag_in = fa; q.flag_out = fb;
+                HIPCHK(c, mrtx_launch_fill_relax(q, c->stream));
+                std::swap(fa, fb);
+            } else {
+                q.w_in = (s & 1) ? d_other : d_fill;
+                q.w = (s & 1) ? d_fill : d_other;
+                HIPCHK(c, mrtx_launch_fill_sweep(q, c->stream));
+            }
+            launches++;
+        }
+        uint32_t last = 0;
+        HIPCHK(c, hipMemcpyAsync(&last, q.changed + (MRTX_FILL_BATCH - 1), sizeof last, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (last == 0) break;       // a whole launch lowered nothing: every later one is empty too
+    }
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    unsigned long long head[2] = {0, 0};                    // visits, bad
+    HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
+    if (out) {
+        std::memset(out, 0, sizeof *out);
+        out->kernel_ms = ms;
+        out->launches = launches;
+    }
+    if (visits) *visits = head[0];
+    if ((uint32_t)head[1])
+        return fail(c, MRTX_E_INVALID, "%u heights of the device table lie outside -2^30 .. 2^30", (uint32_t)head[1]);
+    if (host_fill) HIPCHK(c, hipMemcpy(host_fill, d_fill, 4 * N, hipMemcpyDeviceToHost));
+    return MRTX_OK;
+}
+
+int mrtx_fill_basins(mrtx_ctx* c, int32_t rows, int32_t cols, int32_t wrap, int32_t connectivity, const void* dev_labels,
+                     const int32_t* host_labels, uint32_t n_regions, const void* dev_z, const int32_t* host_z, const void* dev_fill,
+                     const int32_t* host_fill, const uint32_t* row_weight, void* dev_out, MrtxBasin* host_out, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    int rc = regions_lattice(c, rows, cols, wrap);
+    if (rc != MRTX_OK) return rc;
+    if (connectivity != 4 && connectivity != 8) return fail(c, MRTX_E_INVALID, "connectivity must be 4 or 8 (got %d)", connectivity);
+    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
+    if ((dev_z == nullptr) == (host_z == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_z and host_z");
+    if ((dev_fill == nullptr) == (host_fill == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_fill and host_fill");
+    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    const size_t N = (size_t)rows * (size_t)cols;
+    if ((size_t)n_regions > N) return fail(c, MRTX_E_INVALID, "n_regions = %u exceeds the lattice's %zu nodes", n_regions, N);
+    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
+    if (dev_z && (reinterpret_cast<uintptr_t>(dev_z) & 3)) return fail(c, MRTX_E_INVALID, "dev_z must be 4-byte aligned (int32)");
+    if (dev_fill && (reinterpret_cast<uintptr_t>(dev_fill) & 3)) return fail(c, MRTX_E_INVALID, "dev_fill must be 4-byte aligned (int32)");
+    if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 7)) return fail(c, MRTX_E_INVALID, "dev_out must be 8-byte aligned (MrtxBasin)");
+    const size_t out_bytes = sizeof(MrtxBasin) * (size_t)n_regions;
+    if (traverse_overlap(dev_labels, 4 * N, dev_out, out_bytes) || traverse_overlap(dev_z, 4 * N, dev_out, out_bytes) ||
+        traverse_overlap(dev_fill, 4 * N, dev_out, out_bytes))
+        return fail(c, MRTX_E_INVALID, "the device inputs and dev_out must not overlap");
+    if ((rc = fill_host_heights(c, host_z, N)) != MRTX_OK) return rc;
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    // scratch: the counts of bad entries, then the packed pour and depth keys
+    float* d[4] = {nullptr, nullptr, nullptr, nullptr};
+    if ((rc = stage_out(c, dev_out, std::max(out_bytes, sizeof(MrtxBasin)))) != MRTX_OK ||
+        (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, 16 + 16 * (size_t)n_regions)) != MRTX_OK ||
+        (rc = stage_tables(c, {{host_labels, host_labels ? N : 0}, {host_z, host_z ? N : 0}, {host_fill, host_fill ? N : 0},
+                               {row_weight, row_weight ? (size_t)rows : 0}}, d)) != MRTX_OK)
+        return rc;
+    char* tb = reinterpret_cast<char*>(c->trav_buf);
+    BasinC q;
+    std::memset(&q, 0, sizeof q);
+    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_labels);
+    q.z = host_z ? reinterpret_cast<const int32_t*>(d[1]) : static_cast<const int32_t*>(dev_z);
+    q.fill = host_fill ? reinterpret_cast<const int32_t*>(d[2]) : static_cast<const int32_t*>(dev_fill);
+    q.row_weight = row_weight ? reinterpret_cast<const uint32_t*>(d[3]) : nullptr;
+    q.out = static_cast<BasinRec*>(dev_out);
+    q.bad = reinterpret_cast<uint32_t*>(tb);
+    q.keys = reinterpret_cast<unsigned long long*>(tb + 16);
+    q.rows = rows; q.cols = cols; q.wrap = wrap; q.conn8 = connectivity == 8; q.n_regions = n_regions;
+    uint32_t launches = 0, bad[2] = {0, 0};
+    HIPCHK(c, hipMemsetAsync(q.bad, 0, 16, c->stream));
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_fill_basins(q, c->stream, &launches));
+    if ((rc = stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays)) != MRTX_OK) return rc;
+    if (out) out->launches = launches;
+    HIPCHK(c, hipMemcpy(bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad[0]) return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", bad[0], (long long)n_regions - 1);
+    if (bad[1]) return fail(c, MRTX_E_INVALID, "%u heights of the device table lie outside -2^30 .. 2^30", bad[1]);
     return MRTX_OK;
 }
 

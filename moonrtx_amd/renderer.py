@@ -1401,6 +1401,117 @@ class MoonRT:
             stats["fill_ms"] = stats.get("fill_ms", 0.0) + st2.kernel_ms
         return rg.Outlines(rings, vertices, rows, cols, wrap)
 
+    # ---- Terrain depressions
+    @staticmethod
+    def _int32_arg(table, shape, what):
+        """(device pointer, host pointer, keepalive) of a (rows, cols) int32 table: a numpy array or a DeviceBuffer."""
+        if isinstance(table, DeviceBuffer):
+            if table.nbytes < 4 * shape[0] * shape[1]:
+                raise ValueError(f"the {what} DeviceBuffer is smaller than its shape")
+            return table.ptr, None, table
+        a = np.ascontiguousarray(table)
+        if a.shape != tuple(shape) or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{what} must be ({shape[0]}, {shape[1]}) integers")
+        if a.size and (a.min() < -2 ** 31 or a.max() > 2 ** 31 - 1):
+            raise ValueError(f"{what} leaves int32")
+        a = a.astype(np.int32)
+        return None, a.ctypes.data, a
+
+    def fill_depressions(self, heights, outlets=None, edge_outlets=True, connectivity=8, wrap=False, shape=None, stats=None,
+                         unit_m=None):
+        """The level up to which every node of a lattice of integer heights is closed (mrtx_fill): the least, over all paths
+        to an outlet, of the greatest height on the path.  heights: (rows, cols) int32 within +-2^30 (basins.quantise_heights)
+        or a DeviceBuffer (then give shape = (rows, cols); the fill is made in a device table and downloaded together with
+        the heights).  Outlets: with edge_outlets the lattice's border rows and, without wrap, its border columns; and the
+        nonzero nodes of `outlets`, (rows, cols) uint8 or a DeviceBuffer, if given.  unit_m: the metres of one unit of
+        height, remembered by the map.  Needs no DEM.  Returns a moonrtx_amd.basins.FillMap; stats gains launches, kernel_ms
+        and visits."""
+        from . import basins as bs
+        dev = isinstance(heights, DeviceBuffer)
+        if dev:
+            if shape is None:
+                raise ValueError("a DeviceBuffer needs shape = (rows, cols)")
+            rows, cols = int(shape[0]), int(shape[1])
+        else:
+            h = np.asarray(heights)
+            if h.ndim != 2:
+                raise ValueError("heights must be (rows, cols)")
+            rows, cols = int(h.shape[0]), int(h.shape[1])
+        z_d, z_h, z_keep = self._int32_arg(heights, (rows, cols), "heights")
+        o_d = o_h = o_keep = None
+        if isinstance(outlets, DeviceBuffer):
+            if outlets.nbytes < rows * cols:
+                raise ValueError("the outlet DeviceBuffer is smaller than its shape")
+            o_d = outlets.ptr
+        elif outlets is not None:
+            o_keep = np.ascontiguousarray(np.asarray(outlets) != 0, np.uint8)
+            if o_keep.shape != (rows, cols):
+                raise ValueError("outlets and heights differ in shape")
+            o_h = o_keep.ctypes.data
+        f = _lib.MrtxFill(rows, cols, 1 if wrap else 0, int(connectivity), 1 if edge_outlets else 0, 0)
+        st = MrtxStats()
+        visits = C.c_uint64(0)
+        if dev:
+            fb = DeviceBuffer(max(4 * rows * cols, 4), heights.device)
+            try:
+                self._check(self._lib.mrtx_fill(self._ctx, C.byref(f), z_d, None, o_d, o_h, fb.ptr, None, C.byref(visits),
+                                                C.byref(st)), "mrtx_fill")
+                fill = fb.download(np.int32, (rows, cols))
+                z = heights.download(np.int32, (rows, cols))
+            finally:
+                fb.free()
+        else:
+            fill = np.empty((rows, cols), np.int32)
+            self._check(self._lib.mrtx_fill(self._ctx, C.byref(f), None, z_h, o_d, o_h, None, fill.ctypes.data, C.byref(visits),
+                                            C.byref(st)), "mrtx_fill")
+            z = z_keep
+        self._add_stats(stats, st)
+        if isinstance(stats, dict):
+            stats["visits"] = stats.get("visits", 0) + int(visits.value)
+        return bs.FillMap(z, fill, unit_m, int(connectivity), bool(wrap))
+
+    def basins(self, labels, n_regions, fillmap, row_weights=None, connectivity=None, wrap=None, shape=None, stats=None):
+        """One record per region of a label table over a fill (mrtx_fill_basins): weight, volume, the extremes of the fill,
+        the greatest depth and its place, and the pour point, the neighbour outside the region of least (fill, index).
+        labels: (rows, cols) int32, any table, or a DeviceBuffer (then give shape = (rows, cols)); fillmap: a basins.FillMap,
+        or a pair (z, fill) of (rows, cols) int32 arrays or DeviceBuffers; connectivity and wrap default to the map's (8 and
+        False for a pair).  With a DeviceBuffer among the tables the records are made in a device table and downloaded.
+        row_weights: (rows,) uint32 node areas or None.  Returns (n_regions,) basins.BASIN_DTYPE."""
+        from . import basins as bs
+        n_regions = int(n_regions)
+        lab_d, lab_h, rows, cols, _keep = self._label_arg(labels, shape)
+        if isinstance(fillmap, bs.FillMap):
+            z, fill = fillmap.z, fillmap.fill
+            connectivity = fillmap.connectivity if connectivity is None else connectivity
+            wrap = fillmap.wrap if wrap is None else wrap
+        else:
+            z, fill = fillmap
+            connectivity = 8 if connectivity is None else connectivity
+            wrap = False if wrap is None else wrap
+        z_d, z_h, _kz = self._int32_arg(z, (rows, cols), "heights")
+        f_d, f_h, _kf = self._int32_arg(fill, (rows, cols), "fill")
+        weights = self._row_table(row_weights, rows, "row_weights")
+        wp = weights.ctypes.data if weights is not None else None
+        st = MrtxStats()
+        on_dev = [b for b in (labels, z, fill) if isinstance(b, DeviceBuffer)]
+        if on_dev:
+            rec = DeviceBuffer(max(48 * n_regions, 48), on_dev[0].device)
+            try:
+                self._check(self._lib.mrtx_fill_basins(self._ctx, rows, cols, 1 if wrap else 0, int(connectivity), lab_d, lab_h,
+                                                       n_regions, z_d, z_h, f_d, f_h, wp, rec.ptr, None, C.byref(st)),
+                            "mrtx_fill_basins")
+                table = rec.download(bs.BASIN_DTYPE, (n_regions,))
+            finally:
+                rec.free()
+        else:
+            table = np.zeros(max(n_regions, 1), bs.BASIN_DTYPE)
+            self._check(self._lib.mrtx_fill_basins(self._ctx, rows, cols, 1 if wrap else 0, int(connectivity), None, lab_h,
+                                                   n_regions, None, z_h, None, f_h, wp, None, table.ctypes.data, C.byref(st)),
+                        "mrtx_fill_basins")
+            table = table[:n_regions]
+        self._add_stats(stats, st)
+        return table
+
     @staticmethod
     def _add_stats(acc, st, extra=None):
         """Sum the counters of one call into the dict `acc` (if it is one); extra = {key: MrtxStats field} of the call's own."""
