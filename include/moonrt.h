@@ -840,6 +840,52 @@ int mrtx_fill_basins(mrtx_ctx* ctx, int32_t rows, int32_t cols, int32_t wrap, in
                      const void* dev_fill, const int32_t* host_fill, const uint32_t* row_weight, void* dev_out,
                      MrtxBasin* host_out, MrtxStats* out);
 
+/* ---- The depression hierarchy: nested bowls, spill points, peak prominence (additive to ABI 7) ----
+ * Lattice, wrap, connectivity, heights and outlets are mrtx_fill's.  key(v) = (z[v], v), compared lexicographically; the outside
+ * is one virtual node below every key, adjacent to every outlet.  The nodes are taken in ascending key.  A node without a taken
+ * neighbour that is no outlet gives birth to a leaf bowl.  A node that joins two or more closed components (components of taken
+ * nodes that do not hold the outside) makes the current bowl of each spill there and gives birth to a meta bowl, their parent.
+ * A node that is an outlet or touches an open component makes the current bowl of every closed component it touches spill with
+ * parent = -1.  The region of a bowl is every node of its component taken strictly before its spill node, nested bowls
+ * included.  label[v] is the innermost bowl that holds v: the current bowl of v's component just after v was taken, or -1.
+ * Bowls are numbered by ascending key of born_at, so parent > child.  fill[v] == max(z[v], spill_level of the root bowl above
+ * label[v]), and == z[v] where label[v] == -1.  invert = 1: all of the above for -z, the three levels reported negated back, so
+ * that floor_level is a summit's height, spill_level its key col and floor_level - spill_level its prominence; volume is the
+ * sum of row_weight (z - spill_level).  The call needs no DEM, no light and no Moon frame and leaves the render state alone. */
+typedef struct MrtxBowls {
+    int32_t rows, cols, wrap;
+    int32_t connectivity;   /* 4 or 8 */
+    int32_t edge_outlets;   /* 0 or 1 */
+    int32_t invert;         /* 0: depressions; 1: peaks */
+    int32_t reserved[2];    /* 0 */
+} MrtxBowls;
+typedef struct MrtxBowl {
+    uint64_t weight;        /* the sum of row_weight[i] over the region */
+    uint64_t volume;        /* the sum of row_weight[i] * (spill_level - z) over the region, modulo 2^64; 0 if it never spills */
+    uint32_t count;         /* nodes of the region */
+    uint32_t own_count;     /* nodes whose label is this bowl */
+    int32_t floor_at, floor_level;  /* the least-key node of the region and its height */
+    int32_t born_at, born_level;    /* the birth node and its height */
+    int32_t spill_at, spill_level;  /* the spill node and its height; -1 and MRTX_FILL_NONE (-MRTX_FILL_NONE with invert) for a
+                                     * bowl that never spills: only without any outlet */
+    int32_t parent;         /* the parent bowl, or -1 */
+    uint32_t n_children;    /* direct children; 0 for a leaf */
+    uint32_t n_leaves;      /* leaf bowls in the region; 1 for a leaf */
+    uint32_t reserved;      /* 0 */
+} MrtxBowl;
+/* Pointer pairs, alignment, overlap and heights beyond +-2^30 as in mrtx_fill (dev_bowls 8-byte aligned, dev_label 4-byte); edge_outlets = 0
+ * needs an outlet table, and with an all-zero one no bowl ever spills.  row_weight: rows uint32 in host memory or NULL (every
+ * node weighs 1).  The records go
+ * into at most one of dev_bowls and host_bowls, which holds bowl_cap records.  With neither, bowl_cap must be 0 and so must both
+ * label pointers: the call only counts.  When the records do not fit, nothing is written and the call returns MRTX_E_INVALID
+ * naming the needed size; *n_bowls is set all the same.  The labels rows x cols int32 go into at most one of dev_label and
+ * host_label (both NULL: no label table).  rounds (or NULL): the merge rounds of the device stage.  out: launches, kernel_ms (the
+ * device phases; the host's sort and union-find over the minima between them is not counted).  A refused call leaves n_bowls,
+ * rounds and out as they were. */
+int mrtx_bowls(mrtx_ctx* ctx, const MrtxBowls* b, const void* dev_z, const int32_t* host_z, const void* dev_outlet,
+               const uint8_t* host_outlet, const uint32_t* row_weight, void* dev_bowls, MrtxBowl* host_bowls, uint64_t bowl_cap,
+               void* dev_label, int32_t* host_label, uint64_t* n_bowls, uint64_t* rounds, MrtxStats* out);
+
 /* ---- Mast-height horizons and joint windows (additive to ABI 7) ----------------------------------
  * mrtx_horizon_points from a raised origin: point p marches from P = fmaf(hs, u, o), hs = (float)(height_m[p] / radius_m * R),
  * the raised end of mrtx_sight_points (so a mast top is one point for the horizon and for the line of sight).  height_m: n

@@ -159,6 +159,20 @@ class MrtxBasin(C.Structure):
                 ("pour_level", C.c_int32), ("reserved", C.c_uint32)]
 
 
+class MrtxBowls(C.Structure):
+    """The lattice, the outlets and the direction of a depression hierarchy (mrtx_bowls)."""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("wrap", C.c_int32), ("connectivity", C.c_int32),
+                ("edge_outlets", C.c_int32), ("invert", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class MrtxBowl(C.Structure):
+    """One bowl of the hierarchy (mrtx_bowls): 64 bytes, all integers."""
+    _fields_ = [("weight", C.c_uint64), ("volume", C.c_uint64), ("count", C.c_uint32), ("own_count", C.c_uint32),
+                ("floor_at", C.c_int32), ("floor_level", C.c_int32), ("born_at", C.c_int32), ("born_level", C.c_int32),
+                ("spill_at", C.c_int32), ("spill_level", C.c_int32), ("parent", C.c_int32), ("n_children", C.c_uint32),
+                ("n_leaves", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class MrtxIllumEpoch(C.Structure):
     """One date of a Sun-illumination series (mrtx_illum_series): what mrtx_set_light and
     mrtx_set_moon_frame would set for it."""
@@ -298,6 +312,8 @@ SIGNATURES = {
     "mrtx_fill": (C.c_int, [_VP, C.POINTER(MrtxFill), _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
     "mrtx_fill_basins": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP,
                                    _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_bowls": (C.c_int, [_VP, C.POINTER(MrtxBowls), _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP,
+                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
     "mrtx_thermal": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                C.POINTER(MrtxStats)]),
     "mrtx_view_dir_samples": (C.c_int, [C.c_int32, _VP]),

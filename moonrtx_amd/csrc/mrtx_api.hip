@@ -26,6 +26,7 @@
 #include "mrtx_proximity.h"
 #include "mrtx_outline.h"
 #include "mrtx_fill.h"
+#include "mrtx_bowls.h"
 
 hipError_t mrtx_launch_render(const FrameC& f, int S, bool stats, int mode, bool overlay, const PathQ* pq, hipStream_t st);
 uint64_t mrtx_path_chunks(const FrameC& f, int S, uint32_t* grid_a, int* njobs_log2);
@@ -3076,6 +3077,291 @@ int mrtx_fill_basins(mrtx_ctx* c, int32_t rows, int32_t cols, int32_t wrap, int3
     HIPCHK(c, hipMemcpy(bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));
     if (bad[0]) return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", bad[0], (long long)n_regions - 1);
     if (bad[1]) return fail(c, MRTX_E_INVALID, "%u heights of the device table lie outside -2^30 .. 2^30", bad[1]);
+    return MRTX_OK;
+}
+
+// ---- The depression hierarchy: nested bowls, spill points, peak prominence ------------------------
+static_assert(sizeof(MrtxBowls) == 32, "MrtxBowls is 32 bytes");
+static_assert(sizeof(MrtxBowl) == 64 && alignof(MrtxBowl) == 8, "MrtxBowl is 64 bytes");
+static_assert(sizeof(BowlEdge) == 16 && sizeof(BowlWalk) == 16, "the tables the host and the kernels share");
+static_assert(MRTX_BOWLS_ZMAX == MRTX_FILL_ZMAX, "one bound on the heights");
+
+static int32_t bowls_level(unsigned long long key) { return (int32_t)((uint32_t)(key >> 32) - 0x40000000u); }
+
+// The sweep over the minima and the edges of the spanning forest, both in ascending key: the births, spills, parents and floors
+// of section 3.25.  The edges of one pass node are one event.  Levels are still those the sweep saw (negated with invert), and
+// count, weight, volume and n_leaves wait for the sums of the label pass (bowls_finish).  floor: the key of each bowl's floor.
+static void bowls_tree(std::vector<unsigned long long>& minima, std::vector<BowlEdge>& edges, uint32_t outside,
+                       std::vector<MrtxBowl>& rec, std::vector<BowlWalk>& walk) {
+    const size_t M = minima.size();
+    std::sort(minima.begin(), minima.end());
+    std::sort(edges.begin(), edges.end(), [](const BowlEdge& x, const BowlEdge& y) { return x.pass < y.pass; });
+    std::vector<uint32_t> ids(M);
+    for (size_t k = 0; k < M; k++) ids[k] = (uint32_t)minima[k];
+    std::sort(ids.begin(), ids.end());
+    auto dense = [&](uint32_t node) -> uint32_t {
+        return node == outside ? (uint32_t)M : (uint32_t)(std::lower_bound(ids.begin(), ids.end(), node) - ids.begin());
+    };
+    std::vector<uint32_t> up(M + 1);
+    for (size_t k = 0; k <= M; k++) up[k] = (uint32_t)k;
+    auto find = [&](uint32_t x) {
+        while (up[x] != x) {
+            up[x] = up[up[x]];
+            x = up[x];
+        }
+        return x;
+    };
+    std::vector<int32_t> current(M + 1, -1);        // the current bowl of a component's representative; -1: open
+    std::vector<unsigned long long> floor;
+    auto born = [&](unsigned long long key, uint32_t children, unsigned long long floor_key, bool leaf) {
+        MrtxBowl b;
+        std::memset(&b, 0, sizeof b);
+        b.born_at = (int32_t)(uint32_t)key; b.born_level = bowls_level(key);
+        b.floor_at = (int32_t)(uint32_t)floor_key; b.floor_level = bowls_level(floor_key);
+        b.spill_at = -1; b.spill_level = MRTX_FILL_NONE; b.parent = -1; b.n_children = children; b.n_leaves = leaf ? 1u : 0u;
+        rec.push_back(b);
+        floor.push_back(floor_key);
+        BowlWalk w;
+        w.spill = ~0ull; w.parent = -1; w.leaf_at = leaf ? b.born_at : -1;
+        walk.push_back(w);
+        return (int32_t)(rec.size() - 1);
+    };
+    auto spill = [&](int32_t b, unsigned long long key, int32_t parent) {
+        rec[b].spill_at = (int32_t)(uint32_t)key; rec[b].spill_level = bowls_level(key); rec[b].parent = parent;
+        walk[b].spill = key; walk[b].parent = parent;
+    };
+    size_t im = 0, ie = 0;
+    std::vector<uint32_t> cs;
+    while (im < M || ie < edges.size()) {
+        if (im < M && (ie >= edges.size() || minima[im] < edges[ie].pass)) {
+            current[dense((uint32_t)minima[im])] = born(minima[im], 0, minima[im], true);
+            im++;
+            continue;
+        }
+        const unsigned long long pass = edges[ie].pass;
+        cs.clear();
+        for (; ie < edges.size() && edges[ie].pass == pass; ie++)
+            for (uint32_t end : {edges[ie].a, edges[ie].b}) {
+                const uint32_t r = find(dense(end));
+                if (std::find(cs.begin(), cs.end(), r) == cs.end()) cs.push_back(r);
+            }
+        bool open = false;
+        uint32_t to = cs[0];
+        for (uint32_t r : cs)
+            if (current[r] < 0) { open = true; to = r; }
+        int32_t now = -1;
+        if (!open) {
+            unsigned long long least = ~0ull;
+            for (uint32_t r : cs) least = std::min(least, floor[current[r]]);
+            now = born(pass, (uint32_t)cs.size(), least, false);
+        }
+        for (uint32_t r : cs) {
+            if (current[r] >= 0) spill(current[r], pass, now);
+            up[r] = to;
+        }
+        current[to] = now;
+    }
+}
+
+// One pass up the records (parent > child): the sums of each bowl's own nodes become those of its region.  own: nodes, weight
+// and the sum of w z' per bowl.  Then the levels go back into the caller's z.
+static void bowls_finish(std::vector<MrtxBowl>& rec, std::vector<unsigned long long>& own, bool invert) {
+    const size_t n = rec.size();
+    for (size_t b = 0; b < n; b++) rec[b].own_count = (uint32_t)own[3 * b];
+    for (size_t b = 0; b < n; b++) {
+        MrtxBowl& r = rec[b];
+        r.count = (uint32_t)own[3 * b];
+        r.weight = own[3 * b + 1];
+        r.volume = r.spill_at >= 0 ? (unsigned long long)(long long)r.spill_level * r.weight - own[3 * b + 2] : 0ull;
+        if (r.parent >= 0) {
+            const size_t p = (size_t)r.parent;
+            for (int k = 0; k < 3; k++) own[3 * p + k] += own[3 * b + k];
+            rec[p].n_leaves += r.n_leaves;
+        }
+        if (invert) { r.floor_level = -r.floor_level; r.born_level = -r.born_level; r.spill_level = -r.spill_level; }
+    }
+}
+
+// the end of a device phase: its time added to ms (the next phase starts with another record of ev0)
+static int bowls_lap(mrtx_ctx* c, float* ms) {
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    float t = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
+    *ms += t;
+    return MRTX_OK;
+}
+
+int mrtx_bowls(mrtx_ctx* c, const MrtxBowls* w, const void* dev_z, const int32_t* host_z, const void* dev_outlet,
+               const uint8_t* host_outlet, const uint32_t* row_weight, void* dev_bowls, MrtxBowl* host_bowls, uint64_t bowl_cap,
+               void* dev_label, int32_t* host_label, uint64_t* n_bowls, uint64_t* rounds, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!w) return fail(c, MRTX_E_INVALID, "null bowls block");
+    if (w->reserved[0] != 0 || w->reserved[1] != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    int rc = regions_lattice(c, w->rows, w->cols, w->wrap);
+    if (rc != MRTX_OK) return rc;
+    if (w->connectivity != 4 && w->connectivity != 8) return fail(c, MRTX_E_INVALID, "connectivity must be 4 or 8 (got %d)", w->connectivity);
+    if (w->edge_outlets != 0 && w->edge_outlets != 1) return fail(c, MRTX_E_INVALID, "edge_outlets must be 0 or 1 (got %d)", w->edge_outlets);
+    if (w->invert != 0 && w->invert != 1) return fail(c, MRTX_E_INVALID, "invert must be 0 or 1 (got %d)", w->invert);
+    if (dev_outlet && host_outlet) return fail(c, MRTX_E_INVALID, "give at most one of dev_outlet and host_outlet");
+    if (!w->edge_outlets && !dev_outlet && !host_outlet)
+        return fail(c, MRTX_E_INVALID, "no outlet source: edge_outlets = 0 needs an outlet table");
+    if ((dev_z == nullptr) == (host_z == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_z and host_z");
+    if (!n_bowls) return fail(c, MRTX_E_INVALID, "null n_bowls");
+    if (dev_bowls && host_bowls) return fail(c, MRTX_E_INVALID, "give at most one of dev_bowls and host_bowls");
+    if (dev_label && host_label) return fail(c, MRTX_E_INVALID, "give at most one of dev_label and host_label");
+    const bool has_bowls = dev_bowls || host_bowls, has_label = dev_label || host_label;
+    if (!has_bowls && bowl_cap) return fail(c, MRTX_E_INVALID, "without a bowl table bowl_cap must be 0 (got %llu)", (unsigned long long)bowl_cap);
+    if (!has_bowls && has_label) return fail(c, MRTX_E_INVALID, "a label table needs a bowl table: a call without one only counts");
+    const size_t N = (size_t)w->rows * (size_t)w->cols;
+    if (dev_z && (reinterpret_cast<uintptr_t>(dev_z) & 3)) return fail(c, MRTX_E_INVALID, "dev_z must be 4-byte aligned (int32)");
+    if (dev_bowls && (reinterpret_cast<uintptr_t>(dev_bowls) & 7)) return fail(c, MRTX_E_INVALID, "dev_bowls must be 8-byte aligned (MrtxBowl)");
+    if (dev_label && (reinterpret_cast<uintptr_t>(dev_label) & 3)) return fail(c, MRTX_E_INVALID, "dev_label must be 4-byte aligned (int32)");
+    // a lattice never holds more bowls than nodes
+    const size_t bowl_bytes = sizeof(MrtxBowl) * (size_t)std::min<uint64_t>(bowl_cap, N);
+    if (traverse_overlap(dev_z, 4 * N, dev_outlet, N) || traverse_overlap(dev_z, 4 * N, dev_bowls, bowl_bytes) ||
+        traverse_overlap(dev_z, 4 * N, dev_label, 4 * N) || traverse_overlap(dev_outlet, N, dev_bowls, bowl_bytes) ||
+        traverse_overlap(dev_outlet, N, dev_label, 4 * N) || traverse_overlap(dev_bowls, bowl_bytes, dev_label, 4 * N))
+        return fail(c, MRTX_E_INVALID, "dev_z, dev_outlet, dev_bowls and dev_label must not overlap");
+    if ((rc = fill_host_heights(c, host_z, N)) != MRTX_OK) return rc;
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    // scratch: 64 bytes of counters, then ptr, cpar and best2 (N + 1 words each), best (N + 1 double words), and the labels
+    // when they go to the host
+    const size_t words_b = (4 * (N + 1) + 15) & ~(size_t)15, keys_b = (8 * (N + 1) + 15) & ~(size_t)15;
+    const size_t ptr_at = 64, cpar_at = ptr_at + words_b, best2_at = cpar_at + words_b, best_at = best2_at + words_b,
+                 label_at = best_at + keys_b;
+    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, label_at + (host_label ? 4 * N : 0))) != MRTX_OK) return rc;
+    // the host tables: heights, the row weights, then the outlet bytes (the caller's memory stays put until the first wait)
+    const size_t hz_b = host_z ? (4 * N + 15) & ~(size_t)15 : 0, rw_b = row_weight ? (4 * (size_t)w->rows + 15) & ~(size_t)15 : 0;
+    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, hz_b + rw_b + (host_outlet ? N : 0) + 16)) != MRTX_OK) return rc;
+    char* it = reinterpret_cast<char*>(c->illum_tab);
+    if (host_z) HIPCHK(c, hipMemcpyAsync(it, host_z, 4 * N, hipMemcpyHostToDevice, c->stream));
+    if (row_weight) HIPCHK(c, hipMemcpyAsync(it + hz_b, row_weight, 4 * (size_t)w->rows, hipMemcpyHostToDevice, c->stream));
+    if (host_outlet) HIPCHK(c, hipMemcpyAsync(it + hz_b + rw_b, host_outlet, N, hipMemcpyHostToDevice, c->stream));
+    char* tb = reinterpret_cast<char*>(c->trav_buf);
+    BowlC q;
+    std::memset(&q, 0, sizeof q);
+    q.z = host_z ? reinterpret_cast<const int32_t*>(it) : static_cast<const int32_t*>(dev_z);
+    q.row_weight = row_weight ? reinterpret_cast<const uint32_t*>(it + hz_b) : nullptr;
+    q.outlet = host_outlet ? reinterpret_cast<const uint8_t*>(it + hz_b + rw_b) : static_cast<const uint8_t*>(dev_outlet);
+    q.counters = reinterpret_cast<uint32_t*>(tb);
+    q.ptr = reinterpret_cast<uint32_t*>(tb + ptr_at);
+    q.cpar = reinterpret_cast<uint32_t*>(tb + cpar_at);
+    q.best2 = reinterpret_cast<uint32_t*>(tb + best2_at);
+    q.best = reinterpret_cast<unsigned long long*>(tb + best_at);
+    q.rows = w->rows; q.cols = w->cols; q.wrap = w->wrap; q.conn8 = w->connectivity == 8; q.edge_outlets = w->edge_outlets;
+    q.invert = w->invert;
+    static_assert(8 + MRTX_BOWLS_BATCH <= 16, "the counters fit their 64 bytes");
+    HIPCHK(c, hipMemsetAsync(tb, 0, 64, c->stream));
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
+    float ms = 0.0f;
+    uint32_t launches = 1, head[16];
+    HIPCHK(c, mrtx_launch_bowls_init(q, c->stream));
+    // the jumps: a path of L nodes is short of its end after log2 L doublings, and a launch that moved nothing ends them
+    for (;;) {
+        HIPCHK(c, hipMemsetAsync(q.counters + 8, 0, MRTX_BOWLS_BATCH * sizeof(uint32_t), c->stream));
+        for (int s = 0; s < MRTX_BOWLS_BATCH; s++) {
+            q.slot = s;
+            HIPCHK(c, mrtx_launch_bowls_jump(q, c->stream));
+            launches++;
+        }
+        uint32_t last = 0;
+        HIPCHK(c, hipMemcpyAsync(&last, q.counters + 8 + (MRTX_BOWLS_BATCH - 1), sizeof last, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (last == 0) break;
+    }
+    HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
+    auto report = [&]() {
+        if (out) {
+            std::memset(out, 0, sizeof *out);
+            out->kernel_ms = ms;
+            out->launches = launches;
+        }
+    };
+    if (head[0]) {
+        if ((rc = bowls_lap(c, &ms)) != MRTX_OK) return rc;
+        report();
+        return fail(c, MRTX_E_INVALID, "%u heights of the device table lie outside -2^30 .. 2^30", head[0]);
+    }
+    // ---- the spanning forest over the catchments and the outside
+    const uint32_t M = head[1];
+    q.n_min = M;
+    uint64_t n_rounds = 0;
+    std::vector<unsigned long long> minima(M);
+    std::vector<BowlEdge> edges;
+    // the component tables: the minima's keys, the hooks and the edges; the walk table and the sums of the label pass take
+    // their place later (at most 2 M bowls of 16 + 24 bytes)
+    const size_t list_b = (8 * ((size_t)M + 1) + 15) & ~(size_t)15, hook_b = (4 * ((size_t)M + 1) + 15) & ~(size_t)15;
+    if (M) {
+        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, std::max(list_b + hook_b + 16 * ((size_t)M + 1), 80 * (size_t)M + 64))) != MRTX_OK)
+            return rc;
+        char* ob = reinterpret_cast<char*>(c->illum_out);
+        q.list = reinterpret_cast<unsigned long long*>(ob);
+        q.hook = reinterpret_cast<uint32_t*>(ob + list_b);
+        q.edges = reinterpret_cast<BowlEdge*>(ob + list_b + hook_b);
+        HIPCHK(c, mrtx_launch_bowls_list(q, c->stream));
+        launches++;
+        uint32_t n_edges = 0;
+        for (;;) {                                              // a round halves the components that still have a cross edge
+            HIPCHK(c, mrtx_launch_bowls_round(q, c->stream, &launches));
+            HIPCHK(c, hipMemcpyAsync(head, tb, sizeof head, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (head[2] == n_edges) break;                      // nothing hooked: no component has a cross edge left
+            n_edges = head[2];
+            n_rounds++;
+        }
+        if ((rc = bowls_lap(c, &ms)) != MRTX_OK) return rc;
+        if (head[3] != M || head[4] || n_edges > M) {
+            report();
+            return fail(c, MRTX_E_DEVICE, "the bowl stage listed %u of %u minima and chose %u edges", head[3], M, n_edges);
+        }
+        edges.resize(n_edges);
+        HIPCHK(c, hipMemcpy(minima.data(), q.list, 8 * (size_t)M, hipMemcpyDeviceToHost));
+        if (n_edges) HIPCHK(c, hipMemcpy(edges.data(), q.edges, sizeof(BowlEdge) * (size_t)n_edges, hipMemcpyDeviceToHost));
+    } else if ((rc = bowls_lap(c, &ms)) != MRTX_OK) {
+        return rc;
+    }
+    // ---- the host's share: proportional to the minima
+    std::vector<MrtxBowl> rec;
+    std::vector<BowlWalk> walk;
+    bowls_tree(minima, edges, (uint32_t)N, rec, walk);
+    const uint64_t total = rec.size();
+    if (!has_bowls || total > bowl_cap) {
+        report();
+        *n_bowls = total;
+        if (rounds) *rounds = n_rounds;
+        if (has_bowls)
+            return fail(c, MRTX_E_INVALID, "the bowl table is too small: %llu bowls are needed (bowl_cap = %llu)", (unsigned long long)total,
+                        (unsigned long long)bowl_cap);
+        return MRTX_OK;
+    }
+    // ---- the labels and the sums of each bowl's own nodes
+    q.n_bowls = (uint32_t)total;
+    q.label = host_label ? reinterpret_cast<int32_t*>(tb + label_at) : static_cast<int32_t*>(dev_label);
+    std::vector<unsigned long long> own(3 * (size_t)total, 0ull);
+    if (total || has_label) {
+        if (total) {
+            char* ob = reinterpret_cast<char*>(c->illum_out);
+            q.walk = reinterpret_cast<const BowlWalk*>(ob);
+            q.own = reinterpret_cast<unsigned long long*>(ob + sizeof(BowlWalk) * (size_t)total);
+            HIPCHK(c, hipMemcpyAsync(ob, walk.data(), sizeof(BowlWalk) * (size_t)total, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemsetAsync(q.own, 0, 24 * (size_t)total, c->stream));
+        }
+        HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+        HIPCHK(c, mrtx_launch_bowls_label(q, c->stream, &launches));
+        if ((rc = bowls_lap(c, &ms)) != MRTX_OK) return rc;
+        if (total) HIPCHK(c, hipMemcpy(own.data(), q.own, 24 * (size_t)total, hipMemcpyDeviceToHost));
+    }
+    bowls_finish(rec, own, w->invert != 0);
+    report();
+    *n_bowls = total;
+    if (rounds) *rounds = n_rounds;
+    if (total) {
+        if (host_bowls) std::memcpy(host_bowls, rec.data(), sizeof(MrtxBowl) * (size_t)total);
+        else HIPCHK(c, hipMemcpy(dev_bowls, rec.data(), sizeof(MrtxBowl) * (size_t)total, hipMemcpyHostToDevice));
+    }
+    if (host_label) HIPCHK(c, hipMemcpy(host_label, q.label, 4 * N, hipMemcpyDeviceToHost));
     return MRTX_OK;
 }
 

@@ -1512,6 +1512,84 @@ class MoonRT:
         self._add_stats(stats, st)
         return table
 
+    # ---- The depression hierarchy
+    def bowls(self, heights, outlets=None, edge_outlets=True, connectivity=8, wrap=False, invert=False, row_weights=None,
+              labels=True, shape=None, stats=None, unit_m=None):
+        """The nested closed bowls of a lattice of integer heights (mrtx_bowls): one record per bowl with its floor, its spill
+        point, its parent, weight and volume, and per node the innermost bowl that holds it.  heights, outlets, edge_outlets,
+        connectivity, wrap and unit_m as in fill_depressions (a DeviceBuffer needs shape = (rows, cols); the tables are then
+        made on the device and downloaded).  invert: the same for -heights, levels reported in the caller's heights: summits,
+        key cols and prominences.  row_weights: (rows,) uint32 node areas or None.  labels = False leaves the label table out.
+        One call counts, a second fills a table of exactly that size.  Needs no DEM.  Returns a moonrtx_amd.basins.BowlTree;
+        stats gains launches, kernel_ms, rounds and bowls."""
+        from . import basins as bs
+        dev = isinstance(heights, DeviceBuffer)
+        if dev:
+            if shape is None:
+                raise ValueError("a DeviceBuffer needs shape = (rows, cols)")
+            rows, cols = int(shape[0]), int(shape[1])
+        else:
+            h = np.asarray(heights)
+            if h.ndim != 2:
+                raise ValueError("heights must be (rows, cols)")
+            rows, cols = int(h.shape[0]), int(h.shape[1])
+        z_d, z_h, z_keep = self._int32_arg(heights, (rows, cols), "heights")
+        o_d = o_h = o_keep = None
+        if isinstance(outlets, DeviceBuffer):
+            if outlets.nbytes < rows * cols:
+                raise ValueError("the outlet DeviceBuffer is smaller than its shape")
+            o_d = outlets.ptr
+        elif outlets is not None:
+            o_keep = np.ascontiguousarray(np.asarray(outlets) != 0, np.uint8)
+            if o_keep.shape != (rows, cols):
+                raise ValueError("outlets and heights differ in shape")
+            o_h = o_keep.ctypes.data
+        weights = self._row_table(row_weights, rows, "row_weights")
+        wp = weights.ctypes.data if weights is not None else None
+        blk = _lib.MrtxBowls(rows, cols, 1 if wrap else 0, int(connectivity), 1 if edge_outlets else 0, 1 if invert else 0)
+        st, st2 = MrtxStats(), MrtxStats()
+        nb, rounds = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.mrtx_bowls(self._ctx, C.byref(blk), z_d, z_h, o_d, o_h, wp, None, None, 0, None, None, C.byref(nb),
+                                         C.byref(rounds), C.byref(st)), "mrtx_bowls")
+        self._add_stats(stats, st)
+        n = int(nb.value)
+        table = None
+        if dev:
+            rb = DeviceBuffer(max(64 * n, 64), heights.device)
+            lb = DeviceBuffer(max(4 * rows * cols, 4), heights.device) if labels else None
+            try:
+                self._check(self._lib.mrtx_bowls(self._ctx, C.byref(blk), z_d, None, o_d, o_h, wp, rb.ptr, None, n,
+                                                 lb.ptr if labels else None, None, C.byref(nb), C.byref(rounds), C.byref(st2)),
+                            "mrtx_bowls")
+                records = rb.download(bs.BOWL_DTYPE, (n,))
+                if labels:
+                    table = lb.download(np.int32, (rows, cols))
+                z = heights.download(np.int32, (rows, cols))
+            finally:
+                rb.free()
+                if lb is not None:
+                    lb.free()
+        else:
+            records = np.zeros(max(n, 1), bs.BOWL_DTYPE)
+            table = np.empty((rows, cols), np.int32) if labels else None
+            self._check(self._lib.mrtx_bowls(self._ctx, C.byref(blk), None, z_h, o_d, o_h, wp, None, records.ctypes.data, n, None,
+                                             table.ctypes.data if labels else None, C.byref(nb), C.byref(rounds), C.byref(st2)),
+                        "mrtx_bowls")
+            records = records[:n]
+            z = z_keep
+        self._add_stats(stats, st2)
+        if isinstance(stats, dict):
+            stats["rounds"] = stats.get("rounds", 0) + int(rounds.value)
+            stats["bowls"] = stats.get("bowls", 0) + n
+            stats["count_ms"] = stats.get("count_ms", 0.0) + st.kernel_ms
+        return bs.BowlTree(records, table, z, unit_m, int(connectivity), bool(wrap), bool(invert))
+
+    def peaks(self, heights, **kw):
+        """bowls(invert=True): every summit with its key col (spill_at, spill_level), its prominence (floor_level -
+        spill_level) and its parent peak."""
+        kw["invert"] = True
+        return self.bowls(heights, **kw)
+
     @staticmethod
     def _add_stats(acc, st, extra=None):
         """Sum the counters of one call into the dict `acc` (if it is one); extra = {key: MrtxStats field} of the call's own."""
