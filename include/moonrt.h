@@ -886,6 +886,52 @@ int mrtx_bowls(mrtx_ctx* ctx, const MrtxBowls* b, const void* dev_z, const int32
                const uint8_t* host_outlet, const uint32_t* row_weight, void* dev_bowls, MrtxBowl* host_bowls, uint64_t bowl_cap,
                void* dev_label, int32_t* host_label, uint64_t* n_bowls, uint64_t* rounds, MrtxStats* out);
 
+/* ---- Contour lines: the ordered isolines of a lattice at many levels (additive to ABI 7) ----------
+ * Lattice and wrap are mrtx_regions_outline's (at most 2^28 nodes, node (i, j) at v = i cols + j).  Heights z[v]: int32 in
+ * -2^30 .. 2^30, or MRTX_FILL_NONE for a void node.  Levels c[0] < c[1] < ...: n_levels int32 in host memory, each in -2^30 + 1 ..
+ * 2^30.  At level c a node is above when z >= c and below when z < c, so the line is the isoline of c - 1/2 and no node lies
+ * on a line.  Edge 2 v + 0 joins v to its east neighbour (column 0 after column cols - 1 under wrap, else absent there), edge
+ * 2 v + 1 to its south neighbour (absent in the last row).  An edge is crossed at c when both its nodes are valid and exactly one
+ * is above; the crossing lies at t = (2 c - 1 - 2 z_own) / (2 (z_other - z_own)) from the edge's own node v, strictly inside
+ * (0, 1).  A vertex is its edge id.  Cell (i, j) has the corners NW (i, j), NE (i, j + 1), SE (i + 1, j + 1), SW (i + 1, j); it
+ * exists for i < rows - 1 and j < cols - 1 (j < cols under wrap) and carries no segment when a corner is void.  Its sides run
+ * clockwise, N NW -> NE, E NE -> SE, S SE -> SW, W SW -> NW; a crossed side a -> b is an entry when a is above and an exit when b
+ * is.  A segment runs from an entry to an exit, the above side on its right (rows run down, columns right).  With two entries
+ * the centre decides: z_NW + z_NE + z_SE + z_SW >= 4 c - 2 (centre above) pairs each entry with the next side clockwise, else with
+ * the previous one.  An element is a pair (edge, level index); its successor is the exit paired with it in the cell it enters,
+ * if that cell exists and has no void corner.  The components of this partial injection are the lines: cycles (closed) and
+ * paths (open; a crossed edge between two cells that carry no segment is an open line of one vertex).  A line's head is its
+ * start when it is open and its least (edge, level index) when it is closed; lines are numbered by ascending head; the vertex
+ * table holds int32 edge ids, line after line, each line from its head along the successors, a closed line's head not
+ * repeated.  The vertices of level index l are exactly the edges crossed at c[l], each once. */
+typedef struct MrtxContours {
+    int32_t rows, cols, wrap;
+    int32_t n_levels;       /* 1 .. 65536 */
+    int32_t reserved;       /* 0 */
+} MrtxContours;
+typedef struct MrtxContourLine {
+    uint64_t first;         /* index of the line's first vertex in the vertex table */
+    uint32_t n_vertices;
+    int32_t level_index;    /* index into the level table */
+    int32_t level;          /* the level c */
+    int32_t head;           /* edge id of the first vertex */
+    int32_t tail;           /* edge id of the last vertex */
+    uint32_t closed;        /* 0 or 1 */
+} MrtxContourLine;
+/* Heights in exactly one of dev_z (4-byte aligned) and host_z.  *n_lines and *n_vertices receive the true totals whenever the
+ * heights pass their check.  With all four table pointers NULL and both caps 0 the call only counts.  Otherwise exactly one of
+ * dev_lines (8-byte aligned) and host_lines and exactly one of dev_vertices (4-byte aligned) and host_vertices is given, with room
+ * for line_cap records and vertex_cap edge ids; no two device tables may overlap.  When both totals fit, the tables are written;
+ * when either does not, nothing is written to either, the call returns MRTX_E_INVALID naming both needed sizes, and the counts
+ * are still set.  A height outside the range gives MRTX_E_INVALID after the first launches (it is treated as void, so nothing
+ * else goes wrong); 2^31 or more elements give MRTX_E_INVALID after the count.  A refused call leaves the two counts as they
+ * were.  The call needs no DEM, light or Moon frame and leaves the render state alone.  The number of launches depends on the
+ * lattice, n_levels and the number of elements alone.  out: launches, kernel_ms (from the first launch to the last, the host's
+ * reads of the counts between them included); written also when the call fails for a bad height, not when it is refused. */
+int mrtx_contours(mrtx_ctx* ctx, const MrtxContours* k, const void* dev_z, const int32_t* host_z, const int32_t* host_levels,
+                  void* dev_lines, MrtxContourLine* host_lines, uint64_t line_cap, void* dev_vertices, int32_t* host_vertices,
+                  uint64_t vertex_cap, uint64_t* n_lines, uint64_t* n_vertices, MrtxStats* out);
+
 /* ---- Mast-height horizons and joint windows (additive to ABI 7) ----------------------------------
  * mrtx_horizon_points from a raised origin: point p marches from P = fmaf(hs, u, o), hs = (float)(height_m[p] / radius_m * R),
  * the raised end of mrtx_sight_points (so a mast top is one point for the horizon and for the line of sight).  height_m: n

@@ -6,6 +6,8 @@ There is NO CPU fallback: if the shared object is missing or a symbol is absent 
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MOONRT_LIB") or os.path.join(_HERE, "libmoonrt.so")   # MOONRT_LIB: A/B builds only
 
@@ -140,6 +142,24 @@ class MrtxRing(C.Structure):
     _fields_ = [("area", C.c_int64), ("warea", C.c_int64), ("first", C.c_uint64), ("n_sides", C.c_uint32),
                 ("n_vertices", C.c_uint32), ("label", C.c_int32), ("head", C.c_int32), ("wind", C.c_int32),
                 ("reserved", C.c_uint32)]
+
+
+class MrtxContours(C.Structure):
+    """The lattice and the number of levels of a contour call (mrtx_contours)."""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("wrap", C.c_int32), ("n_levels", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MrtxContourLine(C.Structure):
+    """One contour line (mrtx_contours): 32 bytes, all integers."""
+    _fields_ = [("first", C.c_uint64), ("n_vertices", C.c_uint32), ("level_index", C.c_int32), ("level", C.c_int32),
+                ("head", C.c_int32), ("tail", C.c_int32), ("closed", C.c_uint32)]
+
+
+# MrtxContourLine, field for field (32 bytes)
+CONTOUR_LINE_DTYPE = np.dtype([("first", "<u8"), ("n_vertices", "<u4"), ("level_index", "<i4"), ("level", "<i4"), ("head", "<i4"),
+                               ("tail", "<i4"), ("closed", "<u4")])
+assert CONTOUR_LINE_DTYPE.itemsize == 32 == C.sizeof(MrtxContourLine)
+CONTOUR_MAX_LEVELS = 65536
 
 
 FILL_NONE = 2 ** 31 - 1         # MRTX_FILL_NONE: the fill of a lattice without any outlet
@@ -309,6 +329,8 @@ SIGNATURES = {
                                      C.POINTER(MrtxStats)]),
     "mrtx_regions_outline": (C.c_int, [_VP, C.POINTER(MrtxOutline), _VP, _VP, C.c_uint32, _VP, _VP, _VP, C.c_uint64, _VP, _VP,
                                        C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
+    "mrtx_contours": (C.c_int, [_VP, C.POINTER(MrtxContours), _VP, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, C.c_uint64,
+                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
     "mrtx_fill": (C.c_int, [_VP, C.POINTER(MrtxFill), _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
     "mrtx_fill_basins": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP,
                                    _VP, _VP, C.POINTER(MrtxStats)]),

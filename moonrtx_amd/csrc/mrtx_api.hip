@@ -25,6 +25,7 @@
 #include "mrtx_zonal.h"
 #include "mrtx_proximity.h"
 #include "mrtx_outline.h"
+#include "mrtx_contour.h"
 #include "mrtx_fill.h"
 #include "mrtx_bowls.h"
 
@@ -2903,6 +2904,136 @@ int mrtx_regions_outline(mrtx_ctx* c, const MrtxOutline* o, const void* dev_labe
                     (unsigned long long)rings, (unsigned long long)vertices, (unsigned long long)ring_cap, (unsigned long long)vertex_cap);
     if (host_rings && rings) HIPCHK(c, hipMemcpy(host_rings, q.rings, sizeof(MrtxRing) * (size_t)rings, hipMemcpyDeviceToHost));
     if (host_vertices && vertices) HIPCHK(c, hipMemcpy(host_vertices, q.vertices, 8 * (size_t)vertices, hipMemcpyDeviceToHost));
+    return MRTX_OK;
+}
+
+// ---- Contour lines: the ordered isolines of a lattice at many levels ------------------------------
+static_assert(sizeof(MrtxContours) == 20, "MrtxContours is 20 bytes");
+static_assert(sizeof(MrtxContourLine) == 32 && alignof(MrtxContourLine) == 8 && sizeof(ContourLineRec) == sizeof(MrtxContourLine),
+              "MrtxContourLine is 32 bytes");
+static_assert(sizeof(ContourJump) == 16, "one int4");
+static_assert(MRTX_CT_VOID == MRTX_FILL_NONE, "one mark for a node without a height");
+
+int mrtx_contours(mrtx_ctx* c, const MrtxContours* k, const void* dev_z, const int32_t* host_z, const int32_t* host_levels,
+                  void* dev_lines, MrtxContourLine* host_lines, uint64_t line_cap, void* dev_vertices, int32_t* host_vertices,
+                  uint64_t vertex_cap, uint64_t* n_lines, uint64_t* n_vertices, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!k) return fail(c, MRTX_E_INVALID, "null contours block");
+    if (k->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    int rc = regions_lattice(c, k->rows, k->cols, k->wrap);
+    if (rc != MRTX_OK) return rc;
+    if ((int64_t)k->rows * (int64_t)k->cols > MRTX_CT_MAX_NODES)
+        return fail(c, MRTX_E_INVALID, "a contoured lattice holds at most 2^28 nodes (got %d x %d)", k->rows, k->cols);
+    if (k->n_levels < 1 || k->n_levels > MRTX_CT_MAX_LEVELS) return fail(c, MRTX_E_INVALID, "n_levels must lie in 1 .. 65536 (got %d)", k->n_levels);
+    if (!host_levels) return fail(c, MRTX_E_INVALID, "null host_levels");
+    for (int32_t l = 0; l < k->n_levels; l++) {
+        if (host_levels[l] < -MRTX_CT_ZMAX + 1 || host_levels[l] > MRTX_CT_ZMAX)
+            return fail(c, MRTX_E_INVALID, "level %d must lie in -2^30 + 1 .. 2^30 (got %d)", l, host_levels[l]);
+        if (l && host_levels[l] <= host_levels[l - 1])
+            return fail(c, MRTX_E_INVALID, "the levels must ascend strictly (level %d = %d follows %d)", l, host_levels[l], host_levels[l - 1]);
+    }
+    if ((dev_z == nullptr) == (host_z == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_z and host_z");
+    if (!n_lines || !n_vertices) return fail(c, MRTX_E_INVALID, "null n_lines or n_vertices");
+    if (dev_lines && host_lines) return fail(c, MRTX_E_INVALID, "give at most one of dev_lines and host_lines");
+    if (dev_vertices && host_vertices) return fail(c, MRTX_E_INVALID, "give at most one of dev_vertices and host_vertices");
+    const bool has_lines = dev_lines || host_lines, has_vertices = dev_vertices || host_vertices;
+    if (has_lines != has_vertices) return fail(c, MRTX_E_INVALID, "give a line table and a vertex table, or neither to count");
+    if (!has_lines && (line_cap || vertex_cap))
+        return fail(c, MRTX_E_INVALID, "without tables line_cap and vertex_cap must be 0 (got %llu, %llu)", (unsigned long long)line_cap,
+                    (unsigned long long)vertex_cap);
+    const size_t N = (size_t)k->rows * (size_t)k->cols;
+    // a table never needs more than one line and one vertex per element, and there are fewer than 2^31 elements
+    const size_t line_bytes = sizeof(MrtxContourLine) * (size_t)std::min<uint64_t>(line_cap, (uint64_t)1 << 31);
+    const size_t vertex_bytes = 4 * (size_t)std::min<uint64_t>(vertex_cap, (uint64_t)1 << 31);
+    if (dev_z && (reinterpret_cast<uintptr_t>(dev_z) & 3)) return fail(c, MRTX_E_INVALID, "dev_z must be 4-byte aligned (int32)");
+    if (dev_lines && (reinterpret_cast<uintptr_t>(dev_lines) & 7)) return fail(c, MRTX_E_INVALID, "dev_lines must be 8-byte aligned (MrtxContourLine)");
+    if (dev_vertices && (reinterpret_cast<uintptr_t>(dev_vertices) & 3)) return fail(c, MRTX_E_INVALID, "dev_vertices must be 4-byte aligned (int32)");
+    if (traverse_overlap(dev_z, 4 * N, dev_lines, line_bytes) || traverse_overlap(dev_z, 4 * N, dev_vertices, vertex_bytes) ||
+        traverse_overlap(dev_lines, line_bytes, dev_vertices, vertex_bytes))
+        return fail(c, MRTX_E_INVALID, "dev_z, dev_lines and dev_vertices must not overlap");
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const ContourNodeLayout nl = contour_node_layout(k->rows, k->cols, k->n_levels, host_z != nullptr);
+    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, nl.end)) != MRTX_OK) return rc;
+    char* tb = reinterpret_cast<char*>(c->trav_buf);
+    // the host tables (the caller's memory stays put until the end of the call)
+    HIPCHK(c, hipMemcpyAsync(tb + nl.levels_at, host_levels, 4 * (size_t)k->n_levels, hipMemcpyHostToDevice, c->stream));
+    if (host_z) HIPCHK(c, hipMemcpyAsync(tb + nl.z_at, host_z, 4 * N, hipMemcpyHostToDevice, c->stream));
+    ContourC q;
+    std::memset(&q, 0, sizeof q);
+    q.z = host_z ? reinterpret_cast<const int32_t*>(tb + nl.z_at) : static_cast<const int32_t*>(dev_z);
+    q.levels = reinterpret_cast<const int32_t*>(tb + nl.levels_at);
+    q.bad = reinterpret_cast<uint32_t*>(tb);
+    q.totals = reinterpret_cast<unsigned long long*>(tb + 16);
+    q.rank = reinterpret_cast<uint32_t*>(tb + nl.rank_at);
+    q.base = reinterpret_cast<uint32_t*>(tb + nl.base_at);
+    q.node_sums = reinterpret_cast<unsigned long long*>(tb + nl.sums_at);
+    q.rows = k->rows; q.cols = k->cols; q.wrap = k->wrap; q.n_levels = k->n_levels;
+    uint32_t launches = 0;
+    unsigned long long head[6] = {0, 0, 0, 0, 0, 0};            // bad (and padding), then the four totals
+    HIPCHK(c, hipMemsetAsync(tb, 0, 64, c->stream));
+    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_contour_count(q, c->stream, &launches));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                 // also: the pageable tables are no longer read
+    HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
+    if ((uint32_t)head[0] || head[2] >= ((uint64_t)1 << 31)) {  // as the sibling calls: the stage ends, out says what ran
+        if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
+        if (out) out->launches = launches;
+        if ((uint32_t)head[0])
+            return fail(c, MRTX_E_INVALID, "%u heights lie outside -2^30 .. 2^30 and are not MRTX_FILL_NONE", (uint32_t)head[0]);
+        return fail(c, MRTX_E_INVALID, "the levels cross the edges %llu times: a call holds fewer than 2^31 crossings", head[2]);
+    }
+    q.B = (uint32_t)head[2];
+    q.rounds = contour_rounds(q.B);
+    uint64_t lines = 0, vertices = 0;
+    bool fits = true;
+    if (q.B) {
+        const ContourSideLayout sl = contour_side_layout(q.B);
+        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, sl.end)) != MRTX_OK) return rc;
+        char* sb = reinterpret_cast<char*>(c->illum_out);
+        q.eid = reinterpret_cast<int32_t*>(sb + sl.eid_at);
+        q.succ = reinterpret_cast<int32_t*>(sb + sl.succ_at);
+        q.len = reinterpret_cast<uint32_t*>(sb + sl.len_at);
+        q.tailat = reinterpret_cast<int32_t*>(sb + sl.tailat_at);
+        q.lineno = reinterpret_cast<uint32_t*>(sb + sl.lineno_at);
+        q.side_sums = reinterpret_cast<uint2*>(sb + sl.sums_at);
+        q.jump[0] = reinterpret_cast<ContourJump*>(sb + sl.jump_at[0]);
+        q.jump[1] = reinterpret_cast<ContourJump*>(sb + sl.jump_at[1]);
+        q.fin = q.jump[q.rounds & 1];
+        HIPCHK(c, mrtx_launch_contour_trace(q, c->stream, &launches));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
+        if ((head[0] >> 32) || head[5] != q.B) {                // the lines' lengths add up to the elements
+            if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
+            return fail(c, MRTX_E_DEVICE, "the contour trace met %u broken successors and lines of %llu vertices for %u crossings",
+                        (uint32_t)(head[0] >> 32), head[5], q.B);
+        }
+        lines = head[4]; vertices = head[5];
+        fits = lines <= line_cap && vertices <= vertex_cap;
+        if (has_lines && fits) {
+            // the tables bound for the host lie in a block of their own, of exactly their size
+            if ((host_lines || host_vertices) &&
+                (rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, contour_host_vertices_at(lines) + 4 * (size_t)vertices)) != MRTX_OK)
+                return rc;
+            char* hb = reinterpret_cast<char*>(c->illum_tab);
+            q.lines = host_lines ? reinterpret_cast<ContourLineRec*>(hb) : static_cast<ContourLineRec*>(dev_lines);
+            q.vertices = host_vertices ? reinterpret_cast<int32_t*>(hb + contour_host_vertices_at(lines)) : static_cast<int32_t*>(dev_vertices);
+            HIPCHK(c, mrtx_launch_contour_fill(q, lines, c->stream, &launches));
+        }
+    }
+    if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
+    if (out) out->launches = launches;
+    if (has_lines && fits && q.B) {                             // the fill's own check of what the trace handed it
+        HIPCHK(c, hipMemcpy(head, tb, 8, hipMemcpyDeviceToHost));
+        if (head[0] >> 32) return fail(c, MRTX_E_DEVICE, "the contour fill met %u elements without a line", (uint32_t)(head[0] >> 32));
+    }
+    *n_lines = lines;
+    *n_vertices = vertices;
+    if (has_lines && !fits)
+        return fail(c, MRTX_E_INVALID, "the tables are too small: %llu lines and %llu vertices are needed (line_cap = %llu, vertex_cap = %llu)",
+                    (unsigned long long)lines, (unsigned long long)vertices, (unsigned long long)line_cap, (unsigned long long)vertex_cap);
+    if (host_lines && lines) HIPCHK(c, hipMemcpy(host_lines, q.lines, sizeof(MrtxContourLine) * (size_t)lines, hipMemcpyDeviceToHost));
+    if (host_vertices && vertices) HIPCHK(c, hipMemcpy(host_vertices, q.vertices, 4 * (size_t)vertices, hipMemcpyDeviceToHost));
     return MRTX_OK;
 }
 

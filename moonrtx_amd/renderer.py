@@ -1401,6 +1401,65 @@ class MoonRT:
             stats["fill_ms"] = stats.get("fill_ms", 0.0) + st2.kernel_ms
         return rg.Outlines(rings, vertices, rows, cols, wrap)
 
+    # ---- Contour lines
+    def contours(self, z, levels, wrap=False, shape=None, stats=None):
+        """The contour lines of a lattice of integer heights at a table of levels (mrtx_contours): every line an ordered run
+        of crossed edges with the above side (z >= level) on its right, closed, or open where it meets the lattice's edge or
+        a void node.  z: (rows, cols) int32 within +-2^30 (basins.quantise_heights), contours.VOID where there is no node, or
+        a DeviceBuffer (then give shape = (rows, cols); the tables are made on the device and downloaded together with the
+        heights).  levels: strictly ascending int32 (contours.levels_for), at most 65536.  One call counts, a second fills
+        tables of exactly that size.  Needs no DEM.  Returns contours.Contours; stats gains launches, kernel_ms, count_ms and
+        fill_ms."""
+        from . import contours as ct
+        dev = isinstance(z, DeviceBuffer)
+        if dev:
+            if shape is None:
+                raise ValueError("a DeviceBuffer needs shape = (rows, cols)")
+            rows, cols = int(shape[0]), int(shape[1])
+        else:
+            h = np.asarray(z)
+            if h.ndim != 2:
+                raise ValueError("z must be (rows, cols)")
+            rows, cols = int(h.shape[0]), int(h.shape[1])
+        z_d, z_h, z_keep = self._int32_arg(z, (rows, cols), "z")
+        lv = np.asarray(levels)
+        if lv.ndim != 1 or not 1 <= lv.size <= _lib.CONTOUR_MAX_LEVELS or not np.issubdtype(lv.dtype, np.integer):
+            raise ValueError(f"levels must be 1 .. {_lib.CONTOUR_MAX_LEVELS} integers")
+        if lv.min() < -2 ** 31 or lv.max() > 2 ** 31 - 1:
+            raise ValueError("levels leave int32")
+        lv = np.ascontiguousarray(lv, np.int32)
+        k = _lib.MrtxContours(rows, cols, 1 if wrap else 0, int(lv.size), 0)
+        nl, nv = C.c_uint64(0), C.c_uint64(0)
+        st, st2 = MrtxStats(), MrtxStats()
+        self._check(self._lib.mrtx_contours(self._ctx, C.byref(k), z_d, z_h, lv.ctypes.data, None, None, 0, None, None, 0,
+                                            C.byref(nl), C.byref(nv), C.byref(st)), "mrtx_contours")
+        self._add_stats(stats, st)
+        n_l, n_v = int(nl.value), int(nv.value)
+        if dev:
+            lb = DeviceBuffer(max(32 * n_l, 32), z.device)
+            vb = DeviceBuffer(max(4 * n_v, 4), z.device)
+            try:
+                self._check(self._lib.mrtx_contours(self._ctx, C.byref(k), z_d, None, lv.ctypes.data, lb.ptr, None, n_l, vb.ptr, None,
+                                                    n_v, C.byref(nl), C.byref(nv), C.byref(st2)), "mrtx_contours")
+                lines = lb.download(_lib.CONTOUR_LINE_DTYPE, (n_l,))
+                vertices = vb.download(np.int32, (n_v,))
+                heights = z.download(np.int32, (rows, cols))
+            finally:
+                lb.free()
+                vb.free()
+        else:
+            lines = np.zeros(max(n_l, 1), _lib.CONTOUR_LINE_DTYPE)
+            vertices = np.zeros(max(n_v, 1), np.int32)
+            self._check(self._lib.mrtx_contours(self._ctx, C.byref(k), None, z_h, lv.ctypes.data, None, lines.ctypes.data, n_l, None,
+                                                vertices.ctypes.data, n_v, C.byref(nl), C.byref(nv), C.byref(st2)), "mrtx_contours")
+            lines, vertices = lines[:n_l], vertices[:n_v]
+            heights = z_keep
+        self._add_stats(stats, st2)
+        if isinstance(stats, dict):
+            stats["count_ms"] = stats.get("count_ms", 0.0) + st.kernel_ms
+            stats["fill_ms"] = stats.get("fill_ms", 0.0) + st2.kernel_ms
+        return ct.Contours(lines, vertices, heights, lv, wrap)
+
     # ---- Terrain depressions (DESIGN.md section 3.24)
     @staticmethod
     def _int32_arg(table, shape, what):
