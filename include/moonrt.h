@@ -1022,6 +1022,55 @@ int mrtx_thermal_occulted(mrtx_ctx* ctx, const double* latlon_deg, int32_t n, in
                           int64_t extra_len, const MrtxVolatile* species, const MrtxIllumEpoch* occ_source,
                           const MrtxIllumEpoch* occ_body, void* dev_out, void* host_out, MrtxStats* out);
 
+/* ---- Orbiter passes: relay contact windows against terrain horizons (additive to ABI 7) ------------
+ * When can a point talk to a relay orbiter?  S satellites, each a table of m positions in the Moon-fixed frame (the library's
+ * body axes: x = r cos(lat) sin(lon), y = r cos(lat) cos(lon), z = r sin(lat); metres), against the horizons of
+ * mrtx_horizon_points / mrtx_horizon_raised.  A satellite is a point source: in view iff its margin g > 0. */
+#define MRTX_PASSES_FULL    0
+#define MRTX_PASSES_SUMMARY 1
+#define MRTX_PASSES_LIST    2
+typedef struct MrtxPasses {
+    int32_t n_sat;          /* S in [1, 256]                                                                             */
+    int32_t m;              /* epochs per satellite, 1 .. 2^24; S * m <= 2^24                                            */
+    int32_t mode;           /* MRTX_PASSES_*                                                                             */
+    int32_t reserved;       /* 0                                                                                         */
+    double  radius_m;       /* metres of D = 1 (> 0), as mrtx_horizon_raised                                             */
+    double  min_elev_deg;   /* elevation mask above the local horizontal, in [-90, 90)                                   */
+} MrtxPasses;
+typedef struct MrtxPass {   /* 40 bytes */
+    int32_t point, sat, first, count;   /* epochs first .. first + count - 1 have g > 0                                  */
+    int32_t max_at;                     /* earliest epoch of the pass's greatest elevation                               */
+    uint32_t flags;                     /* bit 0: begins at epoch 0, bit 1: ends at epoch m - 1 (open ends)              */
+    float rise_frac, set_frac;          /* AOS = first - rise_frac, LOS = first + count - 1 + set_frac, in epochs        */
+    float max_elev_deg, min_range_m;
+} MrtxPass;
+/* Points, horizons, n_az and "exactly one of dev_horizon and host_horizon" as mrtx_horizon_windows; height_m (NULL: the ground)
+ * as mrtx_horizon_raised: per point in [0, 1e4] metres, the direction to a satellite is taken from P = fmaf(hs, u, o), and NULL
+ * and all-zero heights give the same bits.  sat_pos_m: S x m x 3 doubles; each component becomes (float)(x / radius_m * R).
+ * Per (point, satellite, epoch) in float32: t = X - P, range = |t|, the unit direction, its elevation es and azimuth and the
+ * interpolated horizon hh exactly as mrtx_horizon_sun forms them for a light's centre; g = es - fmaxf(hh, (float)min_elev_deg).
+ *   FULL     n x S x m float4 (es deg, azimuth deg in [0, 360), range in metres = range * (float)(radius_m / R), g), point-major
+ *            then satellite; at most 2^27 outputs per call; into exactly one of dev_out (16-byte aligned) and host_out.
+ *   SUMMARY  n x 8 float32 (dev_out 16-byte aligned), no n x S x m table; with c_k the number of satellites in view at epoch k:
+ *            [0] share of epochs with c_k >= 1             [1] longest run with c_k == 0 (the longest outage)
+ *            [2] longest run with c_k >= 1                 [3] first epoch of that run (the earliest such run; -1 if none)
+ *            [4] number of maximal runs of c_k >= 1        [5] greatest es over all in-view (s, k); -90 if none
+ *            [6] (float)(sum of c_k / (double)m)           [7] share of epochs with c_k >= 2
+ *            Shares are (float)(count / (double)m); runs and indices are exact float counts.
+ *   LIST     MrtxPass records, one per maximal run of g > 0 of one (point, satellite), in ascending (point, sat, first).  With
+ *            g_a = g[first - 1] <= 0 < g_b = g[first]: rise_frac = g_b / (g_b - g_a) (0 with flag bit 0 when first == 0);
+ *            set_frac = g_l / (g_l - g_n) from the last epoch's margin and the next one's (0 with flag bit 1 at m - 1);
+ *            max_elev_deg, max_at and min_range_m over the pass's own epochs.  *n_passes always receives the true total; with
+ *            dev_out == host_out == NULL and pass_cap == 0 the call only counts; when the total exceeds pass_cap nothing is
+ *            written and the call returns MRTX_E_INVALID naming the needed size.  dev_out 8-byte aligned.
+ * pass_cap and n_passes are read in LIST only (n_passes may be NULL otherwise).  Refused with MRTX_E_INVALID before any launch:
+ * a non-finite position, a position within the Moon's bounding sphere (mrtx_occultation's) plus the largest raise, S * m > 2^24,
+ * a bad mode, both outputs or (outside a LIST count) neither, a misaligned dev_out.  Needs a DEM, but neither a light nor a Moon
+ * frame; leaves the light, Moon frame and render state as they were.  out: launches, kernel_ms. */
+int mrtx_horizon_passes(mrtx_ctx* ctx, const MrtxPasses* k, const double* latlon_deg, const double* height_m, int32_t n,
+                        int32_t n_az, const void* dev_horizon, const float* host_horizon, const double* sat_pos_m, void* dev_out,
+                        void* host_out, uint64_t pass_cap, uint64_t* n_passes, MrtxStats* out);
+
 /* Math conformance probe (ABI 7): the kernels' domain-restricted reciprocal (v_rcp_f32 + Newton steps) and square root (v_sqrt_f32 + a
  * +-1 ulp residual fix) against the compiler's IEEE expansions of 1.0f / x and sqrtf(x), ON THE DEVICE, for the n float bit patterns
  * from lo_bits on: which = 0 one Newton step, 1 two steps (what the kernels use), 2 the square root.  mismatches = how many differ;

@@ -193,6 +193,31 @@ class MrtxBowl(C.Structure):
                 ("n_leaves", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+PASSES_FULL, PASSES_SUMMARY, PASSES_LIST = 0, 1, 2         # MRTX_PASSES_*: MoonRT.PASS_MODES names them
+
+
+class MrtxPasses(C.Structure):
+    """The satellites, the mode and the elevation mask of an orbiter-pass call (mrtx_horizon_passes)."""
+    _fields_ = [("n_sat", C.c_int32), ("m", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32), ("radius_m", C.c_double),
+                ("min_elev_deg", C.c_double)]
+
+
+class MrtxPass(C.Structure):
+    """One pass of one satellite over one point (mrtx_horizon_passes): 40 bytes."""
+    _fields_ = [("point", C.c_int32), ("sat", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("max_at", C.c_int32),
+                ("flags", C.c_uint32), ("rise_frac", C.c_float), ("set_frac", C.c_float), ("max_elev_deg", C.c_float),
+                ("min_range_m", C.c_float)]
+
+
+# MrtxPass, field for field (40 bytes)
+PASS_DTYPE = np.dtype([("point", "<i4"), ("sat", "<i4"), ("first", "<i4"), ("count", "<i4"), ("max_at", "<i4"), ("flags", "<u4"),
+                       ("rise_frac", "<f4"), ("set_frac", "<f4"), ("max_elev_deg", "<f4"), ("min_range_m", "<f4")])
+assert PASS_DTYPE.itemsize == 40 == C.sizeof(MrtxPass)
+PASS_COLUMNS = ("share_any", "longest_outage", "longest_contact", "first_contact", "contacts", "max_elev_deg", "mean_in_view",
+                "share_two")
+PASS_OPEN_START, PASS_OPEN_END = 1, 2                       # MrtxPass.flags
+
+
 class MrtxIllumEpoch(C.Structure):
     """One date of a Sun-illumination series (mrtx_illum_series): what mrtx_set_light and
     mrtx_set_moon_frame would set for it."""
@@ -347,6 +372,8 @@ SIGNATURES = {
     "mrtx_thermal_column": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                       C.c_int64, C.POINTER(MrtxVolatile), _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_occultation": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.POINTER(MrtxStats)]),
+    "mrtx_horizon_passes": (C.c_int, [_VP, C.POINTER(MrtxPasses), _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP,
+                                      C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
     "mrtx_thermal_occulted": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                         C.c_int64, C.POINTER(MrtxVolatile), _VP, _VP, _VP, _VP, C.POINTER(MrtxStats)]),
 }

@@ -69,6 +69,7 @@ hipError_t mrtx_launch_horizon(const FrameC& f, HorizonC h, bool stats, hipStrea
 hipError_t mrtx_launch_horizon_sun(const FrameC& f, HorizonSunC q, hipStream_t st);
 hipError_t mrtx_launch_horizon_raised(const FrameC& f, HorizonRaisedC q, bool stats, hipStream_t st);
 hipError_t mrtx_launch_horizon_windows(const FrameC& f, HorizonWindowsC q, hipStream_t st);
+hipError_t mrtx_launch_passes(const FrameC& f, PassesC q, int mode, hipStream_t st);
 hipError_t mrtx_launch_occultation(const FrameC& f, OccultC q, hipStream_t st);
 hipError_t mrtx_launch_power_budget(const FrameC& f, PowerC q, hipStream_t st);
 hipError_t mrtx_launch_sight(const FrameC& f, SightC q, bool stats, hipStream_t st);
@@ -1772,6 +1773,134 @@ int mrtx_occultation(mrtx_ctx* c, const double* latlon, int32_t n, const MrtxIll
     if ((rc = stage_start(c, &cold, false)) != MRTX_OK) return rc;
     HIPCHK(c, mrtx_launch_occultation(f, q, c->stream));
     return stage_finish(c, dev_out, host_out, out_bytes, out, kNoRays);
+}
+
+// ---- Orbiter passes: relay contact windows against terrain horizons -------------------------------
+static_assert(sizeof(MrtxPasses) == 32, "MrtxPasses is 32 bytes");
+static_assert(sizeof(MrtxPass) == 40 && sizeof(PassRec) == sizeof(MrtxPass) && alignof(PassRec) == 4, "MrtxPass is 40 bytes");
+
+int mrtx_horizon_passes(mrtx_ctx* c, const MrtxPasses* k, const double* latlon, const double* height_m, int32_t n, int32_t n_az,
+                        const void* dev_horizon, const float* host_horizon, const double* sat_pos_m, void* dev_out, void* host_out,
+                        uint64_t pass_cap, uint64_t* n_passes, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!k) return fail(c, MRTX_E_INVALID, "null passes block");
+    if (!latlon || !sat_pos_m) return fail(c, MRTX_E_INVALID, "null point list or position table");
+    if (k->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    if (k->mode != MRTX_PASSES_FULL && k->mode != MRTX_PASSES_SUMMARY && k->mode != MRTX_PASSES_LIST)
+        return fail(c, MRTX_E_INVALID, "mode must be 0 (FULL), 1 (SUMMARY) or 2 (LIST) (got %d)", k->mode);
+    if (n < 1) return fail(c, MRTX_E_INVALID, "n must be >= 1 (got %d)", n);
+    if (k->n_sat < 1 || k->n_sat > 256) return fail(c, MRTX_E_INVALID, "n_sat must lie in [1, 256] (got %d)", k->n_sat);
+    // the runs, the indices and the sum of c_k are float counts, exact up to 2^24
+    if (k->m < 1 || k->m > (1 << 24) || (int64_t)k->n_sat * (int64_t)k->m > (int64_t)1 << 24)
+        return fail(c, MRTX_E_INVALID, "m must be >= 1 and n_sat * m at most 2^24 (got %d x %d)", k->n_sat, k->m);
+    if (!horizon_az_ok(n_az)) return fail(c, MRTX_E_INVALID, "n_az must be 4, 8, ..., 4096 (got %d)", n_az);
+    if (!std::isfinite(k->radius_m) || !(k->radius_m > 0.0)) return fail(c, MRTX_E_INVALID, "radius_m must be finite and > 0");
+    if (!(k->min_elev_deg >= -90.0 && k->min_elev_deg < 90.0)) return fail(c, MRTX_E_INVALID, "min_elev_deg must lie in [-90, 90)");
+    const bool list = k->mode == MRTX_PASSES_LIST;
+    const int S = k->n_sat, m = k->m;
+    if ((dev_horizon == nullptr) == (host_horizon == nullptr))
+        return fail(c, MRTX_E_INVALID, "give exactly one of dev_horizon and host_horizon");
+    if ((int64_t)n * (int64_t)n_az > (int64_t)1 << 31) return fail(c, MRTX_E_INVALID, "at most 2^31 horizon samples per call");
+    if (dev_out && host_out) return fail(c, MRTX_E_INVALID, "give at most one of dev_out and host_out");
+    const bool has_out = dev_out || host_out;
+    if (!list && !has_out) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
+    if (list && !n_passes) return fail(c, MRTX_E_INVALID, "null n_passes");
+    if (list && !has_out && pass_cap) return fail(c, MRTX_E_INVALID, "without a table pass_cap must be 0 (got %llu)", (unsigned long long)pass_cap);
+    if (dev_out && ((uintptr_t)dev_out & (list ? 7 : 15)))
+        return fail(c, MRTX_E_INVALID, "dev_out must be %d-byte aligned", list ? 8 : 16);
+    if (k->mode == MRTX_PASSES_FULL && (int64_t)n * S * m > (int64_t)1 << 27)
+        return fail(c, MRTX_E_INVALID, "FULL holds at most 2^27 outputs per call: split the points into more calls");
+    if (list && (int64_t)n * S > (int64_t)1 << 27)
+        return fail(c, MRTX_E_INVALID, "LIST holds at most 2^27 (point, satellite) pairs per call: split the points into more calls");
+    int rc;
+    if ((rc = horizon_entries(c, host_horizon, n, n_az)) != MRTX_OK) return rc;
+    if (!c->dem) return fail(c, MRTX_E_STATE, "no displacement map: call mrtx_upload_dem first");
+    std::vector<float> hs((size_t)n, 0.0f);
+    double hs_max = 0.0;
+    for (int32_t i = 0; height_m && i < n; i++) {
+        const double h = height_m[i];
+        if (!std::isfinite(h) || h < 0.0 || h > 1e4) return fail(c, MRTX_E_INVALID, "point %d: height must lie in [0, 1e4] m", i);
+        hs[(size_t)i] = (float)(h / k->radius_m * c->radius);
+        if (!std::isfinite(hs[(size_t)i])) return fail(c, MRTX_E_INVALID, "point %d: height / radius_m is out of range", i);
+        hs_max = std::max(hs_max, (double)hs[(size_t)i]);
+    }
+    // the satellites' table: one float4 per (satellite, epoch), outside mrtx_occultation's bounding sphere plus the largest raise
+    const double Rb = 1.001 * c->radius + std::fabs((double)c->prm.scene_epsilon) + hs_max;
+    std::vector<float> sat((size_t)S * (size_t)m * 4, 0.0f);
+    for (size_t i = 0; i < (size_t)S * (size_t)m; i++) {
+        double r2 = 0.0;
+        for (int j = 0; j < 3; j++) {
+            const double x = sat_pos_m[3 * i + j];
+            const float xf = (float)(x / k->radius_m * c->radius);
+            if (!std::isfinite(x) || !std::isfinite(xf))
+                return fail(c, MRTX_E_INVALID, "satellite %zu, epoch %zu: the position is not finite", i / (size_t)m, i % (size_t)m);
+            sat[4 * i + j] = xf;
+            r2 += (double)xf * (double)xf;
+        }
+        if (!(std::sqrt(r2) > Rb))
+            return fail(c, MRTX_E_INVALID, "satellite %zu, epoch %zu: the position lies within the Moon's bounding sphere (%g of %g)",
+                        i / (size_t)m, i % (size_t)m, std::sqrt(r2), Rb);
+    }
+    std::vector<float> rtab, ctab;
+    if ((rc = point_tables(c, latlon, n, rtab, ctab)) != MRTX_OK) return rc;
+    FrameC f;
+    FrameCold cold;
+    if ((rc = stage_frame(c, f, cold, false)) != MRTX_OK) return rc;
+    const size_t nh = host_horizon ? (size_t)n * (size_t)n_az : 0;
+    const size_t pairs = (size_t)n * (size_t)S;
+    const size_t out_bytes = k->mode == MRTX_PASSES_FULL ? pairs * (size_t)m * 16 : (size_t)n * 32;
+    float* d[5];
+    if (!list && (rc = stage_out(c, dev_out, out_bytes)) != MRTX_OK) return rc;
+    // LIST: the counts, then the prefix sums (8-byte aligned), in the work buffer
+    const size_t base_at = (pairs * 4 + 15) & ~(size_t)15;
+    if (list && (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, base_at + pairs * 8)) != MRTX_OK) return rc;
+    if ((rc = stage_tables(c, {rtab, ctab, hs, sat, {host_horizon, nh}}, d)) != MRTX_OK) return rc;
+    PassesC q;
+    std::memset(&q, 0, sizeof q);
+    q.g.rtab = d[0]; q.g.ctab = d[1];
+    q.g.rows = n; q.g.cols = n; q.g.points = 1;
+    q.hs = d[2]; q.sat = d[3];
+    q.horizon = host_horizon ? d[4] : (const float*)dev_horizon;
+    q.min_elev = (float)k->min_elev_deg; q.range_scale = (float)(k->radius_m / c->radius);
+    q.az_log2 = log2_of(n_az); q.m = m; q.n_sat = S;
+    if (!list) {
+        q.out = dev_out;
+        if ((rc = stage_start(c, &cold, false)) != MRTX_OK) return rc;
+        HIPCHK(c, mrtx_launch_passes(f, q, k->mode, c->stream));
+        return stage_finish(c, dev_out, static_cast<float*>(host_out), out_bytes, out, kNoRays);
+    }
+    char* const tb = reinterpret_cast<char*>(c->trav_buf);
+    q.counts = reinterpret_cast<uint32_t*>(tb);
+    q.base = reinterpret_cast<const unsigned long long*>(tb + base_at);
+    if ((rc = stage_start(c, &cold, false)) != MRTX_OK) return rc;
+    HIPCHK(c, mrtx_launch_passes(f, q, 2, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                 // also: the pageable tables are no longer read
+    std::vector<uint32_t> counts(pairs);
+    HIPCHK(c, hipMemcpy(counts.data(), q.counts, pairs * 4, hipMemcpyDeviceToHost));
+    std::vector<unsigned long long> base(pairs);
+    uint64_t total = 0;
+    for (size_t i = 0; i < pairs; i++) { base[i] = total; total += counts[i]; }
+    uint32_t launches = 1;
+    const bool fits = total <= pass_cap;
+    const size_t list_bytes = sizeof(MrtxPass) * (size_t)total;
+    if (has_out && fits && total) {
+        if (host_out) {
+            if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, list_bytes)) != MRTX_OK) return rc;
+            dev_out = c->illum_out;
+        }
+        q.out = dev_out;
+        HIPCHK(c, hipMemcpyAsync(tb + base_at, base.data(), pairs * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, mrtx_launch_passes(f, q, 3, c->stream));
+        launches = 2;
+    }
+    const bool filled = launches == 2;
+    if ((rc = stage_finish(c, dev_out, filled ? static_cast<float*>(host_out) : nullptr, list_bytes, out, kNoRays)) != MRTX_OK) return rc;
+    if (out) out->launches = launches;
+    *n_passes = total;
+    if (has_out && !fits)
+        return fail(c, MRTX_E_INVALID, "the table is too small: %llu passes are needed (pass_cap = %llu)", (unsigned long long)total,
+                    (unsigned long long)pass_cap);
+    return MRTX_OK;
 }
 
 // ---- Site power budgets ----------------------------------------------------------------------------

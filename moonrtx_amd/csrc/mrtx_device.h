@@ -400,6 +400,29 @@ struct HorizonMaskC {
     int32_t m;              // epochs
 };
 
+// Orbiter passes (mrtx_horizon_passes, DESIGN.md sections 3.27 and 4.33): HorizonSunC's point list and horizons, the points'
+// raises and a table of satellite positions in the body axes, one float4 (x, y, z, 0) per (satellite, epoch) in scene units.
+// FULL and SUMMARY: one wave per point; LIST: one wave per (point, satellite), first the counts, then the records.
+struct PassRec {            // MrtxPass, field for field: 40 bytes
+    int32_t point, sat, first, count, max_at;
+    uint32_t flags;
+    float rise_frac, set_frac, max_elev_deg, min_range_m;
+};
+struct PassesC {
+    IllumC g;               // the point list (g.rows points), as in HorizonC
+    const float* horizon;   // n_points x n_az float32 elevations (degrees)
+    const float* hs;        // per point: (float)(height_m / radius_m * R), >= 0
+    const float* sat;       // n_sat x m float4, satellite-major
+    void* out;              // FULL: n x n_sat x m float4; SUMMARY: n x 8 float32; LIST: the PassRec table (fill)
+    uint32_t* counts;       // LIST, count: n x n_sat passes per (point, satellite)
+    const unsigned long long* base;   // LIST, fill: n x n_sat exclusive prefix sums of the counts
+    float min_elev;         // (float)min_elev_deg
+    float range_scale;      // (float)(radius_m / R): scene units -> metres
+    int32_t az_log2;        // log2(n_az)
+    int32_t m;              // epochs per satellite
+    int32_t n_sat;
+};
+
 // Terrain relief (mrtx_relief, DESIGN.md sections 3.14 and 4.15; kernels in mrtx_relief.hip).  A window of the DEM's texel
 // lattice as in TraverseC, never wrapped; the footprint of a node is the (2 ri + 1) x (2 rj + 1) lattice nodes around it, read
 // straight from the DEM (rows outside [0, dem_h) make the node NaN, columns wrap modulo dem_w).

@@ -8,6 +8,7 @@
 //   horizon_mask_kernel                     the joint predicate as bits: drive masks (3.19)
 //   power_budget_kernel                     energy-storage need and state of charge (3.17)
 //   occultation_kernel                      the Earth's occultation of the Sun (3.18)
+//   passes_full_kernel, passes_summary_kernel, passes_list_kernel   orbiter passes against the horizons (3.27)
 //   thermal_kernel                          regolith temperatures and subsurface columns (3.9, 3.11, 3.16, 3.18)
 //   view_hits_kernel, view_share_kernel, scatter_flux_kernel   terrain-scattered sunlight and infrared (3.11)
 //   sight_kernel                            line of sight, viewsheds, mast heights (3.12)
@@ -659,6 +660,224 @@ __global__ void __launch_bounds__(64) occultation_kernel(const FrameC f, const O
     }
 }
 
+// Orbiter passes (DESIGN.md sections 3.27 and 4.33): a satellite at X (body axes, scene units) seen from the raised end P of a
+// point -- its range, elevation es and azimuth, and its margin g = es - max(horizon at that azimuth, the elevation mask).  The
+// unit direction, es, the azimuth in turns and the interpolated horizon are disc_fraction's operations restated for a point
+// source (in view iff g > 0, its rule es > hh), so that function stays as it is.
+struct SatLook {
+    float es, az, range, g;     // degrees, degrees in [0, 360), scene units, degrees
+};
+__device__ __forceinline__ SatLook sat_look(const float4 X, float Pa, float Pb, float Pc, const PointFrame& p, const float* hz,
+                                            int n_az, float min_elev) {
+    constexpr float kDeg = 57.2957795130823209f, kInvTurn = 0.159154943091895336f;
+    const float ta = X.x - Pa, tb = X.y - Pb, tc = X.z - Pc;
+    const float dist = sqrt_sh(fmaf(tc, tc, fmaf(tb, tb, ta * ta)));
+    const float inv_dist = rcp_cr(dist);
+    const float la = ta * inv_dist, lb = tb * inv_dist, lc = tc * inv_dist;
+    const float xu = fmaf(p.uc, lc, fmaf(p.ub, lb, p.ua * la));
+    const float xn = fmaf(p.Nc, lc, fmaf(p.Nb, lb, p.Na * la));
+    const float xe = fmaf(-p.ct.x, lb, p.ct.y * la);
+    const float es = atan2f(xu, sqrtf(fmaf(xe, xe, xn * xn))) * kDeg;
+    float ph = atan2f(xe, xn) * kInvTurn;                   // turns from north through east, [-1/2, 1/2]
+    ph = ph < 0.0f ? ph + 1.0f : ph;
+    const float x = ph * (float)n_az;
+    const float x0 = floorf(x);
+    const float w = x - x0;
+    const int i0 = (int)x0 & (n_az - 1), i1 = (i0 + 1) & (n_az - 1);
+    const float h0 = hz[i0], h1 = hz[i1];
+    const float hh = fmaf(w, h1 - h0, h0);
+    const float az = ph * 360.0f;                           // ph + 1 may round to a whole turn: north
+    return {es, az >= 360.0f ? 0.0f : az, dist, es - fmaxf(hh, min_elev)};
+}
+
+// The pointing table and the coverage of a constellation: horizon_windows_kernel's walk -- one wave per point, the epochs 64 at
+// a time with lane = epoch, the vertex, the frame and the raised origin once, the horizon row in L1 -- with a loop over the
+// satellites inside each chunk.  FULL stores (es, azimuth, range in metres, g) per (satellite, epoch).
+template <bool WIDE>
+__global__ void __launch_bounds__(64) passes_full_kernel(const FrameC f, const PassesC q) {
+    const int lane = threadIdx.x;
+    const int pt = (int)blockIdx.x;
+    const int n_az = 1 << q.az_log2;
+    Vertex v;
+    (void)illum_vertex<false, WIDE>(f, q.g, pt, pt, v, nullptr);
+    const PointFrame p = point_frame(f, q.g, pt, pt, v);
+    float Pa, Pb, Pc;
+    sight_end(p, q.hs[pt], Pa, Pb, Pc);
+    const float* const hz = q.horizon + ((int64_t)pt << q.az_log2);
+    const float4* const sat = reinterpret_cast<const float4*>(q.sat);
+    float4* const out = reinterpret_cast<float4*>(q.out) + (int64_t)pt * q.n_sat * q.m;
+    for (int k0 = 0; k0 < q.m; k0 += 64) {
+        const int k = k0 + lane;
+        if (k < q.m)
+            for (int s = 0; s < q.n_sat; s++) {
+                const SatLook l = sat_look(sat[s * q.m + k], Pa, Pb, Pc, p, hz, n_az, q.min_elev);
+                out[(int64_t)s * q.m + k] = make_float4(l.es, l.az, l.range * q.range_scale, l.g);
+            }
+    }
+}
+
+// SUMMARY: per chunk each lane counts the satellites in view at its epoch, c_k, and keeps the greatest es among them; the
+// ballots of c_k >= 1 and c_k >= 2 give the shares, the runs of c_k == 0 and c_k >= 1 go through EpochRuns (the earliest longest
+// contact kept with its first epoch), and the contacts are counted as occultation_kernel counts its eclipses: a set epoch whose
+// predecessor is unset, lane 0's predecessor being the carried last bit of the chunk before.  Everything carried is wave-uniform;
+// the sum of c_k and the greatest es are reduced at the end.  No atomics, no LDS; lane 0 stores the point's two float4.
+template <bool WIDE>
+__global__ void __launch_bounds__(64) passes_summary_kernel(const FrameC f, const PassesC q) {
+    const int lane = threadIdx.x;
+    const int pt = (int)blockIdx.x;
+    const int n_az = 1 << q.az_log2;
+    Vertex v;
+    (void)illum_vertex<false, WIDE>(f, q.g, pt, pt, v, nullptr);
+    const PointFrame p = point_frame(f, q.g, pt, pt, v);
+    float Pa, Pb, Pc;
+    sight_end(p, q.hs[pt], Pa, Pb, Pc);
+    const float* const hz = q.horizon + ((int64_t)pt << q.az_log2);
+    const float4* const sat = reinterpret_cast<const float4*>(q.sat);
+    uint32_t n_any = 0, n_two = 0, n_runs = 0;              // wave-uniform counts
+    uint32_t sum_c = 0;                                     // per lane, reduced at the end (n_sat * m <= 2^24)
+    float e_max = -90.0f;                                   // per lane, reduced at the end
+    EpochRuns outage, contact;                              // the runs of c_k == 0 and of c_k >= 1
+    unsigned long long prev = 0;                            // the c_k >= 1 bit of the previous chunk's last epoch
+    for (int k0 = 0; k0 < q.m; k0 += 64) {
+        const int k = k0 + lane;
+        const bool in = k < q.m;
+        uint32_t c = 0;
+        if (in)
+            for (int s = 0; s < q.n_sat; s++) {
+                const SatLook l = sat_look(sat[s * q.m + k], Pa, Pb, Pc, p, hz, n_az, q.min_elev);
+                if (l.g > 0.0f) { c++; e_max = fmaxf(e_max, l.es); }
+            }
+        sum_c += c;
+        const unsigned long long m1 = __ballot(c >= 1u), m2 = __ballot(c >= 2u), valid = __ballot(in);
+        n_any += (uint32_t)__popcll(m1); n_two += (uint32_t)__popcll(m2);
+        const int last = min(64, q.m - k0) - 1;
+        outage.longest(valid & ~m1, lane, in, last);
+        contact.longest_first(m1, lane, in, last, k0);
+        n_runs += (uint32_t)__popcll(m1 & ~((m1 << 1) | prev));
+        prev = (m1 >> last) & 1ull;
+    }
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        sum_c += __shfl_xor(sum_c, s, 64);
+        e_max = fmaxf(e_max, __shfl_xor(e_max, s, 64));
+    }
+    if (lane == 0) {
+        const double md = (double)q.m;
+        float4* const o = reinterpret_cast<float4*>(q.out) + 2 * (int64_t)pt;
+        o[0] = make_float4((float)((double)n_any / md), (float)outage.best, (float)contact.best, (float)contact.first);
+        o[1] = make_float4((float)n_runs, e_max, (float)((double)sum_c / md), (float)((double)n_two / md));
+    }
+}
+
+// LIST: one wave per (point, satellite), the epochs 64 at a time with lane = epoch.  FILL = false counts the passes -- the set
+// epochs whose predecessor is unset, as above -- and lane 0 stores the count.  FILL = true recomputes the same margins and writes
+// record base[point, satellite] + (passes ended so far) from the lane that ends the pass.  Per chunk: the ballot of the starts
+// keys a segmented scan (plain shuffles) of the greatest es with its earliest epoch and of the least range, so the lane that
+// ends a pass holds them from the pass's start in this chunk on; a pass that came in through the chunk's start joins them with
+// what is carried.  Carried, all wave-uniform and read from the chunk's last valid lane: the in-view bit and the margin of the
+// last epoch (the rise at lane 0 needs it), the open pass's first epoch, rise_frac, greatest es with its epoch and least range,
+// and the passes ended so far.  The margin of the epoch after a lane's own comes by shuffle from the lane above; the top
+// lane's comes from the next chunk, which is evaluated one iteration ahead (a single lane evaluating epoch k0 + 64 would cost the
+// wave a whole evaluation more per chunk).  No atomics, no LDS, nothing between workgroups; the records' order is the prefix
+// sums', so two runs write the same bytes.
+struct PassLane {
+    float g, es, range;
+    bool in;
+};
+template <bool WIDE, bool FILL>
+__global__ void __launch_bounds__(64) passes_list_kernel(const FrameC f, const PassesC q) {
+    const int lane = threadIdx.x;
+    const int pt = (int)(blockIdx.x / (unsigned)q.n_sat), s = (int)(blockIdx.x % (unsigned)q.n_sat);
+    const int n_az = 1 << q.az_log2;
+    Vertex v;
+    (void)illum_vertex<false, WIDE>(f, q.g, pt, pt, v, nullptr);
+    const PointFrame p = point_frame(f, q.g, pt, pt, v);
+    float Pa, Pb, Pc;
+    sight_end(p, q.hs[pt], Pa, Pb, Pc);
+    const float* const hz = q.horizon + ((int64_t)pt << q.az_log2);
+    const float4* const sat = reinterpret_cast<const float4*>(q.sat) + s * q.m;
+    auto eval = [&](int k0) -> PassLane {
+        const int k = k0 + lane;
+        PassLane r{0.0f, -INFINITY, INFINITY, k < q.m};
+        if (r.in) {
+            const SatLook l = sat_look(sat[k], Pa, Pb, Pc, p, hz, n_az, q.min_elev);
+            r.g = l.g; r.es = l.es; r.range = l.range;
+        }
+        return r;
+    };
+    unsigned long long prev = 0;                            // the in-view bit of the previous chunk's last epoch
+    if constexpr (!FILL) {
+        uint32_t n_pass = 0;
+        for (int k0 = 0; k0 < q.m; k0 += 64) {
+            const PassLane c = eval(k0);
+            const unsigned long long mv = __ballot(c.in && c.g > 0.0f);
+            n_pass += (uint32_t)__popcll(mv & ~((mv << 1) | prev));
+            prev = (mv >> (min(64, q.m - k0) - 1)) & 1ull;
+        }
+        if (lane == 0) q.counts[blockIdx.x] = n_pass;
+        return;
+    }
+    PassRec* const rec = reinterpret_cast<PassRec*>(q.out) + q.base[blockIdx.x];
+    const unsigned long long below = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);     // lanes 0 .. lane
+    uint32_t n_done = 0;
+    float g_last = 0.0f;                                    // the margin of the previous chunk's last epoch
+    int c_first = 0, c_at = 0;                              // the pass that reaches the previous chunk's last epoch
+    float c_rise = 0.0f, c_emax = 0.0f, c_rmin = 0.0f;
+    PassLane cur = eval(0);
+    for (int k0 = 0; k0 < q.m; k0 += 64) {
+        const int k = k0 + lane;
+        const bool more = k0 + 64 < q.m;                    // wave-uniform
+        const PassLane nxt = more ? eval(k0 + 64) : PassLane{0.0f, -INFINITY, INFINITY, false};
+        const int last = min(64, q.m - k0) - 1;
+        const bool view = cur.in && cur.g > 0.0f;
+        const unsigned long long mv = __ballot(view);
+        const unsigned long long next_bit = (more && __shfl(nxt.g, 0, 64) > 0.0f) ? 1ull : 0ull;
+        const unsigned long long st = mv & ~((mv << 1) | prev);
+        const unsigned long long en = mv & ~((mv >> 1) | (next_bit << 63));
+        // the margins of the epochs before and after this lane's
+        float g_prev = __shfl_up(cur.g, 1, 64), g_next = __shfl_down(cur.g, 1, 64);
+        const float g_top = __shfl(nxt.g, 0, 64);
+        if (lane == 0) g_prev = g_last;
+        if (lane == 63) g_next = g_top;
+        const float rise = k == 0 ? 0.0f : cur.g / (cur.g - g_prev);
+        const float setf = k == q.m - 1 ? 0.0f : cur.g / (cur.g - g_next);
+        // the segment of this lane: from the nearest start at or below it, or from the chunk's start
+        const unsigned long long hb = st & below;
+        const int head = hb ? 63 - __clzll((long long)hb) : 0;
+        float e = view ? cur.es : -INFINITY, r = view ? cur.range : INFINITY;
+        int at = k;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const float te = __shfl_up(e, d, 64), tr = __shfl_up(r, d, 64);
+            const int ta = __shfl_up(at, d, 64);
+            if (lane - d >= head) {
+                if (te >= e) { e = te; at = ta; }           // the earlier epoch on equal elevations
+                r = fminf(r, tr);
+            }
+        }
+        int first = k0 + head;
+        float rf = __shfl(rise, head, 64);
+        if (!hb) {                                          // the pass came in through the chunk's start
+            first = c_first; rf = c_rise;
+            if (c_emax >= e) { e = c_emax; at = c_at; }
+            r = fminf(r, c_rmin);
+        }
+        if ((en >> lane) & 1ull) {
+            PassRec o;
+            o.point = pt; o.sat = s; o.first = first; o.count = k - first + 1; o.max_at = at;
+            o.flags = (first == 0 ? 1u : 0u) | (k == q.m - 1 ? 2u : 0u);
+            o.rise_frac = rf; o.set_frac = setf; o.max_elev_deg = e; o.min_range_m = r * q.range_scale;
+            rec[n_done + (uint32_t)__popcll(en & (below >> 1))] = o;
+        }
+        n_done += (uint32_t)__popcll(en);
+        prev = (mv >> last) & 1ull;
+        g_last = __shfl(cur.g, last, 64);
+        c_first = __shfl(first, last, 64); c_rise = __shfl(rf, last, 64);
+        c_emax = __shfl(e, last, 64); c_at = __shfl(at, last, 64); c_rmin = __shfl(r, last, 64);
+        cur = nxt;
+    }
+}
+
 // Regolith surface temperatures (DESIGN.md sections 3.10 and 4.11).  One lane = one point: its vertex and local frame are
 // formed once, then per epoch the absorbed flux (the disc fraction of horizon_sun_kernel, illum_mu's mu, the albedo law) and
 // n_sub explicit steps of its heat-conduction column.  The column's temperatures are float64 registers (a deep node moves by
@@ -1204,6 +1423,29 @@ hipError_t mrtx_launch_occultation(const FrameC& f, OccultC q, hipStream_t st) {
     const dim3 grid((unsigned)q.g.rows), block(64);
     if (f.dem_wide) hipLaunchKernelGGL((mrtx::occultation_kernel<true>), grid, block, 0, st, f, q);
     else hipLaunchKernelGGL((mrtx::occultation_kernel<false>), grid, block, 0, st, f, q);
+    return hipGetLastError();
+}
+
+// Orbiter passes (passes_full_kernel, passes_summary_kernel: one wave per point; passes_list_kernel: one wave per (point,
+// satellite)).  mode: MRTX_PASSES_FULL / SUMMARY, 2 = LIST's count, 3 = LIST's fill.
+hipError_t mrtx_launch_passes(const FrameC& f, PassesC q, int mode, hipStream_t st) {
+    if (q.g.rows < 1 || q.az_log2 < 2 || q.az_log2 > 12 || q.m < 1 || q.n_sat < 1 || q.n_sat > 256 ||
+        (int64_t)q.n_sat * q.m > (int64_t)1 << 24 || mode < 0 || mode > 3 || !q.g.points || !q.horizon || !q.hs || !q.sat)
+        return hipErrorInvalidValue;
+    if (mode == 0 && (!q.out || ((uintptr_t)q.out & 15) || (int64_t)q.g.rows * q.n_sat * q.m > (int64_t)1 << 27)) return hipErrorInvalidValue;
+    if (mode == 1 && (!q.out || ((uintptr_t)q.out & 15))) return hipErrorInvalidValue;
+    if (mode >= 2 && (int64_t)q.g.rows * q.n_sat > (int64_t)1 << 27) return hipErrorInvalidValue;
+    if (mode == 2 && !q.counts) return hipErrorInvalidValue;
+    if (mode == 3 && (!q.out || ((uintptr_t)q.out & 7) || !q.base)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(mode >= 2 ? q.g.rows * q.n_sat : q.g.rows)), block(64);
+    pick2(mode & 1, f.dem_wide != 0, [&](auto odd, auto w) {
+        if (mode < 2) {
+            if constexpr (odd()) hipLaunchKernelGGL((mrtx::passes_summary_kernel<w()>), grid, block, 0, st, f, q);
+            else hipLaunchKernelGGL((mrtx::passes_full_kernel<w()>), grid, block, 0, st, f, q);
+        } else {
+            hipLaunchKernelGGL((mrtx::passes_list_kernel<w(), odd()>), grid, block, 0, st, f, q);
+        }
+    });
     return hipGetLastError();
 }
 

@@ -570,6 +570,75 @@ class MoonRT:
             self._add_stats(stats, st)
         return res
 
+    PASS_COLUMNS = _lib.PASS_COLUMNS
+    PASS_MODES = {"full": _lib.PASSES_FULL, "summary": _lib.PASSES_SUMMARY, "list": _lib.PASSES_LIST}
+
+    def horizon_passes(self, lat_deg, lon_deg, horizon, positions_m, *, height_m=None, min_elev_deg=0.0, mode="summary",
+                       n_az=None, radius_m=1737400.0, stats=None, chunk_bytes=256 << 20):
+        """Relay orbiters against the horizons of `horizon` (mrtx_horizon_passes).  positions_m:
+        (S, m, 3) or (m, 3) float64 metres in the Moon-fixed frame (orbits.fixed_from_latlon's axes), S <= 256 satellites at the
+        same m epochs.  A satellite is in view where its margin g = es - max(horizon at its azimuth, min_elev_deg) is > 0; the
+        direction is taken from the mast top height_m above each point (one value or one per point; None: the ground, the same
+        bits as 0).  mode "full": (N, S, m, 4) float32 (elevation deg, azimuth deg in [0, 360), range m, g), the antenna
+        pointing table; "summary": the (N, 8) float32 columns PASS_COLUMNS -- the share of epochs with a satellite in view, the
+        longest outage and the longest contact in epochs, that contact's first epoch (-1: none), the number of contacts, the
+        highest elevation in view (-90: none), the mean number in view and the share with two or more -- with no (N, S, m)
+        table anywhere; "list": a _lib.PASS_DTYPE array, one record per pass in ascending (point, sat, first), counted in one
+        call and filled by a second.  `horizon` as for horizon_sun; calls hold at most chunk_bytes of horizons and output."""
+        la, lo = self._points(lat_deg, lon_deg)
+        if mode not in self.PASS_MODES:
+            raise ValueError(f"mode must be one of {sorted(self.PASS_MODES)} (got {mode!r})")
+        pos = np.asarray(positions_m, np.float64)
+        if pos.ndim == 2:
+            pos = pos[None]
+        if pos.ndim != 3 or pos.shape[2] != 3:
+            raise ValueError("positions_m must be (S, m, 3) or (m, 3)")
+        pos = np.ascontiguousarray(pos)
+        S, m = int(pos.shape[0]), int(pos.shape[1])
+        hts = None
+        if height_m is not None:
+            hts = np.ascontiguousarray(np.broadcast_to(np.asarray(height_m, np.float64).ravel(), (la.size,)))
+        n_az, hz_at = self._horizon_arg(horizon, la.size, n_az)
+        pts = np.ascontiguousarray(np.stack([la, lo], -1))
+        k = _lib.MrtxPasses(S, m, self.PASS_MODES[mode], 0, float(radius_m), float(min_elev_deg))
+        per = max(S * m, 1)
+        if mode == "full":
+            res = np.empty((la.size, S, m, 4), np.float32)
+            step = max(1, min(int(chunk_bytes) // (16 * per), (1 << 27) // per))
+        elif mode == "summary":
+            res = np.empty((la.size, 8), np.float32)
+            step = max(1, int(chunk_bytes) // (4 * (max(int(n_az), 0) + 8)))
+        else:
+            res = []
+            step = max(1, min(int(chunk_bytes) // (4 * max(int(n_az), 0) + 12 * S), (1 << 27) // max(S, 1)))
+        total = C.c_uint64(0)
+        for a in range(0, max(la.size, 1), step):
+            b = min(a + step, la.size)
+            dh, hh = hz_at(a)
+            hp = None if hts is None else hts[a:].ctypes.data
+            st = MrtxStats()
+
+            def call(out_ptr, cap):
+                self._check(self._lib.mrtx_horizon_passes(self._ctx, C.byref(k), pts[a:].ctypes.data, hp, b - a, n_az, dh, hh,
+                                                          pos.ctypes.data, None, out_ptr, cap, C.byref(total), C.byref(st)),
+                            "mrtx_horizon_passes")
+                self._add_stats(stats, st)
+            if mode != "list":
+                call(res[a:].ctypes.data, 0)
+                continue
+            call(None, 0)
+            if isinstance(stats, dict):
+                stats["count_ms"] = stats.get("count_ms", 0.0) + st.kernel_ms
+            part = np.zeros(max(int(total.value), 1), _lib.PASS_DTYPE)
+            need = int(total.value)
+            call(part.ctypes.data, need)
+            if isinstance(stats, dict):
+                stats["fill_ms"] = stats.get("fill_ms", 0.0) + st.kernel_ms
+            part = part[:need]
+            part["point"] += a
+            res.append(part)
+        return np.concatenate(res) if mode == "list" else res
+
     @staticmethod
     def thermal_grid(spacing_s=3600.0, spinup_lunations=None, resets=None, F=None):
         """The MrtxThermalModel of the default regolith for epochs `spacing_s` apart: the layer
