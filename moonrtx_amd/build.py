@@ -5,7 +5,8 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(_HERE, "libmoonrt.so")
-SOURCES = ["mrtx_kernels.hip", "mrtx_terrain.hip", "mrtx_march.h", "mrtx_traverse.hip", "mrtx_relief.hip", "mrtx_regions.hip", "mrtx_regions.h", "mrtx_zonal.hip", "mrtx_zonal.h", "mrtx_proximity.hip", "mrtx_proximity.h", "mrtx_outline.hip", "mrtx_outline.h", "mrtx_contour.hip", "mrtx_contour.h", "mrtx_fill.hip", "mrtx_fill.h", "mrtx_bowls.hip", "mrtx_bowls.h", "mrtx_api.hip", "mrtx_device.h", os.path.join("..", "..", "include", "moonrt.h")]
+# every translation unit and header of csrc/ (the Makefile's own list of units is what gets built), and the public header
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [os.path.join("..", "..", "include", "moonrt.h")]
 
 
 def stale():

@@ -1,4 +1,7 @@
-// mrtx_api.hip -- host side of libmoonrt.so: the C ABI declared in include/moonrt.h.
+// mrtx_api.hip -- host side of libmoonrt.so: the C ABI declared in include/moonrt.h, but for the calls that work on a lattice
+// of nodes and its tables (regions, zonal statistics, proximity, outlines, contours, depressions, bowls), whose host side is
+// mrtx_lattice_api.hip.  What the two units share (the context, the refusal, the staging path) is declared in mrtx_host.h and
+// defined here.
 //
 // The context keeps the scene the way the reference describes it to its renderer object (float64
 // camera / moon frame / light / Sun disk, moon_renderer.py:570-650 and :824-871) and derives the
@@ -19,15 +22,9 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/moonrt.h"
-#include "mrtx_device.h"
-#include "mrtx_regions.h"
-#include "mrtx_zonal.h"
-#include "mrtx_proximity.h"
-#include "mrtx_outline.h"
-#include "mrtx_contour.h"
-#include "mrtx_fill.h"
-#include "mrtx_bowls.h"
+#include "mrtx_host.h"
+
+using namespace mrtx_host;
 
 hipError_t mrtx_launch_render(const FrameC& f, int S, bool stats, int mode, bool overlay, const PathQ* pq, hipStream_t st);
 uint64_t mrtx_path_chunks(const FrameC& f, int S, uint32_t* grid_a, int* njobs_log2);
@@ -80,95 +77,6 @@ hipError_t mrtx_launch_horizon_mask(const FrameC& f, HorizonMaskC q, hipStream_t
 hipError_t mrtx_launch_relief(const ReliefC& q, int tile, hipStream_t st);
 hipError_t mrtx_launch_relief_share(const ShareC& q, hipStream_t st);
 size_t mrtx_relief_tile_lds(int th, int tw, int ri, int rj);
-
-struct mrtx_ctx {
-    MrtxConfig cfg{};
-    MrtxParams prm{};
-    int tiles_x = 0, tiles_y = 0, n_tiles = 0, n_local = 0, slots = 0, tile_shift = 3;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    std::vector<hipEvent_t> evs;         // stage boundaries of a deferred-path call (3 per block)
-    // hand-over records of the deferred path stage (PathQ): 6 float arrays of 64 x chunks + one word per chunk
-    float* path_rec = nullptr; uint32_t* path_meta = nullptr; uint8_t* path_npaths = nullptr; uint64_t path_cap = 0;
-    uint32_t* path_ctr = nullptr;        // 8 x 16 work counters of path_kernel
-    unsigned long long* wd_host = nullptr;   // pinned: path_kernel's watchdog word
-    uint64_t path_budget_bytes = 64ull << 30;   // hand-over buffers: frames that need more are rendered in sub-parts (MOONRT_PATH_MAX_GB).  Sized for 288 GB of HBM:
-                                                // a 4K frame with every pixel on the Moon (34 GB) stays ONE part -- 38.9 ms against 39.2 in two parts of 24 GB
-    bool path_budget_env = false;               // the budget was given explicitly: take it as it is (else: at most half of the free memory)
-    int path_nsub = 4, path_grp_log2 = 3;   // measured at cfg3: (0,1) 37 ms, (1,1) 20.5, (1,4) 16.1, (2,4) 16.3, (3,4) 16.6
-    int path_waves[4] = {0, 0, 0, 0};    // persistent waves of path_kernel<stats, wide>, 0 = not asked yet
-    // launches with fewer samples than this keep their paths inside the render wave (same result, bit for bit): the three
-    // kernels + 5 120 persistent waves of the queue do not pay below ~8 M samples (4K: 1 spp 1.34 ms against 1.48, 2 spp 2.28 /
-    // 2.41, 4 spp 3.42 / 3.16; cfg1 0.33 / 0.53; tools/spp_sweep.py).  MOONRT_PATH_QUEUE_MIN overrides (0 = always the queue).
-    uint64_t path_queue_min = 8000000ull;
-    bool path_fallback_said = false;     // the fall-back to in-wave paths (no memory for the records) was reported
-    // overlapped path stage (MOONRT_PATH_OVERLAP = sub-parts, 0 = off): path_kernel + resolve of sub-part i run on stream2 beside
-    // render_kernel of sub-part i+1 (two sets of hand-over buffers, ping-pong); MOONRT_PATH_OVERLAP_WAVES sizes the persistent
-    // launch while it shares the chip (every path wave holds 96 VGPRs, a render wave 64)
-    int path_overlap = 0, path_overlap_waves = 2048;
-    int path_sets = 1;                   // buffer sets the allocations hold
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ov_done[2] = {nullptr, nullptr}, ov_join = nullptr;
-    uint64_t path_nomem_chunks = 0;      // a hand-over allocation of this many chunks failed: not retried until less is needed or mrtx_reset_accum
-    bool gather_hits = true;             // mrtx_set_gather_hits: the hit buffer travels with the radiance
-    bool path_alloc_fail_test = false;   // MOONRT_TEST_PATH_NOMEM=1: test hook, the hand-over allocation "fails"
-    int path_refill = 32, path_segmin = 16, path_hitmin = 16, path_waves_env = 0;   // cfg3 sweep: (8,24,16) 16.2 ms, (24,24,16) 14.7, (32,16,16) 14.5, (48,24,16) 21.5
-    float* accum = nullptr;
-    float* hits = nullptr;
-    void* scratch = nullptr;  // W*H*16 bytes, resolve target for read-back
-    // "Gamma" post-process tables (tone_table): 256 / 65536 thresholds for the gamma they were built for (0 = not built)
-    float* tone8_dev = nullptr; float tone8_gamma = 0.0f;
-    float* tone16_dev = nullptr; float tone16_gamma = 0.0f;
-    float* dem = nullptr; int dem_h = 0, dem_w = 0;   // padded (h+4) x (w+4) copy, always owned
-    float* hmip = nullptr; int hm_h = 0, hm_w = 0, hm_shift = 0;       // horizon mip: cells of 8 max-mip cells, dilated by one cell (see horizon_kend)
-    float* mip2 = nullptr; int m2_h = 0, m2_w = 0, m2_shift = 0;       // medium max-mip: cells a quarter of the max-mip's (path_kernel's step mask)
-    float* mip = nullptr; int mip_h = 0, mip_w = 0, mip_shift = 0;   // max-mip of it, cell 2^mip_shift texels (+ one-cell border)
-    uint8_t* color = nullptr; bool color_owned = false; int color_h = 0, color_w = 0;
-    uint8_t* bg = nullptr; int bg_h = 0, bg_w = 0;
-    uint32_t* overlay = nullptr;   // D12: frame-sized RGBA8 blended over the tone-mapped image, or null
-    unsigned long long* stats_dev = nullptr;
-    FrameCold* cold_dev = nullptr;
-    FrameCold cold_uploaded;             // what cold_dev holds (valid once cold_valid): re-uploaded only when it changes
-    bool cold_valid = false;
-    // D11 overlay capsules: host copy in scene coordinates; device copies relative to the Moon centre + tile bins
-    std::vector<float> caps_host;            // 12 floats per capsule
-    float* caps_dev = nullptr; int32_t* caps_off_dev = nullptr; int32_t* caps_idx_dev = nullptr;
-    size_t caps_dev_n = 0, caps_idx_cap = 0;
-    std::vector<int32_t> caps_off_host;      // per local tile, valid for caps_version
-    uint64_t caps_version = 0;               // scene_version the bins were built for
-    int32_t* tile_list_dev = nullptr;   // n_local entries
-    std::vector<int32_t> keep_uploaded;  // what tile_list_dev holds
-    std::vector<int32_t> keep_cached;    // cull result for scene_version == cull_version
-    uint64_t culled_px_cached = 0;
-    int keep_front_cached = 0;           // leading entries of keep_cached that can see the Moon / Sun / an overlay (the rest is sky)
-    uint64_t scene_version = 1, cull_version = 0;   // bumped by every setter that can change the cull
-    std::vector<uint8_t> tile_dirty;     // local tiles written since the buffers were last zeroed
-    // gather layout: with the sky cull in force only ACTIVE tiles travel (every rank derives every rank's list from the
-    // scene, which is identical on all ranks by contract); act_slots = the longest list, shorter ones are padded with -1
-    std::vector<std::vector<int32_t>> act_lists;
-    uint64_t act_version = 0;
-    bool act_on = false;
-    int act_slots = 0;
-    int32_t* act_dev = nullptr;          // world x act_slots, uploaded for act_uploaded_version
-    size_t act_dev_cap = 0;
-    uint64_t act_uploaded_version = 0;
-    std::vector<uint8_t> peer_written;   // root: global tiles of other ranks that hold unpacked data
-    int32_t* stale_dev = nullptr;
-    size_t stale_cap = 0;
-    uint32_t blocks_done = 0;
-    double eye[3] = {0, -300, 0}, target[3] = {0, 0, 0}, up[3] = {0, 0, 1}, vfov = 4.2421875;
-    double center[3] = {0, 0, 0}, radius = 10.0, u[3] = {0, 0, 1}, v[3] = {0, -1, 0};
-    double light_pos[3] = {0, -21460, 0}, light_radius = 100.0, light_radiance = 0.0;
-    double sun_pos[3] = {0, 3100, 0}, sun_radius = 0.0, sun_radiance = 2.0;
-    bool moon_set = false, light_set = false;   // mrtx_set_moon_frame / mrtx_set_light were called (the illumination stage needs both)
-    // Sun illumination stage (mrtx_illum_*): its OWN cold block, counters and buffers, so that it leaves the render state alone
-    FrameCold* illum_cold = nullptr;
-    unsigned long long* illum_stats = nullptr;   // ST_N counters
-    float* illum_tab = nullptr; size_t illum_tab_bytes = 0;    // sample table + (sin, cos) tables
-    float* illum_out = nullptr; size_t illum_out_bytes = 0;    // float4 per node when the caller gives no device buffer
-    float* trav_buf = nullptr; size_t trav_bytes = 0;         // mrtx_traverse: tile flags, and the outputs the caller wants on the host
-    std::string err;
-};
 
 // Host -> device copies that feed kernels of this context go through the context's OWN stream (hipStreamNonBlocking: the null
 // stream does not order it) and are waited for before the host buffer is released, so copy and consumer are ordered by the
@@ -225,25 +133,6 @@ void put_event(int dev, hipEvent_t ev) {
     if (pool_events() && dev >= 0 && dev < 16) { std::lock_guard<std::mutex> g(pool().mu); pool().events[dev].push_back(ev); }
     else (void)hipEventDestroy(ev);
 }
-
-int fail(mrtx_ctx* c, int code, const char* fmt, ...) {
-    if (c) {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        c->err = buf;
-    }
-    return code;
-}
-
-#define HIPCHK(c, call)                                                                       \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail((c), MRTX_E_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_));   \
-    } while (0)
 
 const double kPiD = 3.14159265358979323846;
 
@@ -544,6 +433,88 @@ int check_vec(const double* p) {
 }
 
 }  // namespace
+
+// ---- What the host units share (mrtx_host.h): defined here, used by mrtx_lattice_api.hip as well ---------------------------
+int mrtx_host::fail(mrtx_ctx* c, int code, const char* fmt, ...) {
+    if (c) {
+        char buf[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof buf, fmt, ap);
+        va_end(ap);
+        c->err = buf;
+    }
+    return code;
+}
+
+bool mrtx_host::spans_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return a && b && x < y + nb && y < x + na;
+}
+
+// grow one of the stage's device buffers to at least `bytes`
+int mrtx_host::stage_buffer(mrtx_ctx* c, float*& p, size_t& cap, size_t bytes) {
+    if (bytes > cap) {
+        if (p) { HIPCHK(c, hipFree(p)); p = nullptr; cap = 0; }
+        HIPCHK(c, hipMalloc((void**)&p, bytes));
+        cap = bytes;
+    }
+    return MRTX_OK;
+}
+
+// The launch's tables in one device block, c->illum_tab: each segment at an offset rounded up to 16 bytes (the float4 loads
+// of the epoch lights), copied straight from the caller's memory, which must stay put until stage_finish.  dev[i] = segment
+// i's device address.  Called after stage_out, so that every buffer is grown before the first copy is queued.
+int mrtx_host::stage_tables(mrtx_ctx* c, std::initializer_list<HostSeg> segs, float** dev) {
+    size_t words = 0;
+    for (const HostSeg& s : segs) words += (s.n + 3) & ~(size_t)3;
+    const int rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, std::max(words * 4, (size_t)16));
+    if (rc != MRTX_OK) return rc;
+    float* d = c->illum_tab;
+    for (const HostSeg& s : segs) {
+        if (s.n) HIPCHK(c, hipMemcpyAsync(d, s.p, s.n * 4, hipMemcpyHostToDevice, c->stream));
+        *dev++ = d;
+        d += (s.n + 3) & ~(size_t)3;
+    }
+    return MRTX_OK;
+}
+
+// where the launch writes: the caller's dev_out, or else c->illum_out grown to `bytes` (read back by stage_finish)
+int mrtx_host::stage_out(mrtx_ctx* c, void*& dev_out, size_t bytes) {
+    if (dev_out) return MRTX_OK;
+    const int rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, bytes);
+    dev_out = c->illum_out;
+    return rc;
+}
+
+// right before the launch: the cold block (if any) and zeroed counters (if asked) queued, then the start event
+int mrtx_host::stage_start(mrtx_ctx* c, const FrameCold* cold, bool zero) {
+    if (cold) HIPCHK(c, hipMemcpyAsync(c->illum_cold, cold, sizeof *cold, hipMemcpyHostToDevice, c->stream));
+    if (zero) HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    return MRTX_OK;
+}
+
+// right after the launch: the end event, wait, time, read back, counters (rays: reported as shadow_rays or bounce_rays)
+int mrtx_host::stage_finish(mrtx_ctx* c, const void* dev_out, float* host_out, size_t out_bytes, MrtxStats* out, StageRays rays) {
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));     // also: the pageable tables are no longer read
+    float ms = 0.0f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (host_out) HIPCHK(c, hipMemcpy(host_out, dev_out, out_bytes, hipMemcpyDeviceToHost));
+    if (out) {
+        std::memset(out, 0, sizeof *out);
+        out->kernel_ms = ms;
+        out->launches = 1;
+        if (rays != kNoRays) {
+            unsigned long long h[16];
+            HIPCHK(c, hipMemcpy(h, c->illum_stats, sizeof h, hipMemcpyDeviceToHost));
+            (rays == kBounceRays ? out->bounce_rays : out->shadow_rays) = h[rays];
+            out->height_samples = h[3]; out->dem_fetches = h[6]; out->mip_fetches = h[7];
+        }
+    }
+    return MRTX_OK;
+}
 
 extern "C" {
 
@@ -1249,7 +1220,7 @@ static void illum_sc(double deg, float* sc) {
     sc[1] = (float)std::cos(r);
 }
 
-// ---- What every terrain query shares: its tables, frame, staging, output and finish ---------------------------------------
+// ---- What every terrain query shares: its tables and frame (staging, output and finish: "What the host units share") --------
 // The band of a lat/lon map (MrtxIllumGrid, or MrtxSightGrid's targets) checked and as the stage's tables: rtab = the rows'
 // (sin lat, cos lat), ctab = the columns' (sin lon, cos lon).  The illumination grid's n_sun is checked among them.
 extern "C++" template <class G>
@@ -1290,16 +1261,6 @@ static int point_tables(mrtx_ctx* c, const double* latlon, int32_t n, std::vecto
     return MRTX_OK;
 }
 
-// grow one of the stage's device buffers to at least `bytes`
-static int stage_buffer(mrtx_ctx* c, float*& p, size_t& cap, size_t bytes) {
-    if (bytes > cap) {
-        if (p) { HIPCHK(c, hipFree(p)); p = nullptr; cap = 0; }
-        HIPCHK(c, hipMalloc((void**)&p, bytes));
-        cap = bytes;
-    }
-    return MRTX_OK;
-}
-
 // The frame of a terrain launch: the context's DEM and march parameters (and the horizon mip when the launch marches), the
 // stage's own cold block and counters.  sky: the single-epoch illumination calls, which also read the context's Moon frame
 // and light.  Called after every argument check.
@@ -1317,71 +1278,6 @@ static int stage_frame(mrtx_ctx* c, FrameC& f, FrameCold& cold, bool march, bool
     f.cold = c->illum_cold;
     if (c->prm.flags & MRTX_F_FORCE_WIDE) f.dem_wide = 1;
     if (c->prm.flags & MRTX_F_NO_SKIP) f.mip = nullptr;   // (build_frame leaves the horizon mip out as well)
-    return MRTX_OK;
-}
-
-// n 4-byte words (float or int32) of host memory for stage_tables
-struct HostSeg {
-    const void* p;
-    size_t n;
-    HostSeg(const void* p_, size_t n_) : p(p_), n(n_) {}
-    HostSeg(const std::vector<float>& v) : p(v.data()), n(v.size()) {}
-};
-
-// The launch's tables in one device block, c->illum_tab: each segment at an offset rounded up to 16 bytes (the float4 loads
-// of the epoch lights), copied straight from the caller's memory, which must stay put until stage_finish.  dev[i] = segment
-// i's device address.  Called after stage_out, so that every buffer is grown before the first copy is queued.
-static int stage_tables(mrtx_ctx* c, std::initializer_list<HostSeg> segs, float** dev) {
-    size_t words = 0;
-    for (const HostSeg& s : segs) words += (s.n + 3) & ~(size_t)3;
-    const int rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, std::max(words * 4, (size_t)16));
-    if (rc != MRTX_OK) return rc;
-    float* d = c->illum_tab;
-    for (const HostSeg& s : segs) {
-        if (s.n) HIPCHK(c, hipMemcpyAsync(d, s.p, s.n * 4, hipMemcpyHostToDevice, c->stream));
-        *dev++ = d;
-        d += (s.n + 3) & ~(size_t)3;
-    }
-    return MRTX_OK;
-}
-
-// where the launch writes: the caller's dev_out, or else c->illum_out grown to `bytes` (read back by stage_finish)
-static int stage_out(mrtx_ctx* c, void*& dev_out, size_t bytes) {
-    if (dev_out) return MRTX_OK;
-    const int rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, bytes);
-    dev_out = c->illum_out;
-    return rc;
-}
-
-// right before the launch: the cold block (if any) and zeroed counters (if asked) queued, then the start event
-static int stage_start(mrtx_ctx* c, const FrameCold* cold, bool zero) {
-    if (cold) HIPCHK(c, hipMemcpyAsync(c->illum_cold, cold, sizeof *cold, hipMemcpyHostToDevice, c->stream));
-    if (zero) HIPCHK(c, hipMemsetAsync(c->illum_stats, 0, 16 * sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    return MRTX_OK;
-}
-
-// the counter slot of a launch's rays (mrtx_march.h's ST_SHADOW, ST_BOUNCE), or none when it did not count
-enum StageRays { kNoRays = -1, kShadowRays = 2, kBounceRays = 8 };
-
-// right after the launch: the end event, wait, time, read back, counters (rays: reported as shadow_rays or bounce_rays)
-static int stage_finish(mrtx_ctx* c, const void* dev_out, float* host_out, size_t out_bytes, MrtxStats* out, StageRays rays) {
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));     // also: the pageable tables are no longer read
-    float ms = 0.0f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    if (host_out) HIPCHK(c, hipMemcpy(host_out, dev_out, out_bytes, hipMemcpyDeviceToHost));
-    if (out) {
-        std::memset(out, 0, sizeof *out);
-        out->kernel_ms = ms;
-        out->launches = 1;
-        if (rays != kNoRays) {
-            unsigned long long h[16];
-            HIPCHK(c, hipMemcpy(h, c->illum_stats, sizeof h, hipMemcpyDeviceToHost));
-            (rays == kBounceRays ? out->bounce_rays : out->shadow_rays) = h[rays];
-            out->height_samples = h[3]; out->dem_fetches = h[6]; out->mip_fetches = h[7];
-        }
-    }
     return MRTX_OK;
 }
 
@@ -2119,10 +2015,6 @@ int mrtx_traverse_lengths(const MrtxTraverse* t, int32_t dem_h, int32_t dem_w, f
 
 // The caller's device tables: the costs are read and written as 64-bit atomics (8-byte aligned), the penalties as floats
 // (4-byte aligned); no two of them may overlap (the kernels read the penalties while they write costs and codes)
-static bool traverse_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return a && b && x < y + nb && y < x + na;
-}
 static int traverse_dev_buffers(mrtx_ctx* c, const MrtxTraverse* t, const void* dev_penalty, const void* dev_cost,
                                 const void* dev_pred) {
     const size_t N = (size_t)t->rows * (size_t)t->cols;
@@ -2130,8 +2022,8 @@ static int traverse_dev_buffers(mrtx_ctx* c, const MrtxTraverse* t, const void* 
         return fail(c, MRTX_E_INVALID, "dev_cost must be 8-byte aligned (float64, read and written atomically)");
     if (dev_penalty && (reinterpret_cast<uintptr_t>(dev_penalty) & 3))
         return fail(c, MRTX_E_INVALID, "dev_penalty must be 4-byte aligned (float32)");
-    if (traverse_overlap(dev_cost, 8 * N, dev_pred, N) || traverse_overlap(dev_penalty, 4 * N, dev_cost, 8 * N) ||
-        traverse_overlap(dev_penalty, 4 * N, dev_pred, N))
+    if (spans_overlap(dev_cost, 8 * N, dev_pred, N) || spans_overlap(dev_penalty, 4 * N, dev_cost, 8 * N) ||
+        spans_overlap(dev_penalty, 4 * N, dev_pred, N))
         return fail(c, MRTX_E_INVALID, "dev_penalty, dev_cost and dev_pred must not overlap");
     return MRTX_OK;
 }
@@ -2349,8 +2241,8 @@ int mrtx_traverse_timed(mrtx_ctx* c, const MrtxTraverse* t, const MrtxTraverseTi
     const size_t N = (size_t)t->rows * (size_t)t->cols;
     const size_t W64 = table ? ((size_t)tt->n_epochs + 63) / 64 : 0;
     if (dev_avail && (reinterpret_cast<uintptr_t>(dev_avail) & 7)) return fail(c, MRTX_E_INVALID, "dev_avail must be 8-byte aligned");
-    if (traverse_overlap(dev_avail, 8 * N * W64, dev_arrival, 8 * N) || traverse_overlap(dev_avail, 8 * N * W64, dev_pred, N) ||
-        traverse_overlap(dev_avail, 8 * N * W64, dev_penalty, 4 * N))
+    if (spans_overlap(dev_avail, 8 * N * W64, dev_arrival, 8 * N) || spans_overlap(dev_avail, 8 * N * W64, dev_pred, N) ||
+        spans_overlap(dev_avail, 8 * N * W64, dev_penalty, 4 * N))
         return fail(c, MRTX_E_INVALID, "dev_avail must not overlap dev_penalty, dev_arrival or dev_pred");
     // a start tick lies inside the table; without one it leaves room for 2^31 edges of 2^31 ticks below UINT64_MAX
     const uint64_t tick_end = table ? (uint64_t)tt->n_epochs * (uint64_t)tt->ticks_per_epoch : (uint64_t)1 << 62;
@@ -2507,7 +2399,7 @@ int mrtx_relief_share(mrtx_ctx* c, const MrtxReliefShare* s, const void* dev_rel
     if (dev_relief && (reinterpret_cast<uintptr_t>(dev_relief) & 15)) return fail(c, MRTX_E_INVALID, "dev_relief must be 16-byte aligned (float4)");
     if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 3)) return fail(c, MRTX_E_INVALID, "dev_out must be 4-byte aligned (float32)");
     const size_t N = (size_t)s->rows * (size_t)s->cols;
-    if (traverse_overlap(dev_relief, 16 * N, dev_out, 4 * N)) return fail(c, MRTX_E_INVALID, "dev_relief and dev_out must not overlap");
+    if (spans_overlap(dev_relief, 16 * N, dev_out, 4 * N)) return fail(c, MRTX_E_INVALID, "dev_relief and dev_out must not overlap");
     // ---- device work from here
     HIPCHK(c, hipSetDevice(c->cfg.device));
     int rc;
@@ -2526,1102 +2418,6 @@ int mrtx_relief_share(mrtx_ctx* c, const MrtxReliefShare* s, const void* dev_rel
     HIPCHK(c, mrtx_launch_relief_share(q, c->stream));
     if ((rc = stage_finish(c, dev_out, host_out, 4 * N, out, kNoRays)) != MRTX_OK) return rc;
     if (out) out->launches = 3;
-    return MRTX_OK;
-}
-
-// ---- Connected regions of a per-node map ----------------------------------------------------------
-static_assert(sizeof(MrtxRegion) == 56 && sizeof(RegionRec) == sizeof(MrtxRegion), "MrtxRegion is 56 bytes");
-
-// the checks of a lattice that both calls share
-static int regions_lattice(mrtx_ctx* c, int32_t rows, int32_t cols, int32_t wrap) {
-    if (rows < 1 || cols < 1) return fail(c, MRTX_E_INVALID, "empty lattice (%d x %d)", rows, cols);
-    if ((int64_t)rows * (int64_t)cols > (int64_t)1 << 31)
-        return fail(c, MRTX_E_INVALID, "a lattice holds at most 2^31 nodes (got %d x %d)", rows, cols);
-    if (wrap != 0 && wrap != 1) return fail(c, MRTX_E_INVALID, "wrap must be 0 or 1 (got %d)", wrap);
-    if (wrap && cols < 3) return fail(c, MRTX_E_INVALID, "a wrapped lattice needs cols >= 3 (got %d)", cols);
-    return MRTX_OK;
-}
-
-int mrtx_regions_label(mrtx_ctx* c, const MrtxRegions* r, const void* dev_field, const float* host_field, const void* dev_mask,
-                       const uint8_t* host_mask, void* dev_labels, int32_t* host_labels, uint32_t* n_regions, MrtxStats* out) {
-    if (!c) return MRTX_E_INVALID;
-    if (!r) return fail(c, MRTX_E_INVALID, "null regions block");
-    if (r->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
-    int rc = regions_lattice(c, r->rows, r->cols, r->wrap);
-    if (rc != MRTX_OK) return rc;
-    if (r->connectivity != 4 && r->connectivity != 8) return fail(c, MRTX_E_INVALID, "connectivity must be 4 or 8 (got %d)", r->connectivity);
-    const bool has_field = dev_field || host_field, has_mask = dev_mask || host_mask;
-    if (has_field == has_mask) return fail(c, MRTX_E_INVALID, "give exactly one of a field and a mask");
-    if (dev_field && host_field) return fail(c, MRTX_E_INVALID, "give exactly one of dev_field and host_field");
-    if (dev_mask && host_mask) return fail(c, MRTX_E_INVALID, "give exactly one of dev_mask and host_mask");
-    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
-    if (!n_regions) return fail(c, MRTX_E_INVALID, "null n_regions");
-    if (has_field) {
-        if (r->n_ch < 1 || r->n_ch > 16) return fail(c, MRTX_E_INVALID, "n_ch must lie in 1 .. 16 (got %d)", r->n_ch);
-        if (r->ch < 0 || r->ch >= r->n_ch) return fail(c, MRTX_E_INVALID, "ch must lie in 0 .. n_ch - 1 (got %d of %d)", r->ch, r->n_ch);
-        if (std::isnan(r->lo) || std::isnan(r->hi)) return fail(c, MRTX_E_INVALID, "lo and hi must not be NaN");
-        if (r->lo > r->hi) return fail(c, MRTX_E_INVALID, "lo must be <= hi (got %g > %g)", r->lo, r->hi);
-    }
-    if (dev_field && (reinterpret_cast<uintptr_t>(dev_field) & 3)) return fail(c, MRTX_E_INVALID, "dev_field must be 4-byte aligned (float32)");
-    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
-    const size_t N = (size_t)r->rows * (size_t)r->cols;
-    const size_t in_bytes = has_field ? 4 * N * (size_t)r->n_ch : N;
-    if (traverse_overlap(dev_field ? dev_field : dev_mask, in_bytes, dev_labels, 4 * N))
-        return fail(c, MRTX_E_INVALID, "the device input and dev_labels must not overlap");
-    // ---- device work from here
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    RegionsC q;
-    std::memset(&q, 0, sizeof q);
-    q.n_chunks = (uint32_t)((N + MRTX_RG_CHUNK - 1) / MRTX_RG_CHUNK);
-    q.tiles_x = (r->cols + MRTX_RG_TW - 1) / MRTX_RG_TW;
-    // scratch: the forest, the chunks' counts, K
-    const size_t sums_at = 4 * N, total_at = sums_at + 4 * (size_t)q.n_chunks;
-    if ((rc = stage_out(c, dev_labels, 4 * N)) != MRTX_OK ||
-        (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, total_at + 16)) != MRTX_OK)
-        return rc;
-    if (host_field || host_mask) {      // the caller's memory stays put until stage_finish
-        if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, std::max(in_bytes, (size_t)16))) != MRTX_OK) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->illum_tab, host_field ? (const void*)host_field : (const void*)host_mask, in_bytes,
-                                 hipMemcpyHostToDevice, c->stream));
-    }
-    char* tb = reinterpret_cast<char*>(c->trav_buf);
-    if (has_field) q.field = host_field ? c->illum_tab : static_cast<const float*>(dev_field);
-    else q.mask = host_mask ? reinterpret_cast<const uint8_t*>(c->illum_tab) : static_cast<const uint8_t*>(dev_mask);
-    q.parent = reinterpret_cast<int32_t*>(tb);
-    q.sums = reinterpret_cast<uint32_t*>(tb + sums_at);
-    q.total = reinterpret_cast<uint32_t*>(tb + total_at);
-    q.labels = static_cast<int32_t*>(dev_labels);
-    q.rows = r->rows; q.cols = r->cols; q.wrap = r->wrap; q.conn8 = r->connectivity == 8; q.n_ch = r->n_ch; q.ch = r->ch;
-    q.lo = (float)r->lo; q.hi = (float)r->hi;
-    uint32_t launches = 0, K = 0;
-    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
-    HIPCHK(c, mrtx_launch_regions_label(q, c->stream, &launches));
-    if ((rc = stage_finish(c, dev_labels, reinterpret_cast<float*>(host_labels), 4 * N, out, kNoRays)) != MRTX_OK) return rc;
-    HIPCHK(c, hipMemcpy(&K, q.total, sizeof K, hipMemcpyDeviceToHost));
-    *n_regions = K;
-    if (out) out->launches = launches;
-    return MRTX_OK;
-}
-
-int mrtx_regions_stats(mrtx_ctx* c, int32_t rows, int32_t cols, int32_t wrap, const void* dev_labels, const int32_t* host_labels,
-                       uint32_t n_regions, const uint32_t* row_weight, void* dev_out, MrtxRegion* host_out, MrtxStats* out) {
-    if (!c) return MRTX_E_INVALID;
-    int rc = regions_lattice(c, rows, cols, wrap);
-    if (rc != MRTX_OK) return rc;
-    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
-    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
-    const size_t N = (size_t)rows * (size_t)cols;
-    if ((size_t)n_regions > N) return fail(c, MRTX_E_INVALID, "n_regions = %u exceeds the lattice's %zu nodes", n_regions, N);
-    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
-    if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 7)) return fail(c, MRTX_E_INVALID, "dev_out must be 8-byte aligned (MrtxRegion)");
-    const size_t out_bytes = sizeof(MrtxRegion) * (size_t)n_regions;
-    if (traverse_overlap(dev_labels, 4 * N, dev_out, out_bytes)) return fail(c, MRTX_E_INVALID, "dev_labels and dev_out must not overlap");
-    // MOONRT_REGIONS_CATALOGUE=plain: one set of atomics per node, the yardstick of the in-wave run reduction; the same records
-    bool runs = true;
-    if (const char* e = std::getenv("MOONRT_REGIONS_CATALOGUE")) {
-        if (std::strcmp(e, "plain") == 0) runs = false;
-        else if (std::strcmp(e, "runs") != 0) return fail(c, MRTX_E_INVALID, "MOONRT_REGIONS_CATALOGUE must be runs or plain (got %s)", e);
-    }
-    // ---- device work from here
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    float* d[2] = {nullptr, nullptr};
-    if ((rc = stage_out(c, dev_out, std::max(out_bytes, sizeof(MrtxRegion)))) != MRTX_OK ||
-        (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, 16)) != MRTX_OK ||
-        (rc = stage_tables(c, {{host_labels, host_labels ? N : 0}, {row_weight, row_weight ? (size_t)rows : 0}}, d)) != MRTX_OK)
-        return rc;
-    RegionStatsC q;
-    std::memset(&q, 0, sizeof q);
-    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_labels);
-    q.row_weight = row_weight ? reinterpret_cast<const uint32_t*>(d[1]) : nullptr;
-    q.out = static_cast<RegionRec*>(dev_out);
-    q.bad = reinterpret_cast<uint32_t*>(c->trav_buf);
-    q.rows = rows; q.cols = cols; q.wrap = wrap; q.n_regions = n_regions;
-    uint32_t launches = 0, bad = 0;
-    HIPCHK(c, hipMemsetAsync(q.bad, 0, 16, c->stream));
-    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
-    HIPCHK(c, mrtx_launch_regions_stats(q, runs, c->stream, &launches));
-    if ((rc = stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays)) != MRTX_OK) return rc;
-    if (out) out->launches = launches;
-    HIPCHK(c, hipMemcpy(&bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));
-    if (bad) return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", bad, (long long)n_regions - 1);
-    return MRTX_OK;
-}
-
-// ---- Zonal statistics and outlines of labelled regions -------------------------------------------
-static_assert(sizeof(MrtxZonal) == 56 && sizeof(ZonalRec) == sizeof(MrtxZonal), "MrtxZonal is 56 bytes");
-static_assert(sizeof(MrtxRegionShape) == 32 && sizeof(ShapeRec) == sizeof(MrtxRegionShape), "MrtxRegionShape is 32 bytes");
-
-// MOONRT_REGIONS_ZONAL=plain: one set of atomics per node, the yardstick of the in-wave run reduction; the same records
-static int zonal_variant(mrtx_ctx* c, bool* runs) {
-    *runs = true;
-    if (const char* e = std::getenv("MOONRT_REGIONS_ZONAL")) {
-        if (std::strcmp(e, "plain") == 0) *runs = false;
-        else if (std::strcmp(e, "runs") != 0) return fail(c, MRTX_E_INVALID, "MOONRT_REGIONS_ZONAL must be runs or plain (got %s)", e);
-    }
-    return MRTX_OK;
-}
-
-int mrtx_regions_zonal(mrtx_ctx* c, const MrtxZonalSpec* z, const void* dev_labels, const int32_t* host_labels, uint32_t n_regions,
-                       const void* dev_field, const float* host_field, const uint32_t* row_weight, void* dev_out,
-                       MrtxZonal* host_out, void* dev_hist, uint64_t* host_hist, MrtxStats* out) {
-    if (!c) return MRTX_E_INVALID;
-    if (!z) return fail(c, MRTX_E_INVALID, "null zonal block");
-    if (z->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
-    int rc = regions_lattice(c, z->rows, z->cols, z->wrap);
-    if (rc != MRTX_OK) return rc;
-    if (z->n_ch < 1 || z->n_ch > 16) return fail(c, MRTX_E_INVALID, "n_ch must lie in 1 .. 16 (got %d)", z->n_ch);
-    if (!std::isfinite(z->scale) || !(z->scale > 0.0)) return fail(c, MRTX_E_INVALID, "scale must be finite and > 0 (got %g)", z->scale);
-    if (z->n_bins < 0 || z->n_bins > 4096) return fail(c, MRTX_E_INVALID, "n_bins must lie in 0 .. 4096 (got %d)", z->n_bins);
-    if (z->n_bins) {
-        if (z->hist_ch < 0 || z->hist_ch >= z->n_ch)
-            return fail(c, MRTX_E_INVALID, "hist_ch must lie in 0 .. n_ch - 1 (got %d of %d)", z->hist_ch, z->n_ch);
-        if (!std::isfinite(z->hist_lo) || !std::isfinite(z->hist_inv_w) || !(z->hist_inv_w > 0.0))
-            return fail(c, MRTX_E_INVALID, "hist_lo must be finite and hist_inv_w finite and > 0 (got %g, %g)", z->hist_lo, z->hist_inv_w);
-    }
-    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
-    if ((dev_field == nullptr) == (host_field == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_field and host_field");
-    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
-    if (z->n_bins == 0 && (dev_hist || host_hist)) return fail(c, MRTX_E_INVALID, "without bins dev_hist and host_hist must be NULL");
-    if (z->n_bins && (dev_hist == nullptr) == (host_hist == nullptr))
-        return fail(c, MRTX_E_INVALID, "give exactly one of dev_hist and host_hist");
-    const size_t N = (size_t)z->rows * (size_t)z->cols;
-    if ((size_t)n_regions > N) return fail(c, MRTX_E_INVALID, "n_regions = %u exceeds the lattice's %zu nodes", n_regions, N);
-    const size_t H = z->n_bins ? (size_t)n_regions * (size_t)(z->n_bins + 2) : 0;
-    if (H > ((size_t)1 << 28))
-        return fail(c, MRTX_E_INVALID, "a histogram holds at most 2^28 columns (got %u x %d)", n_regions, z->n_bins + 2);
-    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
-    if (dev_field && (reinterpret_cast<uintptr_t>(dev_field) & 3)) return fail(c, MRTX_E_INVALID, "dev_field must be 4-byte aligned (float32)");
-    if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 7)) return fail(c, MRTX_E_INVALID, "dev_out must be 8-byte aligned (MrtxZonal)");
-    if (dev_hist && (reinterpret_cast<uintptr_t>(dev_hist) & 7)) return fail(c, MRTX_E_INVALID, "dev_hist must be 8-byte aligned (uint64)");
-    const size_t R = (size_t)n_regions * (size_t)z->n_ch;
-    const size_t out_bytes = sizeof(MrtxZonal) * R, field_bytes = 4 * N * (size_t)z->n_ch, hist_bytes = 8 * H;
-    if (traverse_overlap(dev_labels, 4 * N, dev_out, out_bytes) || traverse_overlap(dev_field, field_bytes, dev_out, out_bytes) ||
-        traverse_overlap(dev_labels, 4 * N, dev_hist, hist_bytes) || traverse_overlap(dev_field, field_bytes, dev_hist, hist_bytes) ||
-        traverse_overlap(dev_out, out_bytes, dev_hist, hist_bytes))
-        return fail(c, MRTX_E_INVALID, "the device inputs, dev_out and dev_hist must not overlap");
-    bool runs;
-    if ((rc = zonal_variant(c, &runs)) != MRTX_OK) return rc;
-    // ---- device work from here
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    // scratch: the count of bad entries, the packed extremes, and the histogram when it goes to the host
-    const size_t keys_at = 16, hist_at = keys_at + 16 * R;
-    float* d[3] = {nullptr, nullptr, nullptr};
-    if ((rc = stage_out(c, dev_out, std::max(out_bytes, sizeof(MrtxZonal)))) != MRTX_OK ||
-        (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, hist_at + (host_hist ? hist_bytes : 0) + 16)) != MRTX_OK ||
-        (rc = stage_tables(c, {{host_labels, host_labels ? N : 0}, {row_weight, row_weight ? (size_t)z->rows : 0},
-                               {host_field, host_field ? N * (size_t)z->n_ch : 0}}, d)) != MRTX_OK)
-        return rc;
-    char* tb = reinterpret_cast<char*>(c->trav_buf);
-    ZonalC q;
-    std::memset(&q, 0, sizeof q);
-    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_labels);
-    q.row_weight = row_weight ? reinterpret_cast<const uint32_t*>(d[1]) : nullptr;
-    q.field = host_field ? d[2] : static_cast<const float*>(dev_field);
-    q.out = static_cast<ZonalRec*>(dev_out);
-    q.bad = reinterpret_cast<uint32_t*>(tb);
-    q.keys = reinterpret_cast<unsigned long long*>(tb + keys_at);
-    q.hist = !z->n_bins ? nullptr : host_hist ? reinterpret_cast<unsigned long long*>(tb + hist_at) : static_cast<unsigned long long*>(dev_hist);
-    q.scale = z->scale; q.hist_lo = z->hist_lo; q.hist_inv_w = z->hist_inv_w;
-    q.rows = z->rows; q.cols = z->cols; q.n_ch = z->n_ch; q.hist_ch = z->hist_ch; q.n_bins = z->n_bins; q.n_regions = n_regions;
-    uint32_t launches = 0, bad = 0;
-    HIPCHK(c, hipMemsetAsync(q.bad, 0, 16, c->stream));
-    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
-    HIPCHK(c, mrtx_launch_regions_zonal(q, runs, c->stream, &launches));
-    if ((rc = stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays)) != MRTX_OK) return rc;
-    if (out) out->launches = launches;
-    if (host_hist && hist_bytes) HIPCHK(c, hipMemcpy(host_hist, q.hist, hist_bytes, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(&bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));
-    if (bad) return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", bad, (long long)n_regions - 1);
-    return MRTX_OK;
-}
-
-int mrtx_regions_shape(mrtx_ctx* c, int32_t rows, int32_t cols, int32_t wrap, int32_t connectivity, const void* dev_labels,
-                       const int32_t* host_labels, uint32_t n_regions, const uint32_t* side_ew, const uint32_t* side_ns, void* dev_out,
-                       MrtxRegionShape* host_out, MrtxStats* out) {
-    if (!c) return MRTX_E_INVALID;
-    int rc = regions_lattice(c, rows, cols, wrap);
-    if (rc != MRTX_OK) return rc;
-    if (connectivity != 4 && connectivity != 8) return fail(c, MRTX_E_INVALID, "connectivity must be 4 or 8 (got %d)", connectivity);
-    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
-    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
-    if ((side_ew == nullptr) != (side_ns == nullptr)) return fail(c, MRTX_E_INVALID, "give both of side_ew and side_ns or neither");
-    const size_t N = (size_t)rows * (size_t)cols;
-    if ((size_t)n_regions > N) return fail(c, MRTX_E_INVALID, "n_regions = %u exceeds the lattice's %zu nodes", n_regions, N);
-    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
-    if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 7)) return fail(c, MRTX_E_INVALID, "dev_out must be 8-byte aligned (MrtxRegionShape)");
-    const size_t out_bytes = sizeof(MrtxRegionShape) * (size_t)n_regions;
-    if (traverse_overlap(dev_labels, 4 * N, dev_out, out_bytes)) return fail(c, MRTX_E_INVALID, "dev_labels and dev_out must not overlap");
-    bool runs;
-    if ((rc = zonal_variant(c, &runs)) != MRTX_OK) return rc;
-    // ---- device work from here
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    float* d[3] = {nullptr, nullptr, nullptr};
-    if ((rc = stage_out(c, dev_out, std::max(out_bytes, sizeof(MrtxRegionShape)))) != MRTX_OK ||
-        (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, 16)) != MRTX_OK ||
-        (rc = stage_tables(c, {{host_labels, host_labels ? N : 0}, {side_ew, side_ew ? (size_t)rows : 0},
-                               {side_ns, side_ns ? (size_t)rows + 1 : 0}}, d)) != MRTX_OK)
-        return rc;
-    ShapeC q;
-    std::memset(&q, 0, sizeof q);
-    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_labels);
-    q.side_ew = side_ew ? reinterpret_cast<const uint32_t*>(d[1]) : nullptr;
-    q.side_ns = side_ns ? reinterpret_cast<const uint32_t*>(d[2]) : nullptr;
-    q.out = static_cast<ShapeRec*>(dev_out);
-    q.bad = reinterpret_cast<uint32_t*>(c->trav_buf);
-    q.rows = rows; q.cols = cols; q.wrap = wrap; q.conn8 = connectivity == 8; q.n_regions = n_regions;
-    uint32_t launches = 0, bad = 0;
-    HIPCHK(c, hipMemsetAsync(q.bad, 0, 16, c->stream));
-    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
-    HIPCHK(c, mrtx_launch_regions_shape(q, runs, c->stream, &launches));
-    if ((rc = stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays)) != MRTX_OK) return rc;
-    if (out) out->launches = launches;
-    HIPCHK(c, hipMemcpy(&bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));
-    if (bad) return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", bad, (long long)n_regions - 1);
-    return MRTX_OK;
-}
-
-// ---- Proximity maps and the reach of labelled regions ---------------------------------------------
-static_assert(sizeof(MrtxRegionReach) == 32 && sizeof(ReachRec) == sizeof(MrtxRegionReach), "MrtxRegionReach is 32 bytes");
-static_assert(sizeof(MrtxProximity) == 16 && sizeof(ProxBox) == 32 && sizeof(ProxFeat) == 16, "the proximity blocks");
-
-int mrtx_proximity(mrtx_ctx* c, const MrtxProximity* p, const void* dev_pos, const int32_t* host_pos, const void* dev_labels,
-                   const int32_t* host_labels, void* dev_nearest, int32_t* host_nearest, void* dev_dist2, uint64_t* host_dist2,
-                   uint64_t* pairs, MrtxStats* out) {
-    if (!c) return MRTX_E_INVALID;
-    if (!p) return fail(c, MRTX_E_INVALID, "null proximity block");
-    if (p->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
-    int rc = regions_lattice(c, p->rows, p->cols, 0);
-    if (rc != MRTX_OK) return rc;
-    if (p->mode != MRTX_PROX_TO_SET && p->mode != MRTX_PROX_TO_OUTSIDE)
-        return fail(c, MRTX_E_INVALID, "mode must be MRTX_PROX_TO_SET or MRTX_PROX_TO_OUTSIDE (got %d)", p->mode);
-    if ((dev_pos == nullptr) == (host_pos == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_pos and host_pos");
-    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
-    if ((dev_nearest == nullptr) == (host_nearest == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_nearest and host_nearest");
-    if ((dev_dist2 == nullptr) == (host_dist2 == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_dist2 and host_dist2");
-    if (dev_pos && (reinterpret_cast<uintptr_t>(dev_pos) & 3)) return fail(c, MRTX_E_INVALID, "dev_pos must be 4-byte aligned (int32)");
-    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
-    if (dev_nearest && (reinterpret_cast<uintptr_t>(dev_nearest) & 3)) return fail(c, MRTX_E_INVALID, "dev_nearest must be 4-byte aligned (int32)");
-    if (dev_dist2 && (reinterpret_cast<uintptr_t>(dev_dist2) & 7)) return fail(c, MRTX_E_INVALID, "dev_dist2 must be 8-byte aligned (uint64)");
-    const size_t N = (size_t)p->rows * (size_t)p->cols;
-    if (traverse_overlap(dev_pos, 12 * N, dev_labels, 4 * N) || traverse_overlap(dev_pos, 12 * N, dev_nearest, 4 * N) ||
-        traverse_overlap(dev_pos, 12 * N, dev_dist2, 8 * N) || traverse_overlap(dev_labels, 4 * N, dev_nearest, 4 * N) ||
-        traverse_overlap(dev_labels, 4 * N, dev_dist2, 8 * N) || traverse_overlap(dev_nearest, 4 * N, dev_dist2, 8 * N))
-        return fail(c, MRTX_E_INVALID, "dev_pos, dev_labels, dev_nearest and dev_dist2 must not overlap");
-    // MOONRT_PROXIMITY=brute: every tile's features against every node, the yardstick of the pruned scan; the same bytes
-    bool prune = true;
-    if (const char* e = std::getenv("MOONRT_PROXIMITY")) {
-        if (std::strcmp(e, "brute") == 0) prune = false;
-        else if (std::strcmp(e, "prune") != 0) return fail(c, MRTX_E_INVALID, "MOONRT_PROXIMITY must be prune or brute (got %s)", e);
-    }
-    // a host table is refused at its first bad coordinate (a device table's are counted by the tile kernel)
-    if (host_pos)
-        for (size_t n = 0; n < 3 * N; n++)
-            if (host_pos[n] < -MRTX_PX_CMAX || host_pos[n] > MRTX_PX_CMAX)
-                return fail(c, MRTX_E_INVALID, "coordinate %zu of node %zu must lie in -2^29 .. 2^29 (got %d)", n % 3, n / 3, host_pos[n]);
-    // ---- device work from here
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    // scratch: the counters, the tiles' boxes and feature lists, and the outputs the caller wants on the host
-    const ProxLayout at = prox_layout(p->rows, p->cols, host_nearest != nullptr, host_dist2 != nullptr);
-    float* d[2] = {nullptr, nullptr};
-    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, at.end)) != MRTX_OK ||
-        (rc = stage_tables(c, {{host_pos, host_pos ? 3 * N : 0}, {host_labels, host_labels ? N : 0}}, d)) != MRTX_OK)
-        return rc;
-    char* tb = reinterpret_cast<char*>(c->trav_buf);
-    ProxC q;
-    std::memset(&q, 0, sizeof q);
-    q.pos = host_pos ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_pos);
-    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[1]) : static_cast<const int32_t*>(dev_labels);
-    q.nearest = host_nearest ? reinterpret_cast<int32_t*>(tb + at.near_at) : static_cast<int32_t*>(dev_nearest);
-    q.dist2 = host_dist2 ? reinterpret_cast<unsigned long long*>(tb + at.d2_at) : static_cast<unsigned long long*>(dev_dist2);
-    q.pairs = reinterpret_cast<unsigned long long*>(tb);
-    q.bad = reinterpret_cast<uint32_t*>(tb + 8);
-    q.box = reinterpret_cast<ProxBox*>(tb + at.box_at);
-    q.feat = reinterpret_cast<ProxFeat*>(tb + at.feat_at);
-    q.rows = p->rows; q.cols = p->cols; q.outside = p->mode == MRTX_PROX_TO_OUTSIDE; q.tiles_x = at.tiles_x; q.tiles_y = at.tiles_y;
-    uint32_t launches = 0;
-    unsigned long long head[2] = {0, 0};                    // pairs, bad
-    HIPCHK(c, hipMemsetAsync(tb, 0, 32, c->stream));
-    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
-    HIPCHK(c, mrtx_launch_proximity(q, prune, c->stream, &launches));
-    if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
-    if (out) out->launches = launches;
-    HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
-    if ((uint32_t)head[1])
-        return fail(c, MRTX_E_INVALID, "%u coordinates of the device position table lie outside -2^29 .. 2^29", (uint32_t)head[1]);
-    if (host_nearest) HIPCHK(c, hipMemcpy(host_nearest, q.nearest, 4 * N, hipMemcpyDeviceToHost));
-    if (host_dist2) HIPCHK(c, hipMemcpy(host_dist2, q.dist2, 8 * N, hipMemcpyDeviceToHost));
-    if (pairs) *pairs = head[0];
-    return MRTX_OK;
-}
-
-int mrtx_regions_reach(mrtx_ctx* c, int32_t rows, int32_t cols, const void* dev_labels, const int32_t* host_labels, uint32_t n_regions,
-                       const void* dev_dist2, const uint64_t* host_dist2, const void* dev_nearest, const int32_t* host_nearest,
-                       void* dev_out, MrtxRegionReach* host_out, MrtxStats* out) {
-    if (!c) return MRTX_E_INVALID;
-    int rc = regions_lattice(c, rows, cols, 0);
-    if (rc != MRTX_OK) return rc;
-    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
-    if ((dev_dist2 == nullptr) == (host_dist2 == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_dist2 and host_dist2");
-    if ((dev_nearest == nullptr) == (host_nearest == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_nearest and host_nearest");
-    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
-    const size_t N = (size_t)rows * (size_t)cols;
-    if ((size_t)n_regions > N) return fail(c, MRTX_E_INVALID, "n_regions = %u exceeds the lattice's %zu nodes", n_regions, N);
-    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
-    if (dev_dist2 && (reinterpret_cast<uintptr_t>(dev_dist2) & 7)) return fail(c, MRTX_E_INVALID, "dev_dist2 must be 8-byte aligned (uint64)");
-    if (dev_nearest && (reinterpret_cast<uintptr_t>(dev_nearest) & 3)) return fail(c, MRTX_E_INVALID, "dev_nearest must be 4-byte aligned (int32)");
-    if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 7)) return fail(c, MRTX_E_INVALID, "dev_out must be 8-byte aligned (MrtxRegionReach)");
-    const size_t out_bytes = sizeof(MrtxRegionReach) * (size_t)n_regions;
-    if (traverse_overlap(dev_labels, 4 * N, dev_out, out_bytes) || traverse_overlap(dev_dist2, 8 * N, dev_out, out_bytes) ||
-        traverse_overlap(dev_nearest, 4 * N, dev_out, out_bytes))
-        return fail(c, MRTX_E_INVALID, "the device inputs and dev_out must not overlap");
-    // ---- device work from here
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    float* d[3] = {nullptr, nullptr, nullptr};
-    if ((rc = stage_out(c, dev_out, std::max(out_bytes, sizeof(MrtxRegionReach)))) != MRTX_OK ||
-        (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, 16)) != MRTX_OK ||
-        (rc = stage_tables(c, {{host_labels, host_labels ? N : 0}, {host_dist2, host_dist2 ? 2 * N : 0},
-                               {host_nearest, host_nearest ? N : 0}}, d)) != MRTX_OK)
-        return rc;
-    ReachC q;
-    std::memset(&q, 0, sizeof q);
-    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_labels);
-    q.dist2 = host_dist2 ? reinterpret_cast<const unsigned long long*>(d[1]) : static_cast<const unsigned long long*>(dev_dist2);
-    q.nearest = host_nearest ? reinterpret_cast<const int32_t*>(d[2]) : static_cast<const int32_t*>(dev_nearest);
-    q.out = static_cast<ReachRec*>(dev_out);
-    q.bad = reinterpret_cast<uint32_t*>(c->trav_buf);
-    q.rows = rows; q.cols = cols; q.n_regions = n_regions;
-    uint32_t launches = 0, bad = 0;
-    HIPCHK(c, hipMemsetAsync(q.bad, 0, 16, c->stream));
-    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
-    HIPCHK(c, mrtx_launch_regions_reach(q, c->stream, &launches));
-    if ((rc = stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays)) != MRTX_OK) return rc;
-    if (out) out->launches = launches;
-    HIPCHK(c, hipMemcpy(&bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));
-    if (bad) return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", bad, (long long)n_regions - 1);
-    return MRTX_OK;
-}
-
-// ---- Region outlines: the ordered boundary rings of a label table --------------------------------
-static_assert(sizeof(MrtxRing) == 48 && sizeof(RingRec) == sizeof(MrtxRing), "MrtxRing is 48 bytes");
-static_assert(sizeof(OutlineJump) == 32, "two int4");
-
-int mrtx_regions_outline(mrtx_ctx* c, const MrtxOutline* o, const void* dev_labels, const int32_t* host_labels, uint32_t n_regions,
-                         const uint32_t* row_weight, void* dev_rings, MrtxRing* host_rings, uint64_t ring_cap, void* dev_vertices,
-                         int32_t* host_vertices, uint64_t vertex_cap, uint64_t* n_rings, uint64_t* n_vertices, MrtxStats* out) {
-    if (!c) return MRTX_E_INVALID;
-    if (!o) return fail(c, MRTX_E_INVALID, "null outline block");
-    if (o->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
-    int rc = regions_lattice(c, o->rows, o->cols, o->wrap);
-    if (rc != MRTX_OK) return rc;
-    if ((int64_t)o->rows * (int64_t)o->cols > MRTX_OL_MAX_NODES)
-        return fail(c, MRTX_E_INVALID, "an outlined lattice holds at most 2^28 nodes (got %d x %d)", o->rows, o->cols);
-    if (o->connectivity != 4 && o->connectivity != 8) return fail(c, MRTX_E_INVALID, "connectivity must be 4 or 8 (got %d)", o->connectivity);
-    if (o->mode != MRTX_OUTLINE_ALL && o->mode != MRTX_OUTLINE_CORNERS)
-        return fail(c, MRTX_E_INVALID, "mode must be MRTX_OUTLINE_ALL or MRTX_OUTLINE_CORNERS (got %d)", o->mode);
-    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
-    if (!n_rings || !n_vertices) return fail(c, MRTX_E_INVALID, "null n_rings or n_vertices");
-    if (dev_rings && host_rings) return fail(c, MRTX_E_INVALID, "give at most one of dev_rings and host_rings");
-    if (dev_vertices && host_vertices) return fail(c, MRTX_E_INVALID, "give at most one of dev_vertices and host_vertices");
-    const bool has_rings = dev_rings || host_rings, has_vertices = dev_vertices || host_vertices;
-    if (has_rings != has_vertices) return fail(c, MRTX_E_INVALID, "give a ring table and a vertex table, or neither to count");
-    if (!has_rings && (ring_cap || vertex_cap))
-        return fail(c, MRTX_E_INVALID, "without tables ring_cap and vertex_cap must be 0 (got %llu, %llu)", (unsigned long long)ring_cap,
-                    (unsigned long long)vertex_cap);
-    const size_t N = (size_t)o->rows * (size_t)o->cols;
-    if ((size_t)n_regions > N) return fail(c, MRTX_E_INVALID, "n_regions = %u exceeds the lattice's %zu nodes", n_regions, N);
-    // a table never needs more than one ring per three sides and one vertex per side
-    const size_t ring_bytes = sizeof(MrtxRing) * (size_t)std::min<uint64_t>(ring_cap, 4 * N);
-    const size_t vertex_bytes = 8 * (size_t)std::min<uint64_t>(vertex_cap, 4 * N);
-    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
-    if (dev_rings && (reinterpret_cast<uintptr_t>(dev_rings) & 7)) return fail(c, MRTX_E_INVALID, "dev_rings must be 8-byte aligned (MrtxRing)");
-    if (dev_vertices && (reinterpret_cast<uintptr_t>(dev_vertices) & 3)) return fail(c, MRTX_E_INVALID, "dev_vertices must be 4-byte aligned (int32)");
-    if (traverse_overlap(dev_labels, 4 * N, dev_rings, ring_bytes) || traverse_overlap(dev_labels, 4 * N, dev_vertices, vertex_bytes) ||
-        traverse_overlap(dev_rings, ring_bytes, dev_vertices, vertex_bytes))
-        return fail(c, MRTX_E_INVALID, "dev_labels, dev_rings and dev_vertices must not overlap");
-    // MOONRT_REGIONS_OUTLINE=jump: pointer jumping over every boundary side, the yardstick of the contraction of the chains
-    // inside a tile; the same bytes
-    bool contract = MRTX_OL_DEFAULT_CONTRACT;
-    if (const char* e = std::getenv("MOONRT_REGIONS_OUTLINE")) {
-        if (std::strcmp(e, "jump") == 0) contract = false;
-        else if (std::strcmp(e, "contract") == 0) contract = true;
-        else return fail(c, MRTX_E_INVALID, "MOONRT_REGIONS_OUTLINE must be contract or jump (got %s)", e);
-    }
-    // ---- device work from here
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    std::vector<uint64_t> cw;
-    if (row_weight) {
-        cw.assign((size_t)o->rows + 1, 0);
-        for (int32_t i = 0; i < o->rows; i++) cw[(size_t)i + 1] = cw[i] + row_weight[i];
-    }
-    const OutlineNodeLayout nl = outline_node_layout(o->rows, o->cols);
-    float* d[2] = {nullptr, nullptr};
-    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, nl.end)) != MRTX_OK ||
-        (rc = stage_tables(c, {{host_labels, host_labels ? N : 0}, {cw.data(), 2 * cw.size()}}, d)) != MRTX_OK)
-        return rc;
-    char* tb = reinterpret_cast<char*>(c->trav_buf);
-    OutlineC q;
-    std::memset(&q, 0, sizeof q);
-    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_labels);
-    q.cw = row_weight ? reinterpret_cast<const unsigned long long*>(d[1]) : nullptr;
-    q.bad = reinterpret_cast<uint32_t*>(tb);
-    q.totals = reinterpret_cast<unsigned long long*>(tb + 16);
-    q.bits = reinterpret_cast<uint8_t*>(tb + nl.bits_at);
-    q.base = reinterpret_cast<uint32_t*>(tb + nl.base_at);
-    q.node_sums = reinterpret_cast<uint2*>(tb + nl.sums_at);
-    q.rows = o->rows; q.cols = o->cols; q.wrap = o->wrap; q.conn8 = o->connectivity == 8; q.all = o->mode == MRTX_OUTLINE_ALL;
-    q.n_regions = n_regions; q.contract = contract;
-    uint32_t launches = 0;
-    unsigned long long head[6] = {0, 0, 0, 0, 0, 0};            // bad (and padding), then the four totals
-    HIPCHK(c, hipMemsetAsync(tb, 0, 64, c->stream));
-    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
-    HIPCHK(c, mrtx_launch_outline_mark(q, c->stream, &launches));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                 // also: the pageable tables are no longer read
-    HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
-    if ((uint32_t)head[0]) {                                    // as the sibling calls: the stage ends, out says what ran
-        if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
-        if (out) out->launches = launches;
-        return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", (uint32_t)head[0],
-                    (long long)n_regions - 1);
-    }
-    q.B = (uint32_t)head[2];
-    q.rounds = outline_rounds(q.B);
-    uint64_t rings = 0, vertices = 0;
-    bool fits = true;
-    if (q.B) {
-        const OutlineSideLayout sl = outline_side_layout(q.B);
-        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, sl.end)) != MRTX_OK) return rc;
-        char* sb = reinterpret_cast<char*>(c->illum_out);
-        q.sid = reinterpret_cast<int32_t*>(sb + sl.sid_at);
-        q.next = reinterpret_cast<int32_t*>(sb + sl.next_at);
-        q.ringno = reinterpret_cast<uint32_t*>(sb + sl.ringno_at);
-        q.flag = reinterpret_cast<uint8_t*>(sb + sl.flag_at);
-        q.jflag = reinterpret_cast<uint8_t*>(sb + sl.jflag_at);
-        q.jidx = reinterpret_cast<uint32_t*>(sb + sl.jidx_at);
-        q.side_sums = reinterpret_cast<uint2*>(sb + sl.sums_at);
-        q.jump[0] = reinterpret_cast<OutlineJump*>(sb + sl.jump_at[0]);
-        q.jump[1] = reinterpret_cast<OutlineJump*>(sb + sl.jump_at[1]);
-        // where the per-side result ends up, and the buffer that is dead by then (mrtx_outline.h)
-        const int fin_at = (q.rounds & 1) ^ (contract ? 1 : 0);
-        q.fin = q.jump[fin_at];
-        HIPCHK(c, mrtx_launch_outline_trace(q, c->stream, &launches));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
-        if (head[0] >> 32) {
-            if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
-            return fail(c, MRTX_E_DEVICE, "the outline trace met %u broken successors or chains", (uint32_t)(head[0] >> 32));
-        }
-        rings = head[4]; vertices = head[5];
-        fits = rings <= ring_cap && vertices <= vertex_cap;
-        if (has_rings && fits) {
-            // a table bound for the host lies in the jump buffer that the trace left dead
-            char* dead = sb + sl.jump_at[fin_at ^ 1];
-            q.rings = host_rings ? reinterpret_cast<RingRec*>(dead) : static_cast<RingRec*>(dev_rings);
-            q.vertices = host_vertices ? reinterpret_cast<int32_t*>(dead + outline_host_vertices_at(rings)) : static_cast<int32_t*>(dev_vertices);
-            HIPCHK(c, mrtx_launch_outline_fill(q, rings, c->stream, &launches));
-        }
-    }
-    if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
-    if (out) out->launches = launches;
-    if (has_rings && fits && q.B) {                             // the fill's own check of what the trace handed it
-        HIPCHK(c, hipMemcpy(head, tb, 8, hipMemcpyDeviceToHost));
-        if (head[0] >> 32) return fail(c, MRTX_E_DEVICE, "the outline fill met %u sides without a ring", (uint32_t)(head[0] >> 32));
-    }
-    *n_rings = rings;
-    *n_vertices = vertices;
-    if (has_rings && !fits)
-        return fail(c, MRTX_E_INVALID, "the tables are too small: %llu rings and %llu vertices are needed (ring_cap = %llu, vertex_cap = %llu)",
-                    (unsigned long long)rings, (unsigned long long)vertices, (unsigned long long)ring_cap, (unsigned long long)vertex_cap);
-    if (host_rings && rings) HIPCHK(c, hipMemcpy(host_rings, q.rings, sizeof(MrtxRing) * (size_t)rings, hipMemcpyDeviceToHost));
-    if (host_vertices && vertices) HIPCHK(c, hipMemcpy(host_vertices, q.vertices, 8 * (size_t)vertices, hipMemcpyDeviceToHost));
-    return MRTX_OK;
-}
-
-// ---- Contour lines: the ordered isolines of a lattice at many levels ------------------------------
-static_assert(sizeof(MrtxContours) == 20, "MrtxContours is 20 bytes");
-static_assert(sizeof(MrtxContourLine) == 32 && alignof(MrtxContourLine) == 8 && sizeof(ContourLineRec) == sizeof(MrtxContourLine),
-              "MrtxContourLine is 32 bytes");
-static_assert(sizeof(ContourJump) == 16, "one int4");
-static_assert(MRTX_CT_VOID == MRTX_FILL_NONE, "one mark for a node without a height");
-
-int mrtx_contours(mrtx_ctx* c, const MrtxContours* k, const void* dev_z, const int32_t* host_z, const int32_t* host_levels,
-                  void* dev_lines, MrtxContourLine* host_lines, uint64_t line_cap, void* dev_vertices, int32_t* host_vertices,
-                  uint64_t vertex_cap, uint64_t* n_lines, uint64_t* n_vertices, MrtxStats* out) {
-    if (!c) return MRTX_E_INVALID;
-    if (!k) return fail(c, MRTX_E_INVALID, "null contours block");
-    if (k->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
-    int rc = regions_lattice(c, k->rows, k->cols, k->wrap);
-    if (rc != MRTX_OK) return rc;
-    if ((int64_t)k->rows * (int64_t)k->cols > MRTX_CT_MAX_NODES)
-        return fail(c, MRTX_E_INVALID, "a contoured lattice holds at most 2^28 nodes (got %d x %d)", k->rows, k->cols);
-    if (k->n_levels < 1 || k->n_levels > MRTX_CT_MAX_LEVELS) return fail(c, MRTX_E_INVALID, "n_levels must lie in 1 .. 65536 (got %d)", k->n_levels);
-    if (!host_levels) return fail(c, MRTX_E_INVALID, "null host_levels");
-    for (int32_t l = 0; l < k->n_levels; l++) {
-        if (host_levels[l] < -MRTX_CT_ZMAX + 1 || host_levels[l] > MRTX_CT_ZMAX)
-            return fail(c, MRTX_E_INVALID, "level %d must lie in -2^30 + 1 .. 2^30 (got %d)", l, host_levels[l]);
-        if (l && host_levels[l] <= host_levels[l - 1])
-            return fail(c, MRTX_E_INVALID, "the levels must ascend strictly (level %d = %d follows %d)", l, host_levels[l], host_levels[l - 1]);
-    }
-    if ((dev_z == nullptr) == (host_z == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_z and host_z");
-    if (!n_lines || !n_vertices) return fail(c, MRTX_E_INVALID, "null n_lines or n_vertices");
-    if (dev_lines && host_lines) return fail(c, MRTX_E_INVALID, "give at most one of dev_lines and host_lines");
-    if (dev_vertices && host_vertices) return fail(c, MRTX_E_INVALID, "give at most one of dev_vertices and host_vertices");
-    const bool has_lines = dev_lines || host_lines, has_vertices = dev_vertices || host_vertices;
-    if (has_lines != has_vertices) return fail(c, MRTX_E_INVALID, "give a line table and a vertex table, or neither to count");
-    if (!has_lines && (line_cap || vertex_cap))
-        return fail(c, MRTX_E_INVALID, "without tables line_cap and vertex_cap must be 0 (got %llu, %llu)", (unsigned long long)line_cap,
-                    (unsigned long long)vertex_cap);
-    const size_t N = (size_t)k->rows * (size_t)k->cols;
-    // a table never needs more than one line and one vertex per element, and there are fewer than 2^31 elements
-    const size_t line_bytes = sizeof(MrtxContourLine) * (size_t)std::min<uint64_t>(line_cap, (uint64_t)1 << 31);
-    const size_t vertex_bytes = 4 * (size_t)std::min<uint64_t>(vertex_cap, (uint64_t)1 << 31);
-    if (dev_z && (reinterpret_cast<uintptr_t>(dev_z) & 3)) return fail(c, MRTX_E_INVALID, "dev_z must be 4-byte aligned (int32)");
-    if (dev_lines && (reinterpret_cast<uintptr_t>(dev_lines) & 7)) return fail(c, MRTX_E_INVALID, "dev_lines must be 8-byte aligned (MrtxContourLine)");
-    if (dev_vertices && (reinterpret_cast<uintptr_t>(dev_vertices) & 3)) return fail(c, MRTX_E_INVALID, "dev_vertices must be 4-byte aligned (int32)");
-    if (traverse_overlap(dev_z, 4 * N, dev_lines, line_bytes) || traverse_overlap(dev_z, 4 * N, dev_vertices, vertex_bytes) ||
-        traverse_overlap(dev_lines, line_bytes, dev_vertices, vertex_bytes))
-        return fail(c, MRTX_E_INVALID, "dev_z, dev_lines and dev_vertices must not overlap");
-    // ---- device work from here
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    const ContourNodeLayout nl = contour_node_layout(k->rows, k->cols, k->n_levels, host_z != nullptr);
-    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, nl.end)) != MRTX_OK) return rc;
-    char* tb = reinterpret_cast<char*>(c->trav_buf);
-    // the host tables (the caller's memory stays put until the end of the call)
-    HIPCHK(c, hipMemcpyAsync(tb + nl.levels_at, host_levels, 4 * (size_t)k->n_levels, hipMemcpyHostToDevice, c->stream));
-    if (host_z) HIPCHK(c, hipMemcpyAsync(tb + nl.z_at, host_z, 4 * N, hipMemcpyHostToDevice, c->stream));
-    ContourC q;
-    std::memset(&q, 0, sizeof q);
-    q.z = host_z ? reinterpret_cast<const int32_t*>(tb + nl.z_at) : static_cast<const int32_t*>(dev_z);
-    q.levels = reinterpret_cast<const int32_t*>(tb + nl.levels_at);
-    q.bad = reinterpret_cast<uint32_t*>(tb);
-    q.totals = reinterpret_cast<unsigned long long*>(tb + 16);
-    q.rank = reinterpret_cast<uint32_t*>(tb + nl.rank_at);
-    q.base = reinterpret_cast<uint32_t*>(tb + nl.base_at);
-    q.node_sums = reinterpret_cast<unsigned long long*>(tb + nl.sums_at);
-    q.rows = k->rows; q.cols = k->cols; q.wrap = k->wrap; q.n_levels = k->n_levels;
-    uint32_t launches = 0;
-    unsigned long long head[6] = {0, 0, 0, 0, 0, 0};            // bad (and padding), then the four totals
-    HIPCHK(c, hipMemsetAsync(tb, 0, 64, c->stream));
-    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
-    HIPCHK(c, mrtx_launch_contour_count(q, c->stream, &launches));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                 // also: the pageable tables are no longer read
-    HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
-    if ((uint32_t)head[0] || head[2] >= ((uint64_t)1 << 31)) {  // as the sibling calls: the stage ends, out says what ran
-        if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
-        if (out) out->launches = launches;
-        if ((uint32_t)head[0])
-            return fail(c, MRTX_E_INVALID, "%u heights lie outside -2^30 .. 2^30 and are not MRTX_FILL_NONE", (uint32_t)head[0]);
-        return fail(c, MRTX_E_INVALID, "the levels cross the edges %llu times: a call holds fewer than 2^31 crossings", head[2]);
-    }
-    q.B = (uint32_t)head[2];
-    q.rounds = contour_rounds(q.B);
-    uint64_t lines = 0, vertices = 0;
-    bool fits = true;
-    if (q.B) {
-        const ContourSideLayout sl = contour_side_layout(q.B);
-        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, sl.end)) != MRTX_OK) return rc;
-        char* sb = reinterpret_cast<char*>(c->illum_out);
-        q.eid = reinterpret_cast<int32_t*>(sb + sl.eid_at);
-        q.succ = reinterpret_cast<int32_t*>(sb + sl.succ_at);
-        q.len = reinterpret_cast<uint32_t*>(sb + sl.len_at);
-        q.tailat = reinterpret_cast<int32_t*>(sb + sl.tailat_at);
-        q.lineno = reinterpret_cast<uint32_t*>(sb + sl.lineno_at);
-        q.side_sums = reinterpret_cast<uint2*>(sb + sl.sums_at);
-        q.jump[0] = reinterpret_cast<ContourJump*>(sb + sl.jump_at[0]);
-        q.jump[1] = reinterpret_cast<ContourJump*>(sb + sl.jump_at[1]);
-        q.fin = q.jump[q.rounds & 1];
-        HIPCHK(c, mrtx_launch_contour_trace(q, c->stream, &launches));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
-        if ((head[0] >> 32) || head[5] != q.B) {                // the lines' lengths add up to the elements
-            if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
-            return fail(c, MRTX_E_DEVICE, "the contour trace met %u broken successors and lines of %llu vertices for %u crossings",
-                        (uint32_t)(head[0] >> 32), head[5], q.B);
-        }
-        lines = head[4]; vertices = head[5];
-        fits = lines <= line_cap && vertices <= vertex_cap;
-        if (has_lines && fits) {
-            // the tables bound for the host lie in a block of their own, of exactly their size
-            if ((host_lines || host_vertices) &&
-                (rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, contour_host_vertices_at(lines) + 4 * (size_t)vertices)) != MRTX_OK)
-                return rc;
-            char* hb = reinterpret_cast<char*>(c->illum_tab);
-            q.lines = host_lines ? reinterpret_cast<ContourLineRec*>(hb) : static_cast<ContourLineRec*>(dev_lines);
-            q.vertices = host_vertices ? reinterpret_cast<int32_t*>(hb + contour_host_vertices_at(lines)) : static_cast<int32_t*>(dev_vertices);
-            HIPCHK(c, mrtx_launch_contour_fill(q, lines, c->stream, &launches));
-        }
-    }
-    if ((rc = stage_finish(c, nullptr, nullptr, 0, out, kNoRays)) != MRTX_OK) return rc;
-    if (out) out->launches = launches;
-    if (has_lines && fits && q.B) {                             // the fill's own check of what the trace handed it
-        HIPCHK(c, hipMemcpy(head, tb, 8, hipMemcpyDeviceToHost));
-        if (head[0] >> 32) return fail(c, MRTX_E_DEVICE, "the contour fill met %u elements without a line", (uint32_t)(head[0] >> 32));
-    }
-    *n_lines = lines;
-    *n_vertices = vertices;
-    if (has_lines && !fits)
-        return fail(c, MRTX_E_INVALID, "the tables are too small: %llu lines and %llu vertices are needed (line_cap = %llu, vertex_cap = %llu)",
-                    (unsigned long long)lines, (unsigned long long)vertices, (unsigned long long)line_cap, (unsigned long long)vertex_cap);
-    if (host_lines && lines) HIPCHK(c, hipMemcpy(host_lines, q.lines, sizeof(MrtxContourLine) * (size_t)lines, hipMemcpyDeviceToHost));
-    if (host_vertices && vertices) HIPCHK(c, hipMemcpy(host_vertices, q.vertices, 4 * (size_t)vertices, hipMemcpyDeviceToHost));
-    return MRTX_OK;
-}
-
-// ---- Terrain depressions: fill levels and the basin catalogue -------------------------------------
-static_assert(sizeof(MrtxFill) == 24, "MrtxFill is 24 bytes");
-static_assert(sizeof(MrtxBasin) == 48 && sizeof(BasinRec) == sizeof(MrtxBasin), "MrtxBasin is 48 bytes");
-static_assert(MRTX_FILL_NONE == INT32_MAX, "the fill without an outlet");
-
-// a host height table is refused at its first height beyond the bound (a device table's are counted by the kernels)
-static int fill_host_heights(mrtx_ctx* c, const int32_t* host_z, size_t N) {
-    if (host_z)
-        for (size_t n = 0; n < N; n++)
-            if (host_z[n] < -MRTX_FILL_ZMAX || host_z[n] > MRTX_FILL_ZMAX)
-                return fail(c, MRTX_E_INVALID, "height %zu must lie in -2^30 .. 2^30 (got %d)", n, host_z[n]);
-    return MRTX_OK;
-}
-
-int mrtx_fill(mrtx_ctx* c, const MrtxFill* f, const void* dev_z, const int32_t* host_z, const void* dev_outlet,
-              const uint8_t* host_outlet, void* dev_fill, int32_t* host_fill, uint64_t* visits, MrtxStats* out) {
-    if (!c) return MRTX_E_INVALID;
-    if (!f) return fail(c, MRTX_E_INVALID, "null fill block");
-    if (f->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
-    int rc = regions_lattice(c, f->rows, f->cols, f->wrap);
-    if (rc != MRTX_OK) return rc;
-    if (f->connectivity != 4 && f->connectivity != 8) return fail(c, MRTX_E_INVALID, "connectivity must be 4 or 8 (got %d)", f->connectivity);
-    if (f->edge_outlets != 0 && f->edge_outlets != 1) return fail(c, MRTX_E_INVALID, "edge_outlets must be 0 or 1 (got %d)", f->edge_outlets);
-    if (dev_outlet && host_outlet) return fail(c, MRTX_E_INVALID, "give at most one of dev_outlet and host_outlet");
-    if (!f->edge_outlets && !dev_outlet && !host_outlet)
-        return fail(c, MRTX_E_INVALID, "no outlet source: edge_outlets = 0 needs an outlet table");
-    if ((dev_z == nullptr) == (host_z == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_z and host_z");
-    if ((dev_fill == nullptr) == (host_fill == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_fill and host_fill");
-    if (dev_z && (reinterpret_cast<uintptr_t>(dev_z) & 3)) return fail(c, MRTX_E_INVALID, "dev_z must be 4-byte aligned (int32)");
-    if (dev_fill && (reinterpret_cast<uintptr_t>(dev_fill) & 3)) return fail(c, MRTX_E_INVALID, "dev_fill must be 4-byte aligned (int32)");
-    const size_t N = (size_t)f->rows * (size_t)f->cols;
-    if (traverse_overlap(dev_z, 4 * N, dev_fill, 4 * N) || traverse_overlap(dev_z, 4 * N, dev_outlet, N) ||
-        traverse_overlap(dev_outlet, N, dev_fill, 4 * N))
-        return fail(c, MRTX_E_INVALID, "dev_z, dev_outlet and dev_fill must not overlap");
-    // MOONRT_FILL=sweep: one Jacobi step over the whole lattice per launch, the yardstick of the tile scheme; the same bytes
-    bool tiles = true;
-    if (const char* e = std::getenv("MOONRT_FILL")) {
-        if (std::strcmp(e, "sweep") == 0) tiles = false;
-        else if (std::strcmp(e, "tiles") != 0) return fail(c, MRTX_E_INVALID, "MOONRT_FILL must be tiles or sweep (got %s)", e);
-    }
-    if ((rc = fill_host_heights(c, host_z, N)) != MRTX_OK) return rc;
-    // ---- device work from here
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    const int tiles_x = (f->cols + MRTX_FILL_TS - 1) / MRTX_FILL_TS, tiles_y = (f->rows + MRTX_FILL_TS - 1) / MRTX_FILL_TS;
-    const size_t n_tiles = (size_t)tiles_x * (size_t)tiles_y;
-    // scratch: 64 bytes of counters (visits, bad, the change counters), the fill when it goes to the host, then the second
-    // table of the sweep or the two flag arrays of the tiles
-    const size_t tab_b = (4 * N + 15) & ~(size_t)15;
-    const size_t fill_at = 64, work_at = fill_at + (host_fill ? tab_b : 0);
-    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, work_at + (tiles ? 8 * n_tiles : tab_b))) != MRTX_OK) return rc;
-    // the host tables: heights, then the outlet bytes (the caller's memory stays put until the end of the call)
-    const size_t hz_b = host_z ? tab_b : 0;
-    if (host_z || host_outlet) {
-        if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, hz_b + (host_outlet ? N : 0) + 16)) != MRTX_OK) return rc;
-        char* it = reinterpret_cast<char*>(c->illum_tab);
-        if (host_z) HIPCHK(c, hipMemcpyAsync(it, host_z, 4 * N, hipMemcpyHostToDevice, c->stream));
-        if (host_outlet) HIPCHK(c, hipMemcpyAsync(it + hz_b, host_outlet, N, hipMemcpyHostToDevice, c->stream));
-    }
-    char* tb = reinterpret_cast<char*>(c->trav_buf);
-    FillC q;
-    std::memset(&q, 0, sizeof q);
-    q.z = host_z ? reinterpret_cast<const int32_t*>(c->illum_tab) : static_cast<const int32_t*>(dev_z);
-    q.outlet = host_outlet ? reinterpret_cast<const uint8_t*>(c->illum_tab) + hz_b : static_cast<const uint8_t*>(dev_outlet);
-    int32_t* const d_fill = host_fill ? reinterpret_cast<int32_t*>(tb + fill_at) : static_cast<int32_t*>(dev_fill);
-    int32_t* const d_other = reinterpret_cast<int32_t*>(tb + work_at);      // sweep only
-    q.visits = reinterpret_cast<unsigned long long*>(tb);
-    q.bad = reinterpret_cast<uint32_t*>(tb + 8);
-    q.changed = reinterpret_cast<uint32_t*>(tb + 16);
-    q.rows = f->rows; q.cols = f->cols; q.wrap = f->wrap; q.conn8 = f->connectivity == 8; q.edge_outlets = f->edge_outlets;
-    q.tiles_x = tiles_x; q.tiles_y = tiles_y;
-    uint32_t* fa = reinterpret_cast<uint32_t*>(tb + work_at);
-    uint32_t* fb = fa + n_tiles;
-    HIPCHK(c, hipMemsetAsync(tb, 0, 64, c->stream));
-    if (tiles) HIPCHK(c, hipMemsetAsync(fa, 0, 8 * n_tiles, c->stream));
-    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
-    q.w = d_fill;
-    if (tiles) q.flag_in = fa;
-    HIPCHK(c, mrtx_launch_fill_init(q, tiles, c->stream));
-    // no launch cap: every store strictly lowers an int32, so the fixed point is reached after finitely many of them.  The
-    // sweep reads one table and writes the other; a batch is an even number of launches, so it ends in the caller's table.
-    static_assert(MRTX_FILL_BATCH % 2 == 0, "a batch of sweeps ends in the table it started from");
-    uint32_t launches = 1;
-    for (;;) {
-        HIPCHK(c, hipMemsetAsync(q.changed, 0, MRTX_FILL_BATCH * sizeof(uint32_t), c->stream));
-        for (int s = 0; s < MRTX_FILL_BATCH; s++) {
-            q.slot = s;
-            if (tiles) {
-                q.flag_in = fa; q.flag_out = fb;
-                HIPCHK(c, mrtx_launch_fill_relax(q, c->stream));
-                std::swap(fa, fb);
-            } else {
-                q.w_in = (s & 1) ? d_other : d_fill;
-                q.w = (s & 1) ? d_fill : d_other;
-                HIPCHK(c, mrtx_launch_fill_sweep(q, c->stream));
-            }
-            launches++;
-        }
-        uint32_t last = 0;
-        HIPCHK(c, hipMemcpyAsync(&last, q.changed + (MRTX_FILL_BATCH - 1), sizeof last, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (last == 0) break;       // a whole launch lowered nothing: every later one is empty too
-    }
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    unsigned long long head[2] = {0, 0};                    // visits, bad
-    HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
-    if (out) {
-        std::memset(out, 0, sizeof *out);
-        out->kernel_ms = ms;
-        out->launches = launches;
-    }
-    if (visits) *visits = head[0];
-    if ((uint32_t)head[1])
-        return fail(c, MRTX_E_INVALID, "%u heights of the device table lie outside -2^30 .. 2^30", (uint32_t)head[1]);
-    if (host_fill) HIPCHK(c, hipMemcpy(host_fill, d_fill, 4 * N, hipMemcpyDeviceToHost));
-    return MRTX_OK;
-}
-
-int mrtx_fill_basins(mrtx_ctx* c, int32_t rows, int32_t cols, int32_t wrap, int32_t connectivity, const void* dev_labels,
-                     const int32_t* host_labels, uint32_t n_regions, const void* dev_z, const int32_t* host_z, const void* dev_fill,
-                     const int32_t* host_fill, const uint32_t* row_weight, void* dev_out, MrtxBasin* host_out, MrtxStats* out) {
-    if (!c) return MRTX_E_INVALID;
-    int rc = regions_lattice(c, rows, cols, wrap);
-    if (rc != MRTX_OK) return rc;
-    if (connectivity != 4 && connectivity != 8) return fail(c, MRTX_E_INVALID, "connectivity must be 4 or 8 (got %d)", connectivity);
-    if ((dev_labels == nullptr) == (host_labels == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_labels and host_labels");
-    if ((dev_z == nullptr) == (host_z == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_z and host_z");
-    if ((dev_fill == nullptr) == (host_fill == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_fill and host_fill");
-    if ((dev_out == nullptr) == (host_out == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_out and host_out");
-    const size_t N = (size_t)rows * (size_t)cols;
-    if ((size_t)n_regions > N) return fail(c, MRTX_E_INVALID, "n_regions = %u exceeds the lattice's %zu nodes", n_regions, N);
-    if (dev_labels && (reinterpret_cast<uintptr_t>(dev_labels) & 3)) return fail(c, MRTX_E_INVALID, "dev_labels must be 4-byte aligned (int32)");
-    if (dev_z && (reinterpret_cast<uintptr_t>(dev_z) & 3)) return fail(c, MRTX_E_INVALID, "dev_z must be 4-byte aligned (int32)");
-    if (dev_fill && (reinterpret_cast<uintptr_t>(dev_fill) & 3)) return fail(c, MRTX_E_INVALID, "dev_fill must be 4-byte aligned (int32)");
-    if (dev_out && (reinterpret_cast<uintptr_t>(dev_out) & 7)) return fail(c, MRTX_E_INVALID, "dev_out must be 8-byte aligned (MrtxBasin)");
-    const size_t out_bytes = sizeof(MrtxBasin) * (size_t)n_regions;
-    if (traverse_overlap(dev_labels, 4 * N, dev_out, out_bytes) || traverse_overlap(dev_z, 4 * N, dev_out, out_bytes) ||
-        traverse_overlap(dev_fill, 4 * N, dev_out, out_bytes))
-        return fail(c, MRTX_E_INVALID, "the device inputs and dev_out must not overlap");
-    if ((rc = fill_host_heights(c, host_z, N)) != MRTX_OK) return rc;
-    // ---- device work from here
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    // scratch: the counts of bad entries, then the packed pour and depth keys
-    float* d[4] = {nullptr, nullptr, nullptr, nullptr};
-    if ((rc = stage_out(c, dev_out, std::max(out_bytes, sizeof(MrtxBasin)))) != MRTX_OK ||
-        (rc = stage_buffer(c, c->trav_buf, c->trav_bytes, 16 + 16 * (size_t)n_regions)) != MRTX_OK ||
-        (rc = stage_tables(c, {{host_labels, host_labels ? N : 0}, {host_z, host_z ? N : 0}, {host_fill, host_fill ? N : 0},
-                               {row_weight, row_weight ? (size_t)rows : 0}}, d)) != MRTX_OK)
-        return rc;
-    char* tb = reinterpret_cast<char*>(c->trav_buf);
-    BasinC q;
-    std::memset(&q, 0, sizeof q);
-    q.labels = host_labels ? reinterpret_cast<const int32_t*>(d[0]) : static_cast<const int32_t*>(dev_labels);
-    q.z = host_z ? reinterpret_cast<const int32_t*>(d[1]) : static_cast<const int32_t*>(dev_z);
-    q.fill = host_fill ? reinterpret_cast<const int32_t*>(d[2]) : static_cast<const int32_t*>(dev_fill);
-    q.row_weight = row_weight ? reinterpret_cast<const uint32_t*>(d[3]) : nullptr;
-    q.out = static_cast<BasinRec*>(dev_out);
-    q.bad = reinterpret_cast<uint32_t*>(tb);
-    q.keys = reinterpret_cast<unsigned long long*>(tb + 16);
-    q.rows = rows; q.cols = cols; q.wrap = wrap; q.conn8 = connectivity == 8; q.n_regions = n_regions;
-    uint32_t launches = 0, bad[2] = {0, 0};
-    HIPCHK(c, hipMemsetAsync(q.bad, 0, 16, c->stream));
-    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
-    HIPCHK(c, mrtx_launch_fill_basins(q, c->stream, &launches));
-    if ((rc = stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays)) != MRTX_OK) return rc;
-    if (out) out->launches = launches;
-    HIPCHK(c, hipMemcpy(bad, q.bad, sizeof bad, hipMemcpyDeviceToHost));
-    if (bad[0]) return fail(c, MRTX_E_INVALID, "the label table holds %u entries outside -1 .. n_regions - 1 = %lld", bad[0], (long long)n_regions - 1);
-    if (bad[1]) return fail(c, MRTX_E_INVALID, "%u heights of the device table lie outside -2^30 .. 2^30", bad[1]);
-    return MRTX_OK;
-}
-
-// ---- The depression hierarchy: nested bowls, spill points, peak prominence ------------------------
-static_assert(sizeof(MrtxBowls) == 32, "MrtxBowls is 32 bytes");
-static_assert(sizeof(MrtxBowl) == 64 && alignof(MrtxBowl) == 8, "MrtxBowl is 64 bytes");
-static_assert(sizeof(BowlEdge) == 16 && sizeof(BowlWalk) == 16, "the tables the host and the kernels share");
-static_assert(MRTX_BOWLS_ZMAX == MRTX_FILL_ZMAX, "one bound on the heights");
-
-static int32_t bowls_level(unsigned long long key) { return (int32_t)((uint32_t)(key >> 32) - 0x40000000u); }
-
-// The sweep over the minima and the edges of the spanning forest, both in ascending key: the births, spills, parents and floors
-// of section 3.25.  The edges of one pass node are one event.  Levels are still those the sweep saw (negated with invert), and
-// count, weight, volume and n_leaves wait for the sums of the label pass (bowls_finish).  floor: the key of each bowl's floor.
-static void bowls_tree(std::vector<unsigned long long>& minima, std::vector<BowlEdge>& edges, uint32_t outside,
-                       std::vector<MrtxBowl>& rec, std::vector<BowlWalk>& walk) {
-    const size_t M = minima.size();
-    std::sort(minima.begin(), minima.end());
-    std::sort(edges.begin(), edges.end(), [](const BowlEdge& x, const BowlEdge& y) { return x.pass < y.pass; });
-    std::vector<uint32_t> ids(M);
-    for (size_t k = 0; k < M; k++) ids[k] = (uint32_t)minima[k];
-    std::sort(ids.begin(), ids.end());
-    auto dense = [&](uint32_t node) -> uint32_t {
-        return node == outside ? (uint32_t)M : (uint32_t)(std::lower_bound(ids.begin(), ids.end(), node) - ids.begin());
-    };
-    std::vector<uint32_t> up(M + 1);
-    for (size_t k = 0; k <= M; k++) up[k] = (uint32_t)k;
-    auto find = [&](uint32_t x) {
-        while (up[x] != x) {
-            up[x] = up[up[x]];
-            x = up[x];
-        }
-        return x;
-    };
-    std::vector<int32_t> current(M + 1, -1);        // the current bowl of a component's representative; -1: open
-    std::vector<unsigned long long> floor;
-    auto born = [&](unsigned long long key, uint32_t children, unsigned long long floor_key, bool leaf) {
-        MrtxBowl b;
-        std::memset(&b, 0, sizeof b);
-        b.born_at = (int32_t)(uint32_t)key; b.born_level = bowls_level(key);
-        b.floor_at = (int32_t)(uint32_t)floor_key; b.floor_level = bowls_level(floor_key);
-        b.spill_at = -1; b.spill_level = MRTX_FILL_NONE; b.parent = -1; b.n_children = children; b.n_leaves = leaf ? 1u : 0u;
-        rec.push_back(b);
-        floor.push_back(floor_key);
-        BowlWalk w;
-        w.spill = ~0ull; w.parent = -1; w.leaf_at = leaf ? b.born_at : -1;
-        walk.push_back(w);
-        return (int32_t)(rec.size() - 1);
-    };
-    auto spill = [&](int32_t b, unsigned long long key, int32_t parent) {
-        rec[b].spill_at = (int32_t)(uint32_t)key; rec[b].spill_level = bowls_level(key); rec[b].parent = parent;
-        walk[b].spill = key; walk[b].parent = parent;
-    };
-    size_t im = 0, ie = 0;
-    std::vector<uint32_t> cs;
-    while (im < M || ie < edges.size()) {
-        if (im < M && (ie >= edges.size() || minima[im] < edges[ie].pass)) {
-            current[dense((uint32_t)minima[im])] = born(minima[im], 0, minima[im], true);
-            im++;
-            continue;
-        }
-        const unsigned long long pass = edges[ie].pass;
-        cs.clear();
-        for (; ie < edges.size() && edges[ie].pass == pass; ie++)
-            for (uint32_t end : {edges[ie].a, edges[ie].b}) {
-                const uint32_t r = find(dense(end));
-                if (std::find(cs.begin(), cs.end(), r) == cs.end()) cs.push_back(r);
-            }
-        bool open = false;
-        uint32_t to = cs[0];
-        for (uint32_t r : cs)
-            if (current[r] < 0) { open = true; to = r; }
-        int32_t now = -1;
-        if (!open) {
-            unsigned long long least = ~0ull;
-            for (uint32_t r : cs) least = std::min(least, floor[current[r]]);
-            now = born(pass, (uint32_t)cs.size(), least, false);
-        }
-        for (uint32_t r : cs) {
-            if (current[r] >= 0) spill(current[r], pass, now);
-            up[r] = to;
-        }
-        current[to] = now;
-    }
-}
-
-// One pass up the records (parent > child): the sums of each bowl's own nodes become those of its region.  own: nodes, weight
-// and the sum of w z' per bowl.  Then the levels go back into the caller's z.
-static void bowls_finish(std::vector<MrtxBowl>& rec, std::vector<unsigned long long>& own, bool invert) {
-    const size_t n = rec.size();
-    for (size_t b = 0; b < n; b++) rec[b].own_count = (uint32_t)own[3 * b];
-    for (size_t b = 0; b < n; b++) {
-        MrtxBowl& r = rec[b];
-        r.count = (uint32_t)own[3 * b];
-        r.weight = own[3 * b + 1];
-        r.volume = r.spill_at >= 0 ? (unsigned long long)(long long)r.spill_level * r.weight - own[3 * b + 2] : 0ull;
-        if (r.parent >= 0) {
-            const size_t p = (size_t)r.parent;
-            for (int k = 0; k < 3; k++) own[3 * p + k] += own[3 * b + k];
-            rec[p].n_leaves += r.n_leaves;
-        }
-        if (invert) { r.floor_level = -r.floor_level; r.born_level = -r.born_level; r.spill_level = -r.spill_level; }
-    }
-}
-
-// the end of a device phase: its time added to ms (the next phase starts with another record of ev0)
-static int bowls_lap(mrtx_ctx* c, float* ms) {
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    float t = 0.0f;
-    HIPCHK(c, hipEventElapsedTime(&t, c->ev0, c->ev1));
-    *ms += t;
-    return MRTX_OK;
-}
-
-int mrtx_bowls(mrtx_ctx* c, const MrtxBowls* w, const void* dev_z, const int32_t* host_z, const void* dev_outlet,
-               const uint8_t* host_outlet, const uint32_t* row_weight, void* dev_bowls, MrtxBowl* host_bowls, uint64_t bowl_cap,
-               void* dev_label, int32_t* host_label, uint64_t* n_bowls, uint64_t* rounds, MrtxStats* out) {
-    if (!c) return MRTX_E_INVALID;
-    if (!w) return fail(c, MRTX_E_INVALID, "null bowls block");
-    if (w->reserved[0] != 0 || w->reserved[1] != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
-    int rc = regions_lattice(c, w->rows, w->cols, w->wrap);
-    if (rc != MRTX_OK) return rc;
-    if (w->connectivity != 4 && w->connectivity != 8) return fail(c, MRTX_E_INVALID, "connectivity must be 4 or 8 (got %d)", w->connectivity);
-    if (w->edge_outlets != 0 && w->edge_outlets != 1) return fail(c, MRTX_E_INVALID, "edge_outlets must be 0 or 1 (got %d)", w->edge_outlets);
-    if (w->invert != 0 && w->invert != 1) return fail(c, MRTX_E_INVALID, "invert must be 0 or 1 (got %d)", w->invert);
-    if (dev_outlet && host_outlet) return fail(c, MRTX_E_INVALID, "give at most one of dev_outlet and host_outlet");
-    if (!w->edge_outlets && !dev_outlet && !host_outlet)
-        return fail(c, MRTX_E_INVALID, "no outlet source: edge_outlets = 0 needs an outlet table");
-    if ((dev_z == nullptr) == (host_z == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_z and host_z");
-    if (!n_bowls) return fail(c, MRTX_E_INVALID, "null n_bowls");
-    if (dev_bowls && host_bowls) return fail(c, MRTX_E_INVALID, "give at most one of dev_bowls and host_bowls");
-    if (dev_label && host_label) return fail(c, MRTX_E_INVALID, "give at most one of dev_label and host_label");
-    const bool has_bowls = dev_bowls || host_bowls, has_label = dev_label || host_label;
-    if (!has_bowls && bowl_cap) return fail(c, MRTX_E_INVALID, "without a bowl table bowl_cap must be 0 (got %llu)", (unsigned long long)bowl_cap);
-    if (!has_bowls && has_label) return fail(c, MRTX_E_INVALID, "a label table needs a bowl table: a call without one only counts");
-    const size_t N = (size_t)w->rows * (size_t)w->cols;
-    if (dev_z && (reinterpret_cast<uintptr_t>(dev_z) & 3)) return fail(c, MRTX_E_INVALID, "dev_z must be 4-byte aligned (int32)");
-    if (dev_bowls && (reinterpret_cast<uintptr_t>(dev_bowls) & 7)) return fail(c, MRTX_E_INVALID, "dev_bowls must be 8-byte aligned (MrtxBowl)");
-    if (dev_label && (reinterpret_cast<uintptr_t>(dev_label) & 3)) return fail(c, MRTX_E_INVALID, "dev_label must be 4-byte aligned (int32)");
-    // a lattice never holds more bowls than nodes
-    const size_t bowl_bytes = sizeof(MrtxBowl) * (size_t)std::min<uint64_t>(bowl_cap, N);
-    if (traverse_overlap(dev_z, 4 * N, dev_outlet, N) || traverse_overlap(dev_z, 4 * N, dev_bowls, bowl_bytes) ||
-        traverse_overlap(dev_z, 4 * N, dev_label, 4 * N) || traverse_overlap(dev_outlet, N, dev_bowls, bowl_bytes) ||
-        traverse_overlap(dev_outlet, N, dev_label, 4 * N) || traverse_overlap(dev_bowls, bowl_bytes, dev_label, 4 * N))
-        return fail(c, MRTX_E_INVALID, "dev_z, dev_outlet, dev_bowls and dev_label must not overlap");
-    if ((rc = fill_host_heights(c, host_z, N)) != MRTX_OK) return rc;
-    // ---- device work from here
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    // scratch: 64 bytes of counters, then ptr, cpar and best2 (N + 1 words each), best (N + 1 double words), and the labels
-    // when they go to the host
-    const size_t words_b = (4 * (N + 1) + 15) & ~(size_t)15, keys_b = (8 * (N + 1) + 15) & ~(size_t)15;
-    const size_t ptr_at = 64, cpar_at = ptr_at + words_b, best2_at = cpar_at + words_b, best_at = best2_at + words_b,
-                 label_at = best_at + keys_b;
-    if ((rc = stage_buffer(c, c->trav_buf, c->trav_bytes, label_at + (host_label ? 4 * N : 0))) != MRTX_OK) return rc;
-    // the host tables: heights, the row weights, then the outlet bytes (the caller's memory stays put until the first wait)
-    const size_t hz_b = host_z ? (4 * N + 15) & ~(size_t)15 : 0, rw_b = row_weight ? (4 * (size_t)w->rows + 15) & ~(size_t)15 : 0;
-    if ((rc = stage_buffer(c, c->illum_tab, c->illum_tab_bytes, hz_b + rw_b + (host_outlet ? N : 0) + 16)) != MRTX_OK) return rc;
-    char* it = reinterpret_cast<char*>(c->illum_tab);
-    if (host_z) HIPCHK(c, hipMemcpyAsync(it, host_z, 4 * N, hipMemcpyHostToDevice, c->stream));
-    if (row_weight) HIPCHK(c, hipMemcpyAsync(it + hz_b, row_weight, 4 * (size_t)w->rows, hipMemcpyHostToDevice, c->stream));
-    if (host_outlet) HIPCHK(c, hipMemcpyAsync(it + hz_b + rw_b, host_outlet, N, hipMemcpyHostToDevice, c->stream));
-    char* tb = reinterpret_cast<char*>(c->trav_buf);
-    BowlC q;
-    std::memset(&q, 0, sizeof q);
-    q.z = host_z ? reinterpret_cast<const int32_t*>(it) : static_cast<const int32_t*>(dev_z);
-    q.row_weight = row_weight ? reinterpret_cast<const uint32_t*>(it + hz_b) : nullptr;
-    q.outlet = host_outlet ? reinterpret_cast<const uint8_t*>(it + hz_b + rw_b) : static_cast<const uint8_t*>(dev_outlet);
-    q.counters = reinterpret_cast<uint32_t*>(tb);
-    q.ptr = reinterpret_cast<uint32_t*>(tb + ptr_at);
-    q.cpar = reinterpret_cast<uint32_t*>(tb + cpar_at);
-    q.best2 = reinterpret_cast<uint32_t*>(tb + best2_at);
-    q.best = reinterpret_cast<unsigned long long*>(tb + best_at);
-    q.rows = w->rows; q.cols = w->cols; q.wrap = w->wrap; q.conn8 = w->connectivity == 8; q.edge_outlets = w->edge_outlets;
-    q.invert = w->invert;
-    static_assert(8 + MRTX_BOWLS_BATCH <= 16, "the counters fit their 64 bytes");
-    HIPCHK(c, hipMemsetAsync(tb, 0, 64, c->stream));
-    if ((rc = stage_start(c, nullptr, false)) != MRTX_OK) return rc;
-    float ms = 0.0f;
-    uint32_t launches = 1, head[16];
-    HIPCHK(c, mrtx_launch_bowls_init(q, c->stream));
-    // the jumps: a path of L nodes is short of its end after log2 L doublings, and a launch that moved nothing ends them
-    for (;;) {
-        HIPCHK(c, hipMemsetAsync(q.counters + 8, 0, MRTX_BOWLS_BATCH * sizeof(uint32_t), c->stream));
-        for (int s = 0; s < MRTX_BOWLS_BATCH; s++) {
-            q.slot = s;
-            HIPCHK(c, mrtx_launch_bowls_jump(q, c->stream));
-            launches++;
-        }
-        uint32_t last = 0;
-        HIPCHK(c, hipMemcpyAsync(&last, q.counters + 8 + (MRTX_BOWLS_BATCH - 1), sizeof last, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (last == 0) break;
-    }
-    HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
-    auto report = [&]() {
-        if (out) {
-            std::memset(out, 0, sizeof *out);
-            out->kernel_ms = ms;
-            out->launches = launches;
-        }
-    };
-    if (head[0]) {
-        if ((rc = bowls_lap(c, &ms)) != MRTX_OK) return rc;
-        report();
-        return fail(c, MRTX_E_INVALID, "%u heights of the device table lie outside -2^30 .. 2^30", head[0]);
-    }
-    // ---- the spanning forest over the catchments and the outside
-    const uint32_t M = head[1];
-    q.n_min = M;
-    uint64_t n_rounds = 0;
-    std::vector<unsigned long long> minima(M);
-    std::vector<BowlEdge> edges;
-    // the component tables: the minima's keys, the hooks and the edges; the walk table and the sums of the label pass take
-    // their place later (at most 2 M bowls of 16 + 24 bytes)
-    const size_t list_b = (8 * ((size_t)M + 1) + 15) & ~(size_t)15, hook_b = (4 * ((size_t)M + 1) + 15) & ~(size_t)15;
-    if (M) {
-        if ((rc = stage_buffer(c, c->illum_out, c->illum_out_bytes, std::max(list_b + hook_b + 16 * ((size_t)M + 1), 80 * (size_t)M + 64))) != MRTX_OK)
-            return rc;
-        char* ob = reinterpret_cast<char*>(c->illum_out);
-        q.list = reinterpret_cast<unsigned long long*>(ob);
-        q.hook = reinterpret_cast<uint32_t*>(ob + list_b);
-        q.edges = reinterpret_cast<BowlEdge*>(ob + list_b + hook_b);
-        HIPCHK(c, mrtx_launch_bowls_list(q, c->stream));
-        launches++;
-        uint32_t n_edges = 0;
-        for (;;) {                                              // a round halves the components that still have a cross edge
-            HIPCHK(c, mrtx_launch_bowls_round(q, c->stream, &launches));
-            HIPCHK(c, hipMemcpyAsync(head, tb, sizeof head, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (head[2] == n_edges) break;                      // nothing hooked: no component has a cross edge left
-            n_edges = head[2];
-            n_rounds++;
-        }
-        if ((rc = bowls_lap(c, &ms)) != MRTX_OK) return rc;
-        if (head[3] != M || head[4] || n_edges > M) {
-            report();
-            return fail(c, MRTX_E_DEVICE, "the bowl stage listed %u of %u minima and chose %u edges", head[3], M, n_edges);
-        }
-        edges.resize(n_edges);
-        HIPCHK(c, hipMemcpy(minima.data(), q.list, 8 * (size_t)M, hipMemcpyDeviceToHost));
-        if (n_edges) HIPCHK(c, hipMemcpy(edges.data(), q.edges, sizeof(BowlEdge) * (size_t)n_edges, hipMemcpyDeviceToHost));
-    } else if ((rc = bowls_lap(c, &ms)) != MRTX_OK) {
-        return rc;
-    }
-    // ---- the host's share: proportional to the minima
-    std::vector<MrtxBowl> rec;
-    std::vector<BowlWalk> walk;
-    bowls_tree(minima, edges, (uint32_t)N, rec, walk);
-    const uint64_t total = rec.size();
-    if (!has_bowls || total > bowl_cap) {
-        report();
-        *n_bowls = total;
-        if (rounds) *rounds = n_rounds;
-        if (has_bowls)
-            return fail(c, MRTX_E_INVALID, "the bowl table is too small: %llu bowls are needed (bowl_cap = %llu)", (unsigned long long)total,
-                        (unsigned long long)bowl_cap);
-        return MRTX_OK;
-    }
-    // ---- the labels and the sums of each bowl's own nodes
-    q.n_bowls = (uint32_t)total;
-    q.label = host_label ? reinterpret_cast<int32_t*>(tb + label_at) : static_cast<int32_t*>(dev_label);
-    std::vector<unsigned long long> own(3 * (size_t)total, 0ull);
-    if (total || has_label) {
-        if (total) {
-            char* ob = reinterpret_cast<char*>(c->illum_out);
-            q.walk = reinterpret_cast<const BowlWalk*>(ob);
-            q.own = reinterpret_cast<unsigned long long*>(ob + sizeof(BowlWalk) * (size_t)total);
-            HIPCHK(c, hipMemcpyAsync(ob, walk.data(), sizeof(BowlWalk) * (size_t)total, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemsetAsync(q.own, 0, 24 * (size_t)total, c->stream));
-        }
-        HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-        HIPCHK(c, mrtx_launch_bowls_label(q, c->stream, &launches));
-        if ((rc = bowls_lap(c, &ms)) != MRTX_OK) return rc;
-        if (total) HIPCHK(c, hipMemcpy(own.data(), q.own, 24 * (size_t)total, hipMemcpyDeviceToHost));
-    }
-    bowls_finish(rec, own, w->invert != 0);
-    report();
-    *n_bowls = total;
-    if (rounds) *rounds = n_rounds;
-    if (total) {
-        if (host_bowls) std::memcpy(host_bowls, rec.data(), sizeof(MrtxBowl) * (size_t)total);
-        else HIPCHK(c, hipMemcpy(dev_bowls, rec.data(), sizeof(MrtxBowl) * (size_t)total, hipMemcpyHostToDevice));
-    }
-    if (host_label) HIPCHK(c, hipMemcpy(host_label, q.label, 4 * N, hipMemcpyDeviceToHost));
     return MRTX_OK;
 }
 

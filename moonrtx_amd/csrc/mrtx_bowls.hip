@@ -25,10 +25,12 @@
 #include <stdint.h>
 
 #include "mrtx_bowls.h"
+#include "mrtx_lattice_dev.h"
 
 namespace mrtx_bw {
 
 typedef unsigned long long u64;
+using namespace mrtx_lat;       // xor64
 
 constexpr u64 kNoKey = ~0ull;
 
@@ -262,11 +264,6 @@ struct OwnSum {
     u64 weight, wz;
     uint32_t count;
 };
-
-__device__ __forceinline__ u64 xor64(u64 v, int m) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, m), hi = __shfl_xor((uint32_t)(v >> 32), m);
-    return ((u64)hi << 32) | lo;
-}
 
 __device__ __forceinline__ OwnSum wave_sum(OwnSum v) {
     for (int m = 1; m < 64; m <<= 1) {

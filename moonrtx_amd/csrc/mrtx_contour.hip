@@ -4,32 +4,11 @@
 // All integer work; every atomic is an integer count of something that never happens or of a bad input, so no byte depends on
 // a schedule.
 #include "mrtx_contour.h"
+#include "mrtx_lattice_dev.h"
 
 namespace mrtx_ct {
 using u64 = unsigned long long;
-
-__device__ __forceinline__ uint2 add2(uint2 a, uint2 b) { return make_uint2(a.x + b.x, a.y + b.y); }
-
-// the exclusive scan of v over the block's 256 threads; *total receives the block's sum.  sh: 4 entries.
-__device__ __forceinline__ uint2 block_scan(uint2 v, uint2* sh, uint2* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint2 inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t ax = __shfl_up(inc.x, d), ay = __shfl_up(inc.y, d);
-        if (lane >= d) { inc.x += ax; inc.y += ay; }
-    }
-    __syncthreads();            // sh may still be read from the call before
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    uint2 off = make_uint2(0, 0), tot = make_uint2(0, 0);
-    for (int k = 0; k < 4; k++) {
-        const uint2 s = sh[k];
-        if (k < w) off = add2(off, s);
-        tot = add2(tot, s);
-    }
-    *total = tot;
-    return make_uint2(off.x + inc.x - v.x, off.y + inc.y - v.y);
-}
+using namespace mrtx_lat;       // add2, block_scan
 
 // the number of levels <= z: the node is above level l iff l < rank.  MRTX_CT_NORANK for a void node and for a height outside
 // the range, which *nbad (if given) counts.

@@ -22,10 +22,12 @@
 #include <stdint.h>
 
 #include "mrtx_fill.h"
+#include "mrtx_lattice_dev.h"
 
 namespace mrtx_fl {
 
 typedef unsigned long long u64;
+using namespace mrtx_lat;       // label_ok, xor64
 
 constexpr int32_t kNone = 0x7FFFFFFF;                             // MRTX_FILL_NONE: no outlet reached (yet)
 
@@ -215,8 +217,6 @@ __global__ void __launch_bounds__(256) fill_sweep_kernel(const FillC q) {
 }
 
 // ---- the catalogue
-__device__ __forceinline__ bool label_ok(uint32_t n_regions, int32_t l) { return l >= 0 && (uint32_t)l < n_regions; }
-
 __global__ void __launch_bounds__(256) basins_init_kernel(const BasinC q) {
     for (uint32_t r = blockIdx.x * 256u + threadIdx.x; r < q.n_regions; r += gridDim.x * 256u) {
         BasinRec e;
@@ -239,11 +239,6 @@ struct BasinSum {
         return v;
     }
 };
-
-__device__ __forceinline__ u64 xor64(u64 v, int m) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, m), hi = __shfl_xor((uint32_t)(v >> 32), m);
-    return ((u64)hi << 32) | lo;
-}
 
 // the sum over the wave's 64 lanes, in every lane (a lane that takes no part passes none())
 __device__ __forceinline__ BasinSum wave_sum(BasinSum v) {

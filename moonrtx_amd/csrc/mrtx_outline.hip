@@ -4,11 +4,11 @@
 // (contract).
 // All integer work; every atomic is an integer sum, so no byte depends on a schedule.
 #include "mrtx_outline.h"
+#include "mrtx_lattice_dev.h"
 
 namespace mrtx_ol {
 using u64 = unsigned long long;
-
-__device__ __forceinline__ bool label_ok(uint32_t n_regions, int32_t l) { return l >= 0 && (uint32_t)l < n_regions; }
+using namespace mrtx_lat;       // label_ok, add2, block_scan
 
 // the label of node (i, j): -1 outside the lattice (a column past either end is the other end's with wrap) and for a bad entry.
 // *v receives the node's index when it lies inside.
@@ -28,29 +28,6 @@ __device__ __forceinline__ int32_t t_y(int k) { return k == 1 ? 1 : k == 3 ? -1 
 __device__ __forceinline__ int32_t t_x(int k) { return k == 0 ? 1 : k == 2 ? -1 : 0; }
 __device__ __forceinline__ int32_t d_y(int k) { return k == 0 ? -1 : k == 2 ? 1 : 0; }
 __device__ __forceinline__ int32_t d_x(int k) { return k == 1 ? 1 : k == 3 ? -1 : 0; }
-
-__device__ __forceinline__ uint2 add2(uint2 a, uint2 b) { return make_uint2(a.x + b.x, a.y + b.y); }
-
-// the exclusive scan of v over the block's 256 threads; *total receives the block's sum.  sh: 4 entries.
-__device__ __forceinline__ uint2 block_scan(uint2 v, uint2* sh, uint2* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint2 inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t ax = __shfl_up(inc.x, d), ay = __shfl_up(inc.y, d);
-        if (lane >= d) { inc.x += ax; inc.y += ay; }
-    }
-    __syncthreads();            // sh may still be read from the call before
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    uint2 off = make_uint2(0, 0), tot = make_uint2(0, 0);
-    for (int k = 0; k < 4; k++) {
-        const uint2 s = sh[k];
-        if (k < w) off = add2(off, s);
-        tot = add2(tot, s);
-    }
-    *total = tot;
-    return make_uint2(off.x + inc.x - v.x, off.y + inc.y - v.y);
-}
 
 // the boundary bits of node n and the check of its label
 __device__ __forceinline__ uint32_t node_bits(const OutlineC& q, int32_t n, uint32_t* nbad) {

@@ -22,10 +22,12 @@
 #include <stdint.h>
 
 #include "mrtx_proximity.h"
+#include "mrtx_lattice_dev.h"
 
 namespace mrtx_px {
 
 typedef unsigned long long u64;
+using namespace mrtx_lat;       // label_ok, value_now, check_labels
 
 constexpr int TW = MRTX_PX_TW;
 constexpr int TILE = MRTX_PX_TILE;
@@ -214,18 +216,8 @@ __global__ void __launch_bounds__(64) prox_scan_kernel(const ProxC q) {
 }
 
 // ---- the reach of labelled regions
-__device__ __forceinline__ bool label_ok(uint32_t n_regions, int32_t l) { return l >= 0 && (uint32_t)l < n_regions; }
-
-__device__ __forceinline__ u64 value_now(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int32_t value_now(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 __global__ void __launch_bounds__(256) check_kernel(const int32_t* labels, int64_t N, uint32_t n_regions, uint32_t* out) {
-    uint32_t bad = 0;
-    for (int64_t n = blockIdx.x * (int64_t)256 + threadIdx.x; n < N; n += (int64_t)gridDim.x * 256) {
-        const int32_t l = labels[n];
-        bad += l < -1 || (l >= 0 && (uint32_t)l >= n_regions);
-    }
-    if (bad) atomicAdd(out, bad);
+    check_labels(labels, N, n_regions, out);
 }
 
 __global__ void __launch_bounds__(256) reach_init_kernel(const ReachC q) {

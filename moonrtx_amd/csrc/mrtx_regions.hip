@@ -24,8 +24,10 @@
 #include <stdint.h>
 
 #include "mrtx_regions.h"
+#include "mrtx_lattice_dev.h"
 
 namespace mrtx_rg {
+using namespace mrtx_lat;       // value_now
 
 constexpr int TH = MRTX_RG_TH, TW = MRTX_RG_TW, TN = TH * TW;
 constexpr int CHUNK = MRTX_RG_CHUNK;
@@ -243,11 +245,6 @@ __global__ void __launch_bounds__(256) stats_init_kernel(const RegionStatsC q) {
 
 // a table entry is a region's iff 0 <= l < n_regions; -1 is outside every region; anything else is counted as bad
 __device__ __forceinline__ bool label_ok(const RegionStatsC& q, int32_t l) { return l >= 0 && (uint32_t)l < q.n_regions; }
-
-// a record's field as every workgroup of the device sees it
-__device__ __forceinline__ int32_t value_now(const int32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 __global__ void __launch_bounds__(256) stats_root_kernel(const RegionStatsC q) {
     const int64_t N = (int64_t)q.rows * q.cols;

@@ -20,27 +20,20 @@
 #include <stdint.h>
 
 #include "mrtx_zonal.h"
+#include "mrtx_lattice_dev.h"
 
 namespace mrtx_zn {
 
 typedef unsigned long long u64;
+using namespace mrtx_lat;       // label_ok, value_now, check_labels
 
 // a wave takes a stretch of STRETCH x 64 consecutive nodes, 64 at a time, as the catalogue's stats_sum_kernel does
 constexpr int STRETCH = 16;
 // distinct (region, column) keys a wave peels before the lanes that are left add on their own
 constexpr int PEEL = 8;
 
-__device__ __forceinline__ bool label_ok(uint32_t n_regions, int32_t l) { return l >= 0 && (uint32_t)l < n_regions; }
-
-__device__ __forceinline__ u64 value_now(const u64* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 __global__ void __launch_bounds__(256) check_kernel(const int32_t* labels, int64_t N, uint32_t n_regions, uint32_t* out) {
-    uint32_t bad = 0;
-    for (int64_t n = blockIdx.x * (int64_t)256 + threadIdx.x; n < N; n += (int64_t)gridDim.x * 256) {
-        const int32_t l = labels[n];
-        bad += l < -1 || (l >= 0 && (uint32_t)l >= n_regions);
-    }
-    if (bad) atomicAdd(out, bad);
+    check_labels(labels, N, n_regions, out);
 }
 
 // ---- a value of any plain struct of 32-bit words from another lane

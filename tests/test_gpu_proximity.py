@@ -15,6 +15,7 @@ import re
 import numpy as np
 import pytest
 
+import lattice_cases as lc
 import model_cases as mc
 import proximity_model as pm
 import regions_cases as rc
@@ -28,7 +29,7 @@ from test_gpu_illumination import make
 pytestmark = pytest.mark.gpu
 
 NONE = 2 ** 64 - 1
-CMAX = 2 ** 29
+CMAX = lc.CMAX
 VARIANTS = ("prune", "brute")
 POLAR = ((22560, 0, 40, 96, 12, 1), (23040, 1152))
 
@@ -298,11 +299,8 @@ def test_both_modes_and_the_reach_on_region_labels(rt, monkeypatch, name):
     assert np.array_equal(radius, np.where(want["d2_max"] == np.uint64(NONE), np.inf, np.sqrt(want["d2_max"].astype(np.float64)) * 0.5))
 
 
-def reach_call(rt, rows, cols, labels=None, n=1, d2=None, near=None, out=None, dev_labels=None, dev_d2=None, dev_near=None,
-               dev_out=None, st=None):
-    ptr = lambda a: None if a is None else a.ctypes.data
-    return rt._lib.mrtx_regions_reach(rt._ctx, rows, cols, dev_labels, ptr(labels), n, dev_d2, ptr(d2), dev_near, ptr(near), dev_out,
-                                      ptr(out), None if st is None else C.byref(st))
+def reach_call(rt, rows, cols, *args, **kw):
+    return lc.reach_call(rt._lib, rt._ctx, rows, cols, *args, **kw)
 
 
 def test_the_reach_from_device_tables_and_on_a_caller_s_table(rt):
@@ -365,62 +363,21 @@ def test_the_reach_refuses_a_bad_label_table_after_the_launch(rt):
     assert_reach_equal(rt.region_reach(labels, n, (d2, near)), pm.reach(labels, n, d2, near), "afterwards")
 
 
-def prox_call(rt, p="default", pos=None, labels=None, near=None, d2=None, dev_pos=None, dev_labels=None, dev_near=None, dev_d2=None,
-              pairs=None, st=None):
-    ptr = lambda a: None if a is None else a.ctypes.data
-    if isinstance(p, str):
-        p = _lib.MrtxProximity(8, 9, 0, 0)
-    return rt._lib.mrtx_proximity(rt._ctx, None if p is None else C.byref(p), dev_pos, ptr(pos), dev_labels, ptr(labels), dev_near,
-                                  ptr(near), dev_d2, ptr(d2), None if pairs is None else C.byref(pairs),
-                                  None if st is None else C.byref(st))
+def prox_call(rt, **kw):
+    return lc.prox_call(rt._lib, rt._ctx, **kw)
 
 
 def test_every_refusal(rt, monkeypatch):
-    P = _lib.MrtxProximity
     pos, labels = planar(8, 9), sprinkle(8, 9, 0.3, 1)
     near, d2 = np.zeros((8, 9), np.int32), np.zeros((8, 9), np.uint64)
     dev = DeviceBuffer(8192)
     dev.upload(np.zeros(2048, np.int32))
     base = dict(pos=pos, labels=labels, near=near, d2=d2)
-    D = dict(dev_pos=dev.ptr, dev_labels=dev.ptr + 1024, dev_near=dev.ptr + 2048, dev_d2=dev.ptr + 4096)     # 864, 288, 288, 576 bytes
-    off = pos.copy()
-    off[7, 8, 2] = CMAX + 1
-    low = pos.copy()
-    low[0, 0, 0] = -CMAX - 1
-    cases = [
-        ("null proximity block", dict(base, p=None)),
-        ("empty lattice", dict(base, p=P(0, 9, 0, 0))),
-        ("empty lattice", dict(base, p=P(8, -1, 0, 0))),
-        ("at most 2\\^31 nodes", dict(base, p=P(65536, 32769, 0, 0))),
-        ("mode must be", dict(base, p=P(8, 9, 2, 0))),
-        ("mode must be", dict(base, p=P(8, 9, -1, 0))),
-        ("reserved must be 0", dict(base, p=P(8, 9, 0, 1))),
-        ("exactly one of dev_pos and host_pos", dict(base, pos=None)),
-        ("exactly one of dev_pos and host_pos", dict(base, dev_pos=dev.ptr)),
-        ("exactly one of dev_labels and host_labels", dict(base, labels=None)),
-        ("exactly one of dev_labels and host_labels", dict(base, dev_labels=dev.ptr)),
-        ("exactly one of dev_nearest and host_nearest", dict(base, near=None)),
-        ("exactly one of dev_nearest and host_nearest", dict(base, dev_near=dev.ptr)),
-        ("exactly one of dev_dist2 and host_dist2", dict(base, d2=None)),
-        ("exactly one of dev_dist2 and host_dist2", dict(base, dev_d2=dev.ptr)),
-        ("dev_dist2 must be 8-byte aligned", dict(base, d2=None, dev_d2=dev.ptr + 4)),
-        ("dev_pos must be 4-byte aligned", dict(base, pos=None, dev_pos=dev.ptr + 2)),
-        ("dev_labels must be 4-byte aligned", dict(base, labels=None, dev_labels=dev.ptr + 1)),
-        ("dev_nearest must be 4-byte aligned", dict(base, near=None, dev_near=dev.ptr + 2)),
-        ("must not overlap", dict(D, dev_labels=dev.ptr + 860)),
-        ("must not overlap", dict(D, dev_near=dev.ptr + 1024 + 284)),
-        ("must not overlap", dict(D, dev_d2=dev.ptr + 2048 + 280)),
-        ("must not overlap", dict(D, dev_d2=dev.ptr + 8)),
-        ("must not overlap", dict(D, dev_near=dev.ptr + 4096 + 572)),
-        ("must not overlap", dict(D, dev_labels=dev.ptr + 4096)),
-        ("coordinate 2 of node 71 must lie in -2\\^29 .. 2\\^29", dict(base, pos=off)),
-        ("coordinate 0 of node 0 must lie in -2\\^29 .. 2\\^29", dict(base, pos=low)),
-    ]
+    D = lc.prox_device_tables(dev.ptr)
+    off = lc.prox_off_positions(pos)
     try:
-        for text, kw in cases:
-            assert prox_call(rt, **kw) == -1, text
-            msg = rt._lib.mrtx_last_error(rt._ctx).decode()
-            assert re.search(text, msg), (text, msg)
+        for text, kw in lc.prox_refusals(pos, labels, near, d2, dev.ptr):
+            lc.refused(rt._lib, rt._ctx, prox_call(rt, **kw), text)
             assert (near == 0).all() and (d2 == 0).all(), text
         # an unknown value of the switch is refused by name
         monkeypatch.setenv("MOONRT_PROXIMITY", "fast")
@@ -439,32 +396,8 @@ def test_every_refusal(rt, monkeypatch):
             rt.proximity(labels, off.astype(np.int64))
         # the reach's own refusals
         out = np.zeros(4, rg.REACH_DTYPE)
-        R = dict(labels=labels, d2=d2, near=near, out=out, n=4)
-        reach_cases = [
-            ("empty lattice", dict(R, rows=0)),
-            ("at most 2\\^31 nodes", dict(R, rows=65536, cols=32769)),
-            ("exactly one of dev_labels and host_labels", dict(R, labels=None)),
-            ("exactly one of dev_labels and host_labels", dict(R, dev_labels=dev.ptr)),
-            ("exactly one of dev_dist2 and host_dist2", dict(R, d2=None)),
-            ("exactly one of dev_dist2 and host_dist2", dict(R, dev_d2=dev.ptr)),
-            ("exactly one of dev_nearest and host_nearest", dict(R, near=None)),
-            ("exactly one of dev_nearest and host_nearest", dict(R, dev_near=dev.ptr)),
-            ("exactly one of dev_out and host_out", dict(R, out=None)),
-            ("exactly one of dev_out and host_out", dict(R, dev_out=dev.ptr)),
-            ("exceeds the lattice", dict(R, n=73)),
-            ("dev_labels must be 4-byte aligned", dict(R, labels=None, dev_labels=dev.ptr + 2)),
-            ("dev_dist2 must be 8-byte aligned", dict(R, d2=None, dev_d2=dev.ptr + 4)),
-            ("dev_nearest must be 4-byte aligned", dict(R, near=None, dev_near=dev.ptr + 1)),
-            ("dev_out must be 8-byte aligned", dict(R, out=None, dev_out=dev.ptr + 4)),
-            ("must not overlap", dict(R, labels=None, dev_labels=dev.ptr, out=None, dev_out=dev.ptr + 280)),
-            ("must not overlap", dict(R, d2=None, dev_d2=dev.ptr + 64, out=None, dev_out=dev.ptr)),
-            ("must not overlap", dict(R, near=None, dev_near=dev.ptr + 120, out=None, dev_out=dev.ptr)),
-        ]
-        for text, kw in reach_cases:
-            kw = dict(dict(rows=8, cols=9), **kw)
-            assert reach_call(rt, **kw) == -1, text
-            msg = rt._lib.mrtx_last_error(rt._ctx).decode()
-            assert re.search(text, msg), (text, msg)
+        for text, kw in lc.reach_refusals(labels, d2, near, out, dev.ptr):
+            lc.refused(rt._lib, rt._ctx, reach_call(rt, **kw), text)
             assert (out.view(np.uint8) == 0).all(), text
         # the context still works
         want = pm.proximity(labels, pos)

@@ -10,6 +10,7 @@ from datetime import datetime, timezone
 import numpy as np
 import pytest
 
+import lattice_cases as lc
 import model_cases as mc
 import regions_cases as rc
 import regions_model as model
@@ -116,15 +117,11 @@ def test_launches_do_not_depend_on_the_set(rt):
 
 
 # ---- the ABI straight
-def label_call(rt, r, dev_field=None, host_field=None, dev_mask=None, host_mask=None, dev_labels=None, host_labels=None,
-               n=None, block=True):
-    st = _lib.MrtxStats()
-    return rt._lib.mrtx_regions_label(rt._ctx, C.byref(r) if block else None, dev_field, host_field, dev_mask, host_mask,
-                                      dev_labels, host_labels, n, C.byref(st))
+def label_call(rt, r, **kw):
+    return lc.label_call(rt._lib, rt._ctx, r, **kw)
 
 
-def block(rows=8, cols=9, wrap=0, conn=4, n_ch=1, ch=0, lo=-INF, hi=INF, reserved=0):
-    return _lib.MrtxRegions(rows, cols, wrap, conn, n_ch, ch, lo, hi, reserved)
+block = lc.regions_block
 
 
 def test_every_refusal(rt):
@@ -133,67 +130,15 @@ def test_every_refusal(rt):
     labels = np.full((8, 9), 7, np.int32)
     dev = DeviceBuffer(4096)
     dev2 = DeviceBuffer(4096)
-    M, F, L = mask.ctypes.data, field.ctypes.data, labels.ctypes.data
     n = C.c_uint32(4321)
-    N = C.byref(n)
-    cases = [
-        ("null regions block", dict(r=block(), host_mask=M, host_labels=L, n=N, block=False)),
-        ("reserved must be 0", dict(r=block(reserved=1), host_mask=M, host_labels=L, n=N)),
-        ("empty lattice", dict(r=block(rows=0), host_mask=M, host_labels=L, n=N)),
-        ("empty lattice", dict(r=block(cols=-3), host_mask=M, host_labels=L, n=N)),
-        ("at most 2\\^31 nodes", dict(r=block(rows=65536, cols=32769), host_mask=M, host_labels=L, n=N)),
-        ("wrap must be 0 or 1", dict(r=block(wrap=2), host_mask=M, host_labels=L, n=N)),
-        ("cols >= 3", dict(r=block(cols=2, wrap=1), host_mask=M, host_labels=L, n=N)),
-        ("connectivity must be 4 or 8", dict(r=block(conn=6), host_mask=M, host_labels=L, n=N)),
-        ("exactly one of a field and a mask", dict(r=block(), host_mask=M, host_field=F, host_labels=L, n=N)),
-        ("exactly one of a field and a mask", dict(r=block(), dev_mask=dev.ptr, host_field=F, host_labels=L, n=N)),
-        ("exactly one of a field and a mask", dict(r=block(), host_labels=L, n=N)),
-        ("exactly one of dev_field and host_field", dict(r=block(), dev_field=dev.ptr, host_field=F, host_labels=L, n=N)),
-        ("exactly one of dev_mask and host_mask", dict(r=block(), dev_mask=dev.ptr, host_mask=M, host_labels=L, n=N)),
-        ("exactly one of dev_labels and host_labels", dict(r=block(), host_mask=M, n=N)),
-        ("exactly one of dev_labels and host_labels", dict(r=block(), host_mask=M, host_labels=L, dev_labels=dev.ptr, n=N)),
-        ("null n_regions", dict(r=block(), host_mask=M, host_labels=L)),
-        ("n_ch must lie in 1 .. 16", dict(r=block(n_ch=0), host_field=F, host_labels=L, n=N)),
-        ("n_ch must lie in 1 .. 16", dict(r=block(n_ch=17), host_field=F, host_labels=L, n=N)),
-        ("ch must lie in", dict(r=block(n_ch=2, ch=2), host_field=F, host_labels=L, n=N)),
-        ("ch must lie in", dict(r=block(ch=-1), host_field=F, host_labels=L, n=N)),
-        ("lo must be <= hi", dict(r=block(lo=1.0, hi=0.5), host_field=F, host_labels=L, n=N)),
-        ("must not be NaN", dict(r=block(lo=math.nan), host_field=F, host_labels=L, n=N)),
-        ("must not be NaN", dict(r=block(hi=math.nan), host_field=F, host_labels=L, n=N)),
-        ("dev_field must be 4-byte aligned", dict(r=block(), dev_field=dev.ptr + 2, dev_labels=dev2.ptr, n=N)),
-        ("dev_labels must be 4-byte aligned", dict(r=block(), dev_mask=dev.ptr, dev_labels=dev2.ptr + 1, n=N)),
-        ("must not overlap", dict(r=block(), dev_mask=dev.ptr, dev_labels=dev.ptr + 68, n=N)),
-        ("must not overlap", dict(r=block(), dev_field=dev.ptr + 4, dev_labels=dev.ptr, n=N)),
-    ]
     try:
-        for text, kw in cases:
-            assert label_call(rt, **kw) == -1, text
-            msg = rt._lib.mrtx_last_error(rt._ctx).decode()
-            assert __import__("re").search(text, msg), (text, msg)
+        for text, kw in lc.label_refusals(mask, field, labels, n, dev.ptr, dev2.ptr):
+            lc.refused(rt._lib, rt._ctx, label_call(rt, **kw), text)
             assert n.value == 4321 and (labels == 7).all(), text
         # the catalogue's own
         table = np.zeros(4, rg.REGION_DTYPE)
-        T = table.ctypes.data
-
-        def stats_call(rows=8, cols=9, wrap=0, dev_labels=None, host_labels=None, n_regions=4, dev_out=None, host_out=None):
-            return rt._lib.mrtx_regions_stats(rt._ctx, rows, cols, wrap, dev_labels, host_labels, n_regions, None, dev_out,
-                                              host_out, None)
-        for text, kw in [
-            ("empty lattice", dict(rows=0, host_labels=L, host_out=T)),
-            ("cols >= 3", dict(cols=2, wrap=1, host_labels=L, host_out=T)),
-            ("wrap must be 0 or 1", dict(wrap=-1, host_labels=L, host_out=T)),
-            ("exactly one of dev_labels and host_labels", dict(host_out=T)),
-            ("exactly one of dev_labels and host_labels", dict(dev_labels=dev.ptr, host_labels=L, host_out=T)),
-            ("exactly one of dev_out and host_out", dict(host_labels=L)),
-            ("exactly one of dev_out and host_out", dict(host_labels=L, dev_out=dev.ptr, host_out=T)),
-            ("exceeds the lattice", dict(host_labels=L, host_out=T, n_regions=73)),
-            ("dev_labels must be 4-byte aligned", dict(dev_labels=dev.ptr + 2, host_out=T)),
-            ("dev_out must be 8-byte aligned", dict(host_labels=L, dev_out=dev.ptr + 4)),
-            ("must not overlap", dict(dev_labels=dev.ptr, dev_out=dev.ptr + 280)),
-        ]:
-            assert stats_call(**kw) == -1, text
-            msg = rt._lib.mrtx_last_error(rt._ctx).decode()
-            assert __import__("re").search(text, msg), (text, msg)
+        for text, kw in lc.stats_refusals(labels, table, dev.ptr):
+            lc.refused(rt._lib, rt._ctx, lc.stats_call(rt._lib, rt._ctx, **kw), text)
             assert (table.view(np.uint8) == 0).all(), text
         # the context still works
         case = rc.BY_NAME["33x65_wrapped"]

@@ -14,6 +14,7 @@ import math
 import numpy as np
 import pytest
 
+import lattice_cases as lc
 import model_cases as mc
 import regions_cases as rc
 import zonal_model as zm
@@ -309,11 +310,8 @@ def test_histogram_edges(rt, monkeypatch, n_bins):
                 assert_records_equal(z, zm.zonal(lab, 3, x, SCALE, weights), "beside the histogram")
 
 
-def zonal_call(rt, z, labels=None, dev_labels=None, n=1, field=None, dev_field=None, weights=None, dev_out=None, out=None,
-               dev_hist=None, hist=None, block=True):
-    ptr = lambda a: None if a is None else a.ctypes.data
-    return rt._lib.mrtx_regions_zonal(rt._ctx, C.byref(z) if block else None, dev_labels, ptr(labels), n, dev_field, ptr(field),
-                                      ptr(weights), dev_out, ptr(out), dev_hist, ptr(hist), None)
+def zonal_call(rt, z, **kw):
+    return lc.zonal_call(rt._lib, rt._ctx, z, **kw)
 
 
 def test_heavy_weights_and_the_overflow_guard(rt, monkeypatch):
@@ -343,100 +341,27 @@ def test_heavy_weights_and_the_overflow_guard(rt, monkeypatch):
     assert_records_equal(run_zonal(rt, lab, 1, big, w, True, scale=2.0 ** -15), zm.zonal(lab, 1, big, 2.0 ** -15, w), "a lower scale")
 
 
-def spec(rows=8, cols=9, wrap=0, n_ch=1, scale=1.0, hist_ch=0, n_bins=0, lo=0.0, inv_w=1.0, reserved=0):
-    return _lib.MrtxZonalSpec(rows, cols, wrap, n_ch, scale, hist_ch, n_bins, lo, inv_w, reserved)
+spec = lc.zonal_spec
 
 
 def test_every_refusal(rt, monkeypatch):
-    import re
     labels = np.zeros((8, 9), np.int32)
     field = np.ones((8, 9), F32)
     out = np.zeros(4, rg.ZONAL_DTYPE)
     hist = np.zeros(4 * 6, np.uint64)
     dev, dev2 = DeviceBuffer(8192), DeviceBuffer(8192)
     base = dict(labels=labels, field=field, out=out, n=4)
-    H = dict(base, hist=hist)
-    cases = [
-        ("null zonal block", dict(base, z=spec(), block=False)),
-        ("reserved must be 0", dict(base, z=spec(reserved=1))),
-        ("empty lattice", dict(base, z=spec(rows=0))),
-        ("empty lattice", dict(base, z=spec(cols=-3))),
-        ("at most 2\\^31 nodes", dict(base, z=spec(rows=65536, cols=32769))),
-        ("wrap must be 0 or 1", dict(base, z=spec(wrap=2))),
-        ("cols >= 3", dict(base, z=spec(cols=2, wrap=1))),
-        ("n_ch must lie in 1 .. 16", dict(base, z=spec(n_ch=0))),
-        ("n_ch must lie in 1 .. 16", dict(base, z=spec(n_ch=17))),
-        ("scale must be finite and > 0", dict(base, z=spec(scale=0.0))),
-        ("scale must be finite and > 0", dict(base, z=spec(scale=-1.0))),
-        ("scale must be finite and > 0", dict(base, z=spec(scale=INF))),
-        ("scale must be finite and > 0", dict(base, z=spec(scale=math.nan))),
-        ("n_bins must lie in 0 .. 4096", dict(H, z=spec(n_bins=-1))),
-        ("n_bins must lie in 0 .. 4096", dict(H, z=spec(n_bins=4097))),
-        ("hist_ch must lie in", dict(H, z=spec(n_bins=4, hist_ch=1))),
-        ("hist_ch must lie in", dict(H, z=spec(n_bins=4, hist_ch=-1))),
-        ("hist_lo must be finite", dict(H, z=spec(n_bins=4, lo=INF))),
-        ("hist_lo must be finite", dict(H, z=spec(n_bins=4, lo=math.nan))),
-        ("hist_inv_w finite and > 0", dict(H, z=spec(n_bins=4, inv_w=0.0))),
-        ("hist_inv_w finite and > 0", dict(H, z=spec(n_bins=4, inv_w=-2.0))),
-        ("hist_inv_w finite and > 0", dict(H, z=spec(n_bins=4, inv_w=INF))),
-        ("exactly one of dev_labels and host_labels", dict(base, z=spec(), labels=None)),
-        ("exactly one of dev_labels and host_labels", dict(base, z=spec(), dev_labels=dev.ptr)),
-        ("exactly one of dev_field and host_field", dict(base, z=spec(), field=None)),
-        ("exactly one of dev_field and host_field", dict(base, z=spec(), dev_field=dev.ptr)),
-        ("exactly one of dev_out and host_out", dict(base, z=spec(), out=None)),
-        ("exactly one of dev_out and host_out", dict(base, z=spec(), dev_out=dev.ptr)),
-        ("without bins dev_hist and host_hist must be NULL", dict(H, z=spec())),
-        ("without bins dev_hist and host_hist must be NULL", dict(base, z=spec(), dev_hist=dev.ptr)),
-        ("exactly one of dev_hist and host_hist", dict(base, z=spec(n_bins=4))),
-        ("exactly one of dev_hist and host_hist", dict(H, z=spec(n_bins=4), dev_hist=dev.ptr)),
-        ("exceeds the lattice", dict(base, z=spec(), n=73)),
-        ("at most 2\\^28 columns", dict(H, z=spec(rows=32768, cols=32768, n_bins=4094), n=65537)),
-        ("dev_labels must be 4-byte aligned", dict(base, z=spec(), labels=None, dev_labels=dev.ptr + 2)),
-        ("dev_field must be 4-byte aligned", dict(base, z=spec(), field=None, dev_field=dev.ptr + 1)),
-        ("dev_out must be 8-byte aligned", dict(base, z=spec(), out=None, dev_out=dev.ptr + 4)),
-        ("dev_hist must be 8-byte aligned", dict(base, z=spec(n_bins=4), dev_hist=dev.ptr + 4)),
-        ("must not overlap", dict(base, z=spec(), labels=None, dev_labels=dev.ptr, out=None, dev_out=dev.ptr + 280)),
-        ("must not overlap", dict(base, z=spec(), field=None, dev_field=dev.ptr + 8, out=None, dev_out=dev.ptr)),
-        ("must not overlap", dict(base, z=spec(n_bins=4), labels=None, dev_labels=dev.ptr, dev_hist=dev.ptr + 8)),
-        ("must not overlap", dict(base, z=spec(n_bins=4), field=None, dev_field=dev2.ptr, dev_hist=dev2.ptr + 8)),
-        ("must not overlap", dict(base, z=spec(n_bins=4), out=None, dev_out=dev2.ptr, dev_hist=dev2.ptr + 216)),
-    ]
     shape_out = np.zeros(4, rg.SHAPE_DTYPE)
-    ew, ns = np.ones(8, np.uint32), np.ones(9, np.uint32)
-
-    def shape_call(rows=8, cols=9, wrap=0, conn=4, dev_labels=None, host_labels=None, n=4, side_ew=None, side_ns=None, dev_out=None,
-                   host_out=None):
-        ptr = lambda a: None if a is None else a.ctypes.data
-        return rt._lib.mrtx_regions_shape(rt._ctx, rows, cols, wrap, conn, dev_labels, ptr(host_labels), n, ptr(side_ew), ptr(side_ns),
-                                          dev_out, ptr(host_out), None)
     S = dict(host_labels=labels, host_out=shape_out)
-    shape_cases = [
-        ("empty lattice", dict(S, rows=0)),
-        ("at most 2\\^31 nodes", dict(S, rows=65536, cols=32769)),
-        ("wrap must be 0 or 1", dict(S, wrap=-1)),
-        ("cols >= 3", dict(S, cols=2, wrap=1)),
-        ("connectivity must be 4 or 8", dict(S, conn=6)),
-        ("exactly one of dev_labels and host_labels", dict(S, host_labels=None)),
-        ("exactly one of dev_labels and host_labels", dict(S, dev_labels=dev.ptr)),
-        ("exactly one of dev_out and host_out", dict(S, host_out=None)),
-        ("exactly one of dev_out and host_out", dict(S, dev_out=dev.ptr)),
-        ("both of side_ew and side_ns or neither", dict(S, side_ew=ew)),
-        ("both of side_ew and side_ns or neither", dict(S, side_ns=ns)),
-        ("exceeds the lattice", dict(S, n=73)),
-        ("dev_labels must be 4-byte aligned", dict(S, host_labels=None, dev_labels=dev.ptr + 2)),
-        ("dev_out must be 8-byte aligned", dict(S, host_out=None, dev_out=dev.ptr + 4)),
-        ("must not overlap", dict(host_labels=None, dev_labels=dev.ptr, dev_out=dev.ptr + 280)),
-    ]
+
+    def shape_call(**kw):
+        return lc.shape_call(rt._lib, rt._ctx, **kw)
     try:
-        for text, kw in cases:
-            assert zonal_call(rt, **kw) == -1, text
-            msg = rt._lib.mrtx_last_error(rt._ctx).decode()
-            assert re.search(text, msg), (text, msg)
+        for text, kw in lc.zonal_refusals(labels, field, out, hist, dev.ptr, dev2.ptr):
+            lc.refused(rt._lib, rt._ctx, zonal_call(rt, **kw), text)
             assert (out.view(np.uint8) == 0).all() and (hist == 0).all(), text
-        for text, kw in shape_cases:
-            assert shape_call(**kw) == -1, text
-            msg = rt._lib.mrtx_last_error(rt._ctx).decode()
-            assert re.search(text, msg), (text, msg)
+        for text, kw in lc.shape_refusals(labels, shape_out, dev.ptr):
+            lc.refused(rt._lib, rt._ctx, shape_call(**kw), text)
             assert (shape_out.view(np.uint8) == 0).all(), text
         # an unknown value of the switch is refused by name, in both calls
         monkeypatch.setenv("MOONRT_REGIONS_ZONAL", "fast")
