@@ -1,6 +1,7 @@
-// mrtx_host.h -- what the host units of libmoonrt.so share (mrtx_api.hip, mrtx_lattice_api.hip): the
-// context, the refusal with its text, and the staging, launch and read-back path of a stage (section 4.21).  Everything in
-// namespace mrtx_host is defined once, in mrtx_api.hip.  Private: not installed, not part of the C ABI.
+// mrtx_host.h -- what the three host units of libmoonrt.so share (mrtx_api.hip, mrtx_terrain_api.hip, mrtx_lattice_api.hip;
+// DESIGN.md sections 4.34 and 4.35): the context, the refusal with its text and the checks every unit words alike, the scene's
+// frame, and the staging, launch and read-back path of a stage (section 4.21).  Every function in namespace mrtx_host is
+// defined once, in mrtx_api.hip.  Private: not installed, not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -107,6 +108,23 @@ namespace mrtx_host {
 // the refusal: the text into the context (if there is one), the code back
 int fail(mrtx_ctx* c, int code, const char* fmt, ...);
 
+// a table comes from the device or from the host: "give exactly one of dev_<what> and host_<what>"
+int one_of(mrtx_ctx* c, const void* dev, const void* host, const char* what);
+
+// an optional table comes from one of them or from neither: "give at most one of dev_<what> and host_<what>"
+int at_most_one(mrtx_ctx* c, const void* dev, const void* host, const char* what);
+
+// The scene as the launches see it: the vector helpers, the Moon frame's rows and the light's constants that build_frame and
+// the per-epoch tables both form, the per-launch constant blocks, and the march's mip levels (built when the step asks)
+constexpr double kPiD = 3.14159265358979323846;
+int check_vec(const double* p);     // three finite numbers
+void cross(const double a[3], const double b[3], double o[3]);
+void moon_rows(const double u[3], const double v[3], double M[3][3]);
+void light_consts(const double M[3][3], const double center[3], const double pos[3], double radius, double radiance, float Lb[3],
+                  float& rL2, float& rad2);
+void build_frame(const mrtx_ctx* c, FrameC& f, FrameCold& k);
+int ensure_mip(mrtx_ctx* c);
+
 // do the two byte ranges share a byte?  A null pointer is no range.
 bool spans_overlap(const void* a, size_t na, const void* b, size_t nb);
 
@@ -145,4 +163,11 @@ int stage_finish(mrtx_ctx* c, const void* dev_out, float* host_out, size_t out_b
         hipError_t e_ = (call);                                                                          \
         if (e_ != hipSuccess)                                                                            \
             return ::mrtx_host::fail((c), MRTX_E_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_)); \
+    } while (0)
+
+// a check or a step that did not pass ends the call with its code
+#define CHK(call)                         \
+    do {                                  \
+        const int rc_ = (call);           \
+        if (rc_ != MRTX_OK) return rc_;   \
     } while (0)

@@ -29,26 +29,8 @@ using namespace mrtx_host;
 
 namespace {
 
-// a check or a step that did not pass ends the call with its code
-#define CHK(call)                         \
-    do {                                  \
-        const int rc_ = (call);           \
-        if (rc_ != MRTX_OK) return rc_;   \
-    } while (0)
-
-// ---- The vocabulary of the argument checks: each returns MRTX_OK or the code of fail() with its text ------------------------
-// a table comes from the device or from the host
-int one_of(mrtx_ctx* c, const void* dev, const void* host, const char* what) {
-    if ((dev == nullptr) == (host == nullptr)) return fail(c, MRTX_E_INVALID, "give exactly one of dev_%s and host_%s", what, what);
-    return MRTX_OK;
-}
-
-// an optional table comes from one of them or from neither
-int at_most_one(mrtx_ctx* c, const void* dev, const void* host, const char* what) {
-    if (dev && host) return fail(c, MRTX_E_INVALID, "give at most one of dev_%s and host_%s", what, what);
-    return MRTX_OK;
-}
-
+// ---- The vocabulary of the argument checks: each returns MRTX_OK or the code of fail() with its text.  CHK, one_of and
+// at_most_one are mrtx_host.h's: the terrain calls word them alike -------------------------------------------------------------
 // a device table (or none) at a multiple of 4 or 8 bytes
 int aligned(mrtx_ctx* c, const void* p, unsigned bytes, const char* name, const char* type) {
     if (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) return fail(c, MRTX_E_INVALID, "%s must be %u-byte aligned (%s)", name, bytes, type);

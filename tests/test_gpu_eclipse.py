@@ -11,6 +11,7 @@ import pytest
 import eclipse_model as em
 import epoch_patterns as ep
 import model_cases as mc
+import terrain_cases as tc
 import thermal_model as tm
 from common import assert_bit_equal
 from moonrtx_amd import _lib, sunlight, volatiles
@@ -339,14 +340,11 @@ def test_refusals(rt, march, column):
     pts = np.array([[10.0, 20.0], [-60.0, 100.0]])
     out = np.full((2, m), np.nan, np.float32)
     dev = DeviceBuffer(2 * m * 4 + 64)
+    base = tc.occult_base(pts, far, earth, out)
 
-    def call(src=far, body=earth, m=m, mode=0, dev_out=None, host=out.ctypes.data, p=pts, n=2, c=ctx):
-        st = MrtxStats()
-        st.launches = 77
-        rc = lib.mrtx_occultation(c, None if p is None else p.ctypes.data, n, None if src is None else src.ctypes.data,
-                                  None if body is None else body.ctypes.data, m, mode, dev_out, host, C.byref(st))
-        assert rc != 0 or st.launches == 1
-        assert rc == 0 or (st.launches == 77 and np.isnan(out).all()), "a refused call launched or wrote"
+    def call(**kw):
+        rc, st = tc.occult_call(lib, ctx, **dict(base, **kw))
+        assert rc == 0 and st.launches == 1
         return rc
 
     def edit(table, col, value, k=5):
@@ -354,28 +352,12 @@ def test_refusals(rt, march, column):
         t[k, col] = value
         return t
     try:
-        assert call(c=None) == E_INVALID
-        assert call(src=None) == E_INVALID and call(body=None) == E_INVALID and call(p=None) == E_INVALID
-        assert call(m=0) == E_INVALID and call(m=-3) == E_INVALID and call(n=0) == E_INVALID
-        for col in (0, 3, 4, 6, 9, 12):
-            for bad in (float("nan"), float("inf")):
-                assert call(src=edit(far, col, bad)) == E_INVALID, (col, bad)
-                assert call(body=edit(earth, col, bad)) == E_INVALID, (col, bad)
-        assert call(src=edit(far, 3, -1.0)) == E_INVALID
-        assert call(body=edit(earth, 3, 0.0)) == E_INVALID and call(body=edit(earth, 3, -2.0)) == E_INVALID
-        near = earth.copy()                     # the body's centre 1.5 Moon radii from the Moon's, its own radius 3.67
-        near[5, 0:3] = near[5, 5:8] + (near[5, 0:3] - near[5, 5:8]) * (1.5 * scene().radius / np.linalg.norm(near[5, 0:3] - near[5, 5:8]))
-        assert call(body=near) == E_INVALID
-        assert b"bounding sphere" in lib.mrtx_last_error(ctx)
-        assert call(src=earth, body=far) == E_INVALID                          # the body beyond the source
-        assert b"nearer" in lib.mrtx_last_error(ctx)
-        for mode in (-1, 2, 7):
-            assert call(mode=mode) == E_INVALID, mode
-        assert call(host=None) == E_INVALID and call(dev_out=dev.ptr) == E_INVALID
-        assert call(mode=1, dev_out=dev.ptr + 4, host=None) == E_INVALID
-        assert b"16-byte" in lib.mrtx_last_error(ctx)
-        assert call(p=np.array([[91.0, 0.0], [0.0, 0.0]])) == E_INVALID
-        assert call(m=(1 << 24) + 1) == E_INVALID
+        rc, st = tc.occult_call(lib, None, **base)
+        assert rc == E_INVALID and st.launches == tc.LAUNCHES and np.isnan(out).all()
+        for text, _, kw in tc.occult_refusals(pts, far, earth, out, scene().radius, dev.ptr):   # the list (tests/terrain_cases.py)
+            rc, st = tc.occult_call(lib, ctx, **kw)
+            tc.refused(lib, ctx, rc, st, text)
+            assert np.isnan(out).all(), "a refused call wrote: " + text
         # the thermal entry: one table without the other, and the tables' own checks
         c = column
         pt3 = np.ascontiguousarray(np.stack([c["lat"][:3], c["lon"][:3]], -1))

@@ -9,6 +9,7 @@ import pytest
 import epoch_patterns as ep
 import model_cases as mc
 import passes_model as pm
+import terrain_cases as tc
 from common import assert_bit_equal
 from moonrtx_amd import _lib
 from moonrtx_amd._lib import PASS_DTYPE, MrtxPasses, MrtxStats
@@ -164,11 +165,7 @@ def test_bit_exact_properties(native_lib):
 
 
 def raw_call(rt, k, lat, lon, hz, pos, dev_out, host_out, cap, total, st, heights=None, dev_hz=None):
-    pts = np.ascontiguousarray(np.stack([lat, lon], -1))
-    keep = (pts, np.ascontiguousarray(pos, np.float64), np.ascontiguousarray(hz, np.float32))
-    return rt._lib.mrtx_horizon_passes(rt._ctx, C.byref(k), pts.ctypes.data, None if heights is None else heights.ctypes.data,
-                                       lat.size, hz.shape[1], dev_hz, None if dev_hz else keep[2].ctypes.data, keep[1].ctypes.data,
-                                       dev_out, host_out, cap, None if total is None else C.byref(total), C.byref(st))
+    return tc.passes_call(rt._lib, rt._ctx, k, lat, lon, hz, pos, dev_out, host_out, cap, total, st, heights, dev_hz)
 
 
 def test_list_sizing(rt):
@@ -257,46 +254,23 @@ def test_refusals(rt):
     R_m = pm.RADIUS_M
     out = np.zeros((4, 8), np.float32)
     buf = DeviceBuffer(4 * 3 * 16 * 16 + 64)
-
-    def refused(k, pos_=pos, dev=None, host=out.ctypes.data, total=None, cap=0, heights=None, what=""):
-        st = MrtxStats()
-        st.launches = 77
-        tot = C.c_uint64(0) if total is None else total
-        rc = raw_call(rt, k, lat, lon, hz, pos_, dev, host, cap, tot, st, heights)
-        assert rc == -1 and st.launches == 77, (what, rc, st.launches)
-
     ok = MrtxPasses(3, 16, _lib.PASSES_SUMMARY, 0, R_m, 0.0)
     try:
         st = MrtxStats()
         assert raw_call(rt, ok, lat, lon, hz, pos, None, out.ctypes.data, 0, None, st) == 0 and st.launches == 1
-        inside = pos.copy()
-        inside[1, 7] = pos[1, 7] / np.linalg.norm(pos[1, 7]) * (1.0005 * R_m)
-        refused(ok, inside, what="a position inside the bounding sphere")
-        # ... which a raise widens: 1.004 R is outside the sphere, but not outside the sphere plus 10 km
+        # 1.004 R is outside the bounding sphere; the list refuses it with a raise of 10 km
         near = pos.copy()
         near[1, 7] = pos[1, 7] / np.linalg.norm(pos[1, 7]) * (1.004 * R_m)
         assert raw_call(rt, ok, lat, lon, hz, near, None, out.ctypes.data, 0, None, MrtxStats()) == 0
-        refused(ok, near, heights=np.full(4, 1e4), what="a position inside the sphere plus the raise")
-        for bad in (np.nan, np.inf):
-            broken = pos.copy()
-            broken[2, 3, 1] = bad
-            refused(ok, broken, what="a non-finite entry")
-        big = MrtxPasses(256, (1 << 16) + 1, _lib.PASSES_SUMMARY, 0, R_m, 0.0)
-        refused(big, what="S * m > 2^24")                       # refused before the table is read
-        refused(MrtxPasses(3, 16, 3, 0, R_m, 0.0), what="a bad mode")
-        refused(MrtxPasses(3, 16, -1, 0, R_m, 0.0), what="a bad mode")
-        refused(ok, dev=buf.ptr, what="both outputs")
-        refused(ok, host=None, what="neither output")
-        refused(MrtxPasses(3, 16, _lib.PASSES_FULL, 0, R_m, 0.0), host=None, what="FULL without an output")
-        refused(ok, dev=buf.ptr + 4, host=None, what="a misaligned SUMMARY dev_out")
-        refused(MrtxPasses(3, 16, _lib.PASSES_FULL, 0, R_m, 0.0), dev=buf.ptr + 8, host=None, what="a misaligned FULL dev_out")
-        refused(MrtxPasses(3, 16, _lib.PASSES_LIST, 0, R_m, 0.0), dev=buf.ptr + 4, host=None, cap=100, what="a misaligned LIST dev_out")
-        refused(MrtxPasses(3, 16, _lib.PASSES_LIST, 0, R_m, 0.0), host=None, cap=5, what="a cap without a table")
-        refused(MrtxPasses(0, 16, _lib.PASSES_SUMMARY, 0, R_m, 0.0), what="no satellite")
-        refused(MrtxPasses(3, 16, _lib.PASSES_SUMMARY, 1, R_m, 0.0), what="reserved set")
-        refused(MrtxPasses(3, 16, _lib.PASSES_SUMMARY, 0, 0.0, 0.0), what="radius_m = 0")
-        refused(MrtxPasses(3, 16, _lib.PASSES_SUMMARY, 0, R_m, 90.0), what="a mask of 90 degrees")
-        refused(ok, heights=np.array([0.0, 1.0, 2e4, 0.0]), what="a height above 1e4 m")
+        out[:] = 0.0
+        for text, _, kw in tc.passes_refusals(pos, out, buf.ptr):       # the list (tests/terrain_cases.py)
+            st = MrtxStats()
+            st.launches = tc.LAUNCHES
+            rc = tc.passes_call(rt._lib, rt._ctx, kw.pop("k"), lat, lon, hz, kw.pop("pos"), total=C.c_uint64(0), st=st, **kw)
+            tc.refused(rt._lib, rt._ctx, rc, st, text)
+            assert (out == 0.0).all(), "a refused call wrote: " + text
+        inside = pos.copy()
+        inside[1, 7] = pos[1, 7] / np.linalg.norm(pos[1, 7]) * (1.0005 * R_m)
         with pytest.raises(MoonRTError):
             rt.horizon_passes(lat, lon, hz, inside)
     finally:
