@@ -1071,6 +1071,54 @@ int mrtx_horizon_passes(mrtx_ctx* ctx, const MrtxPasses* k, const double* latlon
                         int32_t n_az, const void* dev_horizon, const float* host_horizon, const double* sat_pos_m, void* dev_out,
                         void* host_out, uint64_t pass_cap, uint64_t* n_passes, MrtxStats* out);
 
+/* ---- Joint availability of mask rows: site pairs and the step of greedy site sets (additive to ABI 7)
+ * Rows of W64 = (m + 63) / 64 uint64 words in mrtx_horizon_mask's layout, 1 <= m <= 2^24: table A of n_a rows, table B of n_b
+ * rows; with n_b == 0 and both B pointers null B is A itself.  1 <= n_a, n_b <= 2^24 and n W64 < 2^31 per table.  The bits past
+ * epoch m - 1 of any input row are ignored and may hold garbage, as mrtx_traverse_timed allows.  Joint word w of pair (a, b):
+ * J = ((A[a][w] OP B[b][w]) | base[w]) & V_w with OP = OR (MRTX_PAIRS_ANY: either site available) or AND (MRTX_PAIRS_BOTH: both at
+ * once), base an optional single row (the union of the sites already chosen; null: 0) and V_w all ones but in the last word,
+ * where it keeps bits 0 .. m - 1 - 64 (W64 - 1).  Per pair: count = the set bits of J (uint32); gap = the length of the longest
+ * run of consecutive epochs in [0, m) whose bit is clear (uint32); gap_first = the first epoch of the earliest such run (int32);
+ * with every epoch set gap = 0 and gap_first = -1.
+ * Eligibility: without positions every pair, but a == b when B is A.  Positions are three int32 per row as mrtx_proximity's, each
+ * coordinate in -2^29 .. 2^29, d2 in uint64; with them a pair is eligible iff additionally d2_min <= d2(a, b) <= d2_max, both
+ * ends inclusive (d2_min and d2_max are ignored without positions).
+ *   MRTX_PAIRS_ROWS   B and positions must be null.  n_a records of 16 bytes {int32 partner = -1; uint32 count; uint32 gap;
+ *                     int32 gap_first} of (A[a] | base) & V; op and rank are ignored.  The statistics of any mask row, and the
+ *                     step of a greedy extension: every candidate against the union so far.
+ *   MRTX_PAIRS_BEST   n_a records of the same 16 bytes: partner = the eligible b that is first under the rank, the other fields
+ *                     that pair's.  MRTX_PAIRS_BY_COUNT: largest count, then smallest gap, then least b; MRTX_PAIRS_BY_GAP:
+ *                     smallest gap, then largest count, then least b.  Without an eligible partner {-1, 0, 0, -1}.
+ *   MRTX_PAIRS_TABLE  n_a x n_b records of 8 bytes {uint32 count; uint32 gap}, row-major (n_a x n_a when B is A); an ineligible
+ *                     pair gets {0xFFFFFFFF, 0xFFFFFFFF}; n_a n_b <= 2^28.  rank is ignored.
+ * Nothing depends on the order of evaluation: two runs give the same bytes. */
+#define MRTX_PAIRS_ANY  0
+#define MRTX_PAIRS_BOTH 1
+#define MRTX_PAIRS_ROWS  0
+#define MRTX_PAIRS_BEST  1
+#define MRTX_PAIRS_TABLE 2
+#define MRTX_PAIRS_BY_COUNT 0
+#define MRTX_PAIRS_BY_GAP   1
+typedef struct MrtxMaskPairs {
+    int32_t n_a, n_b, m;
+    int32_t op, mode, rank;     /* MRTX_PAIRS_ANY / BOTH, MRTX_PAIRS_ROWS / BEST / TABLE, MRTX_PAIRS_BY_COUNT / BY_GAP */
+    int32_t reserved[2];        /* 0 */
+    uint64_t d2_min, d2_max;
+} MrtxMaskPairs;                /* 48 bytes */
+/* Exactly one pointer of each required pair (a, out), at most one of each optional pair (b, base, pos_a, pos_b); a B table iff
+ * n_b > 0; pos_b is given iff pos_a is given and B is not A.  Device tables of words and dev_out are 8-byte aligned, positions
+ * 4-byte aligned; no device output overlaps a device input.  A coordinate outside -2^29 .. 2^29 gives MRTX_E_INVALID: in a host
+ * table before any device call, in a device table after the launch (the kernels clamp it, so nothing else goes wrong), as
+ * mrtx_proximity does.  pairs (or NULL): the number of eligible pairs evaluated -- ordered pairs when B is A, n_a in ROWS -- the
+ * same from run to run and in both variants.  MOONRT_PAIRS = prune (default) | brute chooses between skipping the pairs of row
+ * tiles that an exact integer box-to-box bound proves ineligible and looking at every tile pair; both give the same bytes and
+ * the same pairs.  Needs no DEM, no light and no Moon frame and leaves the render state alone; the number of launches depends
+ * on the arguments alone.  out: launches, kernel_ms. */
+int mrtx_mask_pairs(mrtx_ctx* ctx, const MrtxMaskPairs* p, const void* dev_a, const uint64_t* host_a, const void* dev_b,
+                    const uint64_t* host_b, const void* dev_base, const uint64_t* host_base, const void* dev_pos_a,
+                    const int32_t* host_pos_a, const void* dev_pos_b, const int32_t* host_pos_b, void* dev_out, void* host_out,
+                    uint64_t* pairs, MrtxStats* out);
+
 /* Math conformance probe (ABI 7): the kernels' domain-restricted reciprocal (v_rcp_f32 + Newton steps) and square root (v_sqrt_f32 + a
  * +-1 ulp residual fix) against the compiler's IEEE expansions of 1.0f / x and sqrtf(x), ON THE DEVICE, for the n float bit patterns
  * from lo_bits on: which = 0 one Newton step, 1 two steps (what the kernels use), 2 the square root.  mismatches = how many differ;

@@ -218,6 +218,25 @@ PASS_COLUMNS = ("share_any", "longest_outage", "longest_contact", "first_contact
 PASS_OPEN_START, PASS_OPEN_END = 1, 2                       # MrtxPass.flags
 
 
+PAIRS_ANY, PAIRS_BOTH = 0, 1                                # MRTX_PAIRS_*: the op
+PAIRS_ROWS, PAIRS_BEST, PAIRS_TABLE = 0, 1, 2               # the mode
+PAIRS_BY_COUNT, PAIRS_BY_GAP = 0, 1                         # the rank
+PAIRS_CHUNK_WORDS = 32                                      # csrc/mrtx_pairs.h's MRTX_PAIRS_CHUNK: the words staged in LDS at a time
+
+
+class MrtxMaskPairs(C.Structure):
+    """The tables, the operation, the mode and the distance bounds of a joint-availability call (mrtx_mask_pairs, DESIGN.md
+    section 3.28): 48 bytes."""
+    _fields_ = [("n_a", C.c_int32), ("n_b", C.c_int32), ("m", C.c_int32), ("op", C.c_int32), ("mode", C.c_int32),
+                ("rank", C.c_int32), ("reserved", C.c_int32 * 2), ("d2_min", C.c_uint64), ("d2_max", C.c_uint64)]
+
+
+# the BEST and ROWS record (16 bytes) and the TABLE record (8 bytes) of mrtx_mask_pairs
+PAIR_DTYPE = np.dtype([("partner", "<i4"), ("count", "<u4"), ("gap", "<u4"), ("gap_first", "<i4")])
+PAIR_TABLE_DTYPE = np.dtype([("count", "<u4"), ("gap", "<u4")])
+assert PAIR_DTYPE.itemsize == 16 and PAIR_TABLE_DTYPE.itemsize == 8 and C.sizeof(MrtxMaskPairs) == 48
+
+
 class MrtxIllumEpoch(C.Structure):
     """One date of a Sun-illumination series (mrtx_illum_series): what mrtx_set_light and
     mrtx_set_moon_frame would set for it."""
@@ -374,6 +393,8 @@ SIGNATURES = {
     "mrtx_occultation": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.POINTER(MrtxStats)]),
     "mrtx_horizon_passes": (C.c_int, [_VP, C.POINTER(MrtxPasses), _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP,
                                       C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
+    "mrtx_mask_pairs": (C.c_int, [_VP, C.POINTER(MrtxMaskPairs), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                  C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
     "mrtx_thermal_occulted": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP,
                                         C.c_int64, C.POINTER(MrtxVolatile), _VP, _VP, _VP, _VP, C.POINTER(MrtxStats)]),
 }

@@ -441,6 +441,20 @@ int mrtx_host::at_most_one(mrtx_ctx* c, const void* dev, const void* host, const
     return MRTX_OK;
 }
 
+int mrtx_host::aligned(mrtx_ctx* c, const void* p, unsigned bytes, const char* name, const char* type) {
+    if (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) return fail(c, MRTX_E_INVALID, "%s must be %u-byte aligned (%s)", name, bytes, type);
+    return MRTX_OK;
+}
+
+int mrtx_host::variant(mrtx_ctx* c, const char* name, const char* first, const char* second, bool* is_first) {
+    if (const char* e = std::getenv(name)) {
+        if (std::strcmp(e, first) == 0) *is_first = true;
+        else if (std::strcmp(e, second) == 0) *is_first = false;
+        else return fail(c, MRTX_E_INVALID, "%s must be %s or %s (got %s)", name, first, second, e);
+    }
+    return MRTX_OK;
+}
+
 bool mrtx_host::spans_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return a && b && x < y + nb && y < x + na;

@@ -114,6 +114,13 @@ int one_of(mrtx_ctx* c, const void* dev, const void* host, const char* what);
 // an optional table comes from one of them or from neither: "give at most one of dev_<what> and host_<what>"
 int at_most_one(mrtx_ctx* c, const void* dev, const void* host, const char* what);
 
+// a device table (or none) at a multiple of 4 or 8 bytes: "<name> must be <bytes>-byte aligned (<type>)"
+int aligned(mrtx_ctx* c, const void* p, unsigned bytes, const char* name, const char* type);
+
+// A two-valued variant switch of the environment: *is_first keeps the caller's default when the variable is not set.  One
+// value is the stage's scheme, the other its yardstick: the same bytes by the plain scheme.
+int variant(mrtx_ctx* c, const char* name, const char* first, const char* second, bool* is_first);
+
 // The scene as the launches see it: the vector helpers, the Moon frame's rows and the light's constants that build_frame and
 // the per-epoch tables both form, the per-launch constant blocks, and the march's mip levels (built when the step asks)
 constexpr double kPiD = 3.14159265358979323846;

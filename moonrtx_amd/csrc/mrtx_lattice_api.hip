@@ -29,14 +29,8 @@ using namespace mrtx_host;
 
 namespace {
 
-// ---- The vocabulary of the argument checks: each returns MRTX_OK or the code of fail() with its text.  CHK, one_of and
-// at_most_one are mrtx_host.h's: the terrain calls word them alike -------------------------------------------------------------
-// a device table (or none) at a multiple of 4 or 8 bytes
-int aligned(mrtx_ctx* c, const void* p, unsigned bytes, const char* name, const char* type) {
-    if (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) return fail(c, MRTX_E_INVALID, "%s must be %u-byte aligned (%s)", name, bytes, type);
-    return MRTX_OK;
-}
-
+// ---- The vocabulary of the argument checks: each returns MRTX_OK or the code of fail() with its text.  CHK, one_of,
+// at_most_one, aligned and variant are mrtx_host.h's: the terrain calls word them alike ---------------------------------------
 int lattice_ok(mrtx_ctx* c, int32_t rows, int32_t cols, int32_t wrap) {
     if (rows < 1 || cols < 1) return fail(c, MRTX_E_INVALID, "empty lattice (%d x %d)", rows, cols);
     if ((int64_t)rows * (int64_t)cols > (int64_t)1 << 31)
@@ -53,17 +47,6 @@ int connectivity_ok(mrtx_ctx* c, int32_t connectivity) {
 
 int regions_fit(mrtx_ctx* c, uint32_t n_regions, size_t N) {
     if ((size_t)n_regions > N) return fail(c, MRTX_E_INVALID, "n_regions = %u exceeds the lattice's %zu nodes", n_regions, N);
-    return MRTX_OK;
-}
-
-// A two-valued variant switch of the environment: *is_first keeps the caller's default when the variable is not set.  One
-// value is the stage's scheme, the other its yardstick: the same bytes by the plain scheme.
-int variant(mrtx_ctx* c, const char* name, const char* first, const char* second, bool* is_first) {
-    if (const char* e = std::getenv(name)) {
-        if (std::strcmp(e, first) == 0) *is_first = true;
-        else if (std::strcmp(e, second) == 0) *is_first = false;
-        else return fail(c, MRTX_E_INVALID, "%s must be %s or %s (got %s)", name, first, second, e);
-    }
     return MRTX_OK;
 }
 

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "mrtx_host.h"
+#include "mrtx_pairs.h"
 
 using namespace mrtx_host;
 
@@ -483,6 +484,110 @@ int mrtx_horizon_mask(mrtx_ctx* c, const double* latlon, int32_t n, int32_t n_az
     CHK(stage_start(c, &s.cold, false));
     HIPCHK(c, mrtx_launch_horizon_mask(s.f, q, c->stream));
     return stage_finish(c, dev_out, reinterpret_cast<float*>(host_out), out_bytes, out, kNoRays);
+}
+
+// ---- Joint availability of mask rows: pairs of horizon_mask's rows, reduced on the device -------------
+static_assert(sizeof(MrtxMaskPairs) == 48 && sizeof(PairRec) == 16 && sizeof(PairCell) == 8 && sizeof(PairBox) == 24 &&
+              sizeof(PairPick) == 16, "the pair blocks");
+
+// a host position table is refused at its first bad coordinate (a device table's are counted by the box kernel)
+static int pair_positions_ok(mrtx_ctx* c, const int32_t* host_pos, size_t n, const char* name) {
+    for (size_t k = 0; host_pos && k < 3 * n; k++)
+        if (host_pos[k] < -MRTX_PAIRS_CMAX || host_pos[k] > MRTX_PAIRS_CMAX)
+            return fail(c, MRTX_E_INVALID, "coordinate %zu of row %zu of %s must lie in -2^29 .. 2^29 (got %d)", k % 3, k / 3, name,
+                        host_pos[k]);
+    return MRTX_OK;
+}
+
+int mrtx_mask_pairs(mrtx_ctx* c, const MrtxMaskPairs* p, const void* dev_a, const uint64_t* host_a, const void* dev_b,
+                    const uint64_t* host_b, const void* dev_base, const uint64_t* host_base, const void* dev_pos_a,
+                    const int32_t* host_pos_a, const void* dev_pos_b, const int32_t* host_pos_b, void* dev_out, void* host_out,
+                    uint64_t* pairs, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!p) return fail(c, MRTX_E_INVALID, "null pairs block");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    if (p->m < 1 || p->m > (1 << 24)) return fail(c, MRTX_E_INVALID, "m must lie in 1 .. 2^24 (got %d)", p->m);
+    if (p->n_a < 1 || p->n_a > (1 << 24)) return fail(c, MRTX_E_INVALID, "n_a must lie in 1 .. 2^24 (got %d)", p->n_a);
+    if (p->n_b < 0 || p->n_b > (1 << 24)) return fail(c, MRTX_E_INVALID, "n_b must lie in 0 .. 2^24 (got %d)", p->n_b);
+    if (p->mode != MRTX_PAIRS_ROWS && p->mode != MRTX_PAIRS_BEST && p->mode != MRTX_PAIRS_TABLE)
+        return fail(c, MRTX_E_INVALID, "mode must be MRTX_PAIRS_ROWS, MRTX_PAIRS_BEST or MRTX_PAIRS_TABLE (got %d)", p->mode);
+    const bool rows = p->mode == MRTX_PAIRS_ROWS, best = p->mode == MRTX_PAIRS_BEST;
+    if (!rows && p->op != MRTX_PAIRS_ANY && p->op != MRTX_PAIRS_BOTH)
+        return fail(c, MRTX_E_INVALID, "op must be MRTX_PAIRS_ANY or MRTX_PAIRS_BOTH (got %d)", p->op);
+    if (best && p->rank != MRTX_PAIRS_BY_COUNT && p->rank != MRTX_PAIRS_BY_GAP)
+        return fail(c, MRTX_E_INVALID, "rank must be MRTX_PAIRS_BY_COUNT or MRTX_PAIRS_BY_GAP (got %d)", p->rank);
+    CHK(one_of(c, dev_a, host_a, "a"));
+    CHK(at_most_one(c, dev_b, host_b, "b"));
+    CHK(at_most_one(c, dev_base, host_base, "base"));
+    CHK(at_most_one(c, dev_pos_a, host_pos_a, "pos_a"));
+    CHK(at_most_one(c, dev_pos_b, host_pos_b, "pos_b"));
+    CHK(one_of(c, dev_out, host_out, "out"));
+    const bool has_b = dev_b || host_b, has_pa = dev_pos_a || host_pos_a, has_pb = dev_pos_b || host_pos_b;
+    if (has_b != (p->n_b > 0)) return fail(c, MRTX_E_INVALID, "give a B table iff n_b > 0 (n_b == 0: B is A itself)");
+    if (rows && (has_b || has_pa || has_pb)) return fail(c, MRTX_E_INVALID, "MRTX_PAIRS_ROWS takes no B table and no positions");
+    if (has_pb != (has_pa && has_b)) return fail(c, MRTX_E_INVALID, "give pos_b iff pos_a is given and B is not A");
+    const int32_t w64 = (p->m + 63) / 64, n_b = has_b ? p->n_b : p->n_a;
+    if ((int64_t)p->n_a * w64 >= (int64_t)1 << 31 || (int64_t)n_b * w64 >= (int64_t)1 << 31)
+        return fail(c, MRTX_E_INVALID, "a table holds fewer than 2^31 words (got %d and %d rows of %d)", p->n_a, n_b, w64);
+    if (p->mode == MRTX_PAIRS_TABLE && (int64_t)p->n_a * n_b > (int64_t)1 << 28)
+        return fail(c, MRTX_E_INVALID, "MRTX_PAIRS_TABLE holds at most 2^28 pairs (got %d x %d)", p->n_a, n_b);
+    CHK(aligned(c, dev_a, 8, "dev_a", "uint64"));
+    CHK(aligned(c, dev_b, 8, "dev_b", "uint64"));
+    CHK(aligned(c, dev_base, 8, "dev_base", "uint64"));
+    CHK(aligned(c, dev_pos_a, 4, "dev_pos_a", "int32"));
+    CHK(aligned(c, dev_pos_b, 4, "dev_pos_b", "int32"));
+    CHK(aligned(c, dev_out, 8, "dev_out", "records"));
+    const size_t a_words = (size_t)p->n_a * (size_t)w64, b_words = has_b ? (size_t)n_b * (size_t)w64 : 0;
+    const size_t out_bytes = p->mode == MRTX_PAIRS_TABLE ? sizeof(PairCell) * (size_t)p->n_a * (size_t)n_b : sizeof(PairRec) * (size_t)p->n_a;
+    if (spans_overlap(dev_out, out_bytes, dev_a, 8 * a_words) || spans_overlap(dev_out, out_bytes, dev_b, 8 * b_words) ||
+        spans_overlap(dev_out, out_bytes, dev_base, 8 * (size_t)w64) || spans_overlap(dev_out, out_bytes, dev_pos_a, 12 * (size_t)p->n_a) ||
+        spans_overlap(dev_out, out_bytes, dev_pos_b, 12 * (size_t)n_b))
+        return fail(c, MRTX_E_INVALID, "dev_out must not overlap a device input");
+    // MOONRT_PAIRS=brute: every tile pair is looked at, the yardstick of the pruned walk; the same bytes and the same pairs
+    bool prune = true;
+    CHK(variant(c, "MOONRT_PAIRS", "prune", "brute", &prune));
+    CHK(pair_positions_ok(c, host_pos_a, (size_t)p->n_a, "pos_a"));
+    CHK(pair_positions_ok(c, host_pos_b, (size_t)n_b, "pos_b"));
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const PairsLayout at = pairs_layout(p->n_a, n_b, !rows, best, has_pa);
+    float* d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    CHK(stage_out(c, dev_out, out_bytes));
+    CHK(stage_buffer(c, c->trav_buf, c->trav_bytes, at.end));
+    CHK(stage_tables(c, {{host_a, host_a ? 2 * a_words : 0}, {host_b, host_b ? 2 * b_words : 0},
+                         {host_base, host_base ? 2 * (size_t)w64 : 0}, {host_pos_a, host_pos_a ? 3 * (size_t)p->n_a : 0},
+                         {host_pos_b, host_pos_b ? 3 * (size_t)n_b : 0}}, d));
+    char* tb = reinterpret_cast<char*>(c->trav_buf);
+    PairsC q;
+    std::memset(&q, 0, sizeof q);
+    q.a = static_cast<const unsigned long long*>(host_a ? d[0] : dev_a);
+    q.b = has_b ? static_cast<const unsigned long long*>(host_b ? d[1] : dev_b) : q.a;
+    q.base = static_cast<const unsigned long long*>(host_base ? d[2] : dev_base);
+    q.pos_a = static_cast<const int32_t*>(host_pos_a ? d[3] : dev_pos_a);
+    q.pos_b = has_b ? static_cast<const int32_t*>(host_pos_b ? d[4] : dev_pos_b) : q.pos_a;
+    q.out = dev_out;
+    q.part = reinterpret_cast<PairPick*>(tb + at.part_at);
+    q.box_a = reinterpret_cast<PairBox*>(tb + at.box_a_at);
+    q.box_b = reinterpret_cast<PairBox*>(tb + at.box_b_at);
+    q.pairs = reinterpret_cast<unsigned long long*>(tb);
+    q.bad = reinterpret_cast<uint32_t*>(tb + 8);
+    q.d2_min = has_pa ? p->d2_min : 0; q.d2_max = has_pa ? p->d2_max : ~0ull;
+    q.n_a = p->n_a; q.n_b = n_b; q.m = p->m; q.w64 = w64;
+    q.op_and = !rows && p->op == MRTX_PAIRS_BOTH; q.mode = p->mode; q.by_gap = best && p->rank == MRTX_PAIRS_BY_GAP; q.self = !has_b;
+    q.splits = at.splits;
+    uint32_t launches = 0;
+    unsigned long long head[2] = {0, 0};                    // pairs, bad
+    HIPCHK(c, hipMemsetAsync(tb, 0, 32, c->stream));
+    CHK(stage_start(c, nullptr, false));
+    HIPCHK(c, mrtx_launch_mask_pairs(q, prune, c->stream, &launches));
+    CHK(stage_finish(c, nullptr, nullptr, 0, out, kNoRays));
+    if (out) out->launches = launches;
+    HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
+    if ((uint32_t)head[1])
+        return fail(c, MRTX_E_INVALID, "%u coordinates of the device position tables lie outside -2^29 .. 2^29", (uint32_t)head[1]);
+    if (host_out) HIPCHK(c, hipMemcpy(host_out, dev_out, out_bytes, hipMemcpyDeviceToHost));
+    if (pairs) *pairs = rows ? (uint64_t)p->n_a : head[0];
+    return MRTX_OK;
 }
 
 // ---- The Earth's occultation of the Sun ------------------------------------------------------------

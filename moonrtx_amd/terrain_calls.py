@@ -221,6 +221,118 @@ class TerrainCalls(Calls):
         self._point_calls("mrtx_horizon_mask", call, la, lo, max(int(n_az), 0) + 2 * max(w64, 1), chunk_bytes, stats, hz_at)
         return out if out is not None else res
 
+    # ---- Joint availability of mask rows
+    PAIR_OPS = {"any": _lib.PAIRS_ANY, "both": _lib.PAIRS_BOTH}
+    PAIR_MODES = {"rows": _lib.PAIRS_ROWS, "best": _lib.PAIRS_BEST, "table": _lib.PAIRS_TABLE}
+    PAIR_RANKS = {"count": _lib.PAIRS_BY_COUNT, "gap": _lib.PAIRS_BY_GAP}
+
+    @staticmethod
+    def _mask_rows(mask, w64, n_rows, name):
+        """A table of mask rows as (device pointer, host pointer, rows, the array kept alive)."""
+        if isinstance(mask, _device_buffer()):
+            if n_rows is None:
+                raise ValueError(f"{name} is a DeviceBuffer: give its number of rows")
+            n = int(n_rows)
+            if n < 1 or mask.nbytes < 8 * n * w64:
+                raise ValueError(f"the {name} buffer is smaller than its rows x W64 uint64")
+            return mask.ptr, None, n, None
+        a = np.ascontiguousarray(mask, np.uint64)
+        if a.ndim == 1:
+            a = a.reshape(1, -1)
+        if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != w64:
+            raise ValueError(f"{name} must be (rows, {w64}) uint64 words for its epochs (got {a.shape})")
+        if n_rows is not None and int(n_rows) != a.shape[0]:
+            raise ValueError(f"{name} holds {a.shape[0]} rows, not {n_rows}")
+        return None, a.ctypes.data, a.shape[0], a
+
+    @staticmethod
+    def _pair_positions(pos, n, name):
+        from .regions import COORD_MAX
+        if isinstance(pos, _device_buffer()):
+            if pos.nbytes < 12 * n:
+                raise ValueError(f"the {name} buffer is smaller than rows x 3 int32")
+            return pos.ptr, None, None
+        p = np.ascontiguousarray(pos)
+        if p.shape != (n, 3) or not np.issubdtype(p.dtype, np.integer):
+            raise ValueError(f"{name} must be (rows, 3) integers")
+        if p.size and (p.min() < -COORD_MAX or p.max() > COORD_MAX):
+            raise ValueError("a coordinate leaves +-2^29: choose a larger unit")
+        p = p.astype(np.int32)
+        return None, p.ctypes.data, p
+
+    def mask_pairs(self, mask_a, n_epochs, mask_b=None, op="any", mode="best", rank="count", base=None, positions_a=None,
+                   positions_b=None, d2_min=0, d2_max=2 ** 64 - 1, out=None, stats=None, n_rows=None, n_rows_b=None,
+                   out_offset=0):
+        """The joint availability of pairs of mask rows (mrtx_mask_pairs).  mask_a: (n_a, W64) uint64
+        rows in horizon_mask's layout over n_epochs epochs, W64 = (n_epochs + 63) // 64, or a DeviceBuffer of them (then
+        n_rows= is required); mask_b: a second table (n_rows_b= with a buffer), or None: the rows of mask_a against each
+        other, a row never against itself.  The joint row of (a, b) is ((A[a] op B[b]) | base) over the first n_epochs bits:
+        op "any" (either site available) or "both"; base an optional (W64,) row or DeviceBuffer.  Of it: count, the set
+        bits; gap, the longest run of clear bits; gap_first, the start of the earliest such run (-1 when gap == 0).
+        positions_a / positions_b: (rows, 3) integers within +-2^29 (networks.point_positions) or DeviceBuffers of int32;
+        with them only pairs with d2_min <= d2 <= d2_max (the exact squared distance, both ends inclusive) are eligible.
+          mode "rows"   (n_a,) PAIR_DTYPE of (A[a] | base) itself, partner = -1; no mask_b and no positions
+          mode "best"   (n_a,) PAIR_DTYPE: the eligible partner first under rank "count" (largest count, then smallest gap,
+                        then least b) or "gap" (smallest gap, then largest count, then least b), and that pair's fields;
+                        (-1, 0, 0, -1) without an eligible partner
+          mode "table"  (n_a, n_b) PAIR_TABLE_DTYPE, ineligible pairs all ones; at most 2^28 pairs
+        out = a DeviceBuffer: the records are written there from byte out_offset (a multiple of 8) on and `out` is returned;
+        otherwise the structured array.  `stats`, if a dict, receives kernel_ms, launches and pairs, the eligible pairs
+        evaluated.  Needs no DEM."""
+        for value, names, what in ((op, self.PAIR_OPS, "op"), (mode, self.PAIR_MODES, "mode"), (rank, self.PAIR_RANKS, "rank")):
+            if value not in names:
+                raise ValueError(f"{what} must be one of {sorted(names)} (got {value!r})")
+        m = int(n_epochs)
+        if m < 1 or m > 1 << 24:
+            raise ValueError("n_epochs must lie in 1 .. 2^24")
+        w64 = (m + 63) // 64
+        a_dev, a_host, n_a, keep_a = self._mask_rows(mask_a, w64, n_rows, "mask_a")
+        b_dev = b_host = keep_b = None
+        n_b = 0
+        if mask_b is not None:
+            b_dev, b_host, n_b, keep_b = self._mask_rows(mask_b, w64, n_rows_b, "mask_b")
+        if mode == "rows" and (mask_b is not None or positions_a is not None or positions_b is not None):
+            raise ValueError('mode "rows" takes no mask_b and no positions')
+        if (positions_b is not None) != (positions_a is not None and mask_b is not None):
+            raise ValueError("give positions_b iff positions_a is given and mask_b is")
+        base_dev = base_host = keep_base = None
+        if isinstance(base, _device_buffer()):
+            if base.nbytes < 8 * w64:
+                raise ValueError("the base buffer is smaller than W64 uint64")
+            base_dev = base.ptr
+        elif base is not None:
+            keep_base = np.ascontiguousarray(base, np.uint64).reshape(-1)
+            if keep_base.shape != (w64,):
+                raise ValueError(f"base must be one row of {w64} uint64 words")
+            base_host = keep_base.ctypes.data
+        pa = (None, None, None) if positions_a is None else self._pair_positions(positions_a, n_a, "positions_a")
+        pb = (None, None, None) if positions_b is None else self._pair_positions(positions_b, n_b, "positions_b")
+        d2_min, d2_max = int(d2_min), int(d2_max)
+        if not (0 <= d2_min < 1 << 64 and 0 <= d2_max < 1 << 64):
+            raise ValueError("d2_min and d2_max must fit uint64")
+        cols = n_b if mask_b is not None else n_a
+        table = mode == "table"
+        if table and n_a * cols > 1 << 28:
+            raise ValueError("a table holds at most 2^28 pairs")
+        dtype, shape = (_lib.PAIR_TABLE_DTYPE, (n_a, cols)) if table else (_lib.PAIR_DTYPE, (n_a,))
+        out_offset = int(out_offset)
+        nbytes = dtype.itemsize * n_a * (cols if table else 1)
+        if out is not None and (out_offset < 0 or out_offset % 8 or out.nbytes < out_offset + nbytes):
+            raise ValueError("the device buffer is smaller than the records from out_offset (a multiple of 8) on")
+        res = np.empty(shape, dtype) if out is None else None
+        p = _lib.MrtxMaskPairs(n_a, n_b, m, self.PAIR_OPS[op], self.PAIR_MODES[mode], self.PAIR_RANKS[rank], (C.c_int32 * 2)(0, 0),
+                               d2_min, d2_max)
+        st = MrtxStats()
+        pairs = C.c_uint64(0)
+        self._check(self._lib.mrtx_mask_pairs(self._ctx, C.byref(p), a_dev, a_host, b_dev, b_host, base_dev, base_host, pa[0], pa[1],
+                                              pb[0], pb[1], None if out is None else out.ptr + out_offset,
+                                              None if out is not None else res.ctypes.data, C.byref(pairs), C.byref(st)),
+                    "mrtx_mask_pairs")
+        self._add_stats(stats, st)
+        if isinstance(stats, dict):
+            stats["pairs"] = stats.get("pairs", 0) + int(pairs.value)
+        return out if out is not None else res
+
     POWER_COLUMNS = ("generated", "net", "storage_need", "drawdown_first", "drawdown_last", "min_charge", "epochs_unmet",
                      "energy_unmet")
     PANELS = {"track": _lib.PANEL_TRACK, "fixed": _lib.PANEL_FIXED, "azimuth": _lib.PANEL_AZIMUTH}
