@@ -932,6 +932,72 @@ int mrtx_contours(mrtx_ctx* ctx, const MrtxContours* k, const void* dev_z, const
                   void* dev_lines, MrtxContourLine* host_lines, uint64_t line_cap, void* dev_vertices, int32_t* host_vertices,
                   uint64_t vertex_cap, uint64_t* n_lines, uint64_t* n_vertices, MrtxStats* out);
 
+/* ---- Polygon rasterisation: rings and outlines burnt into a label table (additive to ABI 7) ---------
+ * The inverse of mrtx_regions_outline.  Lattice, wrap and corner coordinates are that call's (at most 2^28 nodes): the cell of
+ * node (i, j) has its NW corner at (y, x) = (i, j) and its centre at (i + 1/2, j + 1/2).  Vertices are (y, x) int32 pairs in
+ * units of 2^-s of a cell, s = subcell_bits in 0 .. 8 (s = 0: exactly the outlines' coordinates), every coordinate within
+ * +-2^24 units.  A ring's edges join consecutive vertices; the closing edge goes from the last vertex to (y_first, x_first +
+ * wind cols 2^s), which must lie within +-2^25 units: the way MrtxRing.wind and the unwrapped x of the outline vertices read, so
+ * a ring all the way round a wrapped window closes on the cylinder, and an MRTX_OUTLINE_CORNERS ring without a turn (one
+ * vertex, wind = +-1) is one horizontal edge cols long.  polygon lies in 0 .. n_polygons - 1; a polygon's rings may come in any
+ * order, and a polygon may have none.
+ * The winding number of a node, with a ray from its centre straight towards row -infinity, in doubled units Y = 2 y, X = 2 x,
+ * S = 2^s (unwrapped column ju has its centre at xc = (2 ju + 1) S, row i at yc = (2 i + 1) S): an edge (Y0, X0) -> (Y1, X1)
+ * with X0 != X1 spans every ju with min(X0, X1) <= xc < max(X0, X1), where it sits at y* = Y0 + (xc - X0)(Y1 - Y0) / (X1 - X0);
+ * the crossing counts for every row with yc >= y*, so from i0 = ceil((y* - S) / 2 S) on, in exact integers, with the sign +1
+ * when X1 > X0 and -1 when X1 < X0.  The column is ju mod cols under wrap (an edge longer than cols hits a column more than
+ * once, and each hit counts); without wrap a ju outside 0 .. cols - 1 is dropped.  i0 is clipped up to 0, a crossing with i0 >=
+ * rows has no effect.  w_p(i, j) is the sum of the signs of polygon p's crossings of column j with i0 <= i.  Polygon p covers the
+ * node when w_p != 0 (MRTX_RASTER_NONZERO) or when w_p is odd (MRTX_RASTER_EVENODD); a node centre on an edge shared by two
+ * polygons belongs to exactly one of them.  labels[v]: the least (MRTX_RASTER_FIRST) or the greatest (MRTX_RASTER_LAST, the
+ * painter's order) index among the polygons that cover v, or -1.  Rasterising the rings of mrtx_regions_outline, label as
+ * polygon, gives back the label table they came from, at either connectivity, in either mode and under either rule. */
+#define MRTX_RASTER_NONZERO 0
+#define MRTX_RASTER_EVENODD 1
+#define MRTX_RASTER_FIRST 0
+#define MRTX_RASTER_LAST 1
+typedef struct MrtxRaster {
+    int32_t rows, cols, wrap;
+    int32_t subcell_bits;   /* 0 .. 8 */
+    int32_t rule;           /* MRTX_RASTER_NONZERO or MRTX_RASTER_EVENODD */
+    int32_t order;          /* MRTX_RASTER_FIRST or MRTX_RASTER_LAST */
+    int32_t reserved;       /* 0 */
+} MrtxRaster;
+typedef struct MrtxRasterRing {
+    uint64_t first;         /* index of the ring's first vertex in the vertex table */
+    uint32_t n_vertices;    /* >= 1 */
+    int32_t polygon;
+    int32_t wind;           /* 0 without wrap, else -1, 0 or +1 */
+    uint32_t reserved;      /* 0 */
+} MrtxRasterRing;
+typedef struct MrtxPolygonCover {
+    uint64_t weight;        /* the row_weight sum of the nodes the polygon covers */
+    uint64_t owned_weight;  /* ... of the nodes whose label it is */
+    uint32_t count;         /* the nodes the polygon covers */
+    uint32_t owned;         /* the nodes whose label it is */
+    int32_t i_min, i_max;   /* the row extent of the covered nodes, -1 when there are none */
+    int32_t first_at;       /* the least covered node index, -1 when there is none */
+    uint32_t reserved;      /* 0 */
+} MrtxPolygonCover;
+/* Every table in exactly one of its device pointer (rings and cover 8-byte, vertices and labels 4-byte aligned) and its host
+ * pointer; a table without entries (n_rings, n_vertices or n_polygons == 0) may come without either.  The two inputs may share
+ * memory; no other two device tables may overlap.  row_weight: rows uint32 in host memory or NULL (every row weighs 1).
+ * labels: rows x cols int32; cover: n_polygons records.  n_polygons == 0 or n_rings == 0 is legal and gives an all -1 table.
+ * n_rings and n_vertices stay below 2^31, and n_polygons x ceil(cols / 64) at or below 2^28.  The two input tables are checked
+ * on the device: a record with polygon out of range, first + n_vertices beyond the table, n_vertices == 0, a wind that is not
+ * allowed (or whose closing point leaves +-2^25), reserved != 0, or a coordinate beyond +-2^24 gives MRTX_E_INVALID after the
+ * first launches, with the count of each in the message, and nothing is written; so do 2^31 or more edges or crossings, after
+ * their count.  *n_crossings (may be NULL) receives the number of (edge, column) hits inside the lattice.  A refused call
+ * leaves outputs, the count and the statistics as they were.  The call needs no DEM, light or Moon frame and leaves the render
+ * state alone.  MOONRT_RASTER = bins (default) | brute chooses between crossings gathered per polygon and strip of 64 columns and
+ * every node against every edge; both give the same bytes, the same on every run.  The number of launches depends on the variant
+ * alone.  out: launches, kernel_ms (from the first launch to the last, the host's reads of the counts between them included);
+ * written also when the call fails for a bad table, not when it is refused. */
+int mrtx_rasterise(mrtx_ctx* ctx, const MrtxRaster* r, const void* dev_rings, const MrtxRasterRing* host_rings, uint64_t n_rings,
+                   const void* dev_vertices, const int32_t* host_vertices, uint64_t n_vertices, uint32_t n_polygons,
+                   const uint32_t* row_weight, void* dev_labels, int32_t* host_labels, void* dev_cover,
+                   MrtxPolygonCover* host_cover, uint64_t* n_crossings, MrtxStats* out);
+
 /* ---- Mast-height horizons and joint windows (additive to ABI 7) ----------------------------------
  * mrtx_horizon_points from a raised origin: point p marches from P = fmaf(hs, u, o), hs = (float)(height_m[p] / radius_m * R),
  * the raised end of mrtx_sight_points (so a mast top is one point for the horizon and for the line of sight).  height_m: n

@@ -162,6 +162,28 @@ assert CONTOUR_LINE_DTYPE.itemsize == 32 == C.sizeof(MrtxContourLine)
 CONTOUR_MAX_LEVELS = 65536
 
 
+RASTER_NONZERO, RASTER_EVENODD = 0, 1
+RASTER_FIRST, RASTER_LAST = 0, 1
+
+
+class MrtxRaster(C.Structure):
+    """The lattice and the options of a polygon rasterisation (mrtx_rasterise)."""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("wrap", C.c_int32), ("subcell_bits", C.c_int32), ("rule", C.c_int32),
+                ("order", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MrtxRasterRing(C.Structure):
+    """One ring of a polygon (mrtx_rasterise): 24 bytes."""
+    _fields_ = [("first", C.c_uint64), ("n_vertices", C.c_uint32), ("polygon", C.c_int32), ("wind", C.c_int32),
+                ("reserved", C.c_uint32)]
+
+
+class MrtxPolygonCover(C.Structure):
+    """What one polygon covers and owns (mrtx_rasterise): 40 bytes, all integers."""
+    _fields_ = [("weight", C.c_uint64), ("owned_weight", C.c_uint64), ("count", C.c_uint32), ("owned", C.c_uint32),
+                ("i_min", C.c_int32), ("i_max", C.c_int32), ("first_at", C.c_int32), ("reserved", C.c_uint32)]
+
+
 FILL_NONE = 2 ** 31 - 1         # MRTX_FILL_NONE: the fill of a lattice without any outlet
 FILL_ZMAX = 2 ** 30             # |z| <= 2^30
 
@@ -373,6 +395,8 @@ SIGNATURES = {
                                      C.POINTER(MrtxStats)]),
     "mrtx_regions_outline": (C.c_int, [_VP, C.POINTER(MrtxOutline), _VP, _VP, C.c_uint32, _VP, _VP, _VP, C.c_uint64, _VP, _VP,
                                        C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
+    "mrtx_rasterise": (C.c_int, [_VP, C.POINTER(MrtxRaster), _VP, _VP, C.c_uint64, _VP, _VP, C.c_uint64, C.c_uint32, _VP, _VP, _VP, _VP,
+                                 _VP, C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
     "mrtx_contours": (C.c_int, [_VP, C.POINTER(MrtxContours), _VP, _VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, C.c_uint64,
                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),
     "mrtx_fill": (C.c_int, [_VP, C.POINTER(MrtxFill), _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_uint64), C.POINTER(MrtxStats)]),

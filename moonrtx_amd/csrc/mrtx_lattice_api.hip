@@ -1,7 +1,7 @@
 // mrtx_lattice_api.hip -- host side of the lattice calls of libmoonrt.so: the entry points that work on a
 // lattice of nodes and its tables, not on the DEM and its march.  mrtx_regions_label, mrtx_regions_stats, mrtx_regions_zonal,
-// mrtx_regions_shape, mrtx_proximity, mrtx_regions_reach, mrtx_regions_outline, mrtx_contours, mrtx_fill, mrtx_fill_basins and
-// mrtx_bowls.  Their kernels lie in a unit per stage (mrtx_regions.hip ... mrtx_bowls.hip); the context and the staging, launch
+// mrtx_regions_shape, mrtx_proximity, mrtx_regions_reach, mrtx_regions_outline, mrtx_contours, mrtx_fill, mrtx_fill_basins,
+// mrtx_bowls and mrtx_rasterise.  Their kernels lie in a unit per stage (mrtx_regions.hip ... mrtx_raster.hip); the context and the staging, launch
 // and read-back path are mrtx_api.hip's (mrtx_host.h).  No device code.
 //
 // Every entry point reads: parameters, checks, layout, launches, read-back.  The checks are calls of the small functions below,
@@ -24,6 +24,7 @@
 #include "mrtx_contour.h"
 #include "mrtx_fill.h"
 #include "mrtx_bowls.h"
+#include "mrtx_raster.h"
 
 using namespace mrtx_host;
 
@@ -1115,6 +1116,119 @@ int mrtx_bowls(mrtx_ctx* c, const MrtxBowls* w, const void* dev_z, const int32_t
         else HIPCHK(c, hipMemcpy(dev_bowls, rec.data(), sizeof(MrtxBowl) * (size_t)total, hipMemcpyHostToDevice));
     }
     if (host_label) HIPCHK(c, hipMemcpy(host_label, q.label, 4 * N, hipMemcpyDeviceToHost));
+    return MRTX_OK;
+}
+
+// ---- Polygon rasterisation: rings and outlines burnt into a label table ---------------------------
+static_assert(sizeof(MrtxRaster) == 28, "MrtxRaster is 28 bytes");
+static_assert(sizeof(MrtxRasterRing) == 24 && sizeof(RasterRing) == sizeof(MrtxRasterRing), "MrtxRasterRing is 24 bytes");
+static_assert(sizeof(MrtxPolygonCover) == 40 && sizeof(CoverRec) == sizeof(MrtxPolygonCover), "MrtxPolygonCover is 40 bytes");
+
+int mrtx_rasterise(mrtx_ctx* c, const MrtxRaster* r, const void* dev_rings, const MrtxRasterRing* host_rings, uint64_t n_rings,
+                   const void* dev_vertices, const int32_t* host_vertices, uint64_t n_vertices, uint32_t n_polygons,
+                   const uint32_t* row_weight, void* dev_labels, int32_t* host_labels, void* dev_cover, MrtxPolygonCover* host_cover,
+                   uint64_t* n_crossings, MrtxStats* out) {
+    if (!c) return MRTX_E_INVALID;
+    if (!r) return fail(c, MRTX_E_INVALID, "null raster block");
+    if (r->reserved != 0) return fail(c, MRTX_E_INVALID, "reserved must be 0");
+    CHK(lattice_ok(c, r->rows, r->cols, r->wrap));
+    if ((int64_t)r->rows * (int64_t)r->cols > MRTX_RS_MAX_NODES)
+        return fail(c, MRTX_E_INVALID, "a rasterised lattice holds at most 2^28 nodes (got %d x %d)", r->rows, r->cols);
+    if (r->subcell_bits < 0 || r->subcell_bits > MRTX_RS_MAX_SUBCELL)
+        return fail(c, MRTX_E_INVALID, "subcell_bits must lie in 0 .. 8 (got %d)", r->subcell_bits);
+    if (r->rule != MRTX_RASTER_NONZERO && r->rule != MRTX_RASTER_EVENODD)
+        return fail(c, MRTX_E_INVALID, "rule must be MRTX_RASTER_NONZERO or MRTX_RASTER_EVENODD (got %d)", r->rule);
+    if (r->order != MRTX_RASTER_FIRST && r->order != MRTX_RASTER_LAST)
+        return fail(c, MRTX_E_INVALID, "order must be MRTX_RASTER_FIRST or MRTX_RASTER_LAST (got %d)", r->order);
+    // an empty table may come without a pointer
+    if (n_rings) CHK(one_of(c, dev_rings, host_rings, "rings"));
+    else CHK(at_most_one(c, dev_rings, host_rings, "rings"));
+    if (n_vertices) CHK(one_of(c, dev_vertices, host_vertices, "vertices"));
+    else CHK(at_most_one(c, dev_vertices, host_vertices, "vertices"));
+    if (n_rings > MRTX_RS_MAX_COUNT || n_vertices > MRTX_RS_MAX_COUNT)
+        return fail(c, MRTX_E_INVALID, "a call holds fewer than 2^31 rings and vertices (got %llu, %llu)", (unsigned long long)n_rings,
+                    (unsigned long long)n_vertices);
+    CHK(one_of(c, dev_labels, host_labels, "labels"));
+    if (n_polygons) CHK(one_of(c, dev_cover, host_cover, "cover"));
+    else CHK(at_most_one(c, dev_cover, host_cover, "cover"));
+    const int32_t strips = raster_strips(r->cols);
+    if ((uint64_t)n_polygons * (uint64_t)strips > MRTX_RS_MAX_BINS)
+        return fail(c, MRTX_E_INVALID, "a call holds at most 2^28 bins (got %u polygons x %d strips of 64 columns)", n_polygons, strips);
+    CHK(aligned(c, dev_rings, 8, "dev_rings", "MrtxRasterRing"));
+    CHK(aligned(c, dev_vertices, 4, "dev_vertices", "int32"));
+    CHK(aligned(c, dev_labels, 4, "dev_labels", "int32"));
+    CHK(aligned(c, dev_cover, 8, "dev_cover", "MrtxPolygonCover"));
+    const size_t N = (size_t)r->rows * (size_t)r->cols;
+    const size_t ring_bytes = sizeof(MrtxRasterRing) * (size_t)n_rings, vertex_bytes = 8 * (size_t)n_vertices;
+    const size_t cover_bytes = sizeof(MrtxPolygonCover) * (size_t)n_polygons;
+    if (!disjoint({{dev_rings, ring_bytes}, {dev_vertices, vertex_bytes}, {dev_labels, 4 * N}, {dev_cover, cover_bytes}}, 2))      // two inputs
+        return fail(c, MRTX_E_INVALID, "the device inputs, dev_labels and dev_cover must not overlap");
+    // MOONRT_RASTER=brute: every node against every edge of every polygon, the yardstick of the binned crossings; the same bytes
+    bool bins = true;
+    CHK(variant(c, "MOONRT_RASTER", "bins", "brute", &bins));
+    // ---- device work from here
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    const RasterLayout at = raster_layout(r->rows, r->cols, n_rings, n_polygons, bins, host_labels != nullptr, host_cover != nullptr);
+    float* d[3] = {nullptr, nullptr, nullptr};
+    CHK(stage_buffer(c, c->trav_buf, c->trav_bytes, at.end));
+    CHK(stage_tables(c, {{host_rings, host_rings ? 6 * (size_t)n_rings : 0}, {host_vertices, host_vertices ? 2 * (size_t)n_vertices : 0},
+                         {row_weight, row_weight ? (size_t)r->rows : 0}}, d));
+    char* tb = reinterpret_cast<char*>(c->trav_buf);
+    RasterC q;
+    std::memset(&q, 0, sizeof q);
+    q.rings = in_table<RasterRing>(host_rings, d[0], dev_rings);
+    q.vertices = in_table<int32_t>(host_vertices, d[1], dev_vertices);
+    q.row_weight = in_table<uint32_t>(row_weight, d[2], nullptr);
+    q.labels = out_table<int32_t>(host_labels, tb + at.labels_at, dev_labels);
+    q.cover = out_table<CoverRec>(host_cover, tb + at.cover_at, dev_cover);
+    q.head = reinterpret_cast<unsigned long long*>(tb);
+    q.edge_off = reinterpret_cast<uint32_t*>(tb + at.edge_at);
+    q.bin_off = reinterpret_cast<uint32_t*>(tb + at.bin_at);
+    q.poly_off = reinterpret_cast<uint32_t*>(tb + at.poly_at);
+    q.order = reinterpret_cast<uint32_t*>(tb + at.order_at);
+    q.sums = reinterpret_cast<unsigned long long*>(tb + at.sums_at);
+    q.n_rings = n_rings; q.n_vertices = n_vertices; q.n_polygons = n_polygons;
+    q.n_bins = bins ? n_polygons * (uint32_t)strips : 0;
+    q.rows = r->rows; q.cols = r->cols; q.wrap = r->wrap; q.s = r->subcell_bits; q.evenodd = r->rule == MRTX_RASTER_EVENODD;
+    q.last = r->order == MRTX_RASTER_LAST; q.strips = strips; q.bins = bins;
+    uint32_t launches = 0;
+    unsigned long long head[RS_HEAD] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // the counters, the counts per bin or per polygon and the order of the rings start at zero
+    HIPCHK(c, hipMemsetAsync(tb, 0, at.sums_at, c->stream));
+    CHK(stage_start(c, nullptr, false));
+    HIPCHK(c, mrtx_launch_raster_check(q, c->stream, &launches));
+    HIPCHK(c, hipStreamSynchronize(c->stream));                 // also: the pageable tables are no longer read
+    HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
+    if (head[RS_BAD_RINGS] || head[RS_BAD_COORDS] || head[RS_EDGES] > MRTX_RS_MAX_COUNT) {      // the stage ends, out says what ran
+        CHK(lattice_finish(c, nullptr, nullptr, 0, out, launches));
+        if (head[RS_BAD_RINGS] || head[RS_BAD_COORDS])
+            return fail(c, MRTX_E_INVALID, "the ring table holds %llu bad records and the vertex table %llu coordinates outside -2^24 .. 2^24",
+                        head[RS_BAD_RINGS], head[RS_BAD_COORDS]);
+        return fail(c, MRTX_E_INVALID, "the rings hold %llu edges: a call holds fewer than 2^31", head[RS_EDGES]);
+    }
+    q.n_edges = (uint32_t)head[RS_EDGES];
+    HIPCHK(c, mrtx_launch_raster_count(q, c->stream, &launches));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
+    if (head[RS_CROSSINGS] > MRTX_RS_MAX_COUNT) {
+        CHK(lattice_finish(c, nullptr, nullptr, 0, out, launches));
+        return fail(c, MRTX_E_INVALID, "the edges cross the columns %llu times: a call holds at most 2^31 - 1 crossings", head[RS_CROSSINGS]);
+    }
+    q.n_cross = (uint32_t)head[RS_CROSSINGS];
+    if (bins) {
+        CHK(stage_buffer(c, c->illum_out, c->illum_out_bytes, 8 * (size_t)q.n_cross + 16));
+        q.cross = reinterpret_cast<uint2*>(c->illum_out);
+    }
+    HIPCHK(c, mrtx_launch_raster_cover(q, c->stream, &launches));
+    CHK(lattice_finish(c, nullptr, nullptr, 0, out, launches));
+    if (bins) {                                                 // the scan's own check of what the two passes over the edges found
+        HIPCHK(c, hipMemcpy(head, tb, sizeof head, hipMemcpyDeviceToHost));
+        if (head[RS_BINNED] != head[RS_CROSSINGS])
+            return fail(c, MRTX_E_DEVICE, "the bins hold %llu crossings of %llu", head[RS_BINNED], head[RS_CROSSINGS]);
+    }
+    if (host_labels) HIPCHK(c, hipMemcpy(host_labels, q.labels, 4 * N, hipMemcpyDeviceToHost));
+    if (host_cover && n_polygons) HIPCHK(c, hipMemcpy(host_cover, q.cover, cover_bytes, hipMemcpyDeviceToHost));
+    if (n_crossings) *n_crossings = head[RS_CROSSINGS];
     return MRTX_OK;
 }
 

@@ -1,5 +1,5 @@
-"""The lattice half of MoonRT: regions, zonal statistics, shapes, proximity, outlines, contours, depressions and bowls of
-per-node tables -- the Python side of csrc/mrtx_lattice_api.hip.  MoonRT (renderer.py) inherits these methods.
+"""The lattice half of MoonRT: regions, zonal statistics, shapes, proximity, outlines, polygon rasterisation, contours,
+depressions and bowls of per-node tables -- the Python side of csrc/mrtx_lattice_api.hip.  MoonRT (renderer.py) inherits these methods.
 
 Every library call here takes its tables as (device, host) pointer pairs, one of each pair null.  A method is written once:
 its inputs come as pairs from _label_arg / _int32_arg / _lattice_arg / _outlet_arg, its outputs are _Tables made on the side
@@ -384,6 +384,55 @@ class LatticeCalls(Calls):
             rings = rb.take((n_r,))
             vertices = vb.take((n_v, 2))
         return rg.Outlines(rings, vertices, rows, cols, wrap)
+
+    # ---- Polygon rasterisation
+    def rasterise(self, polygons, shape, wrap=False, rule="nonzero", order="first", row_weights=None, stats=None):
+        """Polygons burnt into a label table (mrtx_rasterise), the inverse of region_outlines: every node of a (rows, cols) =
+        shape lattice gets the least (order="first") or the greatest (order="last", the painter's order) index among the
+        polygons that cover its centre, or -1.  polygons: a regions.Polygons (Outlines.polygons(), Polygons.from_latlon), or
+        the device tables with their counts, (rings DeviceBuffer, n_rings, vertices DeviceBuffer, n_vertices, n_polygons,
+        subcell_bits): the outputs are then made on the device and downloaded.  rule: "nonzero" (an outline's hole rings take
+        its outer ring's winding back to 0) or "evenodd" (for rings whose orientation is not known).  wrap joins the last
+        column to the first (cols >= 3).  row_weights: (rows,) uint32 node areas or None.  Needs no DEM.  Returns (labels (rows,
+        cols) int32, cover (n_polygons,) regions.COVER_DTYPE); stats gains launches, kernel_ms and crossings."""
+        from . import regions as rg
+        rules = {"nonzero": _lib.RASTER_NONZERO, "evenodd": _lib.RASTER_EVENODD}
+        orders = {"first": _lib.RASTER_FIRST, "last": _lib.RASTER_LAST}
+        if rule not in rules:
+            raise ValueError('rule must be "nonzero" or "evenodd"')
+        if order not in orders:
+            raise ValueError('order must be "first" or "last"')
+        rows, cols = int(shape[0]), int(shape[1])
+        if isinstance(polygons, rg.Polygons):
+            device = None
+            n_r, n_v, n_p, s = len(polygons), polygons.vertices.shape[0], polygons.n_polygons, polygons.subcell_bits
+            r_pair = (None, polygons.rings.ctypes.data if n_r else None)
+            v_pair = (None, polygons.vertices.ctypes.data if n_v else None)
+        else:
+            rb, n_r, vb, n_v, n_p, s = polygons
+            if not isinstance(rb, DeviceBuffer) or not isinstance(vb, DeviceBuffer):
+                raise ValueError("polygons must be a regions.Polygons or (rings DeviceBuffer, n_rings, vertices DeviceBuffer, "
+                                 "n_vertices, n_polygons, subcell_bits)")
+            n_r, n_v, n_p, s = int(n_r), int(n_v), int(n_p), int(s)
+            if rb.nbytes < rg.RASTER_RING_DTYPE.itemsize * n_r or vb.nbytes < 8 * n_v:
+                raise ValueError("a DeviceBuffer is smaller than its count")
+            device = rb.device
+            r_pair, v_pair = (rb.ptr if n_r else None, None), (vb.ptr if n_v else None, None)
+        wp, _kw = self._row_table(row_weights, rows, "row_weights")
+        blk = _lib.MrtxRaster(rows, cols, 1 if wrap else 0, s, rules[rule], orders[order], 0)
+        st = MrtxStats()
+        crossings = C.c_uint64(0)
+        with _Tables(device) as t:
+            lab = t.new(np.int32, (rows, cols))
+            rec = t.new(rg.COVER_DTYPE, (n_p,), zeros=True)
+            self._check(self._lib.mrtx_rasterise(self._ctx, C.byref(blk), *r_pair, n_r, *v_pair, n_v, n_p, wp, *lab.pair,
+                                                 *(rec.pair if n_p else _NULL), C.byref(crossings), C.byref(st)), "mrtx_rasterise")
+            labels = lab.take((rows, cols))
+            cover = rec.take((n_p,))
+        self._add_stats(stats, st)
+        if isinstance(stats, dict):
+            stats["crossings"] = stats.get("crossings", 0) + int(crossings.value)
+        return labels, cover
 
     # ---- Contour lines (DESIGN.md section 3.26)
     def contours(self, z, levels, wrap=False, shape=None, stats=None):

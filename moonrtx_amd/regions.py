@@ -31,11 +31,21 @@ assert REACH_DTYPE.itemsize == 32
 RING_DTYPE = np.dtype([("area", "<i8"), ("warea", "<i8"), ("first", "<u8"), ("n_sides", "<u4"), ("n_vertices", "<u4"),
                        ("label", "<i4"), ("head", "<i4"), ("wind", "<i4"), ("reserved", "<u4")])
 assert RING_DTYPE.itemsize == 48
+# mirrors MrtxRasterRing, 24 bytes
+RASTER_RING_DTYPE = np.dtype([("first", "<u8"), ("n_vertices", "<u4"), ("polygon", "<i4"), ("wind", "<i4"), ("reserved", "<u4")])
+assert RASTER_RING_DTYPE.itemsize == 24
+# mirrors MrtxPolygonCover, 40 bytes
+COVER_DTYPE = np.dtype([("weight", "<u8"), ("owned_weight", "<u8"), ("count", "<u4"), ("owned", "<u4"), ("i_min", "<i4"),
+                        ("i_max", "<i4"), ("first_at", "<i4"), ("reserved", "<u4")])
+assert COVER_DTYPE.itemsize == 40
 
 WEIGHT_MAX = 2 ** 32 - 1
 # every coordinate of a node position lies in -COORD_MAX .. COORD_MAX (mrtx_proximity)
 COORD_MAX = 2 ** 29
 NO_FEATURE = np.uint64(2 ** 64 - 1)
+# every vertex coordinate of a polygon lies in -RASTER_COORD_MAX .. RASTER_COORD_MAX (mrtx_rasterise), in units of 2^-s of a cell
+RASTER_COORD_MAX = 2 ** 24
+RASTER_MAX_SUBCELL = 8
 
 
 def row_weights(window, dem_hw, radius_m=1737400.0, unit_m2=1.0):
@@ -252,6 +262,99 @@ class Outlines:
         lat = 90.0 - (w["row0"] + (y - 0.5) * w["stride"] + 0.5) * (180.0 / H)
         lon = -180.0 + (w["col0"] + (x - 0.5) * w["stride"] + 0.5) * (360.0 / W)
         return np.stack([np.clip(lat, -90.0, 90.0), lon], -1)
+
+    def polygons(self, n_regions=None):
+        """The rings as the Polygons of MoonRT.rasterise, label as polygon, in the outlines' own coordinates (subcell_bits 0):
+        rasterising them gives back the label table (n_regions: one more than the greatest label when not given)."""
+        lab = self.rings["label"].astype(np.int64)
+        n = int(n_regions) if n_regions is not None else (int(lab.max()) + 1 if lab.size else 0)
+        rings = np.zeros(len(self), RASTER_RING_DTYPE)
+        for name, src in (("first", "first"), ("n_vertices", "n_vertices"), ("polygon", "label"), ("wind", "wind")):
+            rings[name] = self.rings[src]
+        return Polygons(rings, self.vertices, n, 0)
+
+
+class Polygons:
+    """What MoonRT.rasterise burns into a label table: rings (n,) RASTER_RING_DTYPE, each a run of the
+    vertex table that belongs to a polygon; vertices (m, 2) int32 (y, x) corner coordinates in units of 2^-subcell_bits of a
+    cell, x unwrapped along a ring; n_polygons; subcell_bits 0 .. 8.  A ring closes from its last vertex to its first, wind
+    times round a wrapped window."""
+
+    def __init__(self, rings, vertices, n_polygons, subcell_bits=0):
+        self.rings = np.ascontiguousarray(rings, RASTER_RING_DTYPE).reshape(-1)
+        self.vertices = np.ascontiguousarray(vertices, np.int32).reshape(-1, 2)
+        self.n_polygons, self.subcell_bits = int(n_polygons), int(subcell_bits)
+        if not 0 <= self.subcell_bits <= RASTER_MAX_SUBCELL:
+            raise ValueError("subcell_bits must lie in 0 .. 8")
+        if self.n_polygons < 0:
+            raise ValueError("n_polygons must be >= 0")
+        if int(self.rings["n_vertices"].astype(np.int64).sum()) != self.vertices.shape[0]:
+            raise ValueError("the rings' n_vertices do not add up to the vertex table")
+
+    def __len__(self):
+        return int(self.rings.shape[0])
+
+    def ring(self, r):
+        """(n_vertices, 2) int32: the vertices of ring r, a view of the vertex table."""
+        rec = self.rings[int(r)]
+        return self.vertices[int(rec["first"]):int(rec["first"]) + int(rec["n_vertices"])]
+
+    @classmethod
+    def from_rings(cls, rings, n_polygons=None, subcell_bits=0):
+        """From [(polygon, (n, 2) integer (y, x) vertices[, wind])], ring after ring."""
+        recs = np.zeros(len(rings), RASTER_RING_DTYPE)
+        verts, at = [], 0
+        for k, ring in enumerate(rings):
+            v = np.asarray(ring[1], np.int64).reshape(-1, 2)
+            recs[k] = (at, len(v), int(ring[0]), int(ring[2]) if len(ring) > 2 else 0, 0)
+            verts.append(v)
+            at += len(v)
+        n = int(n_polygons) if n_polygons is not None else (int(recs["polygon"].max()) + 1 if len(recs) else 0)
+        table = np.concatenate(verts) if verts else np.zeros((0, 2), np.int64)
+        if table.size and np.abs(table).max() > 2 ** 31 - 1:
+            raise ValueError("a coordinate leaves int32")
+        return cls(recs, table.astype(np.int32), n, subcell_bits)
+
+    @classmethod
+    def from_latlon(cls, window, dem_hw, polygons, subcell_bits=4):
+        """The inverse of Outlines.corner_latlon: polygons is a sequence of polygons, each a sequence of rings, each (n, 2)
+        (lat, lon) degrees, for a window (row0, col0, rows, cols[, stride[, wrap]]) of an (H, W) DEM.  y = ((90 - lat) H / 180 -
+        1 / 2 - row0) / stride + 1 / 2 and x = ((lon + 180) W / 360 - 1 / 2 - col0) / stride + 1 / 2 in float64, each quantised
+        as floor(v 2^s + 1 / 2).  Longitude is kept continuous along a ring: every vertex takes the longitude nearest to its
+        predecessor's (steps of less than 180 degrees), so a ring across the seam stays unwrapped; a ring that comes back to
+        its first vertex a whole turn on winds round the window (wrap only).  A repeated closing vertex is dropped.
+        ValueError when a coordinate leaves +-2^24 units: lower subcell_bits."""
+        from .traverse import window_dict
+        w = window_dict(window)
+        H, W = (int(v) for v in dem_hw)
+        s = int(subcell_bits)
+        if not 0 <= s <= RASTER_MAX_SUBCELL:
+            raise ValueError("subcell_bits must lie in 0 .. 8")
+        if w["stride"] < 1 or H < 1 or W < 1:
+            raise ValueError("empty window or DEM")
+        out = []
+        for p, poly in enumerate(polygons):
+            for ring in poly:
+                ll = np.asarray(ring, np.float64).reshape(-1, 2)
+                if not len(ll) or not np.all(np.isfinite(ll)):
+                    raise ValueError(f"polygon {p}: a ring needs at least one finite (lat, lon) vertex")
+                lon = ll[:, 1].copy()
+                for k in range(1, len(lon)):
+                    lon[k] = lon[k - 1] + ((lon[k] - lon[k - 1] + 180.0) % 360.0 - 180.0)
+                n, wind = len(ll), 0
+                if n > 1 and ll[-1, 0] == ll[0, 0]:
+                    turns = (lon[-1] - lon[0]) / 360.0
+                    if turns == round(turns):                   # the first vertex again, perhaps a whole turn on
+                        n, wind = n - 1, int(round(turns))
+                if wind and not w["wrap"]:
+                    raise ValueError(f"polygon {p}: a ring goes round the globe, the window does not")
+                y = ((90.0 - ll[:n, 0]) * (H / 180.0) - 0.5 - w["row0"]) / w["stride"] + 0.5
+                x = ((lon[:n] + 180.0) * (W / 360.0) - 0.5 - w["col0"]) / w["stride"] + 0.5
+                q = np.floor(np.stack([y, x], -1) * float(2 ** s) + 0.5)
+                if np.abs(q).max() > RASTER_COORD_MAX:
+                    raise ValueError(f"polygon {p}: a coordinate leaves +-2^24 units of 2^-{s} of a cell: lower subcell_bits")
+                out.append((p, q.astype(np.int64), wind))
+        return cls.from_rings(out, len(polygons), s)
 
 
 class ProximityMap:
